@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- image-pairs/sec of the LoFTR forward on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): per GPU a batch of B=8 synthetic 640x480 grayscale pairs,
@@ -18,7 +18,10 @@ the per-pair match counts (RCCL through the library's C-ABI, loftr_rccl_allgathe
 (BASELINE configs[2]) split over the ranks.  `python bench.py --gpus N` without a launcher spawns the N ranks
 itself (torch.distributed.run on 127.0.0.1); under torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
-The JSON line also carries
+A plain run sets up, warms up, times `--steps` steps and prints the headline (`value` image-pairs/s, `ms_per_step`): nothing
+else runs on the GPU or the host.  `--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<key>.npy
+(float32 / float64; `conf_matrix` as a fixed seeded sample, see dump_outputs).  With `--full` the run also takes the serial
+instrumented steps, records hipEvents around the north_star kernels inside the timed region, and the JSON line also carries
   roofline          -- the kernel group that dominates the hand-written matching path: the linear-attention encoder kernels
                        (encoder_x / proj_kv / fine_pair / linear) against the dense fp16 MFMA roof (executed MFMA rate,
                        hipEvents around every launch in serial instrumented steps of this run; `mfma_busy` =
@@ -572,7 +575,40 @@ def other_configs(lib, ids, dev, sd, backbone, overlap=True, steps=5, warmup=2):
     return out
 
 
-def main():
+DUMP_LIMIT_BYTES = 64 << 20         # everything --dump-outputs writes
+DUMP_WHOLE_BYTES = 8 << 20          # arrays up to this size are written whole, larger ones as a seeded sample
+DUMP_SAMPLE = 1 << 20               # entries drawn (with replacement, then de-duplicated) from a larger array
+DUMP_SEED = 0
+
+
+def dump_outputs(data, out_dir, skip=("image0", "image1")):
+    """Write every tensor of `data` (what LoFTR.forward hands its caller, the inputs in `skip` excluded) to out_dir/<key>.npy:
+    floating point as float32 (float64 stays float64), integers and booleans as float64 (exact).  An array larger than
+    DUMP_WHOLE_BYTES (conf_matrix: 8 x 4800 x 4800) is written as the values at a fixed set of flat indices drawn from
+    default_rng(DUMP_SEED) for its shape -- the same entries in every run and every build -- with the indices next to it as
+    <key>.sample_index.npy.  Returns {file name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for k in sorted(data):
+        v = data[k]
+        if k in skip or not torch.is_tensor(v):
+            continue
+        v = v.detach()
+        if v.numel() * 4 > DUMP_WHOLE_BYTES:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, v.numel(), DUMP_SAMPLE))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+            arrays[k + ".sample_index"] = idx.astype(np.float64)
+        a = v.cpu().numpy()
+        arrays[k] = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total / 2 ** 20:.1f} MiB exceeds the {DUMP_LIMIT_BYTES >> 20} MiB limit")
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k + ".npy": a.shape for k, a in arrays.items()}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -583,8 +619,13 @@ def main():
     ap.add_argument("--total-batch", type=int, default=64, help="pairs per step over ALL GPUs with --scaling strong")
     ap.add_argument("--thr", type=float, default=0.0)
     ap.add_argument("--no-conf", action="store_true", help="elide data['conf_matrix'] (not the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the untimed outdoor / Sinkhorn forwards reported as other_configs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: serial instrumented steps (stage_ms, kernels, rooflines), hipEvents "
+                         "around the north_star kernels in the timed region, other_configs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<key>.npy (float32 / float64, at most 64 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the untimed outdoor / Sinkhorn forwards reported as other_configs")
     ap.add_argument("--no-overlap", action="store_true", help="run the FPN fine branch on the main stream (no second HIP stream)")
     ap.add_argument("--match-type", default="dual_softmax", choices=["dual_softmax", "sinkhorn"],
                     help="sinkhorn = BASELINE configs[4] (indoor_ot); not the headline")
@@ -600,7 +641,11 @@ def main():
     ap.add_argument("--collective", default="auto", choices=["auto", "cabi", "torch"],
                     help="count all-gather transport: the library's C-ABI RCCL call, or torch.distributed (also RCCL); auto = cabi, "
                          "falling back to torch if the communicator cannot be created (recorded in the JSON)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_spawn(sys.argv[1:], args.gpus))
@@ -727,51 +772,52 @@ def main():
         dist.all_reduce(mt)
         assert int(last["data"]["match_counts_global"].sum().item()) == int(mt.item()), "count all-gather mismatch"
 
-    # ---- extra untimed steps with every kernel instrumented, streams serial: per-kernel breakdown
-    lib.loftr_hip_timing_enable((1 << len(ids)) - 1)
-    for kid in ids.values():
-        read_timing(lib, kid)
-    NB = 3                                                   # instrumented steps for the breakdown
-    bb_steps, hot_steps = [], []
-    model.overlap_fine_branch = False                        # serial streams here: clean per-kernel / per-stage times
-    for it in range(NB + 1):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        with torch.no_grad():
-            data = {"image0": img0, "image1": img1}
-            ev[0].record()
-            feats = model.run_backbone(data)
-            ev[1].record()
-            model.match_from_features(*feats, data)
-            ev[2].record()
-        torch.cuda.synchronize()
-        if it == 0:                                          # the first instrumented step creates the library's event pairs (tens of ms of
-            for kid in ids.values():                         # hipEventCreate on some boxes: round-4 runs showed 33 ms "backbone" means): not measured
-                read_timing(lib, kid)
-            continue
-        bb_steps.append(ev[0].elapsed_time(ev[1]))
-        hot_steps.append(ev[1].elapsed_time(ev[2]))
-    backbone_ms, hot_ms = float(np.median(bb_steps)), float(np.median(hot_steps))
-    M = int(data["mconf"].shape[0])
-    L = (H_IMG // 8) * (W_IMG // 8)
-    raw = {name: read_timing(lib, kid) for name, kid in ids.items()}
-    persistent = raw.get("encoder_x_kernel", (0, 0))[1] > 0 and raw.get("proj_kv_kernel", (0, 0))[1] == 0
-    work = algorithmic_work(B, L, L, M, fused=raw.get("encoder_x_kernel", (0, 0))[1] > 0,
-                            fused_fine=raw.get("fine_pair_kernel", (0, 0))[1] > 0, persistent=persistent)
-    kernels = []
-    for name, (ms, n) in raw.items():
-        if name in work and n:
-            e = roofline_entry(name, ms, n, work[name][0], work[name][1], NB)
-            if e:
-                e["traffic"] = pmc_traffic(name)
-                e["mfma_busy"] = pmc_mfma_busy(name)
-                if name in POOLED_FROM:
-                    e["pooled_from"] = POOLED_FROM[name]
-                kernels.append(e)
-    model.overlap_fine_branch = not args.no_overlap
-    kernels.sort(key=lambda k: -k["ms_per_step"])
+    if args.full:
+        # ---- extra untimed steps with every kernel instrumented, streams serial: per-kernel breakdown
+        lib.loftr_hip_timing_enable((1 << len(ids)) - 1)
+        for kid in ids.values():
+            read_timing(lib, kid)
+        NB = 3                                                   # instrumented steps for the breakdown
+        bb_steps, hot_steps = [], []
+        model.overlap_fine_branch = False                        # serial streams here: clean per-kernel / per-stage times
+        for it in range(NB + 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            with torch.no_grad():
+                data = {"image0": img0, "image1": img1}
+                ev[0].record()
+                feats = model.run_backbone(data)
+                ev[1].record()
+                model.match_from_features(*feats, data)
+                ev[2].record()
+            torch.cuda.synchronize()
+            if it == 0:                                          # the first instrumented step creates the library's event pairs (tens of ms of
+                for kid in ids.values():                         # hipEventCreate on some boxes: round-4 runs showed 33 ms "backbone" means): not measured
+                    read_timing(lib, kid)
+                continue
+            bb_steps.append(ev[0].elapsed_time(ev[1]))
+            hot_steps.append(ev[1].elapsed_time(ev[2]))
+        backbone_ms, hot_ms = float(np.median(bb_steps)), float(np.median(hot_steps))
+        M = int(data["mconf"].shape[0])
+        L = (H_IMG // 8) * (W_IMG // 8)
+        raw = {name: read_timing(lib, kid) for name, kid in ids.items()}
+        persistent = raw.get("encoder_x_kernel", (0, 0))[1] > 0 and raw.get("proj_kv_kernel", (0, 0))[1] == 0
+        work = algorithmic_work(B, L, L, M, fused=raw.get("encoder_x_kernel", (0, 0))[1] > 0,
+                                fused_fine=raw.get("fine_pair_kernel", (0, 0))[1] > 0, persistent=persistent)
+        kernels = []
+        for name, (ms, n) in raw.items():
+            if name in work and n:
+                e = roofline_entry(name, ms, n, work[name][0], work[name][1], NB)
+                if e:
+                    e["traffic"] = pmc_traffic(name)
+                    e["mfma_busy"] = pmc_mfma_busy(name)
+                    if name in POOLED_FROM:
+                        e["pooled_from"] = POOLED_FROM[name]
+                    kernels.append(e)
+        model.overlap_fine_branch = not args.no_overlap
+        kernels.sort(key=lambda k: -k["ms_per_step"])
 
-    # ---- timed region: the north_star kernels (score volume AND the encoder group) carry events -- `roofline` is measured HERE
-    timed_ids = [n for n in NORTH_STAR_TIMED + ENCODER_KERNELS if n in ids]
+    # ---- timed region: with --full the north_star kernels (score volume AND the encoder group) carry events -- `roofline` is measured HERE
+    timed_ids = [n for n in NORTH_STAR_TIMED + ENCODER_KERNELS if n in ids] if args.full else []
     if args.match_type != "dual_softmax":
         timed_ids = [n for n in timed_ids if not n.startswith("score_")]
     mask = 0
@@ -791,42 +837,46 @@ def main():
         ms, cnt = read_timing(lib, ids[n])
         if cnt:
             timing[n] = (ms, cnt)
-    # the timed region's match count can differ from the instrumented steps' only if the inputs did (they do not); same work table
-    roof = None
-    if "score_sweep_kernel<1>" in timing:
-        ms, cnt = timing["score_sweep_kernel<1>"]
-        roof = roofline_entry("score_sweep_kernel<1>", ms, cnt, work["score_sweep_kernel<1>"][0], work["score_sweep_kernel<1>"][1], args.steps)
-        roof["bound"], roof["achieved"], roof["peak"], roof["unit"], roof["frac"] = "hbm", roof["alg_GB_s"], HBM_PEAK_GBS, "GB/s", roof["hbm_frac"]
-        roof["traffic"] = pmc_traffic("score_sweep_kernel<1>")
-        roof["note"] = ("north_star score-volume kernel (dual-softmax pass B: recompute the score tile on MFMA, write conf_matrix "
-                        "once): algorithmic bytes = descriptors + conf_matrix (DESIGN.md §4) / in-region hipEvent launch time")
-    # Encoder group (the headline `roofline`): hipEvents around every launch of these kernels INSIDE the timed region (round-5 verdict,
-    # weak #3: until round 5 the headline figure came from serialised instrumented steps while the timed step ran two streams).  The
-    # serial instrumented steps before the timed region give `alone` (the kernels with the GPU to themselves).
-    serial = {k["kernel"]: (k["ms_per_step"] * NB, int(round(k["launches_per_step"] * NB))) for k in kernels}
-    roof_alone = group_roofline([n for n in ENCODER_KERNELS if n in serial], serial, work, NB)
-    roof_bb = group_roofline([n for n in BACKBONE_KERNELS if n in serial], serial, work, NB)
-    roof_enc = group_roofline([n for n in ENCODER_KERNELS if n in timing], timing, work, args.steps)
-    serial_step_ms = backbone_ms + hot_ms
-    if roof_bb:
-        roof_bb["measured"] = "hipEvents around every launch of these kernels in 3 instrumented steps of this run on one stream (kernels alone on the GPU)"
-        roof_bb["share_of_serial_step"] = round(roof_bb["ms_per_step"] / serial_step_ms, 4)
-    if roof_enc:
-        roof_enc["measured"] = (f"hipEvents (recorded by the library on the launch stream) around every launch of these kernels in the {args.steps} steps of the "
-                                "TIMED region" + (", in which the FPN fine branch runs on a second HIP stream next to the coarse transformer" if model.overlap_fine_branch else ""))
-        roof_enc["kernel"] = ("coarse_persistent_kernel (the whole coarse LocalFeatureTransformer: q / k / v projections, K^T V, merge, MLP, LayerNorms; one launch) "
-                              "+ fine_pair_kernel + the fine-level linear kernels: the linear-attention encoder group" if persistent else
-                              "encoder_x_kernel (+ proj_kv / fine_pair / linear: the linear-attention encoder group)")
-        roof_enc["coarse_transformer"] = "one persistent launch (work queue, per-pair / per-tile dependencies)" if persistent else "per-call launches"
-        roof_enc["pooled_from"] = sorted({x for n in ENCODER_KERNELS for x in POOLED_FROM.get(n, [n])})
-        roof_enc["share_of_step"] = round(roof_enc["ms_per_step"] / (elapsed_local / args.steps * 1e3), 4)
-        if roof_alone:
-            roof_enc["alone"] = {k: roof_alone[k] for k in ("achieved", "frac", "executed_TFLOP_s", "executed_frac", "ms_per_step", "launches_per_step")}
-            roof_enc["alone"]["measured"] = "the same kernels in 3 instrumented steps on one stream before the timed region"
-            roof_enc["alone_frac"] = roof_alone["frac"]
-            roof_enc["dominant_share_of_matching_path"] = round(roof_alone["ms_per_step"] / hot_ms, 4)
-    if roof is not None:
-        roof["share_of_serial_step"] = round(roof["ms_per_step"] / serial_step_ms, 4)
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(last["data"], args.dump_outputs)
+        print(f"[bench] --dump-outputs: {len(written)} arrays -> {args.dump_outputs}", file=sys.stderr)
+    if args.full:
+        # the timed region's match count can differ from the instrumented steps' only if the inputs did (they do not); same work table
+        roof = None
+        if "score_sweep_kernel<1>" in timing:
+            ms, cnt = timing["score_sweep_kernel<1>"]
+            roof = roofline_entry("score_sweep_kernel<1>", ms, cnt, work["score_sweep_kernel<1>"][0], work["score_sweep_kernel<1>"][1], args.steps)
+            roof["bound"], roof["achieved"], roof["peak"], roof["unit"], roof["frac"] = "hbm", roof["alg_GB_s"], HBM_PEAK_GBS, "GB/s", roof["hbm_frac"]
+            roof["traffic"] = pmc_traffic("score_sweep_kernel<1>")
+            roof["note"] = ("north_star score-volume kernel (dual-softmax pass B: recompute the score tile on MFMA, write conf_matrix "
+                            "once): algorithmic bytes = descriptors + conf_matrix (DESIGN.md §4) / in-region hipEvent launch time")
+        # Encoder group (the headline `roofline`): hipEvents around every launch of these kernels INSIDE the timed region (round-5 verdict,
+        # weak #3: until round 5 the headline figure came from serialised instrumented steps while the timed step ran two streams).  The
+        # serial instrumented steps before the timed region give `alone` (the kernels with the GPU to themselves).
+        serial = {k["kernel"]: (k["ms_per_step"] * NB, int(round(k["launches_per_step"] * NB))) for k in kernels}
+        roof_alone = group_roofline([n for n in ENCODER_KERNELS if n in serial], serial, work, NB)
+        roof_bb = group_roofline([n for n in BACKBONE_KERNELS if n in serial], serial, work, NB)
+        roof_enc = group_roofline([n for n in ENCODER_KERNELS if n in timing], timing, work, args.steps)
+        serial_step_ms = backbone_ms + hot_ms
+        if roof_bb:
+            roof_bb["measured"] = "hipEvents around every launch of these kernels in 3 instrumented steps of this run on one stream (kernels alone on the GPU)"
+            roof_bb["share_of_serial_step"] = round(roof_bb["ms_per_step"] / serial_step_ms, 4)
+        if roof_enc:
+            roof_enc["measured"] = (f"hipEvents (recorded by the library on the launch stream) around every launch of these kernels in the {args.steps} steps of the "
+                                    "TIMED region" + (", in which the FPN fine branch runs on a second HIP stream next to the coarse transformer" if model.overlap_fine_branch else ""))
+            roof_enc["kernel"] = ("coarse_persistent_kernel (the whole coarse LocalFeatureTransformer: q / k / v projections, K^T V, merge, MLP, LayerNorms; one launch) "
+                                  "+ fine_pair_kernel + the fine-level linear kernels: the linear-attention encoder group" if persistent else
+                                  "encoder_x_kernel (+ proj_kv / fine_pair / linear: the linear-attention encoder group)")
+            roof_enc["coarse_transformer"] = "one persistent launch (work queue, per-pair / per-tile dependencies)" if persistent else "per-call launches"
+            roof_enc["pooled_from"] = sorted({x for n in ENCODER_KERNELS for x in POOLED_FROM.get(n, [n])})
+            roof_enc["share_of_step"] = round(roof_enc["ms_per_step"] / (elapsed_local / args.steps * 1e3), 4)
+            if roof_alone:
+                roof_enc["alone"] = {k: roof_alone[k] for k in ("achieved", "frac", "executed_TFLOP_s", "executed_frac", "ms_per_step", "launches_per_step")}
+                roof_enc["alone"]["measured"] = "the same kernels in 3 instrumented steps on one stream before the timed region"
+                roof_enc["alone_frac"] = roof_alone["frac"]
+                roof_enc["dominant_share_of_matching_path"] = round(roof_alone["ms_per_step"] / hot_ms, 4)
+        if roof is not None:
+            roof["share_of_serial_step"] = round(roof["ms_per_step"] / serial_step_ms, 4)
     elapsed, per_rank_ms = elapsed_local, [round(elapsed_local / args.steps * 1e3, 3)]
     if multi:
         t = torch.tensor([elapsed_local], dtype=torch.float64, device=dev)
@@ -860,28 +910,32 @@ def main():
                        "parity": "image-level goldens of the reference forward, both backbones (incl. a 3-pair batch and the 840 x 840 masked outdoor batch): profiles/r06_parity_margins.txt"},
             "per_rank_ms_per_step": per_rank_ms,
             "collective": {"transport": transport, "ranks_in_communicator": (rccl.ranks_seen if rccl is not None else world) if multi else 1},
-            "pmc_identity": PMC_IDENTITY if pmc_table() else None,      # what ties profiles/pmc_traffic.json to this build: "source" (every kernel source unchanged) / "kernel_code" (machine code of the profiled kernels byte-identical) / None (no traffic figures)
-            "stage_ms": {"backbone": round(backbone_ms, 3), "backbone_impl": args.backbone, "hot_path_hip": round(hot_ms, 3),
-                         "note": "median of 3 instrumented steps (after one unmeasured instrumented step) run WITHOUT the two-stream overlap (serial sum > ms_per_step when "
-                                 "the timed region overlaps the FPN fine branch with the coarse stage); `kernels` likewise"},
-            "fine_branch_overlapped_in_timed_region": bool(model.overlap_fine_branch), "coarse_mode": "persistent" if persistent else "launches", "backbone_halves_on_two_streams": bool((B >= 8 if model.backbone_halves is None else model.backbone_halves) and model.overlap_fine_branch and args.backbone == "hip"),
+            "fine_branch_overlapped_in_timed_region": bool(model.overlap_fine_branch), "backbone_halves_on_two_streams": bool((B >= 8 if model.backbone_halves is None else model.backbone_halves) and model.overlap_fine_branch and args.backbone == "hip"),
             **({"debug_switches": args.debug_switch} if args.debug_switch else {}),
             **({"attempt": int(os.environ["LOFTR_BENCH_ATTEMPT"]), "attempt_note": "the first attempt was killed by a signal (run_with_retry)"}
                if os.environ.get("LOFTR_BENCH_ATTEMPT", "1") != "1" else {}),
-            "hot_path_pairs_per_s": round(B / (hot_ms * 1e-3), 2),
-            # headline roofline = the kernel group that dominates the hand-written matching path (linear-attention encoder, MFMA-bound:
-            # the north_star's "MFMA utilisation on the linear-attention kernel"); the north_star's HBM figure on the score-volume
-            # kernel is `roofline_score_volume`; `roofline_backbone` = the convolution kernels (largest share of the whole step)
-            "roofline": roof_enc if roof_enc else roof, "roofline_score_volume": roof, "roofline_backbone": roof_bb, "kernels": kernels,
-            "pmc_source": ("profiles/pmc_traffic.json (rocprofv3 --pmc passes of this build, source hash " + source_hash() + ")")
-                          if pmc_table() else "no PMC passes for this build of the kernels: traffic / mfma_busy are null",
         }
-        if world == 1 and not args.no_other_configs and args.match_type == "dual_softmax":
+        if args.full:
+            out.update({
+                "pmc_identity": PMC_IDENTITY if pmc_table() else None,      # what ties profiles/pmc_traffic.json to this build: "source" (every kernel source unchanged) / "kernel_code" (machine code of the profiled kernels byte-identical) / None (no traffic figures)
+                "stage_ms": {"backbone": round(backbone_ms, 3), "backbone_impl": args.backbone, "hot_path_hip": round(hot_ms, 3),
+                             "note": "median of 3 instrumented steps (after one unmeasured instrumented step) run WITHOUT the two-stream overlap (serial sum > ms_per_step when "
+                                     "the timed region overlaps the FPN fine branch with the coarse stage); `kernels` likewise"},
+                "coarse_mode": "persistent" if persistent else "launches",
+                "hot_path_pairs_per_s": round(B / (hot_ms * 1e-3), 2),
+                # headline roofline = the kernel group that dominates the hand-written matching path (linear-attention encoder, MFMA-bound:
+                # the north_star's "MFMA utilisation on the linear-attention kernel"); the north_star's HBM figure on the score-volume
+                # kernel is `roofline_score_volume`; `roofline_backbone` = the convolution kernels (largest share of the whole step)
+                "roofline": roof_enc if roof_enc else roof, "roofline_score_volume": roof, "roofline_backbone": roof_bb, "kernels": kernels,
+                "pmc_source": ("profiles/pmc_traffic.json (rocprofv3 --pmc passes of this build, source hash " + source_hash() + ")")
+                              if pmc_table() else "no PMC passes for this build of the kernels: traffic / mfma_busy are null",
+            })
+        if args.full and world == 1 and not args.no_other_configs and args.match_type == "dual_softmax":
             try:
                 out["other_configs"] = other_configs(lib, ids, dev, sd, args.backbone, overlap=not args.no_overlap)
             except Exception as e:                          # noqa: BLE001  (the headline line must not depend on the extras)
                 out["other_configs"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, img0, img1, last.get("data"))
             out["cpu_baseline_kind"] = out["cpu_baseline"].get("kind")       # top level: "reference" (the reference's own forward) or "port" -- never to be mixed
         sys.stdout.flush()

@@ -199,6 +199,12 @@ def make_coarse_train(name):
     print(name, "fine-level training set", len(data["b_ids"]), "of which predictions", int((~data["gt_mask"]).sum()))
 
 
+# Intra-op threads of the CPU training steps behind tstep_* / tfull_*.  oneDNN's float32 convolutions split their work by thread count, so the
+# backbone's pre-activations move by ~1e-6 from one count to another and a unit within that of zero changes sign; at this count the
+# PyTorch-CPU backbone reproduces the recorded forward bit for bit (AVX-512 Xeon and EPYC hosts alike).
+GOLDEN_CPU_THREADS = 8
+
+
 # ---- the whole training-step forward: PL_LoFTR._trainval_inference (lightning_loftr.py:82-93) --------------------------
 # compute_supervision_coarse -> matcher(batch) in .train() mode -> compute_supervision_fine -> LoFTRLoss, on images + depth +
 # poses; matcher weights seeded like the e2e goldens, torch.randint replaced by det_randint.
@@ -237,6 +243,7 @@ def make_step(name):
     from tests.golden.make_golden_e2e import e2e_state_dict
     RefLoFTR, _ = import_reference()
     sup, LoFTRLoss = __import__("oracle.ref_shim", fromlist=["x"]).import_reference_training()
+    torch.set_num_threads(GOLDEN_CPU_THREADS)
     rc = STEP_CASES[name]
     batch, geo = step_batch(rc)
     cfg = step_matcher_cfg(rc)
@@ -281,6 +288,7 @@ def make_step_grads(name):
     from tests.golden.make_golden_e2e import e2e_state_dict
     RefLoFTR, _ = import_reference()
     sup, LoFTRLoss = __import__("oracle.ref_shim", fromlist=["x"]).import_reference_training()
+    torch.set_num_threads(GOLDEN_CPU_THREADS)
     gc = GRAD_STEP_CASES[name]
     rc = STEP_CASES[gc["step"]]
     batch, geo = step_batch(rc)

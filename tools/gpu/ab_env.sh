@@ -2,7 +2,7 @@
 # same-box A/B of an environment switch: bench twice alternating   usage: ab_env.sh VAR=VALUE
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd $R
-one() { env $1 python bench.py --steps ${STEPS:-12} --warmup 3 --no-cpu-baseline --no-overlap 2>/dev/null | python -c "
+one() { env $1 python bench.py --full --steps ${STEPS:-12} --warmup 3 --no-cpu-baseline --no-overlap 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k={e['kernel']:e for e in d.get('kernels',[])}

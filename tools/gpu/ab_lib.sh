@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd $R
 V=$R/loftr_amd/libloftr_hip_$1.so
-one() { python bench.py --steps ${STEPS:-12} --warmup 3 --no-cpu-baseline --no-overlap 2>/dev/null | python -c "
+one() { python bench.py --full --steps ${STEPS:-12} --warmup 3 --no-cpu-baseline --no-overlap 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k={e['kernel']:e for e in d.get('kernels',[])}

@@ -4,4 +4,4 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd $R
 LOFTR_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline
+  bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline

@@ -7,9 +7,9 @@ mkdir -p $O; cd $R
 timeout 900 python -m pytest tests -m gpu -q --timeout 600 2>&1 | tail -40 > $O/${T}_pytest.log
 tail -n 15 $O/${T}_pytest.log
 STEPS=10 bash tools/gpu/ab_env.sh LOFTR_FUSED_ENCODER=0 2>&1 | tee $O/${T}_ab_fused.txt
-timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
 export TMPDIR=/tmp; cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$T -o p -- python $R/bench.py --no-cpu-baseline --warmup 2 --steps 5 --no-overlap > $O/${T}_prof_bench.json 2> $O/${T}_prof.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$T -o p -- python $R/bench.py --full --no-cpu-baseline --warmup 2 --steps 5 --no-overlap > $O/${T}_prof_bench.json 2> $O/${T}_prof.err
 cd $R
 python tools/rocpd_summary.py $(find $O/prof_$T -name '*.db' | head -1) > $O/${T}_kernel_stats_serial.txt 2>&1
 head -24 $O/${T}_kernel_stats_serial.txt

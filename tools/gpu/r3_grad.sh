@@ -6,7 +6,7 @@ timeout 600 python -m pytest tests/test_hip_grad.py -q --timeout 300 2>&1 | tail
 tail -25 $O/${T}_grad.log
 timeout 900 python -m pytest tests -m gpu -q --timeout 600 -k "ot or sinkhorn or training or ties" 2>&1 | tail -8 > $O/${T}_ot.log
 cat $O/${T}_ot.log
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
 python - <<PY
 import json
 d = json.load(open("$O/${T}_bench.json"))

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 T=${1:-r03}
 O=$R/gpurun_out
 mkdir -p $O; export TMPDIR=/tmp LOFTR_BENCH_NO_RETRY=1; cd /tmp
-B="python $R/bench.py --no-cpu-baseline --no-other-configs --warmup 2"
+B="python $R/bench.py --full --no-cpu-baseline --no-other-configs --warmup 2"
 python -c 'import torch' 2> /dev/null     # page the image in before the first timed-out-able run
 # (an aborted process under rocprofv3 does not exit by itself: short timeouts, and stop at the first failure)
 fail() { echo "FAILED: $1"; grep -v "^W2026\|^E2026\|^I2026" $2 | tail -6 | cut -c1-300; exit 1; }
@@ -28,7 +28,7 @@ cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
 head -32 $O/${T}_kernel_stats_serial.txt; head -34 $O/${T}_pmc_traffic.txt
 rm -rf $O/prof_$T $O/profs_$T $O/pmc_fetch_$T $O/pmc_write_$T $O/pmc_sq_$T
 # the bench line as the driver runs it (with the PMC table of THIS build in place)
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err
 python -c "
 import json
 d=json.load(open('$O/${T}_bench.json'))

@@ -6,8 +6,8 @@ python tools/micro/encoder_bench.py 8 5 2>&1 | grep -v amdgpu.ids | tee $O/${T}_
 python tools/micro/fine_bench.py 7700 5 2>&1 | grep -v amdgpu.ids | head -1 | tee -a $O/${T}_micro.txt
 timeout 900 python -m pytest tests -m gpu -q --timeout 600 2>&1 | tail -12 > $O/${T}_pytest.log
 grep -h "passed\|failed" $O/${T}_pytest.log
-timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
-timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-overlap > $O/${T}_bench_serial.json 2> $O/${T}_bench_serial.err
+timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-overlap > $O/${T}_bench_serial.json 2> $O/${T}_bench_serial.err
 python - <<PY
 import json
 for f in ("$O/${T}_bench.json", "$O/${T}_bench_serial.json"):

@@ -2,7 +2,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 O=$R/gpurun_out; mkdir -p $O; cd $R
 python -c 'import torch' 2> /dev/null
-timeout 900 python bench.py --steps 20 --warmup 5 $BENCH_ARGS > $O/r4_bench.json 2> $O/r4_bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 $BENCH_ARGS > $O/r4_bench.json 2> $O/r4_bench.err
 python - <<PY
 import json
 d=json.load(open('$O/r4_bench.json'))

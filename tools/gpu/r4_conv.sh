@@ -8,7 +8,7 @@ for d in 0 3; do
   echo "== LOFTR_CONV_DUO=$d"
   LOFTR_CONV_DUO=$d timeout 300 python tools/micro/conv_layers.py 16 10 2>&1 | tee $O/r4_conv_layers_duo$d.txt
 done
-one() { python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
+one() { python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k={e['kernel']:e for e in d.get('kernels',[])}

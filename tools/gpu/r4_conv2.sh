@@ -7,7 +7,7 @@ for l in "layer1 3x3" "layer2_outconv2.0" "layer1_outconv2.0"; do
   LOFTR_HIP_LIB=$R/loftr_amd/libloftr_hip_p_probe.so timeout 120 python tools/micro/conv_probe.py "$l" 2>&1 | grep -v "^W2026\|amdgpu.ids" | head -2
 done
 timeout 300 python tools/micro/conv_layers.py 16 10 3x3 2>&1 | grep -v "^W2026\|amdgpu.ids" | tee $O/r4_conv_layers_b.txt
-one() { python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
+one() { python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k={e['kernel']:e for e in d.get('kernels',[])}

@@ -14,7 +14,7 @@ run_margins default X=1
 run_margins nofusedfine LOFTR_FUSED_FINE=0
 run_margins nofusedenc LOFTR_FUSED_ENCODER=0
 timeout 300 python tools/micro/conv_layers.py 16 10 2>&1 | tee $O/r4_conv_layers.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/r4a_bench.json 2> $O/r4a_bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r4a_bench.json 2> $O/r4a_bench.err
 python - <<PY
 import json
 d=json.load(open('$O/r4a_bench.json'))

@@ -16,7 +16,7 @@ timeout 1500 python -m pytest tests -m gpu -q --timeout 600 > $O/${T}_pytest_ful
   echo "# (2) full forward from images, both backbones (tests/test_e2e_golden.py; max and RMS distances to the reference's fp64 forward, next to the reference's own fp32 forward)";
   cat $O/parity_e2e.txt; } > $O/${T}_parity_margins.txt
 cd /tmp
-B="python $R/bench.py --no-cpu-baseline --no-other-configs --warmup 2"
+B="python $R/bench.py --full --no-cpu-baseline --no-other-configs --warmup 2"
 fail() { echo "FAILED: $1"; grep -v "^W2026\|^E2026\|^I2026" $2 | tail -6 | cut -c1-300; exit 1; }
 timeout -k 5 180 rocprofv3 --kernel-trace --stats -d $O/prof_$T -o p -- $B --steps 5 > $O/${T}_prof_bench.json 2> $O/${T}_prof.err
 [ $? -eq 0 ] || fail "$O/prof_$T" $O/${T}_prof.err
@@ -52,7 +52,7 @@ bash tools/gpu/r4_enc_sweep.sh > $O/${T}_encoder_rounds.txt 2>&1
 timeout 300 python tools/micro/conv_layers.py 16 10 2>&1 | grep -v "amdgpu.ids\|^W2026" > $O/${T}_conv_layers.txt
 head -14 $O/${T}_kernel_stats_serial.txt | cut -c1-160; head -20 $O/${T}_pmc_traffic.txt | cut -c1-200; cat $O/${T}_coverage.txt
 # the bench line as the driver runs it (with the PMC table of THIS build in place)
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err
 python - <<PY
 import json
 d=json.load(open('$O/${T}_bench.json'))

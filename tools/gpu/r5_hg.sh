@@ -10,7 +10,7 @@ done
 echo "=== product"
 LOFTR_WGRAD_CHUNK=128 timeout 120 python tools/micro/hg_diag.py 2 2>&1 | tail -5
 if [ -n "$BENCH" ]; then
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/r5_base_bench.json 2> $O/r5_base_bench.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/r5_base_bench.json 2> $O/r5_base_bench.err
   python - <<PY
 import json
 d=json.load(open('$O/r5_base_bench.json'))

@@ -9,7 +9,7 @@ for rep in ${REPS:-1 2}; do
 for c in $CONFIGS; do
     mode=${c%%:*}; extra=${c#*:}
     tag=$(echo "${mode}_${extra}" | tr -c 'a-zA-Z0-9_\n' '_')
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --coarse-mode $mode $extra > $O/ab_${tag}_$rep.json 2> $O/ab.err
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --coarse-mode $mode $extra > $O/ab_${tag}_$rep.json 2> $O/ab.err
     python - <<PY
 import json
 d=json.load(open('$O/ab_${tag}_$rep.json'))

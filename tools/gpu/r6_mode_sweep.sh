@@ -6,7 +6,7 @@ cd $R
 for rep in 1 2; do
 for b in 1 2 4 8 16; do
   for m in persistent launches; do
-    python bench.py --no-cpu-baseline --no-other-configs --batch $b --steps 20 --warmup 5 --coarse-mode $m 2> /dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-other-configs --batch $b --steps 20 --warmup 5 --coarse-mode $m 2> /dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('indoor batch $b $m: %.3f ms per step, %.1f pairs/s' % (d['ms_per_step'], d['value']))"

@@ -6,7 +6,7 @@ python -c 'import torch' 2> /dev/null
 ( for i in $(seq 1 60); do echo "t=$i"; rocm-smi --showpower --showclocks --showtemp 2>/dev/null | grep -i "power\|sclk\|mclk\|junction\|edge" ; sleep 0.25; done ) > $O/r06_power_samples.txt 2>&1 &
 SP=$!
 sleep 2
-timeout 200 python bench.py --steps 400 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r06_power_bench.json 2> /dev/null
+timeout 200 python bench.py --full --steps 400 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r06_power_bench.json 2> /dev/null
 wait $SP
 python - <<PY
 import json,re

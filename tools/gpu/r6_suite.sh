@@ -9,7 +9,7 @@ grep -E "passed|failed|^FAILED|^ERROR" $O/r06_pytest_gpu_full.txt | tee $O/r06_p
 cp $O/parity_e2e.txt $O/r06_parity_margins.txt 2> /dev/null
 cat $O/parity_features.txt >> $O/r06_parity_margins.txt 2> /dev/null
 if [ -n "$BENCH" ]; then
-  timeout 900 python bench.py --steps 20 --warmup 5 > $O/r06_bench.json 2> $O/r06_bench.err
+  timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r06_bench.json 2> $O/r06_bench.err
   python - <<PY
 import json
 d=json.load(open('$O/r06_bench.json'))
