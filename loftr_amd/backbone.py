@@ -187,9 +187,37 @@ class _ResNetFPN(nn.Module):
         """fp32 [B,H,W,C] -> logical [B,C,H,W] with channels-last strides (no copy)."""
         return y_nhwc.permute(0, 3, 1, 2)
 
+    def _hip_convs(self):
+        """Every (conv, bn or None) pair forward_hip hands ops.conv_bn_act (the stem reads its weights directly)."""
+        for stage in self._HIP_STAGES:
+            for blk in getattr(self, stage):
+                yield blk.conv1, blk.bn1
+                if blk.downsample is not None:
+                    yield blk.downsample[0], blk.downsample[1]
+                yield blk.conv2, blk.bn2
+        for name in self._HIP_OUTCONVS:
+            yield getattr(self, name), None
+        for name in self._HIP_HEADS:
+            head = getattr(self, name)
+            yield head[0], head[1]
+            yield head[3], None
+
+    @torch.no_grad()
+    def prepare_hip(self):
+        """Fold BatchNorm into every filter forward_hip uses (ops._prepared_conv's cache), on the CURRENT stream; one key comparison
+        per convolution when nothing changed.  A caller that runs forward_hip on several streams calls this first on the stream they
+        all wait for: a cache miss inside forward_hip launches the fold on ITS stream, and another stream that then finds the cached
+        filter would read it with nothing ordering it after that launch."""
+        with torch.cuda.device(self.conv1.weight.device):
+            for conv, bn in self._hip_convs():
+                ops._prepared_conv(conv, bn)
+
 
 class ResNetFPN_8_2(_ResNetFPN):
     """Outputs at 1/8 (coarse) and 1/2 (fine).  resnet_fpn.py:43-118."""
+    _HIP_STAGES = ("layer1", "layer2", "layer3")
+    _HIP_OUTCONVS = ("layer3_outconv", "layer2_outconv", "layer1_outconv")
+    _HIP_HEADS = ("layer2_outconv2", "layer1_outconv2")
 
     def __init__(self, config):
         super().__init__()
@@ -250,6 +278,9 @@ class ResNetFPN_8_2(_ResNetFPN):
 
 class ResNetFPN_16_4(_ResNetFPN):
     """Outputs at 1/16 (coarse) and 1/4 (fine).  resnet_fpn.py:121-199."""
+    _HIP_STAGES = ("layer1", "layer2", "layer3", "layer4")
+    _HIP_OUTCONVS = ("layer4_outconv", "layer3_outconv", "layer2_outconv")
+    _HIP_HEADS = ("layer3_outconv2", "layer2_outconv2")
 
     def __init__(self, config):
         super().__init__()

@@ -428,6 +428,9 @@ class LoFTR(nn.Module):
                 # 14.30 -> 14.00 ms for the 16-image backbone; bit-identical maps), each half's FPN fine branch follows its trunk on the same
                 # stream and is joined before FinePreprocess like the single side stream below.
                 main = torch.cuda.current_stream(x.device)
+                # folded filters made on `main` BEFORE the fork: built inside a half's forward_hip (a fresh model, changed weights) the fold
+                # would run on that half's stream while the other half reads the cached buffer unordered after it
+                self.backbone.prepare_hip()
                 if self._half_streams is None:
                     self._half_streams = [torch.cuda.Stream(device=x.device) for _ in range(2)]
                 outs, fines, evs = [], [], []
@@ -511,6 +514,8 @@ class LoFTR(nn.Module):
         with torch.enable_grad() if grads else contextlib.nullcontext():
             self.coarse_matching(feat_c0, feat_c1, data, mask_c0=mask_c0, mask_c1=mask_c1)
         self._join_fine(feat_f0.device)                      # fine maps come from the side stream(s)
+        if feat_c0.is_cuda:                                  # after the match-count sync: a refused plan / stalled persistent launch raises
+            ops.check_transformer_status(feat_c0.device)
         feat_f0_unfold, feat_f1_unfold = self.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data)
         if feat_f0_unfold.size(0) != 0:
             feat_f0_unfold, feat_f1_unfold = self.loftr_fine(feat_f0_unfold, feat_f1_unfold, inplace=True)

@@ -245,6 +245,47 @@ _COARSE_PLANS = {}
 # profiles/r06_mode_sweep.txt)
 COARSE_MODE = os.environ.get("LOFTR_COARSE_MODE", "auto")
 COARSE_AUTO_MIN_PAIRS = 8
+COARSE_MODES = ("auto", "persistent", "persistent_call_order", "launches")
+
+# The persistent transformer's status word (include/loftr_hip.h, loftr_transformer_fwd_planned: diag) when the caller passes no diag of
+# its own: per (device, stream) a 16-byte device buffer, zeroed before the launch and copied into pinned host memory after it, both on
+# the stream (no host sync).  _STATUS_PENDING holds the copy of the last such call per stream until check_transformer_status reads it.
+_STATUS_BUFS = {}
+_STATUS_PENDING = {}
+
+
+def _status_word(device):
+    """(key, (device buffer, pinned host buffer, event)) of the current stream of `device`."""
+    st = torch.cuda.current_stream(device)
+    key = (str(device), st.cuda_stream)
+    bufs = _STATUS_BUFS.get(key)
+    if bufs is None:
+        bufs = _STATUS_BUFS[key] = (torch.empty(16, dtype=torch.uint8, device=device), torch.zeros(16, dtype=torch.uint8).pin_memory(),
+                                    torch.cuda.Event())
+    return key, bufs
+
+
+def check_transformer_status(device):
+    """Raise LoftrHipError when the last persistent coarse transformer call on the current stream of `device` that had no diag of
+    its caller's reported a failure (2: the plan was built for another shape, nothing was computed; odd v: a workgroup gave up
+    waiting for a dependency at work item (v - 1) / 2).  Meant to follow a host sync the caller makes anyway (the match count): the
+    copy is complete then and waiting on its event costs nothing."""
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    pending = _STATUS_PENDING.pop(key, None)
+    if pending is None:
+        return
+    host, done = pending
+    done.synchronize()
+    v = int(host.view(torch.int32)[0])
+    if v == 0:
+        return
+    if v == 2:
+        why = "its plan was built for another shape or order; nothing was computed"
+    elif v % 2 == 1:
+        why = f"a workgroup gave up waiting for a dependency at work item {(v - 1) // 2}"
+    else:
+        why = f"unknown status {v}"
+    raise _lib.LoftrHipError(f"persistent coarse transformer (loftr_transformer_fwd_planned) failed: {why}")
 
 
 def coarse_plan(kinds, N, L, S, device, order=0):
@@ -272,6 +313,9 @@ def transformer(feat0, feat1, layer_structs, layer_names, nhead, mask0=None, mas
     loftr_transformer_fwd_planned's status word / per-item trace.  ``skip_padded`` (with masks): the caller does not read the
     features of padding tokens -- 128-token tiles without a valid token keep their input values (loftr_transformer_fwd_padded;
     per-call launches whatever ``mode`` says: the persistent form computes every tile)."""
+    mode = mode or COARSE_MODE
+    if mode not in COARSE_MODES:             # (a typo must not select a path: "launches" was the only value tested before)
+        raise ValueError(f"coarse transformer mode {mode!r} (mode= or LOFTR_COARSE_MODE): expected one of {', '.join(COARSE_MODES)}")
     _need(feat0, "feat0"); _need(feat1, "feat1")
     N, L, Cc = feat0.shape
     S = feat1.shape[1]
@@ -293,7 +337,6 @@ def transformer(feat0, feat1, layer_structs, layer_names, nhead, mask0=None, mas
     lib = _lib.load()
     nbytes = lib.loftr_encoder_workspace_bytes(2 * N, L, S, Cc)
     ws = workspace(nbytes, feat0.device)
-    mode = mode or COARSE_MODE
     skip_padded = bool(skip_padded) and m0 is not None
     if skip_padded:
         mode = "launches"
@@ -304,11 +347,19 @@ def transformer(feat0, feat1, layer_structs, layer_names, nhead, mask0=None, mas
         order = 1 if mode == "persistent_call_order" else 0
         plan = coarse_plan(kind_list, N, L, S, feat0.device, order)
     if plan is not None:
+        own = diag is None                   # no diag of the caller's: the status word goes to check_transformer_status
+        if own:
+            key, (diag, host, done) = _status_word(feat0.device)
+            diag.zero_()
         check(lib.loftr_transformer_fwd_planned(_ptr(f0), _ptr(f1), _ptr(m0), _ptr(m1), arr, kinds, n_layers, N, L, S, Cc, nhead,
                                                 _ptr(prepared), prepared.numel() if prepared is not None else 0,
                                                 _ptr(ws), ws.numel(), _ptr(plan), plan.numel(), order,
-                                                _ptr(diag), diag.numel() if diag is not None else 0, _stream()),
+                                                _ptr(diag), diag.numel(), _stream()),
               "loftr_transformer_fwd_planned")
+        if own:
+            host.copy_(diag, non_blocking=True)
+            done.record()
+            _STATUS_PENDING[key] = (host, done)
     elif skip_padded:
         check(lib.loftr_transformer_fwd_padded(_ptr(f0), _ptr(f1), _ptr(m0), _ptr(m1), arr, kinds, n_layers, N, L, S, Cc, nhead,
                                                _ptr(prepared), prepared.numel() if prepared is not None else 0,
