@@ -50,8 +50,9 @@ typedef enum {
  * 22: the persistent coarse transformer (loftr_coarse_plan_bytes / _build / _signature, loftr_transformer_fwd_planned) and the
  *     debug switches (loftr_hip_debug_set / _get) that replace the library's environment variables;
  * 23: loftr_conv_scratch_bytes / loftr_conv_bn_act_prepared_scratch (the 196-channel layers' remainder channels as a tap-decomposed product);
- * 24: loftr_transformer_fwd_padded (padding masks: 128-token tiles without a valid token are not computed) */
-#define LOFTR_HIP_ABI_VERSION 24
+ * 24: loftr_transformer_fwd_padded (padding masks: 128-token tiles without a valid token are not computed);
+ * 25: feature banks (loftr_pos_encode_flatten_gather, loftr_fine_preprocess_gather) */
+#define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
 const char* loftr_hip_status_string(int status);
@@ -243,6 +244,32 @@ int loftr_fine_preprocess_bwd(const loftr_fmap* feat_f0, const loftr_fmap* feat_
                               const float* merge_w, const float* grad_out0, const float* grad_out1, const loftr_fmap* grad_f0,
                               const loftr_fmap* grad_f1, float* grad_c0, float* grad_c1, float* grad_down_w, float* grad_down_b,
                               float* grad_merge_w, float* grad_merge_b, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- feature banks (ABI 25) ----------------------------------------------------------------
+ * A bank is one loftr_fmap whose batch index is a SLOT: the backbone maps of many images, each extracted once, matched in any
+ * pairing (loftr_amd/pairs.py: FeatureBank, LoFTR.match_pairs).  Slot ids are int32 device arrays; slot offsets are computed
+ * in 64 bits, so a bank may hold more than 2^31 elements.  Same per-element arithmetic as the entry points they mirror: a
+ * pair matched through a bank gives the bits of the same pair matched from stacked maps.  A slot id outside [0, n_slots)
+ * reads nothing and yields NaN outputs (callers validate ids on the host; the binding refuses them before any launch).
+ * n == 0 / M == 0 is a no-op success; null pointers otherwise return LOFTR_ERR_BAD_ARG.
+ *
+ * loftr_pos_encode_flatten_gather: out[r] = flatten(bank[slot_ids[r]] + pe) for r < n, out [n, H*W, C] contiguous.
+ *   bank: [n_slots, C, H, W] (any strides; channels-last reads are coalesced), slot_ids [n]. */
+int loftr_pos_encode_flatten_gather(const loftr_fmap* bank, int n_slots, const int32_t* slot_ids, int n,
+                                    const float* pe, int pe_h, int pe_w, float* out, int C, void* stream);
+
+/* loftr_fine_preprocess with the fine maps read from banks: the window of match m comes from bank_f0[slot0[b_ids[m]]] /
+ * bank_f1[slot1[b_ids[m]]] instead of feat_f0[b_ids[m]] / feat_f1[b_ids[m]].  slot0 / slot1 [N] map the batch-local pair b to
+ * the bank slot of each side (the two banks may differ, hence one n_slots per side); feat_c0 / feat_c1 stay per pair.  Every
+ * other argument, and the workspace (loftr_fine_preprocess_workspace_bytes), as for loftr_fine_preprocess. */
+int loftr_fine_preprocess_gather(const loftr_fmap* bank_f0, int n_slots0, const int32_t* slot0,
+                                 const loftr_fmap* bank_f1, int n_slots1, const int32_t* slot1,
+                                 const float* feat_c0, const float* feat_c1, int L, int S, int Cc,
+                                 const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M,
+                                 int w0c, int w1c, int stride, int W, int Cf,
+                                 const float* down_w, const float* down_b, const float* merge_w,
+                                 const float* merge_b, float* out0, float* out1, void* ws,
+                                 size_t ws_bytes, void* stream);
 
 /* ---- FineMatching ---------------------------------------------------------------------------
  * Replaces: FineMatching.forward + get_fine_match (src/loftr/utils/fine_matching.py:15-74).

@@ -2,6 +2,7 @@
 // refinement (FineMatching).
 //   reference: src/loftr/loftr_module/fine_preprocess.py:29-59, src/loftr/utils/fine_matching.py:15-74
 #include "linear.h"
+#include "fine.h"
 
 namespace {
 
@@ -106,18 +107,20 @@ extern "C" size_t loftr_fine_preprocess_workspace_bytes(int M, int W, int Cf) {
   return b + 8192;
 }
 
-extern "C" int loftr_fine_preprocess(const loftr_fmap* feat_f0, const loftr_fmap* feat_f1,
-                                     const float* feat_c0, const float* feat_c1, int L, int S, int Cc,
-                                     const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
-                                     int M, int w0c, int w1c, int stride, int W, int Cf,
-                                     const float* down_w, const float* down_b, const float* merge_w,
-                                     const float* merge_b, float* out0, float* out1, void* ws,
-                                     size_t ws_bytes, void* stream) {
-  LOFTR_CHECK_ARG(M >= 0);
-  if (M == 0) return LOFTR_OK;
-  LOFTR_CHECK_ARG(feat_f0 && feat_f1 && feat_f0->data && feat_f1->data && b_ids && i_ids && j_ids && out0 && out1);
-  LOFTR_CHECK_ARG(w0c > 0 && w1c > 0 && stride > 0 && W > 0 && (W & 1) && Cf > 0 && Cf <= 1024);
-  hipStream_t st = (hipStream_t)stream;
+namespace {
+struct PlainWindows { loftr_fmap f0, f1; const int64_t *b_ids, *i_ids, *j_ids; int M, w0c, w1c, stride, W, Cf; };
+int launch_plain_windows(const void* ctx, sp_t* win0, sp_t* win1, hipStream_t st) {
+  const PlainWindows& a = *(const PlainWindows*)ctx;
+  hipLaunchKernelGGL(gather_windows_kernel, dim3(a.M, 2), dim3(a.Cf < 64 ? 64 : a.Cf), 0, st, a.f0, a.f1, a.b_ids, a.i_ids, a.j_ids,
+                     a.M, a.w0c, a.w1c, a.stride, a.W, a.Cf, win0, win1);
+  return LOFTR_OK;
+}
+}  // namespace
+
+int fine_preprocess_run(const WindowGather& gather, const float* feat_c0, const float* feat_c1, int L, int S, int Cc,
+                        const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M, int W, int Cf,
+                        const float* down_w, const float* down_b, const float* merge_w, const float* merge_b,
+                        float* out0, float* out1, void* ws, size_t ws_bytes, hipStream_t st) {
   const int WW = W * W;
   if (!down_w) {                                   // fine_concat_coarse_feat = False: windows only (fp32 out)
     return LOFTR_ERR_UNSUPPORTED;                  // no shipped config uses it (cvpr_ds_config.py:13, default.py:13)
@@ -146,8 +149,7 @@ extern "C" int loftr_fine_preprocess(const loftr_fmap* feat_f0, const loftr_fmap
     if ((rc = launch_sp_convert(j, st))) return rc;
   }
   { TimedLaunch tl(LOFTR_T_GATHER, st);
-    hipLaunchKernelGGL(gather_windows_kernel, dim3(M, 2), dim3(Cf < 64 ? 64 : Cf), 0, st, *feat_f0, *feat_f1, b_ids,
-                       i_ids, j_ids, M, w0c, w1c, stride, W, Cf, win0, win1); }
+    if ((rc = gather.launch(gather.ctx, win0, win1, st))) return rc; }
   hipLaunchKernelGGL(gather_coarse_kernel, dim3(M, 2), dim3(Cc < 64 ? 64 : (Cc > 1024 ? 1024 : Cc)), 0, st, feat_c0,
                      feat_c1, b_ids, i_ids, j_ids, L, S, Cc, cg0, cg1);
   LOFTR_CHECK_LAUNCH();
@@ -168,6 +170,22 @@ extern "C" int loftr_fine_preprocess(const loftr_fmap* feat_f0, const loftr_fmap
     if ((rc = launch_linear(w, st))) return rc;
   }
   return LOFTR_OK;
+}
+
+extern "C" int loftr_fine_preprocess(const loftr_fmap* feat_f0, const loftr_fmap* feat_f1,
+                                     const float* feat_c0, const float* feat_c1, int L, int S, int Cc,
+                                     const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids,
+                                     int M, int w0c, int w1c, int stride, int W, int Cf,
+                                     const float* down_w, const float* down_b, const float* merge_w,
+                                     const float* merge_b, float* out0, float* out1, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  LOFTR_CHECK_ARG(M >= 0);
+  if (M == 0) return LOFTR_OK;
+  LOFTR_CHECK_ARG(feat_f0 && feat_f1 && feat_f0->data && feat_f1->data && b_ids && i_ids && j_ids && out0 && out1);
+  LOFTR_CHECK_ARG(w0c > 0 && w1c > 0 && stride > 0 && W > 0 && (W & 1) && Cf > 0 && Cf <= 1024);
+  const PlainWindows pw{*feat_f0, *feat_f1, b_ids, i_ids, j_ids, M, w0c, w1c, stride, W, Cf};
+  return fine_preprocess_run(WindowGather{launch_plain_windows, &pw}, feat_c0, feat_c1, L, S, Cc, b_ids, i_ids, j_ids, M, W, Cf,
+                             down_w, down_b, merge_w, merge_b, out0, out1, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int loftr_fine_match(const float* feat_f0, const float* feat_f1, int M, int WW, int C,

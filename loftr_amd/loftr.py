@@ -335,6 +335,22 @@ class FinePreprocess(nn.Module):
         return ops.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
                                    tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride, **kw)
 
+    def forward_gather(self, bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data):
+        """Inference forward with the fine maps of pair b read from bank_f0[slot0[b]] / bank_f1[slot1[b]] (LoFTR.match_pairs)."""
+        W = self.W
+        stride = data["hw0_f"][0] // data["hw0_c"][0]
+        data.update({"W": W})
+        if data["b_ids"].shape[0] == 0:
+            feat0 = torch.empty(0, self.W ** 2, self.d_model_f, device=bank_f0.device)
+            feat1 = torch.empty(0, self.W ** 2, self.d_model_f, device=bank_f0.device)
+            return feat0, feat1
+        kw = {}
+        if self.cat_c_feat:
+            kw = dict(down_w=self.down_proj.weight, down_b=self.down_proj.bias,
+                      merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
+        return ops.fine_preprocess_gather(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
+                                          tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride, **kw)
+
 
 class FineMatching(nn.Module):
     """fine_matching.py:9-74."""
@@ -487,6 +503,11 @@ class LoFTR(nn.Module):
         else:
             feat_c0 = self.pos_encoding(feat_c0)
             feat_c1 = self.pos_encoding(feat_c1)
+        self._match_encoded(feat_c0, feat_c1, data, lambda c0, c1: self.fine_preprocess(feat_f0, feat_f1, c0, c1, data))
+
+    def _match_encoded(self, feat_c0, feat_c1, data, fine_preprocess):
+        """Steps 3-5 of forward from the position-encoded coarse features [N, L, C] (shared by match_from_features and match_pairs):
+        coarse transformer, coarse matching, fine stage.  fine_preprocess(feat_c0, feat_c1) -> the two window tensors."""
         mask_c0 = mask_c1 = None
         if "mask0" in data:
             mask_c0, mask_c1 = data["mask0"].flatten(-2), data["mask1"].flatten(-2)
@@ -505,7 +526,7 @@ class LoFTR(nn.Module):
         # launches leave partly filled rounds that the convolution workgroups use, the score-volume kernels do not -- sharing the
         # GPU only doubled their duration (660 vs 340 us for pass B, profiles/r03_overlap_ab.txt) without shortening the step.
         if not self.fine_join_late:
-            self._join_fine(feat_f0.device)
+            self._join_fine(feat_c0.device)
         full = self.training and self.full_grads
         grads = self.training and self.head_grads and not full
         if grads:
@@ -513,10 +534,10 @@ class LoFTR(nn.Module):
             data["_head_inputs"] = {"feat_c0": feat_c0, "feat_c1": feat_c1}
         with torch.enable_grad() if grads else contextlib.nullcontext():
             self.coarse_matching(feat_c0, feat_c1, data, mask_c0=mask_c0, mask_c1=mask_c1)
-        self._join_fine(feat_f0.device)                      # fine maps come from the side stream(s)
+        self._join_fine(feat_c0.device)                      # fine maps come from the side stream(s)
         if feat_c0.is_cuda:                                  # after the match-count sync: a refused plan / stalled persistent launch raises
             ops.check_transformer_status(feat_c0.device)
-        feat_f0_unfold, feat_f1_unfold = self.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data)
+        feat_f0_unfold, feat_f1_unfold = fine_preprocess(feat_c0, feat_c1)
         if feat_f0_unfold.size(0) != 0:
             feat_f0_unfold, feat_f1_unfold = self.loftr_fine(feat_f0_unfold, feat_f1_unfold, inplace=True)
         if grads:
@@ -547,6 +568,15 @@ class LoFTR(nn.Module):
         with torch.cuda.device(dev):                 # streams / workspaces / launches all on the tensors' GPU
             feat_c0, feat_c1, feat_f0, feat_f1 = self.run_backbone(data)
             self.match_from_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
+
+    def match_pairs(self, bank0, ids0, bank1=None, ids1=None):
+        """Match n pairs of images whose backbone maps are in feature banks (loftr_amd/pairs.py: FeatureBank): pair k is
+        (bank0[ids0[k]], bank1[ids1[k]]); bank1 defaults to bank0.  Returns the dict forward leaves for image0 = the images of
+        ids0 and image1 = the images of ids1, without the images themselves: the same keys, dtypes and order (mask0 / mask1 and
+        scale0 / scale1 gathered from the banks when their slots have them), bit for bit with backbone_impl 'hip'.  Inference
+        only; runs without a graph."""
+        from .pairs import match_pairs
+        return match_pairs(self, bank0, ids0, bank1, ids1)
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         for k in list(state_dict.keys()):

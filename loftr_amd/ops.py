@@ -457,6 +457,80 @@ def fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0
     return out0, out1
 
 
+def _slot_ids(ids, n_slots, name, device):
+    """Slot ids -> int32 tensor on `device`, checked on the host against [0, n_slots) before any launch (the kernels would
+    write NaN for an id outside it)."""
+    host = ids.detach().cpu() if isinstance(ids, torch.Tensor) else torch.as_tensor(ids)
+    if host.dim() != 1 or host.dtype.is_floating_point or host.dtype == torch.bool:
+        raise _lib.LoftrHipError(f"{name}: expected a 1-D integer tensor of slot ids, got {tuple(host.shape)} {host.dtype}")
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n_slots):
+        raise _lib.LoftrHipError(f"{name}: slot id out of range [0, {n_slots}) (min {int(host.min())}, max {int(host.max())})")
+    if isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous() and ids.device == device:
+        return ids
+    return host.to(torch.int32).to(device)
+
+
+def _bank_map(bank, name):
+    """A bank [n_slots, C, H, W] (any strides, e.g. the channels-last view of FeatureBank's [n_slots, H, W, C] storage)."""
+    if not isinstance(bank, torch.Tensor) or not bank.is_cuda or bank.dtype != torch.float32 or bank.dim() != 4:
+        raise _lib.LoftrHipError(f"{name}: expected a 4-D float32 GPU tensor [n_slots, C, H, W]")
+    if bank.shape[0] == 0:
+        raise _lib.LoftrHipError(f"{name}: empty bank")
+    return bank
+
+
+@_on_device
+def pos_encode_flatten_gather(bank, slot_ids, pe, out=None):
+    """pos_encode_flatten(bank[slot_ids]) without gathering the maps: bank [n_slots,C,H,W] (any strides), slot_ids [n] ->
+    [n, H*W, C].  ``out``: a contiguous [n, H*W, C] float32 tensor to write into (e.g. one half of the coarse transformer's
+    [2n, L, C] buffer)."""
+    _bank_map(bank, "bank")
+    _need(pe, "pe")
+    n_slots, Cc, H, W = bank.shape
+    ids = _slot_ids(slot_ids, n_slots, "slot_ids", bank.device)
+    n = ids.shape[0]
+    if out is None:
+        out = torch.empty(n, H * W, Cc, device=bank.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, H * W, Cc):
+        raise _lib.LoftrHipError(f"out: expected shape {(n, H * W, Cc)}, got {tuple(out.shape)}")
+    _need(out, "out")
+    fm = _fmap(bank)
+    check(_lib.load().loftr_pos_encode_flatten_gather(C.byref(fm), n_slots, _ptr(ids), n, _ptr(pe), pe.shape[-2], pe.shape[-1],
+                                                      _ptr(out), Cc, _stream()), "loftr_pos_encode_flatten_gather")
+    return out
+
+
+@_on_device
+def fine_preprocess_gather(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride,
+                           down_w=None, down_b=None, merge_w=None, merge_b=None):
+    """fine_preprocess with the fine maps of pair b read from bank_f0[slot0[b]] / bank_f1[slot1[b]] (banks [n_slots,Cf,h,w],
+    any strides; slot0 / slot1 [N] for the N pairs of feat_c0 / feat_c1).  Returns (feat_f0_unfold, feat_f1_unfold) [M, W*W, Cf]."""
+    _bank_map(bank_f0, "bank_f0"); _bank_map(bank_f1, "bank_f1")
+    _need(feat_c0, "feat_c0"); _need(feat_c1, "feat_c1")
+    N = feat_c0.shape[0]
+    s0 = _slot_ids(slot0, bank_f0.shape[0], "slot0", bank_f0.device)
+    s1 = _slot_ids(slot1, bank_f1.shape[0], "slot1", bank_f1.device)
+    if s0.shape[0] != N or s1.shape[0] != N:
+        raise _lib.LoftrHipError(f"slot0 / slot1: expected {N} slot ids (one per pair), got {s0.shape[0]} / {s1.shape[0]}")
+    M = b_ids.shape[0]
+    Cf = bank_f0.shape[1]
+    dev = bank_f0.device
+    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)     # one buffer, as fine_preprocess
+    out0, out1 = out[:M], out[M:]
+    if M == 0:
+        return out0, out1
+    lib = _lib.load()
+    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
+    f0, f1 = _fmap(bank_f0), _fmap(bank_f1)
+    check(lib.loftr_fine_preprocess_gather(C.byref(f0), bank_f0.shape[0], _ptr(s0), C.byref(f1), bank_f1.shape[0], _ptr(s1),
+                                           _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[2],
+                                           _ptr(_need(b_ids, "b_ids", torch.int64)), _ptr(_need(i_ids, "i_ids", torch.int64)),
+                                           _ptr(_need(j_ids, "j_ids", torch.int64)), M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf,
+                                           _ptr(down_w), _ptr(down_b), _ptr(merge_w), _ptr(merge_b), _ptr(out0), _ptr(out1),
+                                           _ptr(ws), ws.numel(), _stream()), "loftr_fine_preprocess_gather")
+    return out0, out1
+
+
 @_on_device
 def fine_preprocess_bwd(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride, down_w, down_b, merge_w,
                         grad_out0, grad_out1):
