@@ -51,7 +51,9 @@ typedef enum {
  *     debug switches (loftr_hip_debug_set / _get) that replace the library's environment variables;
  * 23: loftr_conv_scratch_bytes / loftr_conv_bn_act_prepared_scratch (the 196-channel layers' remainder channels as a tap-decomposed product);
  * 24: loftr_transformer_fwd_padded (padding masks: 128-token tiles without a valid token are not computed);
- * 25: feature banks (loftr_pos_encode_flatten_gather, loftr_fine_preprocess_gather) */
+ * 25: feature banks (loftr_pos_encode_flatten_gather, loftr_fine_preprocess_gather); later, without a bump (purely additive: a
+ *     binding that needs them refuses a library without them when it loads): batched pose estimation on the GPU
+ *     (loftr_estimate_pose_batched, loftr_estimate_pose_batched_workspace_bytes) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -464,6 +466,28 @@ int loftr_sinkhorn_bwd(const float* feat_c0, const float* feat_c1, const loftr_c
 int loftr_estimate_pose(const float* kpts0, const float* kpts1, long M, const float* K0, const float* K1, float thresh_px,
                         float conf, unsigned seed, float* R_out, float* t_out, uint8_t* inliers_out, long* n_inliers);
 int loftr_five_point(const double* q0, const double* q1, int n, double* E_out, int* n_solutions);
+
+/* loftr_estimate_pose for every pair of a batch, on the GPU (csrc/pose_gpu.hip).  CONTRACT: for every pair p the result is
+ * the one loftr_estimate_pose returns for that pair's matches with the same seed -- same n_inliers, same inlier mask, R and t
+ * equal after the float32 rounding.  Parity against OpenCV stays UNPINNED, as for the host estimator.
+ *   mkpts0_f / mkpts1_f [M,2] f32 pixels, m_bids [M] i64: device memory, grouped by ascending pair id as the matcher emits
+ *   them (pair p = the matches with m_bids == p, in match order); K0 / K1 [P,3,3] f32 row-major, device memory;
+ *   thresh_px, conf: as loftr_estimate_pose; seed: one seed shared by every pair (compute_pose_errors uses 0).
+ * Outputs (device memory): R_out [P,9], t_out [P,3] f32; inliers_out [M] u8 in match order (RANSAC inliers in front of both
+ * cameras); n_inliers [P] i64 = their number, or -1 where loftr_estimate_pose returns -1 (fewer than 5 matches, no model, no
+ * point passes the cheirality test) -- there R, t and the pair's mask are 0.
+ * Stream-ordered on `stream`; the keypoints never leave the device.  The call copies the per-hypothesis inlier counts to the
+ * host once, replays the RANSAC loop there (the host estimator's own pow / log) and waits for the stream before it returns:
+ * two host round trips per batch, whatever P.  Workspace: loftr_estimate_pose_batched_workspace_bytes(M, P), about 830 kB
+ * per pair plus 33 bytes per match.
+ * Status: LOFTR_ERR_BAD_ARG for a null pointer, M < 0 or P < 0, P == 0 with M > 0, and for m_bids outside [0, P) or not
+ * grouped by ascending pair (found on the device, reported at the call's own synchronisation; the outputs are then not
+ * written); LOFTR_ERR_WORKSPACE for a short workspace; LOFTR_ERR_UNSUPPORTED for M >= 2^31 or P >= 2^31 / 1000.
+ * M == 0 is valid (every pair gets -1); P == 0 and M == 0 is a no-op success. */
+size_t loftr_estimate_pose_batched_workspace_bytes(long M, int P);
+int loftr_estimate_pose_batched(const float* mkpts0_f, const float* mkpts1_f, const long* m_bids, long M, const float* K0,
+                                const float* K1, int P, float thresh_px, float conf, unsigned seed, float* R_out, float* t_out,
+                                uint8_t* inliers_out, long* n_inliers, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

@@ -109,6 +109,8 @@ SIGNATURES = {
     "loftr_fine_match_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "loftr_estimate_pose": (_i, [_p, _p, _l, _p, _p, _f, _f, C.c_uint, _p, _p, _p, C.POINTER(_l)]),
     "loftr_five_point": (_i, [_p, _p, _i, _p, C.POINTER(_i)]),
+    "loftr_estimate_pose_batched_workspace_bytes": (_sz, [_l, _i]),
+    "loftr_estimate_pose_batched": (_i, [_p, _p, _p, _l, _p, _p, _i, _f, _f, C.c_uint, _p, _p, _p, _p, _p, _sz, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
@@ -150,7 +152,10 @@ def load():
             "(needs hipcc). There is no CPU / PyTorch fallback for the matching path.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
+        fn = getattr(lib, name, None)
+        if fn is None:                   # a library older than this binding (entry points added without an ABI bump)
+            raise LoftrHipError(f"{LIB_PATH} does not export {name}: it predates this binding; rebuild "
+                                "(`python -m loftr_amd.build --force`)")
         fn.restype = res
         fn.argtypes = args
     if lib.loftr_hip_abi_version() != ABI_VERSION:

@@ -14,7 +14,8 @@ for ``from loftr_amd.evaluation import ...``.
   the reference's;
 * pose estimation (metrics.py:71-140) is OpenCV in the reference (`cv2.findEssentialMat` RANSAC + `cv2.recoverPose`):
   used when cv2 is importable; otherwise `estimate_pose_native` -- the library's own five-point RANSAC + cheirality
-  (csrc/pose.hip: Nister's solver, Sampson distance, OpenCV's documented parameters; host code like cv2's).  PARITY
+  (csrc/pose.hip: Nister's solver, Sampson distance, OpenCV's documented parameters; host code like cv2's), or
+  `estimate_pose_native_gpu` -- the same estimator with the same results, the whole batch in one GPU call.  PARITY
   UNPINNED against OpenCV (absent from this image; its sampling sequence cannot be reproduced): tests/test_pose.py
   checks the solver on exact data and the recovered pose on synthetic scenes with known ground truth.
 """
@@ -108,6 +109,35 @@ def estimate_pose_native(kpts0, kpts1, K0, K1, thresh, conf=0.99999, seed=0):
     return R.astype(np.float64), t.astype(np.float64), inl.astype(bool)
 
 
+def estimate_pose_native_gpu(kpts0, kpts1, K0, K1, thresh, conf=0.99999, seed=0):
+    """estimate_pose_native on the GPU (ops.estimate_poses, csrc/pose_gpu.hip): the same result for the same seed -- same
+    inlier mask, R and t equal after the float32 rounding.  Called on one pair it takes host arrays like estimate_pose_native;
+    passed as compute_pose_errors' estimator it is the explicit form of on_missing='native_gpu' and runs the whole batch in
+    one call."""
+    k0 = np.ascontiguousarray(kpts0, np.float32).reshape(-1, 2)
+    if k0.shape[0] < 5:
+        return None
+    k0 = torch.as_tensor(k0).cuda()
+    k1 = torch.as_tensor(np.ascontiguousarray(kpts1, np.float32).reshape(-1, 2)).cuda()
+    K = [torch.as_tensor(np.ascontiguousarray(k, np.float32)).reshape(1, 3, 3).cuda() for k in (K0, K1)]
+    R, t, inl, n = ops.estimate_poses(k0, k1, torch.zeros(k0.shape[0], dtype=torch.int64, device=k0.device), K[0], K[1], thresh, conf,
+                                      seed)
+    if int(n[0]) < 0:
+        return None
+    return R[0].cpu().numpy().astype(np.float64), t[0].cpu().numpy().astype(np.float64), inl.cpu().numpy()
+
+
+def _poses_native_gpu(data, pixel_thr, conf):
+    """The batch path of estimate_pose_native_gpu: one ops.estimate_poses call for every pair of `data` -> per pair
+    (R, t, inlier mask) or None, as the per-pair estimators return them."""
+    dev = data["mkpts0_f"].device if data["mkpts0_f"].is_cuda else torch.device("cuda")
+    f32 = lambda k: data[k].to(device=dev, dtype=torch.float32)
+    m_bids = data["m_bids"].to(device=dev, dtype=torch.int64)
+    R, t, inl, n = ops.estimate_poses(f32("mkpts0_f"), f32("mkpts1_f"), m_bids, f32("K0"), f32("K1"), pixel_thr, conf)
+    R, t, inl, n, bids = R.cpu().numpy(), t.cpu().numpy(), inl.cpu().numpy(), n.cpu().numpy(), m_bids.cpu().numpy()
+    return [None if n[b] < 0 else (R[b].astype(np.float64), t[b].astype(np.float64), inl[bids == b]) for b in range(len(n))]
+
+
 _WARNED_NATIVE = []
 
 
@@ -121,11 +151,13 @@ def compute_pose_errors(data, config=None, estimator=None, on_missing="raise"):
       'inf'    record R_err = t_err = inf for every pair (the reference's value for a failed estimate);
       'native' the library's five-point RANSAC (csrc/pose.hip).  PARITY UNPINNED against cv2.findEssentialMat /
                recoverPose (own sampling sequence): a one-time warning says so; passing estimator=estimate_pose_native is
-               the explicit form of the same opt-in."""
+               the explicit form of the same opt-in;
+      'native_gpu' the same estimator on the GPU for the whole batch in one call (csrc/pose_gpu.hip): the same R_errs,
+               t_errs and inliers as 'native', the same warning; estimator=estimate_pose_native_gpu is its explicit form."""
     pixel_thr = _cfg_get(config, ("TRAINER", "RANSAC_PIXEL_THR"), 0.5)
     conf = _cfg_get(config, ("TRAINER", "RANSAC_CONF"), 0.99999)
-    if on_missing not in ("raise", "inf", "native"):
-        raise ValueError(f"on_missing={on_missing!r}: expected 'raise', 'inf' or 'native'")
+    if on_missing not in ("raise", "inf", "native", "native_gpu"):
+        raise ValueError(f"on_missing={on_missing!r}: expected 'raise', 'inf', 'native' or 'native_gpu'")
     name = getattr(estimator, "__name__", "custom") if estimator is not None else None
     if estimator is None:
         try:
@@ -135,8 +167,9 @@ def compute_pose_errors(data, config=None, estimator=None, on_missing="raise"):
             if on_missing == "raise":
                 raise ImportError("compute_pose_errors needs OpenCV (cv2.findEssentialMat / recoverPose, metrics.py:72-98); pass "
                                   "on_missing='native' (library five-point RANSAC, parity unpinned) or 'inf', or an estimator")
-            if on_missing == "native":
-                estimator, name = estimate_pose_native, "estimate_pose_native"
+            if on_missing in ("native", "native_gpu"):
+                estimator = estimate_pose_native if on_missing == "native" else estimate_pose_native_gpu
+                name = estimator.__name__
                 if not _WARNED_NATIVE:
                     _WARNED_NATIVE.append(True)
                     import warnings
@@ -146,12 +179,16 @@ def compute_pose_errors(data, config=None, estimator=None, on_missing="raise"):
                 name = "none (inf)"
     data["pose_estimator"] = name
     data.update({"R_errs": [], "t_errs": [], "inliers": []})
+    batched = _poses_native_gpu(data, pixel_thr, conf) if estimator is estimate_pose_native_gpu else None
     m_bids = data["m_bids"].cpu().numpy()
     pts0, pts1 = data["mkpts0_f"].cpu().numpy(), data["mkpts1_f"].cpu().numpy()
     K0, K1, T = data["K0"].cpu().numpy(), data["K1"].cpu().numpy(), data["T_0to1"].cpu().numpy()
     for bs in range(K0.shape[0]):
         mask = m_bids == bs
-        ret = None if estimator is None else estimator(pts0[mask], pts1[mask], K0[bs], K1[bs], pixel_thr, conf=conf)
+        if batched is not None:
+            ret = batched[bs]
+        else:
+            ret = None if estimator is None else estimator(pts0[mask], pts1[mask], K0[bs], K1[bs], pixel_thr, conf=conf)
         if ret is None:
             data["R_errs"].append(np.inf)
             data["t_errs"].append(np.inf)

@@ -835,6 +835,37 @@ def epipolar_errors(mkpts0_f, mkpts1_f, m_bids, T_0to1, K0, K1):
     return out
 
 
+@_on_device
+def estimate_poses(mkpts0_f, mkpts1_f, m_bids, K0, K1, thresh_px, conf, seed=0):
+    """Five-point RANSAC + cheirality for every pair of a batch on the GPU (csrc/pose_gpu.hip): for each pair, what the host
+    estimator loftr_estimate_pose (evaluation.estimate_pose_native) returns for that pair's matches with the same seed.
+    mkpts0_f / mkpts1_f [M,2] f32, m_bids [M] i64 grouped by ascending pair id (as the matcher emits them), K0 / K1 [P,3,3] f32.
+    -> (R [P,3,3] f32, t [P,3] f32, inliers [M] bool in match order, n_inliers [P] i64), device tensors; n_inliers[p] == -1
+    where the host estimator returns None (R, t and that pair's mask are zero there).  Synchronises the stream once."""
+    for name, t, dt in (("mkpts0_f", mkpts0_f, torch.float32), ("mkpts1_f", mkpts1_f, torch.float32), ("m_bids", m_bids, torch.int64),
+                        ("K0", K0, torch.float32), ("K1", K1, torch.float32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise _lib.LoftrHipError(f"{name}: expected a {dt} GPU tensor (the pose kernels have no CPU fallback)")
+    M, P = mkpts0_f.shape[0], K0.shape[0]
+    if mkpts0_f.shape != (M, 2) or mkpts1_f.shape != (M, 2) or m_bids.shape != (M,):
+        raise _lib.LoftrHipError(f"estimate_poses: expected mkpts0_f / mkpts1_f [M,2] and m_bids [M], got {tuple(mkpts0_f.shape)}, "
+                                 f"{tuple(mkpts1_f.shape)}, {tuple(m_bids.shape)}")
+    if K0.shape != (P, 3, 3) or K1.shape != (P, 3, 3):
+        raise _lib.LoftrHipError(f"estimate_poses: expected K0 / K1 [P,3,3], got {tuple(K0.shape)}, {tuple(K1.shape)}")
+    dev = mkpts0_f.device
+    args = [t.contiguous() for t in (mkpts0_f, mkpts1_f, m_bids, K0, K1)]
+    R = torch.zeros(P, 3, 3, dtype=torch.float32, device=dev)
+    t = torch.zeros(P, 3, dtype=torch.float32, device=dev)
+    inl = torch.zeros(M, dtype=torch.uint8, device=dev)
+    n = torch.full((P,), -1, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_estimate_pose_batched_workspace_bytes(M, P)), dtype=torch.uint8, device=dev)
+    check(lib.loftr_estimate_pose_batched(*[_ptr(a) for a in args[:3]], M, _ptr(args[3]), _ptr(args[4]), P, float(thresh_px), float(conf),
+                                          int(seed), _ptr(R), _ptr(t), _ptr(inl), _ptr(n), _ptr(ws), ws.numel(), _stream()),
+          "loftr_estimate_pose_batched (m_bids must lie in [0, P) and be grouped by ascending pair)")
+    return R, t, inl.view(torch.bool), n
+
+
 # ---- training-mode glue of the backbone (csrc/train_glue.hip; resnet_fpn.py:22-40,66-77,110-116) ------------------------------------------
 def _dense4(t, name):
     """A 4-D fp32 GPU tensor [N,C,H,W] stored densely either NCHW or NHWC (channels_last: what the convolution nodes produce); returns
