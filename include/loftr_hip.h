@@ -53,7 +53,8 @@ typedef enum {
  * 24: loftr_transformer_fwd_padded (padding masks: 128-token tiles without a valid token are not computed);
  * 25: feature banks (loftr_pos_encode_flatten_gather, loftr_fine_preprocess_gather); later, without a bump (purely additive: a
  *     binding that needs them refuses a library without them when it loads): batched pose estimation on the GPU
- *     (loftr_estimate_pose_batched, loftr_estimate_pose_batched_workspace_bytes) */
+ *     (loftr_estimate_pose_batched, loftr_estimate_pose_batched_workspace_bytes) and the fine head at matched windows only
+ *     (loftr_window_head, loftr_fine_preprocess_window_head) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -272,6 +273,32 @@ int loftr_fine_preprocess_gather(const loftr_fmap* bank_f0, int n_slots0, const 
                                  const float* down_w, const float* down_b, const float* merge_w,
                                  const float* merge_b, float* out0, float* out1, void* ws,
                                  size_t ws_bytes, void* stream);
+
+/* ---- the fine head at matched windows only (ABI 25, additive) ------------------------------------------
+ * The fine map has one consumer in the inference forward: the W x W windows of FinePreprocess.  These entry points evaluate the
+ * LAST convolution of the FPN fine head (3x3, stride 1, pad 1, no BatchNorm, no activation) only at the window pixels and write
+ * the windows directly -- no fine map.  Bit for bit the windows loftr_fine_preprocess gathers from the dense convolution's output
+ * (same MFMA, same k order, same epilogue expression).
+ *   h_sp0 / h_sp1: output of the head's FIRST convolution (+ BN + LeakyReLU) for the image0 / image1 batch, SP [N, H, Wm, ceil32(Cin)]
+ *                  (both batches of one size; they may be the two halves of one tensor);
+ *   prepared:      the second convolution's filter from loftr_conv_prepare (Cin, Cout, 3, 3, no BatchNorm).
+ * Supported: W = 5, ceil32(Cout) = 128; anything else returns LOFTR_ERR_UNSUPPORTED (callers take the dense head).
+ *
+ * loftr_window_head: the windows alone, win0_sp / win1_sp SP [M, W*W, 128] (the GEMM operand format of the library).
+ * loftr_fine_preprocess_window_head: loftr_fine_preprocess with the windows computed this way; every other argument, and the
+ *   workspace (loftr_fine_preprocess_workspace_bytes), as there.  Cf = Cout. */
+int loftr_window_head(const uint32_t* h_sp0, const uint32_t* h_sp1, int N, int H, int Wm, int Cin,
+                      const void* prepared, size_t prepared_bytes, int Cout, const int64_t* b_ids,
+                      const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int W,
+                      uint32_t* win0_sp, uint32_t* win1_sp, void* stream);
+int loftr_fine_preprocess_window_head(const uint32_t* h_sp0, const uint32_t* h_sp1, int N, int H, int Wm, int Cin,
+                                      const void* prepared, size_t prepared_bytes,
+                                      const float* feat_c0, const float* feat_c1, int L, int S, int Cc,
+                                      const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M,
+                                      int w0c, int w1c, int stride, int W, int Cf,
+                                      const float* down_w, const float* down_b, const float* merge_w,
+                                      const float* merge_b, float* out0, float* out1, void* ws, size_t ws_bytes,
+                                      void* stream);
 
 /* ---- FineMatching ---------------------------------------------------------------------------
  * Replaces: FineMatching.forward + get_fine_match (src/loftr/utils/fine_matching.py:15-74).

@@ -247,14 +247,27 @@ class ResNetFPN_8_2(_ResNetFPN):
         x1_out = self.layer1_outconv2(self.layer1_outconv(x1) + self._up(x2_out))
         return [x3_out, x1_out]
 
+    # The fine head whose last convolution ops.fine_preprocess_windows can evaluate at the matched windows only
+    WINDOW_HEAD = "layer1_outconv2"
+
+    def fine_head_last(self, h_sp):
+        """The dense fine map [B, C, H, W] from ``fine_fn()``'s ``head_input=True`` result (the head's last convolution)."""
+        head = self.layer1_outconv2
+        _, x1_f32 = ops.conv_bn_act(h_sp, head[0].out_channels, head[3], None, act=0, want_sp=False, want_f32=True)
+        return self._nchw_view(x1_f32)
+
     @torch.no_grad()
-    def forward_hip(self, x, defer_fine=False):
+    def forward_hip(self, x, defer_fine=False, head_input=False):
         """Same function as ``forward`` (resnet_fpn.py:100-118) on the HIP implicit-GEMM convolutions.
 
         defer_fine=True returns ``[coarse, fine_fn]``: ``fine_fn()`` runs the FPN top-down branch (everything
         after ``layer3_outconv``) and returns the fine map.  The coarse map does not depend on it, so the caller
         can enqueue it on a second HIP stream next to the coarse matching stage (``fine_fn.reads`` lists the
-        tensors it consumes, for ``Tensor.record_stream``)."""
+        tensors it consumes, for ``Tensor.record_stream``).
+        head_input=True (with defer_fine): ``fine_fn()`` stops before the LAST convolution of the fine head and returns
+        its input, SP int32 [B, H/2, W/2, ceil32(d2)] -- the caller evaluates that convolution at the matched windows only
+        (ops.fine_preprocess_windows) or densely (``fine_head_last``)."""
+        assert defer_fine or not head_input
         a0 = self._stem_hip(x)
         a1 = self._stage_hip(self.layer1, a0)       # 1/2
         a2 = self._stage_hip(self.layer2, a1)       # 1/4
@@ -267,6 +280,9 @@ class ResNetFPN_8_2(_ResNetFPN):
             x2_out, _ = self._head_hip(self.layer2_outconv2, (t2, d3), want_f32=False, shared_gpu=defer_fine)
             d2 = self.layer2_outconv2[3].out_channels
             t1 = self._topdown_hip(a1, self.layer1_outconv, x2_out, d2)
+            if head_input:
+                head = self.layer1_outconv2
+                return ops.conv_bn_act(t1, d2, head[0], head[1], act=2, shared_gpu=defer_fine)[0]
             _, x1_f32 = self._head_hip(self.layer1_outconv2, (t1, d2), want_f32=True, shared_gpu=defer_fine)
             return self._nchw_view(x1_f32)
 

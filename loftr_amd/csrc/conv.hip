@@ -9,6 +9,7 @@
 // bias while they are re-laid out [Cout, Cin, KH, KW] fp32 -> [Cout, KH*KW*Cp] SP; the epilogue adds
 // the bias and the residual branch and applies ReLU / LeakyReLU.
 #include "gemm.h"
+#include "conv_prepared.h"
 #include <stdlib.h>
 
 namespace {
@@ -744,17 +745,7 @@ __global__ __launch_bounds__(256) void conv_rem_gather_kernel(const float* __res
   dst[0] = oh; dst[1] = z; dst[2] = z; dst[3] = z; dst[4] = ol; dst[5] = z; dst[6] = z; dst[7] = z;
 }
 
-// Folded weights live in a caller-owned buffer laid out [SP weights Cout x K][bias Cout][inverse row scales Cout][zero page 256 B]
-// (loftr_conv_workspace_bytes): conv_prepare fills it, conv_run consumes it.
-struct ConvPrepared { sp_t* wsp; float* bias; float* wscale; sp_t* zeros; };
-static bool conv_prepared_layout(void* buf, size_t bytes, int Cin, int Cout, int KH, int KW, ConvPrepared& o) {
-  WsAlloc wa(buf, bytes);
-  o.wsp = wa.take<sp_t>((size_t)Cout * KH * KW * ceil32(Cin));
-  o.bias = wa.take<float>(Cout);
-  o.wscale = wa.take<float>(Cout);
-  o.zeros = wa.take<sp_t>(64);
-  return wa.ok();
-}
+// (ConvPrepared / conv_prepared_layout: conv_prepared.h)
 
 static int conv_prepare(const float* weight, const long* weight_strides, int Cin, int Cout, int KH, int KW,
                         const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps,

@@ -305,6 +305,7 @@ class FinePreprocess(nn.Module):
         d_model_c = self.config["coarse"]["d_model"]
         d_model_f = self.config["fine"]["d_model"]
         self.d_model_f = d_model_f
+        self.last_head = None                    # forward_windows: the form its last call took ("windows" / "dense")
         if self.cat_c_feat:
             self.down_proj = nn.Linear(d_model_c, d_model_f, bias=True)
             self.merge_feat = nn.Linear(2 * d_model_f, d_model_f, bias=True)
@@ -334,6 +335,28 @@ class FinePreprocess(nn.Module):
                                             (tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride), **kw)
         return ops.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
                                    tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride, **kw)
+
+    def forward_windows(self, h_sp0, h_sp1, cin, conv, dense_fn, fine_head, feat_c0, feat_c1, data):
+        """Inference forward from the INPUTS of the fine head's last convolution `conv` (SP [N, H, W, ceil32(cin)] per image batch): the
+        convolution is evaluated at the matched windows only (csrc/window_head.hip), or -- fine_head None and too many windows for that
+        to be the cheaper form (ops.window_head_wins) -- densely by `dense_fn(h_sp)` and gathered as in forward.  Bit-identical either
+        way (tests/test_hip_window_head.py runs both).  fine_head: None or "windows" (LoFTR.forward does not come here with "dense")."""
+        M = data["b_ids"].shape[0]
+        dense_pixels = 2 * h_sp0.shape[0] * h_sp0.shape[1] * h_sp0.shape[2]
+        windows = fine_head == "windows" or ops.window_head_wins(M, dense_pixels)
+        if M == 0 or not windows or not ops.window_head_supported(self.W, cin, conv.out_channels, h_sp0, h_sp1):
+            self.last_head = "dense"
+            if M == 0:                                      # (forward reads nothing but the device of its maps then)
+                return self.forward(h_sp0, h_sp1, feat_c0, feat_c1, data)
+            return self.forward(dense_fn(h_sp0), dense_fn(h_sp1), feat_c0, feat_c1, data)
+        self.last_head = "windows"
+        W = self.W
+        stride = data["hw0_f"][0] // data["hw0_c"][0]
+        data.update({"W": W})
+        return ops.fine_preprocess_windows(h_sp0, h_sp1, cin, conv, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
+                                           tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride,
+                                           down_w=self.down_proj.weight, down_b=self.down_proj.bias,
+                                           merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
 
     def forward_gather(self, bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data):
         """Inference forward with the fine maps of pair b read from bank_f0[slot0[b]] / bank_f1[slot1[b]] (LoFTR.match_pairs)."""
@@ -404,6 +427,12 @@ class LoFTR(nn.Module):
         # more than the filled tails give); True / False: always / never
         self.backbone_halves = None
         self._half_streams = None
+        # The last convolution of the fine head has one consumer in the inference forward, the 5 x 5 windows of FinePreprocess.  None:
+        # forward evaluates it at the matched windows only (csrc/window_head.hip) while that is the cheaper form (ops.window_head_wins)
+        # and densely otherwise; "windows" / "dense": always that form where the window form applies at all (eval mode, HIP backbone,
+        # ResNetFPN_8_2, equally sized images, one backbone batch).  Bit-identical results.  run_backbone / match_from_features / match_pairs
+        # keep the dense maps.
+        self.fine_head = None
         # .train() only: hand the two matching heads their inputs as autograd LEAVES (data['_head_inputs']) and run the heads
         # with a graph, so that LoFTRLoss(...)(data); data['loss'].backward() leaves d loss / d (transformer outputs) in
         # their .grad -- the part of the reference's backward pass this library provides (loftr_amd/autograd.py).
@@ -422,19 +451,34 @@ class LoFTR(nn.Module):
         self.loftr_fine = LocalFeatureTransformer(config["fine"])
         self.fine_matching = FineMatching()
 
-    def run_backbone(self, data):
-        """Step 1 of forward (loftr.py:39-54): returns (feat_c0, feat_c1, feat_f0, feat_f1)."""
+    def _window_head_applies(self, data):
+        """forward may hand FinePreprocess the inputs of the fine head's last convolution instead of the fine maps."""
+        img0, img1 = data["image0"], data["image1"]
+        if (self.fine_head == "dense" or self.training or self.backbone_impl != "hip" or not img0.is_cuda
+                or img0.shape[2:] != img1.shape[2:] or not hasattr(self.backbone, "WINDOW_HEAD") or not self.fine_preprocess.cat_c_feat):
+            return False
+        return img0.shape[0] + img1.shape[0] <= self._backbone_cap(img0)           # (chunked batches: dense)
+
+    def _backbone_cap(self, x):
+        """Images of x's size one backbone call takes: the convolution kernels index an activation tensor with 32 bits (conv.hip: images *
+        pixels * channels < 2^31 at the widest 1/2-resolution map); larger batches go through in chunks (> 62 pairs at 640 x 480)."""
+        return getattr(self, "_backbone_chunk_images", None) or max(1, (2 ** 31 - 1) // ((x.shape[2] // 2) * (x.shape[3] // 2) * 256))
+
+    def run_backbone(self, data, head_input=False):
+        """Step 1 of forward (loftr.py:39-54): returns (feat_c0, feat_c1, feat_f0, feat_f1).
+        head_input=True (forward only, where _window_head_applies): the last two are the SP inputs of the fine head's last convolution
+        (backbone.forward_hip) instead of the fine maps."""
         data.update({"bs": data["image0"].size(0),
                      "hw0_i": data["image0"].shape[2:], "hw1_i": data["image1"].shape[2:]})
         cl = lambda img: img.contiguous(memory_format=torch.channels_last)   # C == 1: a restride, no copy
         use_hip = self.backbone_impl == "hip" and data["image0"].is_cuda and not self.training
         run = self.backbone.forward_hip if use_hip else self.backbone
         self._fine_join = None
+        assert not head_input or (use_hip and data["hw0_i"] == data["hw1_i"])
+        hkw = dict(head_input=True) if head_input else {}
         if data["hw0_i"] == data["hw1_i"]:
             x = cl(torch.cat([data["image0"], data["image1"]], dim=0))
-            # the convolution kernels index an activation tensor with 32 bits (conv.hip: images * pixels * channels < 2^31 at the
-            # widest 1/2-resolution map): larger batches go through the backbone in chunks (> 62 pairs at 640 x 480)
-            cap = getattr(self, "_backbone_chunk_images", None) or max(1, (2 ** 31 - 1) // ((x.shape[2] // 2) * (x.shape[3] // 2) * 256))
+            cap = self._backbone_cap(x)
             if use_hip and x.shape[0] > cap:
                 outs = [run(x[i:i + cap]) for i in range(0, x.shape[0], cap)]
                 feats_c, feats_f = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
@@ -455,7 +499,7 @@ class LoFTR(nn.Module):
                     xk = data["image0"] if k == 0 else data["image1"]
                     xk.record_stream(st)
                     with torch.cuda.stream(st):
-                        fc, fine_fn = run(cl(xk), defer_fine=True)
+                        fc, fine_fn = run(cl(xk), defer_fine=True, **hkw)
                         ev = torch.cuda.Event(); ev.record(st)
                         ff = fine_fn()
                     outs.append(fc); fines.append(ff); evs.append(ev)
@@ -465,7 +509,7 @@ class LoFTR(nn.Module):
                 self._fine_join = list(self._half_streams)
                 return outs[0], outs[1], fines[0], fines[1]
             elif use_hip and self.overlap_fine_branch:
-                feats_c, fine_fn = run(x, defer_fine=True)
+                feats_c, fine_fn = run(x, defer_fine=True, **hkw)
                 main = torch.cuda.current_stream(x.device)
                 if self._side_stream is None:
                     self._side_stream = torch.cuda.Stream(device=x.device)    # (ROCm's priority range is (0, -1): no LOW priority to give it)
@@ -477,6 +521,9 @@ class LoFTR(nn.Module):
                     feats_f = fine_fn()
                 feats_f.record_stream(main)                  # allocated on the side stream, consumed on this one
                 self._fine_join = side                       # joined in match_from_features before FinePreprocess
+            elif head_input:
+                feats_c, fine_fn = run(x, defer_fine=True, **hkw)
+                feats_f = fine_fn()
             else:
                 feats_c, feats_f = run(x)
             (feat_c0, feat_c1), (feat_f0, feat_f1) = feats_c.split(data["bs"]), feats_f.split(data["bs"])
@@ -491,10 +538,14 @@ class LoFTR(nn.Module):
                 torch.cuda.current_stream(device).wait_stream(st)
             self._fine_join = None
 
-    def match_from_features(self, feat_c0, feat_c1, feat_f0, feat_f1, data):
-        """Steps 2-5 of forward (loftr.py:51-75): THE hot path.  `data` needs bs, hw0_i, hw1_i."""
-        data.update({"hw0_c": feat_c0.shape[2:], "hw1_c": feat_c1.shape[2:],
-                     "hw0_f": feat_f0.shape[2:], "hw1_f": feat_f1.shape[2:]})
+    def match_from_features(self, feat_c0, feat_c1, feat_f0, feat_f1, data, head_input=False):
+        """Steps 2-5 of forward (loftr.py:51-75): THE hot path.  `data` needs bs, hw0_i, hw1_i.
+        head_input=True (forward): feat_f0 / feat_f1 are run_backbone(head_input=True)'s SP tensors [N, H, W, Cp]."""
+        data.update({"hw0_c": feat_c0.shape[2:], "hw1_c": feat_c1.shape[2:]})
+        if head_input:
+            data.update({"hw0_f": feat_f0.shape[1:3], "hw1_f": feat_f1.shape[1:3]})
+        else:
+            data.update({"hw0_f": feat_f0.shape[2:], "hw1_f": feat_f1.shape[2:]})
         # (not with a graph: as_strided's backward only reaches the FIRST half's tensor, the second half's gradient would be dropped)
         both = (ops.stacked_halves(feat_c0, feat_c1)
                 if feat_c0.shape == feat_c1.shape and not autograd.wants_grad(feat_c0, feat_c1) else None)
@@ -503,7 +554,13 @@ class LoFTR(nn.Module):
         else:
             feat_c0 = self.pos_encoding(feat_c0)
             feat_c1 = self.pos_encoding(feat_c1)
-        self._match_encoded(feat_c0, feat_c1, data, lambda c0, c1: self.fine_preprocess(feat_f0, feat_f1, c0, c1, data))
+        if head_input:
+            head = getattr(self.backbone, self.backbone.WINDOW_HEAD)
+            fine_pre = lambda c0, c1: self.fine_preprocess.forward_windows(feat_f0, feat_f1, head[0].out_channels, head[3], self.backbone.fine_head_last,
+                                                                           self.fine_head, c0, c1, data)
+        else:
+            fine_pre = lambda c0, c1: self.fine_preprocess(feat_f0, feat_f1, c0, c1, data)
+        self._match_encoded(feat_c0, feat_c1, data, fine_pre)
 
     def _match_encoded(self, feat_c0, feat_c1, data, fine_preprocess):
         """Steps 3-5 of forward from the position-encoded coarse features [N, L, C] (shared by match_from_features and match_pairs):
@@ -566,8 +623,9 @@ class LoFTR(nn.Module):
             feat_c0, feat_c1, feat_f0, feat_f1 = self.run_backbone(data)
             return self.match_from_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
         with torch.cuda.device(dev):                 # streams / workspaces / launches all on the tensors' GPU
-            feat_c0, feat_c1, feat_f0, feat_f1 = self.run_backbone(data)
-            self.match_from_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
+            head_input = self._window_head_applies(data)
+            feat_c0, feat_c1, feat_f0, feat_f1 = self.run_backbone(data, head_input=head_input)
+            self.match_from_features(feat_c0, feat_c1, feat_f0, feat_f1, data, head_input=head_input)
 
     def match_pairs(self, bank0, ids0, bank1=None, ids1=None):
         """Match n pairs of images whose backbone maps are in feature banks (loftr_amd/pairs.py: FeatureBank): pair k is

@@ -457,6 +457,80 @@ def fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0
     return out0, out1
 
 
+# ---- the fine head at matched windows only (csrc/window_head.hip) -------------------------------------------------------
+# The window form computes 2 M windows x 49 first-layer-equivalent pixels where the dense head computes every pixel of both fine
+# maps; it is taken while 2 M * 49 <= WINDOW_HEAD_MAX_FILL * (dense pixels).  The factor is where the op-level timing table
+# profiles/window_head_crossover.txt says the window form stops winning (tools/micro/window_head_crossover.py: ahead by 271 us at
+# 1.46, behind by 90 us at 1.95 -- level at about 1.8).
+WINDOW_HEAD_MAX_FILL = 1.8
+
+
+def window_head_wins(M, dense_pixels):
+    """The dispatch rule of LoFTR.fine_head = None: True while the window form of the fine head is the cheaper one for M matches on
+    fine maps of `dense_pixels` pixels in all (both image batches)."""
+    return 0 < 2 * M * 49 <= WINDOW_HEAD_MAX_FILL * dense_pixels
+
+
+def window_head_supported(W, Cin, Cout, h_sp0, h_sp1):
+    """What loftr_fine_preprocess_window_head covers: 5 x 5 windows, 128 output channels (its window rows are Cf dwords wide), two
+    equally sized SP batches."""
+    return (W == 5 and Cout == 128 and h_sp0.shape == h_sp1.shape and h_sp0.shape[3] == ceil32(Cin)
+            and h_sp0.numel() < 2 ** 31)
+
+
+def _window_head_common(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids):
+    for t, n in ((h_sp0, "h_sp0"), (h_sp1, "h_sp1")):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 4:
+            raise _lib.LoftrHipError(f"{n}: expected a contiguous int32 (SP) GPU tensor [N, H, W, Cp]")
+    if h_sp0.shape != h_sp1.shape or h_sp0.shape[3] != ceil32(Cin):
+        raise _lib.LoftrHipError(f"window head: SP maps {tuple(h_sp0.shape)} / {tuple(h_sp1.shape)} for {Cin} channels")
+    Cout, Cin_w, KH, KW = conv.weight.shape
+    if (Cin_w, KH, KW) != (Cin, 3, 3) or conv.stride[0] != 1 or conv.padding[0] != 1:
+        raise _lib.LoftrHipError("window head: a 3x3 / stride-1 / pad-1 convolution expected")
+    ids = [_ptr(_need(t, n, torch.int64)) for t, n in ((b_ids, "b_ids"), (i_ids, "i_ids"), (j_ids, "j_ids"))]
+    return Cout, _prepared_conv(conv, None), ids
+
+
+@_on_device
+def window_head(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride):
+    """The W x W windows of conv(h) at the matched cells, without the map: (win0, win1) int32 SP [M, W*W, 128] -- bit for bit the
+    window tiles loftr_fine_preprocess gathers from the dense convolution's fp32 output."""
+    Cout, prepared, ids = _window_head_common(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids)
+    M = b_ids.shape[0]
+    win = torch.empty(2, M, W * W, ceil32(Cout), dtype=torch.int32, device=h_sp0.device)
+    if M:
+        N, H, Wm, _ = h_sp0.shape
+        check(_lib.load().loftr_window_head(_ptr(h_sp0), _ptr(h_sp1), N, H, Wm, Cin, _ptr(prepared), prepared.numel(), Cout, *ids,
+                                            M, hw0_c[1], hw1_c[1], int(stride), int(W), _ptr(win[0]), _ptr(win[1]),
+                                            _stream()), "loftr_window_head")
+    return win[0], win[1]
+
+
+@_on_device
+def fine_preprocess_windows(h_sp0, h_sp1, Cin, conv, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride,
+                            down_w, down_b, merge_w, merge_b):
+    """fine_preprocess with the fine head's last convolution `conv` evaluated at the matched windows only: h_sp0 / h_sp1 are that
+    convolution's inputs (SP [N, H, W, ceil32(Cin)]) for the image0 / image1 batch.  Same results, bit for bit, as fine_preprocess on
+    the dense maps conv_bn_act(h, Cin, conv) gives."""
+    Cf, prepared, ids = _window_head_common(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids)
+    _need(feat_c0, "feat_c0"); _need(feat_c1, "feat_c1")
+    M = b_ids.shape[0]
+    dev = h_sp0.device
+    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)
+    out0, out1 = out[:M], out[M:]
+    if M == 0:
+        return out0, out1
+    lib = _lib.load()
+    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
+    N, H, Wm, _ = h_sp0.shape
+    check(lib.loftr_fine_preprocess_window_head(_ptr(h_sp0), _ptr(h_sp1), N, H, Wm, Cin, _ptr(prepared), prepared.numel(),
+                                                _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[2],
+                                                *ids, M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf, _ptr(down_w), _ptr(down_b),
+                                                _ptr(merge_w), _ptr(merge_b), _ptr(out0), _ptr(out1), _ptr(ws), ws.numel(),
+                                                _stream()), "loftr_fine_preprocess_window_head")
+    return out0, out1
+
+
 def _slot_ids(ids, n_slots, name, device):
     """Slot ids -> int32 tensor on `device`, checked on the host against [0, n_slots) before any launch (the kernels would
     write NaN for an id outside it)."""
