@@ -54,7 +54,8 @@ typedef enum {
  * 25: feature banks (loftr_pos_encode_flatten_gather, loftr_fine_preprocess_gather); later, without a bump (purely additive: a
  *     binding that needs them refuses a library without them when it loads): batched pose estimation on the GPU
  *     (loftr_estimate_pose_batched, loftr_estimate_pose_batched_workspace_bytes) and the fine head at matched windows only
- *     (loftr_window_head, loftr_fine_preprocess_window_head) */
+ *     (loftr_window_head, loftr_fine_preprocess_window_head), homography / fundamental-matrix RANSAC (loftr_estimate_geometry,
+ *     loftr_geometry_minimal, loftr_estimate_geometry_batched, loftr_estimate_geometry_batched_workspace_bytes) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -515,6 +516,55 @@ size_t loftr_estimate_pose_batched_workspace_bytes(long M, int P);
 int loftr_estimate_pose_batched(const float* mkpts0_f, const float* mkpts1_f, const long* m_bids, long M, const float* K0,
                                 const float* K1, int P, float thresh_px, float conf, unsigned seed, float* R_out, float* t_out,
                                 uint8_t* inliers_out, long* n_inliers, void* ws, size_t ws_bytes, void* stream);
+
+/* Geometric verification without intrinsics: a homography (model 0: x1 ~ H x0) or a fundamental matrix (model 1: x1^T F x0 = 0)
+ * by RANSAC over minimal solvers and a least-squares refit (csrc/geometry.hip; what cv2.findHomography(RANSAC) /
+ * cv2.findFundamentalMat(FM_RANSAC) are used for on planar and on uncalibrated pairs).  HOST function: all pointers are host
+ * memory, the call is synchronous.  kpts0 / kpts1 [M,2] pixels; thresh_px and every residual are in pixels.
+ *   Sampling: loftr_estimate_pose's own -- xorshift64* from `seed`, distinct indices, at most 1000 iterations, a hypothesis
+ *   replaces the best only with strictly more inliers, the adaptive stop log(1 - conf) / log(1 - w^s) with sample size s = 4 (H)
+ *   or 7 (F).  The sample stream does not depend on the scores.
+ *   Solvers (fp64, Hartley normalisation of the s sample points per image): H = null vector of the 8 x 9 DLT matrix; a sample is
+ *   rejected when any three of its four points are collinear in either image -- |signed area| of the triple (twice the
+ *   triangle's area, measured in the normalised frame of the four points: centroid 0, mean distance sqrt 2) below 1e-3 -- or when a
+ *   triple's orientation differs between the images.  F = the up to three real roots of det(a F1 + (1 - a) F2) = 0 over the two
+ *   null vectors of the 7 x 9 matrix.
+ *   Residuals: H squared forward transfer error |x1 - pi(H x0)|^2 (a match whose H x0 has a non-positive third coordinate, with
+ *   the sign that makes it positive at the sample, is an outlier); F squared Sampson distance.  Inlier: residual <= thresh_px^2.
+ *   Refit: normalised least squares over the inliers of the best hypothesis (rank 2 enforced for F; skipped for F with fewer than
+ *   8 inliers), adopted when it has at least as many inliers, and repeated on the adopted model's inliers while it strictly gains
+ *   inliers (at most 4 fits: the adaptive stop can end on a hypothesis that holds only part of the inliers).  Its sums run in a fixed order (256 strided partials, partial k over
+ *   the matches i = k mod 256 in ascending i, then a pairwise tree), which the GPU estimator reproduces.
+ * Outputs: mat_out [9] row-major with unit Frobenius norm and a fixed sign (H: positive third coordinate of H x0 at the inliers;
+ * F: the entry of largest magnitude positive), inliers_out [M] and *n_inliers of the returned model; *n_inliers = -1 (outputs
+ * untouched) when M < s, no sample gave a model, or the best model has fewer than s inliers.
+ * PARITY UNPINNED against OpenCV (absent from this image): published algorithms restated, own sampling sequence and degeneracy
+ * tests.
+ * loftr_geometry_minimal exposes the minimal solvers: p0 / p1 [s,2] pixels (double) -> up to 3 matrices in mats_out [3,9]. */
+int loftr_estimate_geometry(const float* kpts0, const float* kpts1, long M, int model, float thresh_px, float conf, unsigned seed,
+                            float* mat_out, uint8_t* inliers_out, long* n_inliers);
+int loftr_geometry_minimal(const double* p0, const double* p1, int model, double* mats_out, int* n_solutions);
+
+/* loftr_estimate_geometry for every pair of a batch, on the GPU (csrc/geometry_gpu.hip).  CONTRACT: for every pair p the result
+ * is the one loftr_estimate_geometry returns for that pair's matches with the same seed and model -- same n_inliers, same inlier
+ * mask, the matrix equal after the float32 rounding.  Parity against OpenCV stays UNPINNED, as for the host estimator.
+ *   mkpts0_f / mkpts1_f [M,2] f32 pixels, m_bids [M] i64: device memory, grouped by ascending pair id as the matcher emits
+ *   them (pair p = the matches with m_bids == p, in match order); model, thresh_px, conf: as loftr_estimate_geometry; seed: one
+ *   seed shared by every pair.
+ * Outputs (device memory): mat_out [P,9] f32; inliers_out [M] u8 in match order; n_inliers [P] i64, or -1 where
+ * loftr_estimate_geometry returns -1 -- there the matrix and the pair's mask are 0.
+ * Stream-ordered on `stream`; the keypoints never leave the device.  The call copies the per-hypothesis inlier counts to the
+ * host once, replays the RANSAC loop there (the host estimator's own pow / log), copies one decision per pair back and waits for
+ * the stream before it returns: two host round trips per batch, whatever P.  Workspace:
+ * loftr_estimate_geometry_batched_workspace_bytes(M, P, model), about 96 kB (H) / 270 kB (F) per pair plus 33 bytes per match.
+ * Status: LOFTR_ERR_BAD_ARG for a null pointer, M < 0 or P < 0, model outside {0, 1}, P == 0 with M > 0, and for m_bids outside
+ * [0, P) or not grouped by ascending pair (found on the device, reported at the call's own synchronisation; the outputs are then
+ * not written); LOFTR_ERR_WORKSPACE for a short workspace; LOFTR_ERR_UNSUPPORTED for M >= 2^31 or P >= 2^31 / 1000.
+ * M == 0 is valid (every pair gets -1); P == 0 and M == 0 is a no-op success. */
+size_t loftr_estimate_geometry_batched_workspace_bytes(long M, int P, int model);
+int loftr_estimate_geometry_batched(const float* mkpts0_f, const float* mkpts1_f, const long* m_bids, long M, int P, int model,
+                                    float thresh_px, float conf, unsigned seed, float* mat_out, uint8_t* inliers_out,
+                                    long* n_inliers, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

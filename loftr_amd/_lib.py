@@ -114,6 +114,10 @@ SIGNATURES = {
     "loftr_five_point": (_i, [_p, _p, _i, _p, C.POINTER(_i)]),
     "loftr_estimate_pose_batched_workspace_bytes": (_sz, [_l, _i]),
     "loftr_estimate_pose_batched": (_i, [_p, _p, _p, _l, _p, _p, _i, _f, _f, C.c_uint, _p, _p, _p, _p, _p, _sz, _p]),
+    "loftr_estimate_geometry": (_i, [_p, _p, _l, _i, _f, _f, C.c_uint, _p, _p, C.POINTER(_l)]),
+    "loftr_geometry_minimal": (_i, [_p, _p, _i, _p, C.POINTER(_i)]),
+    "loftr_estimate_geometry_batched_workspace_bytes": (_sz, [_l, _i, _i]),
+    "loftr_estimate_geometry_batched": (_i, [_p, _p, _p, _l, _i, _i, _f, _f, C.c_uint, _p, _p, _p, _p, _sz, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

@@ -138,6 +138,98 @@ def _poses_native_gpu(data, pixel_thr, conf):
     return [None if n[b] < 0 else (R[b].astype(np.float64), t[b].astype(np.float64), inl[bids == b]) for b in range(len(n))]
 
 
+# ---- geometric verification without intrinsics (csrc/geometry.hip, csrc/geometry_gpu.hip) -------------------------------
+def _geometry_native(kpts0, kpts1, model, thresh, conf, seed):
+    import ctypes as C
+    from . import _lib
+    k0 = np.ascontiguousarray(kpts0, np.float32).reshape(-1, 2)
+    k1 = np.ascontiguousarray(kpts1, np.float32).reshape(-1, 2)
+    M = k0.shape[0]
+    if M < (4 if model == "homography" else 7):
+        return None
+    mat, inl, n = np.zeros(9, np.float32), np.zeros(M, np.uint8), C.c_long(-1)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.load().loftr_estimate_geometry(ptr(k0), ptr(k1), M, ops.GEOMETRY_MODELS[model], float(thresh), float(conf), int(seed),
+                                                   ptr(mat), ptr(inl), C.byref(n)), "loftr_estimate_geometry")
+    if n.value < 0:
+        return None
+    return mat.reshape(3, 3).astype(np.float64), inl.astype(bool)
+
+
+def _geometry_native_gpu(kpts0, kpts1, model, thresh, conf, seed):
+    k0 = np.ascontiguousarray(kpts0, np.float32).reshape(-1, 2)
+    if k0.shape[0] < (4 if model == "homography" else 7):
+        return None
+    k0 = torch.as_tensor(k0).cuda()
+    k1 = torch.as_tensor(np.ascontiguousarray(kpts1, np.float32).reshape(-1, 2)).cuda()
+    mat, inl, n = ops.estimate_geometry(k0, k1, torch.zeros(k0.shape[0], dtype=torch.int64, device=k0.device), 1, model, thresh, conf, seed)
+    if int(n[0]) < 0:
+        return None
+    return mat[0].cpu().numpy().astype(np.float64), inl.cpu().numpy()
+
+
+def estimate_homography_native(kpts0, kpts1, thresh=3.0, conf=0.999, seed=0):
+    """Homography x1 ~ H x0 of one pair from pixel matches [M,2] (numpy): 4-point RANSAC + least-squares refit, the library's
+    own host estimator (csrc/geometry.hip; parity against cv2.findHomography unpinned).  thresh is the forward transfer error in
+    pixels.  Returns (H [3,3] with unit Frobenius norm, inlier mask [M] bool), or None without a model (fewer than 4 matches, only
+    degenerate samples, fewer than 4 inliers)."""
+    return _geometry_native(kpts0, kpts1, "homography", thresh, conf, seed)
+
+
+def estimate_fundamental_native(kpts0, kpts1, thresh=1.0, conf=0.999, seed=0):
+    """Fundamental matrix x1^T F x0 = 0 of one pair from pixel matches [M,2] (numpy): 7-point RANSAC + rank-2 least-squares
+    refit, the library's own host estimator (csrc/geometry.hip; parity against cv2.findFundamentalMat unpinned).  thresh is the
+    Sampson distance in pixels.  Returns (F [3,3] with unit Frobenius norm, inlier mask [M] bool), or None without a model."""
+    return _geometry_native(kpts0, kpts1, "fundamental", thresh, conf, seed)
+
+
+def estimate_homography_native_gpu(kpts0, kpts1, thresh=3.0, conf=0.999, seed=0):
+    """estimate_homography_native on the GPU (ops.estimate_geometry): the same result for the same seed -- same inlier mask, H equal
+    after the float32 rounding."""
+    return _geometry_native_gpu(kpts0, kpts1, "homography", thresh, conf, seed)
+
+
+def estimate_fundamental_native_gpu(kpts0, kpts1, thresh=1.0, conf=0.999, seed=0):
+    """estimate_fundamental_native on the GPU (ops.estimate_geometry): the same result for the same seed."""
+    return _geometry_native_gpu(kpts0, kpts1, "fundamental", thresh, conf, seed)
+
+
+def verify_matches(data, model="fundamental", thresh_px=None, conf=0.999, seed=0):
+    """Geometric verification of every pair of the batch dict that forward / match_pairs leaves, in one GPU call (ops.estimate_geometry):
+    no intrinsics needed, the keypoints stay on the device.  Update: data['inliers'] bool [M] in match order, data['F'] (model
+    'fundamental') or data['H'] ('homography') float32 [N,3,3] with unit Frobenius norm (zero where no model was found) and
+    data['n_inliers'] int64 [N] (-1 there).  N is data['bs'].
+    Defaults: thresh_px = 1.0 px Sampson distance for the fundamental matrix, 3.0 px transfer error for the homography, conf 0.999,
+    seed 0.  They are this project's choice (common settings of such verifiers); nothing in the reference fixes them."""
+    if thresh_px is None:
+        thresh_px = 3.0 if model == "homography" else 1.0
+    N = int(data["bs"]) if "bs" in data else int(data["image0"].shape[0])
+    mat, inl, n = ops.estimate_geometry(data["mkpts0_f"].to(torch.float32), data["mkpts1_f"].to(torch.float32), data["m_bids"].to(torch.int64),
+                                        N, model, thresh_px, conf, seed)
+    data.update({"inliers": inl, "H" if model == "homography" else "F": mat, "n_inliers": n})
+    return data
+
+
+def homography_corner_errors(H, H_gt, hw):
+    """Mean corner transfer error per pair in pixels: the four corners of an image of size hw = (h, w) mapped by the estimate and by
+    the ground truth, the mean of the four distances (the HPatches protocol of the LoFTR paper; its AUC at 3 / 5 / 10 px is homography_auc(errs)).
+    H, H_gt [N,3,3] or [3,3] (any scale); a pair whose estimate is all zero (no model) gets inf."""
+    H = np.asarray(H.cpu() if isinstance(H, torch.Tensor) else H, np.float64).reshape(-1, 3, 3)
+    G = np.asarray(H_gt.cpu() if isinstance(H_gt, torch.Tensor) else H_gt, np.float64).reshape(-1, 3, 3)
+    h, w = hw
+    corners = np.array([[0, 0, 1], [w - 1, 0, 1], [w - 1, h - 1, 1], [0, h - 1, 1]], np.float64)
+    errs = []
+    for A, B in zip(H, G):
+        if not A.any():
+            errs.append(np.inf)
+            continue
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a, b = corners @ A.T, corners @ B.T
+            d = np.linalg.norm(a[:, :2] / a[:, 2:] - b[:, :2] / b[:, 2:], axis=1)
+        errs.append(float(np.mean(d)) if np.isfinite(d).all() else np.inf)
+    return np.array(errs)
+
+
 _WARNED_NATIVE = []
 
 
@@ -217,6 +309,15 @@ def error_auc(errors, thresholds=(5, 10, 20)):
     e = np.concatenate([[0.0], np.sort(np.asarray(list(errors), dtype=np.float64))])
     recall = np.linspace(0, 1, len(e))
     return {f"auc@{t}": _area_under_recall(e, recall, t) / t for t in (5, 10, 20)}
+
+
+def homography_auc(errors, thresholds=(3, 5, 10)):
+    """error_auc's normalised area under the cumulative error curve for homography_corner_errors, at 3 / 5 / 10 px (the HPatches table
+    of the LoFTR paper).  error_auc itself keeps the reference's behaviour of ignoring its thresholds, so the same curve and the same
+    area routine are evaluated at the thresholds given here."""
+    e = np.concatenate([[0.0], np.sort(np.asarray(list(errors), dtype=np.float64))])
+    recall = np.linspace(0, 1, len(e))
+    return {f"auc@{t}": _area_under_recall(e, recall, t) / t for t in thresholds}
 
 
 def epidist_prec(errors, thresholds, ret_dict=False):

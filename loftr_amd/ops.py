@@ -940,6 +940,39 @@ def estimate_poses(mkpts0_f, mkpts1_f, m_bids, K0, K1, thresh_px, conf, seed=0):
     return R, t, inl.view(torch.bool), n
 
 
+GEOMETRY_MODELS = {"homography": 0, "fundamental": 1}
+
+
+def estimate_geometry(mkpts0_f, mkpts1_f, m_bids, P, model, thresh_px, conf, seed=0):
+    """Homography / fundamental-matrix RANSAC + least-squares refit for every pair of a batch on the GPU
+    (csrc/geometry_gpu.hip): for each pair, what the host estimator loftr_estimate_geometry (evaluation.estimate_homography_native /
+    estimate_fundamental_native) returns for that pair's matches with the same seed.  No intrinsics are needed; thresh_px is in pixels.
+    mkpts0_f / mkpts1_f [M,2] f32, m_bids [M] i64 grouped by ascending pair id (as the matcher emits them), P pairs,
+    model "homography" (x1 ~ H x0) or "fundamental" (x1^T F x0 = 0).
+    -> (mat [P,3,3] f32 with unit Frobenius norm, inliers [M] bool in match order, n_inliers [P] i64), device tensors; n_inliers[p] == -1
+    where the host estimator finds no model (the matrix and that pair's mask are zero there)."""
+    if model not in GEOMETRY_MODELS:
+        raise _lib.LoftrHipError(f"estimate_geometry: model must be one of {sorted(GEOMETRY_MODELS)}, got {model!r}")
+    for name, t, dt in (("mkpts0_f", mkpts0_f, torch.float32), ("mkpts1_f", mkpts1_f, torch.float32), ("m_bids", m_bids, torch.int64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise _lib.LoftrHipError(f"{name}: expected a {dt} GPU tensor (the geometry kernels have no CPU fallback)")
+    M, P = mkpts0_f.shape[0], int(P)
+    if mkpts0_f.shape != (M, 2) or mkpts1_f.shape != (M, 2) or m_bids.shape != (M,) or P < 0:
+        raise _lib.LoftrHipError(f"estimate_geometry: expected mkpts0_f / mkpts1_f [M,2], m_bids [M] and P >= 0, got "
+                                 f"{tuple(mkpts0_f.shape)}, {tuple(mkpts1_f.shape)}, {tuple(m_bids.shape)}, P = {P}")
+    dev = mkpts0_f.device
+    args = [t.contiguous() for t in (mkpts0_f, mkpts1_f, m_bids)]
+    mat = torch.zeros(P, 3, 3, dtype=torch.float32, device=dev)
+    inl = torch.zeros(M, dtype=torch.uint8, device=dev)
+    n = torch.full((P,), -1, dtype=torch.int64, device=dev)
+    lib, kind = _lib.load(), GEOMETRY_MODELS[model]
+    ws = torch.empty(max(1, lib.loftr_estimate_geometry_batched_workspace_bytes(M, P, kind)), dtype=torch.uint8, device=dev)
+    check(lib.loftr_estimate_geometry_batched(*[_ptr(a) for a in args], M, P, kind, float(thresh_px), float(conf), int(seed), _ptr(mat),
+                                              _ptr(inl), _ptr(n), _ptr(ws), ws.numel(), _stream()),
+          "loftr_estimate_geometry_batched (m_bids must lie in [0, P) and be grouped by ascending pair)")
+    return mat, inl.view(torch.bool), n
+
+
 # ---- training-mode glue of the backbone (csrc/train_glue.hip; resnet_fpn.py:22-40,66-77,110-116) ------------------------------------------
 def _dense4(t, name):
     """A 4-D fp32 GPU tensor [N,C,H,W] stored densely either NCHW or NHWC (channels_last: what the convolution nodes produce); returns
