@@ -55,7 +55,8 @@ typedef enum {
  *     binding that needs them refuses a library without them when it loads): batched pose estimation on the GPU
  *     (loftr_estimate_pose_batched, loftr_estimate_pose_batched_workspace_bytes) and the fine head at matched windows only
  *     (loftr_window_head, loftr_fine_preprocess_window_head), homography / fundamental-matrix RANSAC (loftr_estimate_geometry,
- *     loftr_geometry_minimal, loftr_estimate_geometry_batched, loftr_estimate_geometry_batched_workspace_bytes) */
+ *     loftr_geometry_minimal, loftr_estimate_geometry_batched, loftr_estimate_geometry_batched_workspace_bytes), both convolutions
+ *     of the fine head at matched windows (loftr_window_head_first, loftr_window_head_last, loftr_fine_preprocess_window_head2) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -300,6 +301,35 @@ int loftr_fine_preprocess_window_head(const uint32_t* h_sp0, const uint32_t* h_s
                                       const float* down_w, const float* down_b, const float* merge_w,
                                       const float* merge_b, float* out0, float* out1, void* ws, size_t ws_bytes,
                                       void* stream);
+
+/* ---- both convolutions of the fine head at matched windows only (ABI 25, additive) ----------------------
+ * The output of the head's FIRST convolution (3x3, stride 1, pad 1, BatchNorm, LeakyReLU 0.01) is read by loftr_window_head at
+ * the 7 x 7 neighbourhood of each window only.  loftr_window_head_first evaluates it there, from the FPN top-down map:
+ *   t_sp0 / t_sp1: input of the head for the image0 / image1 batch, SP [N, H, Wm, ceil32(Cin)];
+ *   prepared:      the first convolution's folded filter from loftr_conv_prepare (Cin, Cout, 3, 3, with its BatchNorm);
+ *   nb_sp:         SP [2 M, 49, ceil32(Cout)]: window w = side * M + m, row py * 7 + px = the dense layer's SP row of pixel
+ *                  (y0 - 1 + py, x0 - 1 + px), (y0, x0) the window's top-left pixel; ZERO words for pixels outside the map (the
+ *                  second convolution's zero padding) and in the pad channels.  Bit for bit the dense layer's words.
+ * loftr_window_head_last: loftr_window_head reading those rows instead of the dense map (prepared: the second filter).
+ * loftr_fine_preprocess_window_head2: loftr_fine_preprocess_window_head with both convolutions computed this way (prepared0 /
+ *   prepared1: first / second filter, Cmid the channels between them); nb_sp is caller-owned scratch of 2 M * 49 * ceil32(Cmid) dwords.
+ * Supported: W = 5, channels 196 -> 196 -> 128, 2 M * 49 * 224 < 2^31; anything else returns LOFTR_ERR_UNSUPPORTED. */
+int loftr_window_head_first(const uint32_t* t_sp0, const uint32_t* t_sp1, int N, int H, int Wm, int Cin,
+                            const void* prepared, size_t prepared_bytes, int Cout, const int64_t* b_ids,
+                            const int64_t* i_ids, const int64_t* j_ids, int M, int w0c, int w1c, int stride, int W,
+                            uint32_t* nb_sp, void* stream);
+int loftr_window_head_last(const uint32_t* nb_sp, int H, int Wm, int Cin, const void* prepared, size_t prepared_bytes,
+                           int Cout, const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M, int w0c,
+                           int w1c, int stride, int W, uint32_t* win0_sp, uint32_t* win1_sp, void* stream);
+int loftr_fine_preprocess_window_head2(const uint32_t* t_sp0, const uint32_t* t_sp1, int N, int H, int Wm, int Cin,
+                                       const void* prepared0, size_t prepared0_bytes, int Cmid,
+                                       const void* prepared1, size_t prepared1_bytes,
+                                       const float* feat_c0, const float* feat_c1, int L, int S, int Cc,
+                                       const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M,
+                                       int w0c, int w1c, int stride, int W, int Cf,
+                                       const float* down_w, const float* down_b, const float* merge_w,
+                                       const float* merge_b, float* out0, float* out1, void* ws, size_t ws_bytes,
+                                       uint32_t* nb_sp, void* stream);
 
 /* ---- FineMatching ---------------------------------------------------------------------------
  * Replaces: FineMatching.forward + get_fine_match (src/loftr/utils/fine_matching.py:15-74).

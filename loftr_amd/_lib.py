@@ -81,6 +81,10 @@ SIGNATURES = {
     "loftr_window_head": (_i, [_p, _p, _i, _i, _i, _i, _p, _sz, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "loftr_fine_preprocess_window_head": (_i, [_p, _p, _i, _i, _i, _i, _p, _sz, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i,
                                                _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "loftr_window_head_first": (_i, [_p, _p, _i, _i, _i, _i, _p, _sz, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "loftr_window_head_last": (_i, [_p, _i, _i, _i, _p, _sz, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "loftr_fine_preprocess_window_head2": (_i, [_p, _p, _i, _i, _i, _i, _p, _sz, _i, _p, _sz, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i,
+                                                _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "loftr_conv_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "loftr_conv_bn_act": (_i, [_p, _i, _i, _i, _i, _p, C.POINTER(_l), _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _sz, _p, _p]),
     "loftr_stem_conv_bn_relu": (_i, [_p, C.POINTER(_l), _i, _i, _i, _p, C.POINTER(_l), _i, _p, _p, _p, _p, _f, _p, _p]),

@@ -250,6 +250,12 @@ class ResNetFPN_8_2(_ResNetFPN):
     # The fine head whose last convolution ops.fine_preprocess_windows can evaluate at the matched windows only
     WINDOW_HEAD = "layer1_outconv2"
 
+    def fine_head_first(self, t_sp):
+        """The head's first layer (convolution + BN + LeakyReLU), dense, from ``fine_fn()``'s ``head_input="t1"`` result: SP, the
+        ``head_input=True`` result."""
+        head = self.layer1_outconv2
+        return ops.conv_bn_act(t_sp, head[0].in_channels, head[0], head[1], act=2)[0]
+
     def fine_head_last(self, h_sp):
         """The dense fine map [B, C, H, W] from ``fine_fn()``'s ``head_input=True`` result (the head's last convolution)."""
         head = self.layer1_outconv2
@@ -266,7 +272,10 @@ class ResNetFPN_8_2(_ResNetFPN):
         tensors it consumes, for ``Tensor.record_stream``).
         head_input=True (with defer_fine): ``fine_fn()`` stops before the LAST convolution of the fine head and returns
         its input, SP int32 [B, H/2, W/2, ceil32(d2)] -- the caller evaluates that convolution at the matched windows only
-        (ops.fine_preprocess_windows) or densely (``fine_head_last``)."""
+        (ops.fine_preprocess_windows) or densely (``fine_head_last``).
+        head_input="t1" (with defer_fine): ``fine_fn()`` stops before the WHOLE fine head and returns the FPN top-down map it reads
+        (same shape) -- the caller evaluates both convolutions at the matched windows (ops.fine_preprocess_windows2), or the first
+        one densely (``fine_head_first``) and goes on as with head_input=True."""
         assert defer_fine or not head_input
         a0 = self._stem_hip(x)
         a1 = self._stage_hip(self.layer1, a0)       # 1/2
@@ -280,6 +289,8 @@ class ResNetFPN_8_2(_ResNetFPN):
             x2_out, _ = self._head_hip(self.layer2_outconv2, (t2, d3), want_f32=False, shared_gpu=defer_fine)
             d2 = self.layer2_outconv2[3].out_channels
             t1 = self._topdown_hip(a1, self.layer1_outconv, x2_out, d2)
+            if head_input == "t1":
+                return t1
             if head_input:
                 head = self.layer1_outconv2
                 return ops.conv_bn_act(t1, d2, head[0], head[1], act=2, shared_gpu=defer_fine)[0]

@@ -306,6 +306,7 @@ class FinePreprocess(nn.Module):
         d_model_f = self.config["fine"]["d_model"]
         self.d_model_f = d_model_f
         self.last_head = None                    # forward_windows: the form its last call took ("windows" / "dense")
+        self.last_head_first = None              # forward_windows2: the form the head's FIRST convolution took ("windows" / "dense")
         if self.cat_c_feat:
             self.down_proj = nn.Linear(d_model_c, d_model_f, bias=True)
             self.merge_feat = nn.Linear(2 * d_model_f, d_model_f, bias=True)
@@ -357,6 +358,34 @@ class FinePreprocess(nn.Module):
                                            tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride,
                                            down_w=self.down_proj.weight, down_b=self.down_proj.bias,
                                            merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
+
+    def forward_windows2(self, t_sp0, t_sp1, cin, head, first_fn, dense_fn, fine_head, feat_c0, feat_c1, data):
+        """Inference forward from the INPUTS of the fine head `head` (conv, BN, LeakyReLU, conv; SP [N, H, W, ceil32(cin)] per image
+        batch).  Three forms, bit-identical (tests/test_hip_window_head_first.py): both convolutions at the matched windows
+        (csrc/window_head_first.hip) while ops.window_head_first_wins says so or fine_head is "windows"; otherwise the first one
+        densely by `first_fn(t_sp)` and then forward_windows (the last one at the windows, or densely too)."""
+        M = data["b_ids"].shape[0]
+        dense_pixels = 2 * t_sp0.shape[0] * t_sp0.shape[1] * t_sp0.shape[2]
+        both = (M > 0 and (fine_head == "windows" or ops.window_head_first_wins(M, dense_pixels))
+                and ops.window_head_first_supported(self.W, cin, head[0], head[3], t_sp0, t_sp1, M))
+        if not both:
+            self.last_head_first = "dense"
+            if M == 0:                                      # (nothing is read but the device of the maps)
+                return self.forward_windows(t_sp0, t_sp1, head[0].out_channels, head[3], dense_fn, fine_head, feat_c0, feat_c1, data)
+            stacked = ops.stacked_halves(t_sp0, t_sp1)      # the halves of one backbone batch: one launch
+            if stacked is not None:
+                h_sp0, h_sp1 = first_fn(stacked).split(t_sp0.shape[0])
+            else:
+                h_sp0, h_sp1 = first_fn(t_sp0), first_fn(t_sp1)
+            return self.forward_windows(h_sp0, h_sp1, head[0].out_channels, head[3], dense_fn, fine_head, feat_c0, feat_c1, data)
+        self.last_head = self.last_head_first = "windows"
+        W = self.W
+        stride = data["hw0_f"][0] // data["hw0_c"][0]
+        data.update({"W": W})
+        return ops.fine_preprocess_windows2(t_sp0, t_sp1, cin, head[0], head[1], head[3], feat_c0, feat_c1, data["b_ids"], data["i_ids"],
+                                            data["j_ids"], tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride,
+                                            down_w=self.down_proj.weight, down_b=self.down_proj.bias,
+                                            merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
 
     def forward_gather(self, bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data):
         """Inference forward with the fine maps of pair b read from bank_f0[slot0[b]] / bank_f1[slot1[b]] (LoFTR.match_pairs)."""
@@ -429,8 +458,9 @@ class LoFTR(nn.Module):
         self._half_streams = None
         # The last convolution of the fine head has one consumer in the inference forward, the 5 x 5 windows of FinePreprocess.  None:
         # forward evaluates it at the matched windows only (csrc/window_head.hip) while that is the cheaper form (ops.window_head_wins)
-        # and densely otherwise; "windows" / "dense": always that form where the window form applies at all (eval mode, HIP backbone,
-        # ResNetFPN_8_2, equally sized images, one backbone batch).  Bit-identical results.  run_backbone / match_from_features / match_pairs
+        # and densely otherwise -- and the head's first convolution at the windows' 7 x 7 neighbourhoods only
+        # (csrc/window_head_first.hip) while ops.window_head_first_wins; "windows" / "dense": always that form where the window form
+        # applies at all (eval mode, HIP backbone, ResNetFPN_8_2, equally sized images, one backbone batch).  Bit-identical results.  run_backbone / match_from_features / match_pairs
         # keep the dense maps.
         self.fine_head = None
         # .train() only: hand the two matching heads their inputs as autograd LEAVES (data['_head_inputs']) and run the heads
@@ -467,7 +497,7 @@ class LoFTR(nn.Module):
     def run_backbone(self, data, head_input=False):
         """Step 1 of forward (loftr.py:39-54): returns (feat_c0, feat_c1, feat_f0, feat_f1).
         head_input=True (forward only, where _window_head_applies): the last two are the SP inputs of the fine head's last convolution
-        (backbone.forward_hip) instead of the fine maps."""
+        (backbone.forward_hip) instead of the fine maps; head_input="t1": the SP inputs of the whole fine head."""
         data.update({"bs": data["image0"].size(0),
                      "hw0_i": data["image0"].shape[2:], "hw1_i": data["image1"].shape[2:]})
         cl = lambda img: img.contiguous(memory_format=torch.channels_last)   # C == 1: a restride, no copy
@@ -475,7 +505,7 @@ class LoFTR(nn.Module):
         run = self.backbone.forward_hip if use_hip else self.backbone
         self._fine_join = None
         assert not head_input or (use_hip and data["hw0_i"] == data["hw1_i"])
-        hkw = dict(head_input=True) if head_input else {}
+        hkw = dict(head_input=head_input) if head_input else {}
         if data["hw0_i"] == data["hw1_i"]:
             x = cl(torch.cat([data["image0"], data["image1"]], dim=0))
             cap = self._backbone_cap(x)
@@ -540,7 +570,7 @@ class LoFTR(nn.Module):
 
     def match_from_features(self, feat_c0, feat_c1, feat_f0, feat_f1, data, head_input=False):
         """Steps 2-5 of forward (loftr.py:51-75): THE hot path.  `data` needs bs, hw0_i, hw1_i.
-        head_input=True (forward): feat_f0 / feat_f1 are run_backbone(head_input=True)'s SP tensors [N, H, W, Cp]."""
+        head_input=True / "t1" (forward): feat_f0 / feat_f1 are run_backbone(head_input=...)'s SP tensors [N, H, W, Cp]."""
         data.update({"hw0_c": feat_c0.shape[2:], "hw1_c": feat_c1.shape[2:]})
         if head_input:
             data.update({"hw0_f": feat_f0.shape[1:3], "hw1_f": feat_f1.shape[1:3]})
@@ -554,7 +584,11 @@ class LoFTR(nn.Module):
         else:
             feat_c0 = self.pos_encoding(feat_c0)
             feat_c1 = self.pos_encoding(feat_c1)
-        if head_input:
+        if head_input == "t1":
+            head = getattr(self.backbone, self.backbone.WINDOW_HEAD)
+            fine_pre = lambda c0, c1: self.fine_preprocess.forward_windows2(feat_f0, feat_f1, head[0].in_channels, head, self.backbone.fine_head_first,
+                                                                            self.backbone.fine_head_last, self.fine_head, c0, c1, data)
+        elif head_input:
             head = getattr(self.backbone, self.backbone.WINDOW_HEAD)
             fine_pre = lambda c0, c1: self.fine_preprocess.forward_windows(feat_f0, feat_f1, head[0].out_channels, head[3], self.backbone.fine_head_last,
                                                                            self.fine_head, c0, c1, data)
@@ -623,7 +657,9 @@ class LoFTR(nn.Module):
             feat_c0, feat_c1, feat_f0, feat_f1 = self.run_backbone(data)
             return self.match_from_features(feat_c0, feat_c1, feat_f0, feat_f1, data)
         with torch.cuda.device(dev):                 # streams / workspaces / launches all on the tensors' GPU
-            head_input = self._window_head_applies(data)
+            # (the side streams stop before the fine head: after coarse matching it runs at the matched windows, or its first
+            # convolution densely on this stream -- FinePreprocess.forward_windows2)
+            head_input = "t1" if self._window_head_applies(data) else False
             feat_c0, feat_c1, feat_f0, feat_f1 = self.run_backbone(data, head_input=head_input)
             self.match_from_features(feat_c0, feat_c1, feat_f0, feat_f1, data, head_input=head_input)
 

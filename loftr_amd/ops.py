@@ -531,6 +531,106 @@ def fine_preprocess_windows(h_sp0, h_sp1, Cin, conv, feat_c0, feat_c1, b_ids, i_
     return out0, out1
 
 
+# ---- both convolutions of the fine head at matched windows only (csrc/window_head_first.hip) -----------------------------
+# The head's FIRST convolution has one consumer left once the last one runs at the windows: the 7 x 7 neighbourhood of each window,
+# 2 M * 49 pixels.  It is evaluated there (into a scratch tensor the last convolution's window kernel stages its patches from) while
+# 2 M * 49 <= WINDOW_HEAD_FIRST_MAX_FILL * (dense pixels) AND the last convolution takes its window form (window_head_wins).  The
+# factor is where profiles/window_head_first_crossover.txt (tools/micro/window_head_first_crossover.py, op level, the bench's maps)
+# says the pair of window kernels stops winning against the dense first convolution + window_head (ahead by 406 us at fill 0.73,
+# behind by 357 us at 0.98 -- level at about 0.85).
+WINDOW_HEAD_FIRST_MAX_FILL = 0.85
+
+
+def window_head_first_wins(M, dense_pixels):
+    """The dispatch rule of LoFTR.fine_head = None for the head's FIRST convolution: True while evaluating it at the 7 x 7
+    neighbourhoods of the M matches' windows is cheaper than on the `dense_pixels` pixels of both image batches' maps."""
+    return window_head_wins(M, dense_pixels) and 2 * M * 49 <= WINDOW_HEAD_FIRST_MAX_FILL * dense_pixels
+
+
+def window_head_first_supported(W, Cin, conv0, conv1, t_sp0, t_sp1, M):
+    """What loftr_fine_preprocess_window_head2 covers: 5 x 5 windows, channels 196 -> 196 -> 128, two equally sized SP batches, a
+    scratch tensor indexed with 32 bits."""
+    return (window_head_supported(W, Cin, conv1.out_channels, t_sp0, t_sp1) and Cin == 196 and conv0.out_channels == 196
+            and conv1.in_channels == 196 and 2 * M * 49 * 224 < 2 ** 31)
+
+
+def _window_head_first_common(t_sp0, t_sp1, Cin, conv, bn, b_ids, i_ids, j_ids):
+    for t, n in ((t_sp0, "t_sp0"), (t_sp1, "t_sp1")):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 4:
+            raise _lib.LoftrHipError(f"{n}: expected a contiguous int32 (SP) GPU tensor [N, H, W, Cp]")
+    if t_sp0.shape != t_sp1.shape or t_sp0.shape[3] != ceil32(Cin):
+        raise _lib.LoftrHipError(f"window head: SP maps {tuple(t_sp0.shape)} / {tuple(t_sp1.shape)} for {Cin} channels")
+    Cout, Cin_w, KH, KW = conv.weight.shape
+    if (Cin_w, KH, KW) != (Cin, 3, 3) or conv.stride[0] != 1 or conv.padding[0] != 1:
+        raise _lib.LoftrHipError("window head: a 3x3 / stride-1 / pad-1 convolution expected")
+    ids = [_ptr(_need(t, n, torch.int64)) for t, n in ((b_ids, "b_ids"), (i_ids, "i_ids"), (j_ids, "j_ids"))]
+    return Cout, _prepared_conv(conv, bn), ids
+
+
+@_on_device
+def window_head_first(t_sp0, t_sp1, Cin, conv, bn, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride):
+    """act(bn(conv(t))) (LeakyReLU 0.01: the fine head's first layer) at the 7 x 7 neighbourhoods of the matched W x W windows, without
+    the map: int32 SP [2 M, 49, ceil32(Cout)], window side * M + m, row py * 7 + px -- bit for bit the dense layer's SP rows
+    conv_bn_act(t, Cin, conv, bn, act=2) at those pixels, zeros outside the map."""
+    Cout, prepared, ids = _window_head_first_common(t_sp0, t_sp1, Cin, conv, bn, b_ids, i_ids, j_ids)
+    M = b_ids.shape[0]
+    nb = torch.empty(2 * M, 49, ceil32(Cout), dtype=torch.int32, device=t_sp0.device)
+    if M:
+        N, H, Wm, _ = t_sp0.shape
+        check(_lib.load().loftr_window_head_first(_ptr(t_sp0), _ptr(t_sp1), N, H, Wm, Cin, _ptr(prepared), prepared.numel(), Cout, *ids,
+                                                  M, hw0_c[1], hw1_c[1], int(stride), int(W), _ptr(nb), _stream()),
+              "loftr_window_head_first")
+    return nb
+
+
+@_on_device
+def window_head_last(nb, hw_f, Cin, conv, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride):
+    """window_head from window_head_first's neighbourhood rows `nb` instead of the dense map (hw_f: the map's height and width)."""
+    M = b_ids.shape[0]
+    if not nb.is_cuda or nb.dtype != torch.int32 or not nb.is_contiguous() or tuple(nb.shape) != (2 * M, 49, ceil32(Cin)):
+        raise _lib.LoftrHipError(f"nb: expected a contiguous int32 (SP) GPU tensor [{2 * M}, 49, {ceil32(Cin)}]")
+    Cout = conv.weight.shape[0]
+    prepared = _prepared_conv(conv, None)
+    ids = [_ptr(_need(t, n, torch.int64)) for t, n in ((b_ids, "b_ids"), (i_ids, "i_ids"), (j_ids, "j_ids"))]
+    win = torch.empty(2, M, W * W, ceil32(Cout), dtype=torch.int32, device=nb.device)
+    if M:
+        check(_lib.load().loftr_window_head_last(_ptr(nb), int(hw_f[0]), int(hw_f[1]), Cin, _ptr(prepared), prepared.numel(), Cout, *ids,
+                                                 M, hw0_c[1], hw1_c[1], int(stride), int(W), _ptr(win[0]), _ptr(win[1]), _stream()),
+              "loftr_window_head_last")
+    return win[0], win[1]
+
+
+@_on_device
+def fine_preprocess_windows2(t_sp0, t_sp1, Cin, conv0, bn0, conv1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride,
+                             down_w, down_b, merge_w, merge_b):
+    """fine_preprocess with BOTH convolutions of the fine head (conv0 + bn0 + LeakyReLU, conv1) evaluated at the matched windows only:
+    t_sp0 / t_sp1 are the head's inputs (SP [N, H, W, ceil32(Cin)]) for the image0 / image1 batch.  Same results, bit for bit, as
+    fine_preprocess_windows on conv_bn_act(t, Cin, conv0, bn0, act=2)."""
+    Cmid, prepared0, ids = _window_head_first_common(t_sp0, t_sp1, Cin, conv0, bn0, b_ids, i_ids, j_ids)
+    Cf = conv1.weight.shape[0]
+    if tuple(conv1.weight.shape[1:]) != (Cmid, 3, 3) or conv1.stride[0] != 1 or conv1.padding[0] != 1:
+        raise _lib.LoftrHipError("window head: a 3x3 / stride-1 / pad-1 second convolution expected")
+    prepared1 = _prepared_conv(conv1, None)
+    _need(feat_c0, "feat_c0"); _need(feat_c1, "feat_c1")
+    M = b_ids.shape[0]
+    dev = t_sp0.device
+    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)
+    out0, out1 = out[:M], out[M:]
+    if M == 0:
+        return out0, out1
+    lib = _lib.load()
+    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
+    nb = torch.empty(2 * M, 49, ceil32(Cmid), dtype=torch.int32, device=dev)     # the first convolution's neighbourhood rows
+    N, H, Wm, _ = t_sp0.shape
+    check(lib.loftr_fine_preprocess_window_head2(_ptr(t_sp0), _ptr(t_sp1), N, H, Wm, Cin, _ptr(prepared0), prepared0.numel(), Cmid,
+                                                 _ptr(prepared1), prepared1.numel(),
+                                                 _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[2],
+                                                 *ids, M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf, _ptr(down_w), _ptr(down_b),
+                                                 _ptr(merge_w), _ptr(merge_b), _ptr(out0), _ptr(out1), _ptr(ws), ws.numel(),
+                                                 _ptr(nb), _stream()), "loftr_fine_preprocess_window_head2")
+    return out0, out1
+
+
 def _slot_ids(ids, n_slots, name, device):
     """Slot ids -> int32 tensor on `device`, checked on the host against [0, n_slots) before any launch (the kernels would
     write NaN for an id outside it)."""
