@@ -56,7 +56,9 @@ typedef enum {
  *     (loftr_estimate_pose_batched, loftr_estimate_pose_batched_workspace_bytes) and the fine head at matched windows only
  *     (loftr_window_head, loftr_fine_preprocess_window_head), homography / fundamental-matrix RANSAC (loftr_estimate_geometry,
  *     loftr_geometry_minimal, loftr_estimate_geometry_batched, loftr_estimate_geometry_batched_workspace_bytes), both convolutions
- *     of the fine head at matched windows (loftr_window_head_first, loftr_window_head_last, loftr_fine_preprocess_window_head2) */
+ *     of the fine head at matched windows (loftr_window_head_first, loftr_window_head_last, loftr_fine_preprocess_window_head2),
+ *     absolute pose from matches and depth (loftr_estimate_absolute_pose, loftr_p3p, loftr_estimate_absolute_pose_batched,
+ *     loftr_estimate_absolute_pose_batched_workspace_bytes, loftr_lift_keypoints) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -595,6 +597,72 @@ size_t loftr_estimate_geometry_batched_workspace_bytes(long M, int P, int model)
 int loftr_estimate_geometry_batched(const float* mkpts0_f, const float* mkpts1_f, const long* m_bids, long M, int P, int model,
                                     float thresh_px, float conf, unsigned seed, float* mat_out, uint8_t* inliers_out,
                                     long* n_inliers, void* ws, size_t ws_bytes, void* stream);
+
+/* Absolute pose (camera resection, PnP) from 2D-3D matches: x_cam = R X + t by P3P inside RANSAC and a Gauss-Newton refit on the
+ * pixel reprojection error (csrc/absolute_pose.hip; what cv2.solvePnPRansac is used for when one image of the pair has a depth map:
+ * InLoc / Aachen localisation, RGB-D re-localisation).  The result is metric -- in the units of the 3D points -- and does not
+ * degenerate on planar scenes or small baselines as the five-point path does.  HOST function: all pointers are host memory, the call
+ * is synchronous.  pts3d [M,3] points (any rigid frame), kpts [M,2] pixels of the camera to resect, K [3,3] its intrinsics: upper
+ * triangular (fx, skew, cx, fy, cy are read; K[2] is taken as (0, 0, 1)).  thresh_px and every residual are in pixels.
+ *   Sampling: loftr_estimate_pose's own -- xorshift64* from `seed`, 3 distinct indices, at most 1000 iterations, a hypothesis replaces
+ *   the best only with strictly more inliers (the solutions of one sample in solver order), the adaptive stop
+ *   log(1 - conf) / log(1 - w^3).  The sample stream does not depend on the scores.
+ *   Solver (fp64): unit bearings f = K^-1 (u, v, 1) by the closed-form inverse; Grunert's P3P as in Haralick et al. (IJCV 1994): the
+ *   quartic in the depth ratio v = s3 / s1, its real positive roots by the Aberth-Ehrlich + Newton finder, the three distances
+ *   polished by 4 Newton steps on the cosine-law equations (a solution is kept when each holds to 1e-10 x the longest squared side),
+ *   R and t from the orthonormal frames of the two point triples.  Up to 4 poses.  Degenerate samples give none:
+ *   |(P2 - P1) x (P3 - P1)|^2 <= (1e-6)^2 x (longest squared side)^2 (collinear world points), or |f_i x f_j|^2 <= (1e-7)^2 for two
+ *   of the bearings (coincident bearings).  Both rules are relative (scale-free).
+ *   Residual: p = K (R X + t); inlier iff p_z > 0 and |(p_x / p_z, p_y / p_z) - kpt|^2 <= thresh_px^2.
+ *   Refit: 5 Gauss-Newton steps on the reprojection error over the inliers of the best hypothesis (left rotation increment applied
+ *   through the normalised quaternion (1, w / 2), additive translation; a non-positive pivot of the 6 x 6 elimination fails the fit
+ *   and keeps the current model; skipped below 4 inliers), adopted when it has at least as many inliers, and repeated on the adopted
+ *   model's inliers while it strictly gains inliers (at most 4 fits).  Its 27 sums run in a fixed order (256 strided partials,
+ *   partial k over the matches i = k mod 256 in ascending i, then a pairwise tree), which the GPU estimator reproduces.
+ * Outputs: R_out [9] row-major, t_out [3], inliers_out [M] and *n_inliers of the returned model; *n_inliers = -1 with R, t and the mask
+ * zero when M < 3, no sample gave a model, or the best model has fewer than 3 inliers.
+ * PARITY UNPINNED against OpenCV's solvePnPRansac (absent from this image): published algorithms restated, own sampling sequence and
+ * degeneracy tests.
+ * loftr_p3p exposes the minimal solver: X [3,3] world points, bearings [3,3] (normalised by the call) -> n_solutions <= 4 poses in
+ * R_out [4,9] / t_out [4,3] (double). */
+int loftr_estimate_absolute_pose(const float* pts3d, const float* kpts, long M, const float* K, float thresh_px, float conf, unsigned seed,
+                                 float* R_out, float* t_out, uint8_t* inliers_out, long* n_inliers);
+int loftr_p3p(const double* X, const double* bearings, double* R_out, double* t_out, int* n_solutions);
+
+/* loftr_estimate_absolute_pose for every pair of a batch, on the GPU (csrc/absolute_pose_gpu.hip).  CONTRACT: for every pair p the
+ * result is the one loftr_estimate_absolute_pose returns for that pair's matches and K[p] with the same seed -- same n_inliers, same
+ * inlier mask, R and t equal after the float32 rounding.  Parity against OpenCV stays UNPINNED, as for the host estimator.
+ *   pts3d [M,3] f32, kpts [M,2] f32 pixels, m_bids [M] i64, K [P,3,3] f32: device memory; the matches grouped by ascending pair id as
+ *   the matcher emits them (pair p = the matches with m_bids == p, in match order); thresh_px, conf: as the host estimator; seed: one
+ *   seed shared by every pair.
+ * Outputs (device memory): R_out [P,9], t_out [P,3] f32; inliers_out [M] u8 in match order; n_inliers [P] i64, or -1 where the host
+ * estimator returns -1 -- there R, t and the pair's mask are 0.
+ * Stream-ordered on `stream`; the matches never leave the device.  The call copies the per-hypothesis inlier counts to the host once,
+ * replays the RANSAC loop there (the host estimator's own pow / log), copies one decision per pair back and waits for the stream
+ * before it returns: two host round trips per batch, whatever P.  Workspace:
+ * loftr_estimate_absolute_pose_batched_workspace_bytes(M, P), about 430 kB per pair plus 65 bytes per match.
+ * Status: LOFTR_ERR_BAD_ARG for a null pointer, M < 0 or P < 0, P == 0 with M > 0, and for m_bids outside [0, P) or not grouped by
+ * ascending pair (found on the device, reported at the call's own synchronisation; the outputs are then not written);
+ * LOFTR_ERR_WORKSPACE for a short workspace; LOFTR_ERR_UNSUPPORTED for M >= 2^31 or P >= 2^31 / 1000.
+ * M == 0 is valid (every pair gets -1); P == 0 and M == 0 is a no-op success. */
+size_t loftr_estimate_absolute_pose_batched_workspace_bytes(long M, int P);
+int loftr_estimate_absolute_pose_batched(const float* pts3d, const float* kpts, const long* m_bids, long M, const float* K, int P,
+                                         float thresh_px, float conf, unsigned seed, float* R_out, float* t_out, uint8_t* inliers_out,
+                                         long* n_inliers, void* ws, size_t ws_bytes, void* stream);
+
+/* Matched keypoints of the image that has a depth map -> 3D points: the first half of the reference's warp_kpts
+ * (src/loftr/utils/geometry.py:22-37), fp32 as there, a thread per match (csrc/absolute_pose_gpu.hip).  Device memory, stream-ordered.
+ *   kpts [M,2] pixels of the depth map's image, m_bids [M] i64 pair ids, depth [P,dh,dw] f32, K [P,3,3] f32 upper triangular,
+ *   T [P,4,4] f32 camera-to-world or NULL.
+ * The depth is read at the keypoint rounded half to even (rintf, = torch.round); valid = the rounded keypoint lies inside the map and
+ * that depth != 0.  X = K^-1 (x d, y d, d) with the UNROUNDED keypoint and the closed-form inverse
+ * (Y = (y d - cy d) / fy, X = (x d - skew Y - cx d) / fx, Z = d), then X <- T[:3,:3] X + T[:3,3] when T is given; every product and
+ * sum is rounded on its own (no fused multiply-add), left to right.
+ * Outputs: pts3d_out [M,3] f32, valid_out [M] u8.  Invalid rows are (0, 0, 0): a keypoint outside the map (or not a number) and a pair
+ * id outside [0, P) are invalid, never clamped, and no depth is read for them.  Nearest lookup only (no bilinear interpolation).
+ * Status: LOFTR_ERR_BAD_ARG for a null pointer, negative sizes or P == 0 with M > 0; M == 0 is a no-op success. */
+int loftr_lift_keypoints(const float* kpts, const long* m_bids, long M, const float* depth, int dh, int dw, const float* K, const float* T,
+                         int P, float* pts3d_out, uint8_t* valid_out, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

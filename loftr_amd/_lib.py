@@ -122,6 +122,11 @@ SIGNATURES = {
     "loftr_geometry_minimal": (_i, [_p, _p, _i, _p, C.POINTER(_i)]),
     "loftr_estimate_geometry_batched_workspace_bytes": (_sz, [_l, _i, _i]),
     "loftr_estimate_geometry_batched": (_i, [_p, _p, _p, _l, _i, _i, _f, _f, C.c_uint, _p, _p, _p, _p, _sz, _p]),
+    "loftr_estimate_absolute_pose": (_i, [_p, _p, _l, _p, _f, _f, C.c_uint, _p, _p, _p, C.POINTER(_l)]),
+    "loftr_p3p": (_i, [_p, _p, _p, _p, C.POINTER(_i)]),
+    "loftr_estimate_absolute_pose_batched_workspace_bytes": (_sz, [_l, _i]),
+    "loftr_estimate_absolute_pose_batched": (_i, [_p, _p, _p, _l, _p, _i, _f, _f, C.c_uint, _p, _p, _p, _p, _p, _sz, _p]),
+    "loftr_lift_keypoints": (_i, [_p, _p, _l, _p, _i, _i, _p, _p, _i, _p, _p, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

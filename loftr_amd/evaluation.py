@@ -17,7 +17,10 @@ for ``from loftr_amd.evaluation import ...``.
   (csrc/pose.hip: Nister's solver, Sampson distance, OpenCV's documented parameters; host code like cv2's), or
   `estimate_pose_native_gpu` -- the same estimator with the same results, the whole batch in one GPU call.  PARITY
   UNPINNED against OpenCV (absent from this image; its sampling sequence cannot be reproduced): tests/test_pose.py
-  checks the solver on exact data and the recovered pose on synthetic scenes with known ground truth.
+  checks the solver on exact data and the recovered pose on synthetic scenes with known ground truth;
+* beyond the reference's evaluation: geometric verification without intrinsics (`verify_matches`: homography / fundamental
+  matrix, csrc/geometry*.hip) and metric localisation from matches and a depth map (`localize`: lifting + P3P RANSAC,
+  csrc/absolute_pose*.hip), each one GPU call per batch with a host estimator that defines the result.
 """
 import os
 
@@ -208,6 +211,100 @@ def verify_matches(data, model="fundamental", thresh_px=None, conf=0.999, seed=0
                                         N, model, thresh_px, conf, seed)
     data.update({"inliers": inl, "H" if model == "homography" else "F": mat, "n_inliers": n})
     return data
+
+
+# ---- absolute pose from matches and depth (csrc/absolute_pose.hip, csrc/absolute_pose_gpu.hip) ---------------------------
+def estimate_absolute_pose_native(pts3d, kpts, K, thresh=3.0, conf=0.999, seed=0):
+    """Camera pose x_cam = R X + t of one image from 2D-3D matches (numpy: pts3d [M,3], kpts [M,2] pixels, K [3,3]): P3P RANSAC + a
+    Gauss-Newton refit on the reprojection error, the library's own host estimator (csrc/absolute_pose.hip; parity against
+    cv2.solvePnPRansac unpinned).  thresh is the reprojection error in pixels; t is in the units of pts3d.
+    Returns (R [3,3], t [3], inlier mask [M] bool), or None without a model (fewer than 3 matches, only degenerate samples)."""
+    import ctypes as C
+    from . import _lib
+    X = np.ascontiguousarray(pts3d, np.float32).reshape(-1, 3)
+    k = np.ascontiguousarray(kpts, np.float32).reshape(-1, 2)
+    M = X.shape[0]
+    if M < 3:
+        return None
+    Kc = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+    R, t, inl, n = np.zeros(9, np.float32), np.zeros(3, np.float32), np.zeros(M, np.uint8), C.c_long(-1)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.load().loftr_estimate_absolute_pose(ptr(X), ptr(k), M, ptr(Kc), float(thresh), float(conf), int(seed), ptr(R), ptr(t),
+                                                        ptr(inl), C.byref(n)), "loftr_estimate_absolute_pose")
+    if n.value < 0:
+        return None
+    return R.reshape(3, 3).astype(np.float64), t.astype(np.float64), inl.astype(bool)
+
+
+def estimate_absolute_pose_native_gpu(pts3d, kpts, K, thresh=3.0, conf=0.999, seed=0):
+    """estimate_absolute_pose_native on the GPU (ops.estimate_absolute_poses): the same result for the same seed -- same inlier mask,
+    R and t equal after the float32 rounding."""
+    X = np.ascontiguousarray(pts3d, np.float32).reshape(-1, 3)
+    if X.shape[0] < 3:
+        return None
+    X = torch.as_tensor(X).cuda()
+    k = torch.as_tensor(np.ascontiguousarray(kpts, np.float32).reshape(-1, 2)).cuda()
+    Kc = torch.as_tensor(np.ascontiguousarray(K, np.float32)).reshape(1, 3, 3).cuda()
+    R, t, inl, n = ops.estimate_absolute_poses(X, k, torch.zeros(X.shape[0], dtype=torch.int64, device=X.device), Kc, thresh, conf, seed)
+    if int(n[0]) < 0:
+        return None
+    return R[0].cpu().numpy().astype(np.float64), t[0].cpu().numpy().astype(np.float64), inl.cpu().numpy()
+
+
+def localize(data, db_side=0, depth=None, K_db=None, K_query=None, T_world_from_db=None, thresh_px=3.0, conf=0.999, seed=0):
+    """Metric pose of the query image of every pair of the batch dict that forward / match_pairs leaves, from the matches and the depth
+    map of the other (database) image, in GPU calls only: the database keypoints are lifted to 3D (ops.lift_keypoints: nearest depth,
+    the reference's warp_kpts arithmetic), matches without depth are dropped, and the query camera is resected from the 2D-3D
+    matches (ops.estimate_absolute_poses: P3P RANSAC + Gauss-Newton refit), one call for the whole batch.
+    db_side 0: image 0 is the database image (defaults data['depth0'], data['K0'], query intrinsics data['K1']); db_side 1: the roles
+    swapped (data['depth1'], data['K1'], data['K0']).  T_world_from_db [N,4,4] (database camera to world) puts the 3D points into a
+    world frame; without it they stay in the database camera's frame and (R, t) estimates T_0to1 (db_side 0) / T_1to0 (db_side 1), with
+    a metric translation.
+    Update: data['R_abs'] float32 [N,3,3], data['t_abs'] float32 [N,3] (x_query = R X + t; zero where no model was found),
+    data['inliers'] bool [M] in match order (False for dropped matches), data['n_inliers'] int64 [N] (-1 without a model) and
+    data['n_lifted'] int64 [N] (matches with a valid depth).  N is data['bs'].
+    Defaults: thresh_px = 3.0 px reprojection error, conf 0.999, seed 0.  They are this project's choice (common settings of such
+    localisers); nothing in the reference fixes them."""
+    if db_side not in (0, 1):
+        raise ValueError(f"localize: db_side must be 0 or 1, got {db_side!r}")
+    d, q = str(db_side), str(1 - db_side)
+    N = int(data["bs"]) if "bs" in data else int(data["image0"].shape[0])
+    f32 = lambda t: t.to(torch.float32)
+    depth = f32(data["depth" + d] if depth is None else depth)
+    K_db = f32(data["K" + d] if K_db is None else K_db)
+    K_query = f32(data["K" + q] if K_query is None else K_query)
+    T = None if T_world_from_db is None else f32(T_world_from_db)
+    m_bids = data["m_bids"].to(torch.int64)
+    pts3d, valid = ops.lift_keypoints(f32(data["mkpts" + d + "_f"]), m_bids, depth, K_db, T)
+    keep = valid.nonzero().squeeze(1)                        # boolean selection keeps the grouping by ascending pair
+    R, t, inl, n = ops.estimate_absolute_poses(pts3d[keep], f32(data["mkpts" + q + "_f"])[keep], m_bids[keep], K_query, thresh_px, conf, seed)
+    inliers = torch.zeros_like(valid)
+    inliers[keep] = inl
+    n_lifted = torch.zeros(N, dtype=torch.int64, device=valid.device).index_add_(0, m_bids, valid.to(torch.int64))
+    data.update({"R_abs": R, "t_abs": t, "inliers": inliers, "n_inliers": n, "n_lifted": n_lifted})
+    return data
+
+
+def absolute_pose_error(T_gt, R, t):
+    """(rotation error in degrees, distance between the camera centres in the units of the depth) of an estimate x_cam = R X + t
+    against the ground truth T_gt [4,4] or [3,4] (same convention): the geodesic angle of R^T R_gt and |R^T t - R_gt^T t_gt|, the two
+    figures the localisation benchmarks (Aachen, InLoc) threshold."""
+    T_gt = np.asarray(T_gt.cpu() if isinstance(T_gt, torch.Tensor) else T_gt, np.float64)
+    R = np.asarray(R.cpu() if isinstance(R, torch.Tensor) else R, np.float64)
+    t = np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, np.float64)
+    gt_R, gt_t = T_gt[:3, :3], T_gt[:3, 3]
+    R_err = abs(_angle_deg((np.trace(R.T @ gt_R) - 1.0) / 2.0))
+    return R_err, float(np.linalg.norm(R.T @ t - gt_R.T @ gt_t))
+
+
+def localization_recall(t_errs, R_errs, thresholds=((0.25, 2), (0.5, 5), (5, 10))):
+    """Fraction of queries localised within each (distance, degrees) pair -- by default the Aachen Day-Night triples
+    (0.25 m, 2 deg), (0.5 m, 5 deg), (5 m, 10 deg).  A failed query carries inf errors.  -> {'recall@0.25/2': ...}."""
+    t_errs, R_errs = np.asarray(t_errs, np.float64), np.asarray(R_errs, np.float64)
+    out = {}
+    for dt, dr in thresholds:
+        out[f"recall@{dt:g}/{dr:g}"] = float(np.mean((t_errs <= dt) & (R_errs <= dr))) if len(t_errs) else 0.0
+    return out
 
 
 def homography_corner_errors(H, H_gt, hw):

@@ -1073,6 +1073,62 @@ def estimate_geometry(mkpts0_f, mkpts1_f, m_bids, P, model, thresh_px, conf, see
     return mat, inl.view(torch.bool), n
 
 
+@_on_device
+def estimate_absolute_poses(pts3d, kpts, m_bids, K, thresh_px, conf, seed=0):
+    """Absolute pose (P3P RANSAC + Gauss-Newton refit on the reprojection error) for every pair of a batch on the GPU
+    (csrc/absolute_pose_gpu.hip): for each pair, what the host estimator loftr_estimate_absolute_pose
+    (evaluation.estimate_absolute_pose_native) returns for that pair's 2D-3D matches with the same seed.
+    pts3d [M,3] f32 (units of the depth), kpts [M,2] f32 pixels of the camera to resect, m_bids [M] i64 grouped by ascending pair id,
+    K [P,3,3] f32 intrinsics of that camera per pair (upper triangular).
+    -> (R [P,3,3] f32, t [P,3] f32 with x_cam = R X + t, inliers [M] bool in match order, n_inliers [P] i64), device tensors;
+    n_inliers[p] == -1 where the host estimator finds no model (R, t and that pair's mask are zero there).  Synchronises the stream."""
+    for name, t, dt in (("pts3d", pts3d, torch.float32), ("kpts", kpts, torch.float32), ("m_bids", m_bids, torch.int64), ("K", K, torch.float32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise _lib.LoftrHipError(f"{name}: expected a {dt} GPU tensor (the absolute-pose kernels have no CPU fallback)")
+    M, P = pts3d.shape[0], K.shape[0]
+    if pts3d.shape != (M, 3) or kpts.shape != (M, 2) or m_bids.shape != (M,) or K.shape != (P, 3, 3):
+        raise _lib.LoftrHipError(f"estimate_absolute_poses: expected pts3d [M,3], kpts [M,2], m_bids [M] and K [P,3,3], got "
+                                 f"{tuple(pts3d.shape)}, {tuple(kpts.shape)}, {tuple(m_bids.shape)}, {tuple(K.shape)}")
+    dev = pts3d.device
+    args = [t.contiguous() for t in (pts3d, kpts, m_bids, K)]
+    R = torch.zeros(P, 3, 3, dtype=torch.float32, device=dev)
+    t = torch.zeros(P, 3, dtype=torch.float32, device=dev)
+    inl = torch.zeros(M, dtype=torch.uint8, device=dev)
+    n = torch.full((P,), -1, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_estimate_absolute_pose_batched_workspace_bytes(M, P)), dtype=torch.uint8, device=dev)
+    check(lib.loftr_estimate_absolute_pose_batched(*[_ptr(a) for a in args[:3]], M, _ptr(args[3]), P, float(thresh_px), float(conf), int(seed),
+                                                   _ptr(R), _ptr(t), _ptr(inl), _ptr(n), _ptr(ws), ws.numel(), _stream()),
+          "loftr_estimate_absolute_pose_batched (m_bids must lie in [0, P) and be grouped by ascending pair)")
+    return R, t, inl.view(torch.bool), n
+
+
+@_on_device
+def lift_keypoints(kpts, m_bids, depth, K, T=None):
+    """Matched keypoints of the image that has a depth map -> 3D points on the GPU (loftr_lift_keypoints: the first half of the
+    reference's warp_kpts, fp32): the depth at the keypoint rounded half to even, X = K^-1 (x d, y d, d) with the unrounded keypoint,
+    then the optional camera-to-world transform.
+    kpts [M,2] f32, m_bids [M] i64, depth [P,dh,dw] f32, K [P,3,3] f32, T [P,4,4] f32 or None.
+    -> (pts3d [M,3] f32, valid [M] bool): invalid (zero row) where the keypoint falls outside the map or the depth there is 0."""
+    for name, t, dt in (("kpts", kpts, torch.float32), ("m_bids", m_bids, torch.int64), ("depth", depth, torch.float32), ("K", K, torch.float32)) + \
+            ((("T", T, torch.float32),) if T is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+            raise _lib.LoftrHipError(f"{name}: expected a {dt} GPU tensor (the lifting kernel has no CPU fallback)")
+    M, P = kpts.shape[0], K.shape[0]
+    if kpts.shape != (M, 2) or m_bids.shape != (M,) or depth.dim() != 3 or depth.shape[0] != P or K.shape != (P, 3, 3) or \
+            (T is not None and T.shape != (P, 4, 4)):
+        raise _lib.LoftrHipError(f"lift_keypoints: expected kpts [M,2], m_bids [M], depth [P,dh,dw], K [P,3,3] and T [P,4,4] or None, got "
+                                 f"{tuple(kpts.shape)}, {tuple(m_bids.shape)}, {tuple(depth.shape)}, {tuple(K.shape)}, "
+                                 f"{None if T is None else tuple(T.shape)}")
+    dev = kpts.device
+    args = [None if t is None else t.contiguous() for t in (kpts, m_bids, depth, K, T)]
+    out = torch.zeros(M, 3, dtype=torch.float32, device=dev)
+    valid = torch.zeros(M, dtype=torch.uint8, device=dev)
+    check(_lib.load().loftr_lift_keypoints(_ptr(args[0]), _ptr(args[1]), M, _ptr(args[2]), depth.shape[1], depth.shape[2], _ptr(args[3]),
+                                           _ptr(args[4]), P, _ptr(out), _ptr(valid), _stream()), "loftr_lift_keypoints")
+    return out, valid.view(torch.bool)
+
+
 # ---- training-mode glue of the backbone (csrc/train_glue.hip; resnet_fpn.py:22-40,66-77,110-116) ------------------------------------------
 def _dense4(t, name):
     """A 4-D fp32 GPU tensor [N,C,H,W] stored densely either NCHW or NHWC (channels_last: what the convolution nodes produce); returns
