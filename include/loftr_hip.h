@@ -664,6 +664,65 @@ int loftr_estimate_absolute_pose_batched(const float* pts3d, const float* kpts, 
 int loftr_lift_keypoints(const float* kpts, const long* m_bids, long M, const float* depth, int dh, int dw, const float* K, const float* T,
                          int P, float* pts3d_out, uint8_t* valid_out, void* stream);
 
+/* ---- keypoint atlas: pair-list matches -> consolidated keypoints, index matches, tracks ------------------------------
+ * LoFTR has no detector: every pair yields fresh sub-pixel points.  The atlas snaps the matched points of each image to a grid of
+ * cell_px cells, keeps one keypoint per occupied cell, rewrites every row's matches as keypoint index pairs (one-to-one per row) and
+ * links them into tracks -- the step between the pair-list driver and any multi-view consumer.  All of it is integer and order-defined:
+ * loftr_atlas_host (csrc/atlas.hip, plain C++ on host arrays) DEFINES the result, loftr_atlas_observe + loftr_atlas_finalize
+ * (csrc/atlas_gpu.hip) reproduce it bit for bit, whatever the arrival order of the atomics.
+ *   Rule 1: cell = ((int)floorf(x * inv), (int)floorf(y * inv)), inv = fp32(1) / fp32(cell_px) computed by the caller, on a gw x gh grid per
+ *     image.  A match is dropped for the FIRST of these reasons (counts[4 + reason]; 0 = valid): 1 its m_bids entry is outside [0, n);
+ *     2 its mask byte is 0; 3 a coordinate or its confidence is not finite; 4 its confidence is negative; 5 a cell lies outside the grid.
+ *     Dropped matches contribute nothing (neither of their two observations is used).
+ *   Rule 2: one keypoint per (image, cell) with an observation: position and score of the observation with the greatest confidence, ties
+ *     to the smallest observation index (2 m + side, m the match index in arrival order); n_obs = observations in the cell; keypoints
+ *     ordered by image, then row-major by cell.
+ *   Rule 3: a match (k_a, k_b) is kept when, on each side, it is the best (greatest confidence, then smallest match index) among its ROW's
+ *     valid matches that share its keypoint on that side.  Kept matches stay in input order; matches hold LOCAL keypoint indices.
+ *   Rule 4: tracks = connected components over the kept matches; label = smallest global keypoint index; components of at least
+ *     min_track_len keypoints are numbered by ascending label; track_ok = no two keypoints of the component in one image.
+ * The rows of one observe call must come in ascending m_bids order (as the matcher emits them), so that matches are grouped by row.
+ * Limits (LOFTR_ERR_UNSUPPORTED beyond): M <= 2^31 - 2 matches, n_images * gh * gw < 2^31 cells, R <= 2^30 rows, gw, gh <= 2^24.
+ *
+ * Outputs (host memory for loftr_atlas_host, device memory for loftr_atlas_finalize), sized by the bound Kb = min(2 M, n_images gh gw):
+ *   kp_offsets [n_images+1] i64, keypoints [Kb,2] f32, score [Kb] f32, n_obs [Kb] i32, row_offsets [R+1] i64, matches [M,2] i32,
+ *   match_conf [M] f32, track_id [Kb] i32 (-1: none), track_len [Kb] i32, track_ok [Kb] u8, counts [16] i64:
+ *   counts[0] = K keypoints, [1] = Mk kept matches, [2] = T tracks, [3] = status bits of the observe calls (1: an m_bids entry out of
+ *   range, 2: m_bids not ascending), [4 + reason] = matches per reason.  Only the first K / Mk / T entries are written. */
+typedef struct {
+  long* kp_offsets; float* keypoints; float* score; int* n_obs;
+  long* row_offsets; int* matches; float* match_conf;
+  int* track_id; int* track_len; uint8_t* track_ok; long* counts;
+} LoftrAtlasOut;
+
+/* The defining host routine.  kpts0 / kpts1 [M,2] f32, conf [M] f32, rows [M] i32 global row of each match in ascending order, mask [M] u8
+ * or NULL, row_images [R,2] i32 (image of side 0 / side 1 of every row; a != b, both in [0, n_images)).
+ * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, rows out of [0, R) or not ascending, bad row_images; M == 0 and R == 0 succeed. */
+int loftr_atlas_host(const float* kpts0, const float* kpts1, const float* conf, const int* rows, const uint8_t* mask, long M,
+                     const int* row_images, long R, int n_images, int gh, int gw, float inv, int min_track_len, const LoftrAtlasOut* out);
+
+/* Observe (what KeypointAtlas.add runs; stream-ordered, never waits): one thread per match of the chunk.  Match i of the chunk is global
+ * match match_base + i and belongs to row row_base + m_bids[i]; its record (obs_xy [2 cap,2] f32, obs_cell [2 cap] i32 global cell or -1,
+ * m_conf [cap] f32, m_row [cap] i32, m_reason [cap] u8; cap >= match_base + n) is stored and each valid observation issues one 64-bit
+ * atomicMax into grid [n_images * gh * gw] u64 (zero before the first call).  row_images [>= row_base + n_rows, 2] i32 device,
+ * status [1] i32 device (zero before the first call; bits as counts[3]).  n == 0 is a no-op success. */
+int loftr_atlas_observe(const float* kpts0, const float* kpts1, const float* conf, const long* m_bids, const uint8_t* mask, long n,
+                        int n_rows, long match_base, long row_base, const int* row_images, int n_images, int gh, int gw, float inv,
+                        unsigned long long* grid, float* obs_xy, int* obs_cell, float* m_conf, int* m_row, uint8_t* m_reason, int* status,
+                        void* stream);
+
+/* Finalize: compact the grid into keypoints (the grid words become keypoint indices: one finalize per atlas), resolve the matches, apply
+ * the mutual-best rule through one open-addressing table (64-bit atomicCAS claims, 64-bit atomicMax reduces), union-find the kept edges,
+ * number the tracks.  Stream-ordered, no host synchronisation unless stage_ms is given: the caller reads counts back once and trims.
+ * stage_ms: NULL, or LOFTR_ATLAS_STAGES host floats that receive the GPU time of each stage (events; the call then waits for the stream):
+ * 0 compact, 1 resolve, 2 mutual best, 3 write matches, 4 union-find, 5 labels + lengths, 6 number tracks.
+ * Workspace: loftr_atlas_finalize_workspace_bytes(M, n_images, gh, gw): the table's 64 to 128 bytes per match (16 bytes per slot, a power of two of at least 4 M slots) plus 30 more. */
+#define LOFTR_ATLAS_STAGES 7
+size_t loftr_atlas_finalize_workspace_bytes(long M, int n_images, int gh, int gw);
+int loftr_atlas_finalize(unsigned long long* grid, const float* obs_xy, const int* obs_cell, const float* m_conf, const int* m_row,
+                         const uint8_t* m_reason, long M, long R, int n_images, int gh, int gw, int min_track_len, const int* status,
+                         const LoftrAtlasOut* out, void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the
  * bottom / right (pad_bottom_right), `float / 255`, the padding mask and its coarse version

@@ -6,3 +6,4 @@ Public surface mirrors ``src.loftr`` of zju3dv/LoFTR (src/loftr/__init__.py:1-2)
 from .config import default_cfg, full_default_cfg, get_cfg       # noqa: F401
 from .loftr import LoFTR                                           # noqa: F401
 from .pairs import FeatureBank                                     # noqa: F401
+from .atlas import KeypointAtlas, SfmResult                       # noqa: F401

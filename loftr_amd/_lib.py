@@ -41,6 +41,11 @@ class FMap(C.Structure):
     _fields_ = [("data", _p), ("sn", _l), ("sc", _l), ("sh", _l), ("sw", _l), ("H", _i), ("W", _i)]
 
 
+class AtlasOut(C.Structure):
+    _fields_ = [(n, _p) for n in ("kp_offsets", "keypoints", "score", "n_obs", "row_offsets", "matches", "match_conf",
+                                  "track_id", "track_len", "track_ok", "counts")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/loftr_hip.h
 SIGNATURES = {
     "loftr_hip_abi_version": (_i, []),
@@ -127,6 +132,10 @@ SIGNATURES = {
     "loftr_estimate_absolute_pose_batched_workspace_bytes": (_sz, [_l, _i]),
     "loftr_estimate_absolute_pose_batched": (_i, [_p, _p, _p, _l, _p, _i, _f, _f, C.c_uint, _p, _p, _p, _p, _p, _sz, _p]),
     "loftr_lift_keypoints": (_i, [_p, _p, _l, _p, _i, _i, _p, _p, _i, _p, _p, _p]),
+    "loftr_atlas_host": (_i, [_p, _p, _p, _p, _p, _l, _p, _l, _i, _i, _i, _f, _i, C.POINTER(AtlasOut)]),
+    "loftr_atlas_observe": (_i, [_p, _p, _p, _p, _p, _l, _i, _l, _l, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "loftr_atlas_finalize_workspace_bytes": (_sz, [_l, _i, _i, _i]),
+    "loftr_atlas_finalize": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, C.POINTER(AtlasOut), _p, _sz, _p, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

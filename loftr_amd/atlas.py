@@ -1,0 +1,260 @@
+"""Keypoint atlas: from the matches of a pair list to consolidated keypoints, index matches and tracks.
+
+LoFTR has no detector.  ``mkpts1_f`` is a fresh sub-pixel point in every pair, ``mkpts0_f`` sits on the coarse grid, and an image is
+side 0 in some rows of a pair list and side 1 in others, so two rows that share an image share no keypoint.  Multi-view consumers
+(COLMAP / hloc-style SfM, triangulation, localisation from database poses) need the opposite: repeatable keypoints per image, matches
+as index pairs, and tracks.  ``KeypointAtlas`` builds them on the device while the pair list is being matched::
+
+    atlas = KeypointAtlas(n_images, image_hw, cell_px=2.0, device=dev)
+    for rows, data in pairs.match_pair_list(model, pair_list, load, hw):
+        atlas.add(pair_list[rows.start:rows.stop], data, mask=data.get("inliers"))     # no host synchronisation
+    sfm = atlas.finalize(min_track_len=2)
+
+The rules (include/loftr_hip.h):
+
+1. every matched point falls into a ``cell_px`` cell of its image; a match whose mask bit is clear, whose numbers are not finite, whose
+   confidence is negative or whose points leave the grid is counted in ``stats`` and otherwise ignored;
+2. every occupied cell is one keypoint: position and score of its most confident observation (ties: the earliest), ordered by image,
+   then row-major by cell;
+3. within a row, a match is kept when it is the best of its keypoint on both sides (mutual best, one-to-one per row);
+4. tracks are the connected components of the kept matches; ``track_ok`` is false when a track visits an image twice.
+
+Everything is integer and order-defined: the host routine ``loftr_atlas_host`` defines the result (``device='cpu'`` runs it), the HIP
+kernels reproduce it bit for bit.
+"""
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import LoftrHipError
+
+_KEYS = ("mkpts0_f", "mkpts1_f", "mconf", "m_bids")
+
+
+def _grid(image_hw, cell_px):
+    """(inv, gh, gw): the fp32 reciprocal of the cell size that host and device multiply by, and the grid it gives."""
+    H, W = float(image_hw[0]), float(image_hw[1])
+    cell = np.float32(cell_px)
+    if not (np.isfinite(cell) and cell > 0 and H > 0 and W > 0):
+        raise ValueError(f"KeypointAtlas: image_hw and cell_px must be positive, got {tuple(image_hw)}, {cell_px}")
+    inv = np.float32(1) / cell
+    gh, gw = int(np.ceil(np.float32(H) * inv)), int(np.ceil(np.float32(W) * inv))
+    if max(gh, gw) > 1 << 24:
+        raise ValueError(f"KeypointAtlas: a {gh} x {gw} grid is beyond the supported 2^24 cells per side")
+    return float(inv), gh, gw
+
+
+class SfmResult:
+    """What ``KeypointAtlas.finalize`` returns (tensors on the atlas's device).
+
+    ``kp_offsets [n_images+1] i64`` delimits the images in ``keypoints [K,2] f32``, ``score [K] f32``, ``n_obs [K] i32``;
+    ``row_offsets [R+1] i64`` delimits the rows in ``matches [Mk,2] i32`` (LOCAL keypoint indices of image a / image b of the row)
+    and ``match_conf [Mk] f32``; ``track_id [K] i32`` (-1: none), ``track_len [T] i32``, ``track_ok [T] bool``; ``row_images [R,2] i32``;
+    ``stats``: dict of counts."""
+
+    FIELDS = ("kp_offsets", "keypoints", "score", "n_obs", "row_offsets", "matches", "match_conf", "track_id", "track_len", "track_ok",
+              "row_images")
+
+    def __init__(self, stats, **tensors):
+        self.stats = stats
+        for k in self.FIELDS:
+            setattr(self, k, tensors[k])
+
+    def keypoint_image(self):
+        """Image of every keypoint [K] i64."""
+        n = self.kp_offsets.numel() - 1
+        return torch.repeat_interleave(torch.arange(n, device=self.kp_offsets.device), self.kp_offsets[1:] - self.kp_offsets[:-1])
+
+    def tracks(self, consistent_only=True):
+        """CSR view of the tracks: (offsets [T'+1] i64, image [N] i64, local keypoint [N] i64), tracks in ascending id, the keypoints of
+        a track in ascending global index (so by image).  consistent_only drops the tracks with track_ok false."""
+        tid = self.track_id.to(torch.int64)
+        use = tid >= 0
+        ok = self.track_ok if consistent_only else torch.ones_like(self.track_ok)
+        if tid.numel():
+            use &= ok[tid.clamp(min=0)] if ok.numel() else torch.zeros_like(use)
+        kp = torch.nonzero(use).reshape(-1)
+        order = torch.sort(tid[kp], stable=True).indices
+        kp = kp[order]
+        image = self.keypoint_image()[kp]
+        counts = torch.bincount(tid[kp], minlength=self.track_len.numel())[ok]
+        offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=tid.device)
+        offsets[1:] = torch.cumsum(counts, 0)
+        return offsets, image, kp - self.kp_offsets[image]
+
+    def to_host(self):
+        """dict of numpy arrays (plus 'stats')."""
+        out = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}
+        out["stats"] = dict(self.stats)
+        return out
+
+
+class KeypointAtlas:
+    """Accumulates the matches of a pair list (``add``) and consolidates them (``finalize``); see the module docstring.
+
+    ``image_hw``: extents (H, W) of the keypoint coordinates (after scale0 / scale1), the same for every image.  ``device='cpu'`` runs the
+    defining host routine on host arrays; a GPU device keeps everything on it: one 8-byte word per cell of every image
+    (``bytes_needed``; refused beyond ``max_bytes``, default half the free device memory) plus 29 bytes per match, grown geometrically
+    from ``capacity`` matches."""
+
+    def __init__(self, n_images, image_hw, cell_px=2.0, device="cuda", max_bytes=None, capacity=4096):
+        self.n_images = int(n_images)
+        if self.n_images < 1:
+            raise ValueError(f"KeypointAtlas: n_images must be positive, got {n_images}")
+        self.image_hw = (float(image_hw[0]), float(image_hw[1]))
+        self.cell_px = float(cell_px)
+        self.inv, self.gh, self.gw = _grid(image_hw, cell_px)
+        if self.n_images * self.gh * self.gw >= 2 ** 31:
+            raise ValueError(f"KeypointAtlas: {self.n_images} images of {self.gh} x {self.gw} cells are beyond the supported 2^31 cells")
+        self.device = torch.device(device)
+        self.n_rows = 0
+        self.n_matches = 0
+        self._done = False
+        need = self.bytes_needed(n_images, image_hw, cell_px)
+        if self.device.type != "cuda":
+            if self.device.type != "cpu":
+                raise LoftrHipError(f"KeypointAtlas: device must be a GPU or 'cpu' (the host routine), got {self.device}")
+            self._chunks, self._row_images = [], []
+            return
+        if not torch.cuda.is_available():
+            raise LoftrHipError("KeypointAtlas: no GPU here; device='cpu' runs the host routine (there is no silent fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        if need > int(max_bytes):
+            raise ValueError(f"KeypointAtlas: the cell grid needs {need} bytes ({self.n_images} images x {self.gh} x {self.gw} cells x 8), "
+                             f"more than max_bytes = {int(max_bytes)}; use a larger cell_px")
+        self.grid = torch.zeros(self.n_images * self.gh * self.gw, dtype=torch.int64, device=self.device)
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._cap = self._row_cap = 0
+        self._store = {}
+        self._rows_dev = None
+        self._reserve(max(1, int(capacity)), 16)
+
+    @staticmethod
+    def bytes_needed(n_images, image_hw, cell_px=2.0):
+        """Device bytes of the cell grid: one 64-bit word per cell of every image."""
+        _, gh, gw = _grid(image_hw, cell_px)
+        return 8 * int(n_images) * gh * gw
+
+    # ---- storage: grows geometrically, like a list; the copies are stream-ordered --------------------------------------------------
+    _LAYOUT = (("obs_xy", 4, torch.float32), ("obs_cell", 2, torch.int32), ("m_conf", 1, torch.float32), ("m_row", 1, torch.int32),
+               ("m_reason", 1, torch.uint8))
+
+    def _reserve(self, matches, rows):
+        if matches > self._cap:
+            cap = max(matches, 2 * self._cap)
+            for name, width, dt in self._LAYOUT:
+                new = torch.empty(cap * width, dtype=dt, device=self.device)
+                if self.n_matches:
+                    new[:self.n_matches * width].copy_(self._store[name][:self.n_matches * width])
+                self._store[name] = new
+            self._cap = cap
+        if rows > self._row_cap:
+            cap = max(rows, 2 * self._row_cap)
+            new = torch.empty(cap, 2, dtype=torch.int32, device=self.device)
+            if self.n_rows:
+                new[:self.n_rows].copy_(self._rows_dev[:self.n_rows])
+            self._rows_dev, self._row_cap = new, cap
+
+    def add(self, image_ids, data, mask=None):
+        """Add the matches of ``n`` pair-list rows.  ``image_ids`` [n,2]: images (a, b) of the rows; ``data``: the dict that ``forward`` /
+        ``match_pairs`` leaves for them (``mkpts0_f``, ``mkpts1_f``, ``mconf``, ``m_bids``; ``m_bids`` in [0, n), ascending, as the matcher
+        emits them); ``mask`` [M] bool: matches to use (e.g. ``data['inliers']`` of ``verify_matches``).  Rows get ids in arrival order.
+        On a GPU nothing here waits for the device: ``m_bids`` that live there are checked by the kernel and reported by ``finalize``."""
+        if self._done:
+            raise ValueError("KeypointAtlas.add: the atlas is finalized; build a new one")
+        ids = np.asarray(image_ids.cpu() if isinstance(image_ids, torch.Tensor) else image_ids)
+        if ids.ndim != 2 or ids.shape[1] != 2 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"KeypointAtlas.add: image_ids must be an integer array [n, 2], got {ids.shape} {ids.dtype}")
+        n = ids.shape[0]
+        if n and (ids.min() < 0 or ids.max() >= self.n_images):
+            raise ValueError(f"KeypointAtlas.add: image ids outside [0, {self.n_images}): {ids[((ids < 0) | (ids >= self.n_images)).any(1)][:8].tolist()}")
+        if n and (ids[:, 0] == ids[:, 1]).any():
+            raise ValueError(f"KeypointAtlas.add: rows that pair an image with itself: {np.nonzero(ids[:, 0] == ids[:, 1])[0][:8].tolist()}")
+        missing = [k for k in _KEYS if k not in data]
+        if missing:
+            raise ValueError(f"KeypointAtlas.add: data lacks {missing} (pass the dict that forward / match_pairs leaves)")
+        t = [torch.as_tensor(data[k]) for k in _KEYS]
+        M = t[0].shape[0]
+        if tuple(t[0].shape) != (M, 2) or tuple(t[1].shape) != (M, 2) or tuple(t[2].shape) != (M,) or tuple(t[3].shape) != (M,):
+            raise ValueError(f"KeypointAtlas.add: expected mkpts0_f / mkpts1_f [M,2], mconf / m_bids [M], got {[tuple(x.shape) for x in t]}")
+        if t[3].dtype.is_floating_point or t[3].dtype == torch.bool:
+            raise ValueError(f"KeypointAtlas.add: m_bids must be integers, got {t[3].dtype}")
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            if tuple(mask.shape) != (M,) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"KeypointAtlas.add: mask must be bool [{M}], got {tuple(mask.shape)} {mask.dtype}")
+        for x in t + ([mask] if mask is not None else []):
+            if x.is_cuda and x.device != self.device:
+                raise LoftrHipError(f"KeypointAtlas.add: data on {x.device}, the atlas on {self.device}")
+        if M and n == 0:
+            raise ValueError(f"KeypointAtlas.add: {M} matches but no row")
+        if M and not t[3].is_cuda:                                 # host ids: checked here; device ids: by the kernel, reported by finalize
+            self._check_bids(t[3].numpy(), n)
+        if self.n_matches + M > 2 ** 31 - 2:
+            raise ValueError("KeypointAtlas.add: more than 2^31 - 2 matches")
+        ids32 = np.ascontiguousarray(ids, np.int32)
+        if self.device.type == "cpu":
+            k0, k1, c = (x.detach().to("cpu", torch.float32).numpy().copy() for x in t[:3])
+            bids = t[3].detach().cpu().numpy()
+            self._check_bids(bids, n)
+            self._chunks.append((k0, k1, c, (self.n_rows + bids).astype(np.int32),
+                                 np.ones(M, np.uint8) if mask is None else (mask.detach().cpu().numpy() != 0).astype(np.uint8)))
+            self._row_images.append(ids32)
+        else:
+            self._reserve(self.n_matches + M, self.n_rows + n)
+            with torch.cuda.device(self.device):
+                if n:
+                    self._rows_dev[self.n_rows:self.n_rows + n].copy_(torch.from_numpy(ids32), non_blocking=True)
+                if M:
+                    k0, k1, c = (x.detach().to(self.device, torch.float32, non_blocking=True).contiguous() for x in t[:3])
+                    bids = t[3].detach().to(self.device, torch.int64, non_blocking=True).contiguous()
+                    mk = None if mask is None else mask.detach().to(self.device, non_blocking=True).to(torch.uint8).contiguous()
+                    s = self._store
+                    ops.atlas_observe(k0, k1, c, bids, mk, n, self.n_matches, self.n_rows, self._rows_dev, self.n_images, self.gh, self.gw,
+                                      self.inv, self.grid, s["obs_xy"], s["obs_cell"], s["m_conf"], s["m_row"], s["m_reason"], self._status)
+        self.n_rows += n
+        self.n_matches += M
+
+    @staticmethod
+    def _check_bids(bids, n):
+        if bids.size and (bids.min() < 0 or bids.max() >= n):
+            raise ValueError(f"KeypointAtlas.add: m_bids outside [0, {n})")
+        if bids.size and (np.diff(bids) < 0).any():
+            raise ValueError("KeypointAtlas.add: m_bids must ascend (matches grouped by row, as the matcher emits them)")
+
+    def finalize(self, min_track_len=2, timings=None):
+        """Consolidate: -> SfmResult.  One readback of a constant number of counts (K, Mk, T, status, reasons), whatever the number of
+        rows or images.  The atlas accepts no ``add`` afterwards.  timings: a list that receives (stage, ms) pairs of the GPU stages."""
+        if self._done:
+            raise ValueError("KeypointAtlas.finalize: the atlas is already finalized")
+        if int(min_track_len) < 1:
+            raise ValueError(f"KeypointAtlas.finalize: min_track_len must be at least 1, got {min_track_len}")
+        M, R = self.n_matches, self.n_rows
+        if self.device.type == "cpu":
+            cat = lambda i, shape, dt: np.concatenate([c[i] for c in self._chunks]) if self._chunks else np.zeros(shape, dt)
+            rows = np.concatenate(self._row_images) if self._row_images else np.zeros((0, 2), np.int32)
+            out = ops.atlas_host(cat(0, (0, 2), np.float32), cat(1, (0, 2), np.float32), cat(2, (0,), np.float32), cat(3, (0,), np.int32),
+                                 cat(4, (0,), np.uint8), rows, self.n_images, self.gh, self.gw, self.inv, int(min_track_len))
+            out = {k: torch.from_numpy(v) for k, v in out.items()}
+            row_images = torch.from_numpy(rows)
+        else:
+            s = self._store
+            out = ops.atlas_finalize(self.grid, s["obs_xy"], s["obs_cell"], s["m_conf"], s["m_row"], s["m_reason"], self._status, M, R,
+                                     self.n_images, self.gh, self.gw, int(min_track_len), timings=timings)
+            row_images = self._rows_dev[:R]
+        self._done = True
+        counts = out["counts"].cpu().tolist()                      # the one readback
+        K, Mk, T, status = counts[:4]
+        if status & 1:
+            raise ValueError("KeypointAtlas: an add received m_bids outside [0, n) (found on the device)")
+        if status & 2:
+            raise ValueError("KeypointAtlas: an add received m_bids that do not ascend (found on the device)")
+        stats = {"n_images": self.n_images, "n_rows": R, "n_matches": M, "n_keypoints": K, "n_kept": Mk, "n_tracks": T}
+        stats.update({name: counts[4 + i] for i, name in enumerate(ops.ATLAS_REASONS) if name != "n_bad_row"})
+        return SfmResult(stats, kp_offsets=out["kp_offsets"], keypoints=out["keypoints"][:K], score=out["score"][:K], n_obs=out["n_obs"][:K],
+                         row_offsets=out["row_offsets"], matches=out["matches"][:Mk], match_conf=out["match_conf"][:Mk],
+                         track_id=out["track_id"][:K], track_len=out["track_len"][:T], track_ok=out["track_ok"][:T].to(torch.bool),
+                         row_images=row_images)

@@ -1129,6 +1129,99 @@ def lift_keypoints(kpts, m_bids, depth, K, T=None):
     return out, valid.view(torch.bool)
 
 
+# ---- keypoint atlas (csrc/atlas.hip, csrc/atlas_gpu.hip) -----------------------------------------------------------------
+ATLAS_COUNTS = 16
+ATLAS_REASONS = ("n_valid", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside")     # counts[4 + reason]
+ATLAS_STAGES = ("compact", "resolve", "mutual_best", "write_matches", "union_find", "labels", "number_tracks")
+
+
+def _atlas_out(arrays, ptr):
+    return _lib.AtlasOut(**{k: ptr(arrays[k]) for k, _ in _lib.AtlasOut._fields_})
+
+
+def atlas_host(kpts0, kpts1, conf, rows, mask, row_images, n_images, gh, gw, inv, min_track_len):
+    """loftr_atlas_host: the host routine that DEFINES the atlas (rules 1-4 of include/loftr_hip.h) on numpy arrays.
+    kpts0 / kpts1 [M,2] f32, conf [M] f32, rows [M] i32 ascending, mask [M] u8 or None, row_images [R,2] i32.
+    -> dict of numpy arrays of the bound sizes (see LoftrAtlasOut) with 'counts' [16] i64; the caller trims by counts[0..2]."""
+    import numpy as np
+    k0, k1 = (np.ascontiguousarray(a, np.float32).reshape(-1, 2) for a in (kpts0, kpts1))
+    c = np.ascontiguousarray(conf, np.float32).reshape(-1)
+    r = np.ascontiguousarray(rows, np.int32).reshape(-1)
+    ri = np.ascontiguousarray(row_images, np.int32).reshape(-1, 2)
+    mk = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    M, R = k0.shape[0], ri.shape[0]
+    if k1.shape[0] != M or c.shape[0] != M or r.shape[0] != M or (mk is not None and mk.shape[0] != M):
+        raise ValueError(f"atlas_host: kpts0, kpts1, conf, rows and mask must agree on M, got {k0.shape}, {k1.shape}, {c.shape}, {r.shape}")
+    Kb = max(1, min(2 * M, int(n_images) * int(gh) * int(gw)))
+    out = {"kp_offsets": np.zeros(int(n_images) + 1, np.int64), "keypoints": np.zeros((Kb, 2), np.float32), "score": np.zeros(Kb, np.float32),
+           "n_obs": np.zeros(Kb, np.int32), "row_offsets": np.zeros(R + 1, np.int64), "matches": np.zeros((max(M, 1), 2), np.int32),
+           "match_conf": np.zeros(max(M, 1), np.float32), "track_id": np.full(Kb, -1, np.int32), "track_len": np.zeros(Kb, np.int32),
+           "track_ok": np.zeros(Kb, np.uint8), "counts": np.zeros(ATLAS_COUNTS, np.int64)}
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    st = _atlas_out(out, ptr)
+    check(_lib.load().loftr_atlas_host(ptr(k0), ptr(k1), ptr(c), ptr(r), ptr(mk), M, ptr(ri), R, int(n_images), int(gh), int(gw), float(inv),
+                                       int(min_track_len), C.byref(st)),
+          "loftr_atlas_host (rows must ascend within [0, R); row images must differ and lie in [0, n_images))")
+    return out
+
+
+@_on_device
+def atlas_observe(kpts0, kpts1, conf, m_bids, mask, n_rows, match_base, row_base, row_images, n_images, gh, gw, inv, grid, obs_xy, obs_cell,
+                  m_conf, m_row, m_reason, status):
+    """loftr_atlas_observe: record one chunk of matches and max them into the cell grid (stream-ordered, never waits).
+    kpts0 / kpts1 [n,2] f32, conf [n] f32, m_bids [n] i64, mask [n] u8 or None; the remaining tensors are the atlas's storage."""
+    n = kpts0.shape[0]
+    for name, t, dt in (("kpts0", kpts0, torch.float32), ("kpts1", kpts1, torch.float32), ("conf", conf, torch.float32),
+                        ("m_bids", m_bids, torch.int64), ("row_images", row_images, torch.int32), ("grid", grid, torch.int64),
+                        ("obs_xy", obs_xy, torch.float32), ("obs_cell", obs_cell, torch.int32), ("m_conf", m_conf, torch.float32),
+                        ("m_row", m_row, torch.int32), ("m_reason", m_reason, torch.uint8), ("status", status, torch.int32)) + \
+            ((("mask", mask, torch.uint8),) if mask is not None else ()):
+        _need(t, name, dt)
+    if kpts0.shape != (n, 2) or kpts1.shape != (n, 2) or conf.shape != (n,) or m_bids.shape != (n,) or (mask is not None and mask.shape != (n,)):
+        raise _lib.LoftrHipError(f"atlas_observe: expected kpts0 / kpts1 [n,2], conf / m_bids / mask [n], got {tuple(kpts0.shape)}, "
+                                 f"{tuple(kpts1.shape)}, {tuple(conf.shape)}, {tuple(m_bids.shape)}")
+    end = int(match_base) + n
+    if obs_xy.numel() < 4 * end or obs_cell.numel() < 2 * end or min(m_conf.numel(), m_row.numel(), m_reason.numel()) < end or \
+            row_images.numel() < 2 * (int(row_base) + int(n_rows)) or grid.numel() != int(n_images) * int(gh) * int(gw):
+        raise _lib.LoftrHipError("atlas_observe: the atlas storage is smaller than the matches it is asked to hold")
+    check(_lib.load().loftr_atlas_observe(_ptr(kpts0), _ptr(kpts1), _ptr(conf), _ptr(m_bids), _ptr(mask), n, int(n_rows), int(match_base),
+                                          int(row_base), _ptr(row_images), int(n_images), int(gh), int(gw), float(inv), _ptr(grid), _ptr(obs_xy),
+                                          _ptr(obs_cell), _ptr(m_conf), _ptr(m_row), _ptr(m_reason), _ptr(status), _stream()),
+          "loftr_atlas_observe")
+
+
+@_on_device
+def atlas_finalize(grid, obs_xy, obs_cell, m_conf, m_row, m_reason, status, M, R, n_images, gh, gw, min_track_len, timings=None):
+    """loftr_atlas_finalize: keypoints, index matches and tracks from the observed matches (one finalize per grid: its words become
+    keypoint indices).  -> dict of device tensors of the bound sizes (see LoftrAtlasOut) with 'counts' [16] i64; nothing is read back
+    here -- the caller reads counts once and trims.  timings: a list that receives (stage, ms) pairs (the call then waits for the stream)."""
+    for name, t, dt in (("grid", grid, torch.int64), ("obs_xy", obs_xy, torch.float32), ("obs_cell", obs_cell, torch.int32),
+                        ("m_conf", m_conf, torch.float32), ("m_row", m_row, torch.int32), ("m_reason", m_reason, torch.uint8),
+                        ("status", status, torch.int32)):
+        _need(t, name, dt)
+    M, R = int(M), int(R)
+    G = int(n_images) * int(gh) * int(gw)
+    if grid.numel() != G or obs_xy.numel() < 4 * M or obs_cell.numel() < 2 * M or min(m_conf.numel(), m_row.numel(), m_reason.numel()) < M:
+        raise _lib.LoftrHipError("atlas_finalize: the atlas storage is smaller than the matches it is said to hold")
+    dev = grid.device
+    Kb = max(1, min(2 * M, G))
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = {"kp_offsets": e(int(n_images) + 1, torch.int64), "keypoints": e((Kb, 2), torch.float32), "score": e(Kb, torch.float32),
+           "n_obs": e(Kb, torch.int32), "row_offsets": e(R + 1, torch.int64), "matches": e((max(M, 1), 2), torch.int32),
+           "match_conf": e(max(M, 1), torch.float32), "track_id": e(Kb, torch.int32), "track_len": e(Kb, torch.int32),
+           "track_ok": e(Kb, torch.uint8), "counts": e(ATLAS_COUNTS, torch.int64)}
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_atlas_finalize_workspace_bytes(M, int(n_images), int(gh), int(gw))), dtype=torch.uint8, device=dev)
+    st = _atlas_out(out, _ptr)
+    ms = (C.c_float * len(ATLAS_STAGES))() if timings is not None else None
+    check(lib.loftr_atlas_finalize(_ptr(grid), _ptr(obs_xy), _ptr(obs_cell), _ptr(m_conf), _ptr(m_row), _ptr(m_reason), M, R, int(n_images),
+                                   int(gh), int(gw), int(min_track_len), _ptr(status), C.byref(st), _ptr(ws), ws.numel(),
+                                   C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_atlas_finalize")
+    if timings is not None:
+        timings.extend(zip(ATLAS_STAGES, (float(v) for v in ms)))
+    return out
+
+
 # ---- training-mode glue of the backbone (csrc/train_glue.hip; resnet_fpn.py:22-40,66-77,110-116) ------------------------------------------
 def _dense4(t, name):
     """A 4-D fp32 GPU tensor [N,C,H,W] stored densely either NCHW or NHWC (channels_last: what the convolution nodes produce); returns
