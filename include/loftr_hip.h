@@ -58,7 +58,9 @@ typedef enum {
  *     loftr_geometry_minimal, loftr_estimate_geometry_batched, loftr_estimate_geometry_batched_workspace_bytes), both convolutions
  *     of the fine head at matched windows (loftr_window_head_first, loftr_window_head_last, loftr_fine_preprocess_window_head2),
  *     absolute pose from matches and depth (loftr_estimate_absolute_pose, loftr_p3p, loftr_estimate_absolute_pose_batched,
- *     loftr_estimate_absolute_pose_batched_workspace_bytes, loftr_lift_keypoints) */
+ *     loftr_estimate_absolute_pose_batched_workspace_bytes, loftr_lift_keypoints), the keypoint atlas (loftr_atlas_*), triangulation
+ *     of tracks (loftr_triangulate_tracks_host, loftr_triangulation_pairs, loftr_triangulate_tracks,
+ *     loftr_triangulate_tracks_workspace_bytes) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -722,6 +724,59 @@ size_t loftr_atlas_finalize_workspace_bytes(long M, int n_images, int gh, int gw
 int loftr_atlas_finalize(unsigned long long* grid, const float* obs_xy, const int* obs_cell, const float* m_conf, const int* m_row,
                          const uint8_t* m_reason, long M, long R, int n_images, int gh, int gw, int min_track_len, const int* status,
                          const LoftrAtlasOut* out, void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
+/* ---- triangulation of tracks from known camera poses (csrc/triangulate_core.h holds all the arithmetic) -----------------
+ * From the tracks of an atlas plus database poses to one 3D point per track: what hloc / COLMAP's point triangulator is used for before
+ * localisation against an SfM model.  loftr_triangulate_tracks_host (csrc/triangulate.hip, host memory) DEFINES the result,
+ * loftr_triangulate_tracks (csrc/triangulate_gpu.hip, device memory) reproduces it bit for bit, whatever `group` is.
+ * Input: tracks in CSR form -- offsets [T+1] i64 (0 first, N last, ascending), obs_image [N] i32 in [0, n_images), obs_xy [N,2] f32
+ *   pixels; K [n_images,3,3] f64 (only fx, skew, cx, fy, cy are read), T_cam_from_world [n_images,4,4] f64 (the top 3 x 4; R is taken as
+ *   orthonormal and not checked); thresh_px; cos_min_angle = cos(minimum triangulation angle), computed by the caller.
+ * Arithmetic: fp64 without FMA contraction, + - * / sqrt only.
+ * Per image (24 doubles): P = K [R | t], centre c = -R^T t, M = R^T K^-1 (K^-1 by back substitution).  A camera is INVALID when an
+ *   entry read, or an entry of its table, is not finite, or fx or fy is 0.
+ * Per track with observations 0 .. L-1 in CSR order:
+ *   1. rays: d_i = M_i (u, v, 1), normalised.
+ *   2. hypothesis pairs, no random numbers: for s = 1 .. L/2 and, inside, i = 0 .. L-1 (only to L/2 - 1 when 2 s = L) the pair
+ *      (i, (i + s) mod L); the enumeration stops after 64 pairs (every pair for L <= 11; loftr_triangulation_pairs exposes it).
+ *   3. hypothesis h from pair (i, j): the midpoint of the two rays.  w = c_i - c_j, a = d_i.d_i, b = d_i.d_j, c = d_j.d_j, d = d_i.w,
+ *      e = d_j.w, den = a c - b^2; rejected if den <= 1e-12 a c, if b / sqrt(a c) > cos_min_angle, or if s = (b e - c d) / den <= 0 or
+ *      t = (a e - b d) / den <= 0 (two observations of one image reject themselves here);
+ *      X = ((c_i + s d_i) + (c_j + t d_j)) / 2.  A NaN in any comparison rejects.
+ *   4. observation k is an inlier iff p = P_k (X, 1) has p_z > 0 and its squared pixel distance is <= thresh_px^2; a hypothesis whose
+ *      own two observations are not both inliers is discarded.
+ *   5. best = greatest inlier count, then smallest h: one unsigned 64-bit maximum of count << 32 | (0xFFFFFFFF - h), 0 = none.
+ *   6. refit: five Gauss-Newton steps (three unknowns) on the pixel reprojection error over the inliers of the current point; J^T J and
+ *      J^T r summed sequentially in ascending observation order (p_z <= 0 adds nothing); 3 x 3 elimination in a fixed order without
+ *      pivoting; a non-positive pivot or a non-finite step fails the fit and keeps the point.  A fit is adopted when it keeps at least
+ *      as many inliers and repeated on the adopted point's inliers while the count strictly grows, at most 4 fits.
+ *   7. tri_cos = the smallest cosine between X - c_i and X - c_j over the pairs of step 2 whose two observations are final inliers (a
+ *      pair with a zero-length ray is skipped); status small_angle when tri_cos > cos_min_angle or no such pair exists.
+ * Output per track: xyz [T,3] f32 (the fp64 point rounded once; NaN unless status is ok), n_inliers [T] i32 and rms_px [T] f32 (root
+ *   mean squared pixel error over the final inliers) and tri_cos [T] f32 (0 / NaN / NaN unless ok or small_angle; tri_cos NaN without
+ *   a pair), status [T] u8: 0 ok, 1 too_short (L < 2), 2 no_hypothesis, 3 small_angle, 4 bad_camera (L >= 2 and the track touches an
+ *   invalid camera).  Per observation: obs_inlier [N] u8, zero for tracks that are not ok.
+ *   counts [8] i64: [0..4] tracks per status, [5] error bits found on the device (1: an obs_image outside [0, n_images), 2: offsets
+ *   that do not start at 0, end at N and ascend), [6] inlier observations of the ok tracks, [7] 0.
+ * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, thresh_px < 0, cos_min_angle outside [-1, 1], group outside {0, 8, 64};
+ *   the host routine also for bad obs_image / offsets (the kernels raise counts[5] instead: they never wait for the device, and no
+ *   output is defined then); LOFTR_ERR_UNSUPPORTED for T or N >= 2^31; LOFTR_ERR_WORKSPACE for a short workspace. */
+int loftr_triangulate_tracks_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, long N, const double* K,
+                                  const double* T_cam_from_world, int n_images, double thresh_px, double cos_min_angle, float* xyz,
+                                  int* n_inliers, float* rms_px, float* tri_cos, uint8_t* status, uint8_t* obs_inlier, long* counts);
+/* The pairs of step 2 for a track of L observations: pairs [64,2] (the first *n rows written), *n = min(64, L (L - 1) / 2). */
+int loftr_triangulation_pairs(int L, int* pairs, int* n);
+/* The kernels.  group: 0 = a group of 8 lanes per track of at most 64 observations and of 64 lanes per longer track (two launches over
+ * all tracks; the boundary is a measured tuning constant), 8 / 64 = that group size for every track (one launch); the result does not depend on it.  Stream-ordered, no host
+ * synchronisation unless stage_ms is given: NULL, or LOFTR_TRIANGULATE_STAGES host floats that receive the GPU time (events; the call
+ * then waits for the stream) of 0 the camera table, 1 the 8-lane launch, 2 the 64-lane launch.
+ * Workspace: loftr_triangulate_tracks_workspace_bytes(T, N, n_images), the camera table (192 bytes per image); 0 for sizes out of range. */
+#define LOFTR_TRIANGULATE_STAGES 3
+size_t loftr_triangulate_tracks_workspace_bytes(long T, long N, int n_images);
+int loftr_triangulate_tracks(const long* offsets, long T, const int* obs_image, const float* obs_xy, long N, const double* K,
+                             const double* T_cam_from_world, int n_images, double thresh_px, double cos_min_angle, float* xyz,
+                             int* n_inliers, float* rms_px, float* tri_cos, uint8_t* status, uint8_t* obs_inlier, long* counts, int group,
+                             void* ws, size_t ws_bytes, float* stage_ms, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

@@ -7,3 +7,4 @@ from .config import default_cfg, full_default_cfg, get_cfg       # noqa: F401
 from .loftr import LoFTR                                           # noqa: F401
 from .pairs import FeatureBank                                     # noqa: F401
 from .atlas import KeypointAtlas, SfmResult                       # noqa: F401
+from .triangulation import Points3D, triangulate_tracks           # noqa: F401

@@ -136,6 +136,10 @@ SIGNATURES = {
     "loftr_atlas_observe": (_i, [_p, _p, _p, _p, _p, _l, _i, _l, _l, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
     "loftr_atlas_finalize_workspace_bytes": (_sz, [_l, _i, _i, _i]),
     "loftr_atlas_finalize": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, C.POINTER(AtlasOut), _p, _sz, _p, _p]),
+    "loftr_triangulate_tracks_host": (_i, [_p, _l, _p, _p, _l, _p, _p, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p]),
+    "loftr_triangulation_pairs": (_i, [_i, _p, C.POINTER(_i)]),
+    "loftr_triangulate_tracks_workspace_bytes": (_sz, [_l, _l, _i]),
+    "loftr_triangulate_tracks": (_i, [_p, _l, _p, _p, _l, _p, _p, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

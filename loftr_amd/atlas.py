@@ -82,6 +82,22 @@ class SfmResult:
         offsets[1:] = torch.cumsum(counts, 0)
         return offsets, image, kp - self.kp_offsets[image]
 
+    def triangulate(self, K, T_cam_from_world, thresh_px=4.0, min_angle_deg=1.5, consistent_only=True, group=0):
+        """One 3D point per track from the images' poses (triangulation.triangulate_tracks) -> Points3D on this result's
+        device, with the CSR arrays of ``tracks(consistent_only)`` attached (``offsets``, ``image``, ``keypoint``).
+        K [n_images,3,3], T_cam_from_world [n_images,4,4] (float32 or float64, tensors or arrays; moved to the device)."""
+        from .triangulation import triangulate_tracks
+        dev = self.keypoints.device
+        K, T = (torch.as_tensor(x).detach().to(dev, torch.float64) for x in (K, T_cam_from_world))
+        n = self.kp_offsets.numel() - 1
+        if tuple(K.shape) != (n, 3, 3) or tuple(T.shape) != (n, 4, 4):
+            raise ValueError(f"SfmResult.triangulate: expected K [{n},3,3] and T_cam_from_world [{n},4,4], got {tuple(K.shape)}, {tuple(T.shape)}")
+        offsets, image, local = self.tracks(consistent_only)
+        xy = self.keypoints[self.kp_offsets[image] + local]
+        pts = triangulate_tracks(offsets, image.to(torch.int32), xy, K, T, thresh_px=thresh_px, min_angle_deg=min_angle_deg, group=group)
+        pts.offsets, pts.image, pts.keypoint = offsets, image, local
+        return pts
+
     def to_host(self):
         """dict of numpy arrays (plus 'stats')."""
         out = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}

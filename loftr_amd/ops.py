@@ -1222,6 +1222,85 @@ def atlas_finalize(grid, obs_xy, obs_cell, m_conf, m_row, m_reason, status, M, R
     return out
 
 
+# ---- triangulation of tracks (csrc/triangulate.hip, csrc/triangulate_gpu.hip) --------------------------------------------
+TRI_COUNTS = 8
+TRI_STATUS = ("ok", "too_short", "no_hypothesis", "small_angle", "bad_camera")            # status codes 0..4 = counts[0..4]
+TRI_STAGES = ("camera_table", "solve_8", "solve_64")
+_TRI_ARGS = (("offsets", "int64", 1), ("obs_image", "int32", 1), ("obs_xy", "float32", 2), ("K", "float64", 3), ("T_cam_from_world", "float64", 3))
+
+
+def _tri_shapes(what, arrays, dtype_of):
+    """Dtype and shape checks shared by the two triangulation wrappers -> (T, N, n_images)."""
+    for (name, dt, nd), a in zip(_TRI_ARGS, arrays):
+        if dtype_of(a) != dt or a.ndim != nd:
+            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
+    offsets, obs_image, obs_xy, K, T = arrays
+    N, n = obs_image.shape[0], K.shape[0]
+    if offsets.shape[0] < 1 or tuple(obs_xy.shape) != (N, 2) or tuple(K.shape) != (n, 3, 3) or tuple(T.shape) != (n, 4, 4):
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], K [n,3,3] and T_cam_from_world [n,4,4], got "
+                                 f"{[tuple(a.shape) for a in arrays]}")
+    return offsets.shape[0] - 1, N, n
+
+
+def triangulation_pairs(L):
+    """loftr_triangulation_pairs: the hypothesis pairs (step 2 of the rule) of a track of L observations -> list of (i, j)."""
+    buf, n = (C.c_int * 128)(), C.c_int(0)
+    check(_lib.load().loftr_triangulation_pairs(int(L), C.cast(buf, C.c_void_p), C.byref(n)), "loftr_triangulation_pairs")
+    return [(buf[2 * h], buf[2 * h + 1]) for h in range(n.value)]
+
+
+def triangulate_tracks_host(offsets, obs_image, obs_xy, K, T_cam_from_world, thresh_px, cos_min_angle):
+    """loftr_triangulate_tracks_host: the host routine that DEFINES the triangulation (include/loftr_hip.h) on numpy arrays:
+    offsets [T+1] i64, obs_image [N] i32, obs_xy [N,2] f32, K [n,3,3] f64, T_cam_from_world [n,4,4] f64.
+    -> dict of numpy arrays: xyz [T,3] f32, n_inliers [T] i32, rms_px [T] f32, tri_cos [T] f32, status [T] u8, obs_inlier [N] u8,
+    counts [8] i64."""
+    import numpy as np
+    arrays = (offsets, obs_image, obs_xy, K, T_cam_from_world)
+    if not all(isinstance(a, np.ndarray) for a in arrays):
+        raise _lib.LoftrHipError("triangulate_tracks_host: expected numpy arrays (GPU tensors go to triangulate_tracks)")
+    T, N, n = _tri_shapes("triangulate_tracks_host", arrays, lambda a: a.dtype.name)
+    arrays = [np.ascontiguousarray(a) for a in arrays]
+    out = {"xyz": np.zeros((T, 3), np.float32), "n_inliers": np.zeros(T, np.int32), "rms_px": np.zeros(T, np.float32),
+           "tri_cos": np.zeros(T, np.float32), "status": np.zeros(T, np.uint8), "obs_inlier": np.zeros(N, np.uint8),
+           "counts": np.zeros(TRI_COUNTS, np.int64)}
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    a = arrays
+    check(_lib.load().loftr_triangulate_tracks_host(ptr(a[0]), T, ptr(a[1]), ptr(a[2]), N, ptr(a[3]), ptr(a[4]), n, float(thresh_px),
+                                                    float(cos_min_angle), *[ptr(out[k]) for k in out]),
+          "loftr_triangulate_tracks_host (offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images))")
+    return out
+
+
+@_on_device
+def triangulate_tracks(offsets, obs_image, obs_xy, K, T_cam_from_world, thresh_px, cos_min_angle, group=0, timings=None):
+    """loftr_triangulate_tracks: the triangulation kernels (csrc/triangulate_gpu.hip) on GPU tensors of the dtypes and shapes of
+    triangulate_tracks_host; the same result bit for bit, whatever group (0, 8 or 64) is.  -> dict of device tensors; nothing is read
+    back here: bad offsets / obs_image raise bits in counts[5], which the caller reads once.  timings: a list that receives
+    (stage, ms) pairs (the call then waits for the stream)."""
+    arrays = (offsets, obs_image, obs_xy, K, T_cam_from_world)
+    for (name, _, _), a in zip(_TRI_ARGS, arrays):
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the triangulation kernels have no CPU fallback; the host routine is "
+                                     "triangulate_tracks_host)")
+    T, N, n = _tri_shapes("triangulate_tracks", arrays, lambda a: str(a.dtype).replace("torch.", ""))
+    if int(group) not in (0, 8, 64):
+        raise _lib.LoftrHipError(f"triangulate_tracks: group must be 0, 8 or 64, got {group}")
+    dev = offsets.device
+    a = [x.contiguous() for x in arrays]
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    out = {"xyz": z((T, 3), torch.float32), "n_inliers": z(T, torch.int32), "rms_px": z(T, torch.float32), "tri_cos": z(T, torch.float32),
+           "status": z(T, torch.uint8), "obs_inlier": z(N, torch.uint8), "counts": z(TRI_COUNTS, torch.int64)}
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_triangulate_tracks_workspace_bytes(T, N, n)), dtype=torch.uint8, device=dev)
+    ms = (C.c_float * len(TRI_STAGES))() if timings is not None else None
+    check(lib.loftr_triangulate_tracks(_ptr(a[0]), T, _ptr(a[1]), _ptr(a[2]), N, _ptr(a[3]), _ptr(a[4]), n, float(thresh_px), float(cos_min_angle),
+                                       *[_ptr(out[k]) for k in out], int(group), _ptr(ws), ws.numel(),
+                                       C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_triangulate_tracks")
+    if timings is not None:
+        timings.extend(zip(TRI_STAGES, (float(v) for v in ms)))
+    return out
+
+
 # ---- training-mode glue of the backbone (csrc/train_glue.hip; resnet_fpn.py:22-40,66-77,110-116) ------------------------------------------
 def _dense4(t, name):
     """A 4-D fp32 GPU tensor [N,C,H,W] stored densely either NCHW or NHWC (channels_last: what the convolution nodes produce); returns
