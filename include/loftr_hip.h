@@ -60,7 +60,8 @@ typedef enum {
  *     absolute pose from matches and depth (loftr_estimate_absolute_pose, loftr_p3p, loftr_estimate_absolute_pose_batched,
  *     loftr_estimate_absolute_pose_batched_workspace_bytes, loftr_lift_keypoints), the keypoint atlas (loftr_atlas_*), triangulation
  *     of tracks (loftr_triangulate_tracks_host, loftr_triangulation_pairs, loftr_triangulate_tracks,
- *     loftr_triangulate_tracks_workspace_bytes) */
+ *     loftr_triangulate_tracks_workspace_bytes), localisation against the triangulated model (loftr_model_cells_host,
+ *     loftr_model_cells, loftr_model_lookup_host, loftr_model_lookup_workspace_bytes, loftr_model_lookup) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -777,6 +778,72 @@ int loftr_triangulate_tracks(const long* offsets, long T, const int* obs_image, 
                              const double* T_cam_from_world, int n_images, double thresh_px, double cos_min_angle, float* xyz,
                              int* n_inliers, float* rms_px, float* tri_cos, uint8_t* status, uint8_t* obs_inlier, long* counts, int group,
                              void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
+/* ---- localisation against a triangulated model: query matches -> fused 2D-3D correspondences ---------------------------
+ * The link between the atlas + triangulation and loftr_estimate_absolute_pose_batched: a query image is matched against several
+ * database images of the model; every database-side match point is looked up among the atlas keypoints of that image, its 3D point
+ * fetched, and the rows of one query merged so that no 3D point is used twice.  All of it is integer and order-defined:
+ * loftr_model_lookup_host (csrc/model_lookup.hip, host memory) DEFINES the result, loftr_model_lookup (csrc/model_lookup_gpu.hip,
+ * device memory) reproduces it bit for bit, whatever the arrival order of the atomics.  csrc/model_lookup_core.h holds what they share.
+ * Model (built once): kp_offsets [n_images+1] i64 (0 first, K last, ascending); kp_cell [K] i32, the cell cy * gw + cx of every
+ *   keypoint's stored position under rule 1 of the atlas (strictly ascending within an image: loftr_model_cells computes and checks it);
+ *   kp_point [K] i32, the row of xyz of the keypoint or -1; xyz [P,3] f32; inv, gh, gw as for the atlas.
+ * Queries: kpts_db / kpts_q [M,2] f32 (the match's point in the database image / in the query image), conf [M] f32, rows [M] i32
+ *   ascending, mask [M] u8 or NULL, row_db [R] i32 (database image of every row), row_query [R] i32 (query of every row, in [0, Q),
+ *   non-decreasing: the rows of a query are contiguous).
+ *   Rule 1: a match gets the FIRST reason that applies (match_reason; counts[4 + reason]): 1 bad row (an error, below); 2 its mask byte
+ *     is 0; 3 a coordinate of either point or its confidence is not finite; 4 its confidence is negative (-0.0 is not); 5 the cell of
+ *     the database point lies outside the grid (the query point needs no grid); 6 no_keypoint: no keypoint of image row_db[row] has that
+ *     cell (the search never leaves kp_offsets[d] .. kp_offsets[d+1]); 7 no_point: kp_point is -1 (an entry >= P, which a checked model
+ *     does not have, counts the same and is never used as an index).  Anything else is a candidate of (query, point).
+ *   Rule 2: of the candidates of one (query, point) the one with the greatest confidence, then the smallest match index, is kept
+ *     (reason 0; one unsigned 64-bit max of conf_bits << 32 | (0xFFFFFFFF - m)), the others are fused (reason 8).  Two candidates that
+ *     share a query point but reach different 3D points are both kept.
+ *   Rule 3: the C kept correspondences in ascending match index (so grouped by ascending query): pts3d [C,3] f32 copies of xyz rows,
+ *     kpts [C,2] f32 the query points unchanged, q_ids [C] i64, match [C] i32, point [C] i32, conf [C] f32; q_offsets [Q+1] i64;
+ *     match_reason [M] u8; counts [16] i64: [0] = C, [3] = status bits, [4 + reason] = matches per reason (they sum to M under status 0).
+ *     Outputs are sized by the bound C <= M; only the first C entries are written.
+ *   Rule 4, status bits: 1 a rows entry outside [0, R); 2 rows descending; 4 a row_query entry outside [0, Q) or descending; 8 a row_db
+ *     entry outside [0, n_images).  The host routine returns LOFTR_ERR_BAD_ARG; the kernels raise the bit in counts[3], read nothing
+ *     through the bad value and leave the other outputs undefined: they never wait for the device.
+ * Limits (LOFTR_ERR_UNSUPPORTED beyond, answered before a data pointer is read): M <= 2^31 - 2; Q, P, R < 2^31; K, gh * gw < 2^31;
+ *   gw, gh <= 2^24.  Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes and (host routines) kp_offsets that do not start at 0,
+ *   end at K and ascend; LOFTR_ERR_WORKSPACE for a short workspace; M == 0, R == 0 and Q == 0 succeed. */
+typedef struct {
+  const long* kp_offsets; const int* kp_cell; const int* kp_point; const float* xyz;
+  long K, P;
+  int n_images, gh, gw;
+  float inv;
+} LoftrModel;
+typedef struct {
+  float* pts3d; float* kpts; long* q_ids; int* match; int* point; float* conf;
+  long* q_offsets; uint8_t* match_reason; long* counts;
+} LoftrModelLookupOut;
+
+/* kp_cell [K] of keypoints [K,2] f32, and *status (one int32; host memory for the host form, device memory for the kernel, which
+ * zeroes it first and never waits): bit 16 when a keypoint lies outside the grid (or is not finite) or the cells do not ascend strictly
+ * within an image, bit 32 when a kp_point entry leaves [-1, P). */
+int loftr_model_cells_host(const long* kp_offsets, int n_images, const float* keypoints, const int* kp_point, long K, long P, int gh, int gw,
+                           float inv, int* kp_cell, int* status);
+int loftr_model_cells(const long* kp_offsets, int n_images, const float* keypoints, const int* kp_point, long K, long P, int gh, int gw,
+                      float inv, int* kp_cell, int* status, void* stream);
+
+/* The defining host routine (every pointer, those inside *model too, is host memory). */
+int loftr_model_lookup_host(const LoftrModel* model, const float* kpts_db, const float* kpts_q, const float* conf, const int* rows,
+                            const uint8_t* mask, long M, const int* row_db, const int* row_query, long R, long Q,
+                            const LoftrModelLookupOut* out);
+/* The kernels (*model and *out are host structs of device pointers): lookup (a thread per match and per row; table of 16-byte slots, a
+ * power of two of at least 2 M, claimed by 64-bit atomicCAS and reduced by 64-bit atomicMax), keep (the table's winners; counts per
+ * block and per query), two u32 scans, write.  Stream-ordered, no data-dependent grid and no host synchronisation unless stage_ms is
+ * given: NULL, or LOFTR_MODEL_LOOKUP_STAGES host floats that receive the GPU time (events; the call then waits for the stream) of
+ * 0 lookup (with the clearing of the table), 1 keep + scans, 2 write.  The caller reads counts back once and trims.
+ * Workspace: loftr_model_lookup_workspace_bytes(M, Q): the table's 32 to 64 bytes per match, 8 more per match, 4 per query; 0 for
+ * sizes out of range. */
+#define LOFTR_MODEL_LOOKUP_STAGES 3
+size_t loftr_model_lookup_workspace_bytes(long M, long Q);
+int loftr_model_lookup(const LoftrModel* model, const float* kpts_db, const float* kpts_q, const float* conf, const int* rows,
+                       const uint8_t* mask, long M, const int* row_db, const int* row_query, long R, long Q, const LoftrModelLookupOut* out,
+                       void* ws, size_t ws_bytes, float* stage_ms, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

@@ -46,6 +46,15 @@ class AtlasOut(C.Structure):
                                   "track_id", "track_len", "track_ok", "counts")]
 
 
+class Model(C.Structure):
+    _fields_ = [(n, _p) for n in ("kp_offsets", "kp_cell", "kp_point", "xyz")] + [("K", _l), ("P", _l), ("n_images", _i), ("gh", _i), ("gw", _i),
+                                                                                   ("inv", _f)]
+
+
+class ModelLookupOut(C.Structure):
+    _fields_ = [(n, _p) for n in ("pts3d", "kpts", "q_ids", "match", "point", "conf", "q_offsets", "match_reason", "counts")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/loftr_hip.h
 SIGNATURES = {
     "loftr_hip_abi_version": (_i, []),
@@ -140,6 +149,11 @@ SIGNATURES = {
     "loftr_triangulation_pairs": (_i, [_i, _p, C.POINTER(_i)]),
     "loftr_triangulate_tracks_workspace_bytes": (_sz, [_l, _l, _i]),
     "loftr_triangulate_tracks": (_i, [_p, _l, _p, _p, _l, _p, _p, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p, _p]),
+    "loftr_model_cells_host": (_i, [_p, _i, _p, _p, _l, _l, _i, _i, _f, _p, _p]),
+    "loftr_model_cells": (_i, [_p, _i, _p, _p, _l, _l, _i, _i, _f, _p, _p, _p]),
+    "loftr_model_lookup_host": (_i, [C.POINTER(Model), _p, _p, _p, _p, _p, _l, _p, _p, _l, _l, C.POINTER(ModelLookupOut)]),
+    "loftr_model_lookup_workspace_bytes": (_sz, [_l, _l]),
+    "loftr_model_lookup": (_i, [C.POINTER(Model), _p, _p, _p, _p, _p, _l, _p, _p, _l, _l, C.POINTER(ModelLookupOut), _p, _sz, _p, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

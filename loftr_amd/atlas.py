@@ -50,7 +50,7 @@ class SfmResult:
     ``kp_offsets [n_images+1] i64`` delimits the images in ``keypoints [K,2] f32``, ``score [K] f32``, ``n_obs [K] i32``;
     ``row_offsets [R+1] i64`` delimits the rows in ``matches [Mk,2] i32`` (LOCAL keypoint indices of image a / image b of the row)
     and ``match_conf [Mk] f32``; ``track_id [K] i32`` (-1: none), ``track_len [T] i32``, ``track_ok [T] bool``; ``row_images [R,2] i32``;
-    ``stats``: dict of counts."""
+    ``stats``: dict of counts.  ``image_hw`` / ``cell_px``: the atlas's grid geometry (None for a result built by hand)."""
 
     FIELDS = ("kp_offsets", "keypoints", "score", "n_obs", "row_offsets", "matches", "match_conf", "track_id", "track_len", "track_ok",
               "row_images")
@@ -59,6 +59,7 @@ class SfmResult:
         self.stats = stats
         for k in self.FIELDS:
             setattr(self, k, tensors[k])
+        self.image_hw = self.cell_px = None                            # set by KeypointAtlas.finalize
 
     def keypoint_image(self):
         """Image of every keypoint [K] i64."""
@@ -270,7 +271,9 @@ class KeypointAtlas:
             raise ValueError("KeypointAtlas: an add received m_bids that do not ascend (found on the device)")
         stats = {"n_images": self.n_images, "n_rows": R, "n_matches": M, "n_keypoints": K, "n_kept": Mk, "n_tracks": T}
         stats.update({name: counts[4 + i] for i, name in enumerate(ops.ATLAS_REASONS) if name != "n_bad_row"})
-        return SfmResult(stats, kp_offsets=out["kp_offsets"], keypoints=out["keypoints"][:K], score=out["score"][:K], n_obs=out["n_obs"][:K],
-                         row_offsets=out["row_offsets"], matches=out["matches"][:Mk], match_conf=out["match_conf"][:Mk],
-                         track_id=out["track_id"][:K], track_len=out["track_len"][:T], track_ok=out["track_ok"][:T].to(torch.bool),
-                         row_images=row_images)
+        sfm = SfmResult(stats, kp_offsets=out["kp_offsets"], keypoints=out["keypoints"][:K], score=out["score"][:K], n_obs=out["n_obs"][:K],
+                        row_offsets=out["row_offsets"], matches=out["matches"][:Mk], match_conf=out["match_conf"][:Mk],
+                        track_id=out["track_id"][:K], track_len=out["track_len"][:T], track_ok=out["track_ok"][:T].to(torch.bool),
+                        row_images=row_images)
+        sfm.image_hw, sfm.cell_px = self.image_hw, self.cell_px       # the grid geometry (plain attributes: LocalizationModel.from_atlas)
+        return sfm

@@ -20,7 +20,9 @@ for ``from loftr_amd.evaluation import ...``.
   checks the solver on exact data and the recovered pose on synthetic scenes with known ground truth;
 * beyond the reference's evaluation: geometric verification without intrinsics (`verify_matches`: homography / fundamental
   matrix, csrc/geometry*.hip) and metric localisation from matches and a depth map (`localize`: lifting + P3P RANSAC,
-  csrc/absolute_pose*.hip), each one GPU call per batch with a host estimator that defines the result.
+  csrc/absolute_pose*.hip), each one GPU call per batch with a host estimator that defines the result;
+* poses of queries localised against a triangulated model (`loftr_amd.localization.QueryLocalizer.solve`, no depth maps) are scored
+  with `absolute_pose_error` and `localization_recall`, like `localize`'s.
 """
 import os
 

@@ -1301,6 +1301,161 @@ def triangulate_tracks(offsets, obs_image, obs_xy, K, T_cam_from_world, thresh_p
     return out
 
 
+# ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip) ------------------------
+MODEL_COUNTS = 16
+MODEL_REASONS = ("n_kept", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside", "n_no_keypoint", "n_no_point",
+                 "n_fused")                                                                  # match_reason codes 0..8 = counts[4 + reason]
+MODEL_STATUS = ((1, "rows outside [0, R)"), (2, "rows that do not ascend"), (4, "row_query outside [0, Q) or descending"),
+                (8, "row_db outside [0, n_images)"), (16, "keypoints outside the grid, or cells that do not ascend strictly within an image"),
+                (32, "kp_point outside [-1, P)"))
+MODEL_STAGES = ("lookup", "keep", "write")
+_MODEL_ARGS = (("kp_offsets", "int64", 1), ("kp_cell", "int32", 1), ("kp_point", "int32", 1), ("xyz", "float32", 2))
+_QUERY_ARGS = (("kpts_db", "float32", 2), ("kpts_q", "float32", 2), ("conf", "float32", 1), ("rows", "int32", 1), ("mask", "uint8", 1),
+               ("row_db", "int32", 1), ("row_query", "int32", 1))
+_MODEL_OUT = (("pts3d", 3, "float32"), ("kpts", 2, "float32"), ("q_ids", 0, "int64"), ("match", 0, "int32"), ("point", 0, "int32"),
+              ("conf", 0, "float32"))
+
+
+def _model_shapes(what, named, dtype_of):
+    """Dtype and shape checks shared by the model wrappers; named: (name, dtype, ndim, array) tuples."""
+    for name, dt, nd, a in named:
+        if a is not None and (dtype_of(a) != dt or a.ndim != nd):
+            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
+
+
+def _model_geometry(what, kp_offsets, gh, gw):
+    if kp_offsets.shape[0] < 1 or min(int(gh), int(gw)) < 0:
+        raise _lib.LoftrHipError(f"{what}: expected kp_offsets [n_images+1] and a grid of gh x gw >= 0 cells, got {tuple(kp_offsets.shape)}, {gh} x {gw}")
+    return kp_offsets.shape[0] - 1
+
+
+def _lookup_sizes(what, model, queries):
+    """(n_images, K, P, M, R) after the shape checks of one lookup; model = (kp_offsets, kp_cell, kp_point, xyz), queries in _QUERY_ARGS order."""
+    kp_offsets, kp_cell, kp_point, xyz = model
+    kd, kq, c, rows, mask, row_db, row_query = queries
+    K, P, M, R = kp_cell.shape[0], xyz.shape[0], kd.shape[0], row_db.shape[0]
+    if kp_offsets.shape[0] < 1 or kp_point.shape[0] != K or tuple(xyz.shape) != (P, 3):
+        raise _lib.LoftrHipError(f"{what}: expected kp_offsets [n_images+1], kp_cell / kp_point [K] and xyz [P,3], got "
+                                 f"{[tuple(a.shape) for a in model]}")
+    if tuple(kd.shape) != (M, 2) or tuple(kq.shape) != (M, 2) or c.shape[0] != M or rows.shape[0] != M or \
+            (mask is not None and mask.shape[0] != M) or row_query.shape[0] != R:
+        raise _lib.LoftrHipError(f"{what}: expected kpts_db / kpts_q [M,2], conf / rows / mask [M] and row_db / row_query [R], got "
+                                 f"{[None if a is None else tuple(a.shape) for a in queries]}")
+    return kp_offsets.shape[0] - 1, K, P, M, R
+
+
+def _lookup_structs(model, sizes, gh, gw, inv, out, ptr):
+    n_images, K, P, _, _ = sizes
+    md = _lib.Model(kp_offsets=ptr(model[0]), kp_cell=ptr(model[1]), kp_point=ptr(model[2]), xyz=ptr(model[3]), K=K, P=P, n_images=n_images,
+                    gh=int(gh), gw=int(gw), inv=float(inv))
+    return md, _lib.ModelLookupOut(**{k: ptr(out[k]) for k, _ in _lib.ModelLookupOut._fields_})
+
+
+def model_cells_host(kp_offsets, keypoints, kp_point, P, gh, gw, inv):
+    """loftr_model_cells_host on numpy arrays: kp_offsets [n_images+1] i64, keypoints [K,2] f32, kp_point [K] i32 -> (kp_cell [K] i32,
+    status bits: 16 cells not strictly ascending within an image or outside the grid, 32 kp_point outside [-1, P))."""
+    import numpy as np
+    arrays = (kp_offsets, keypoints, kp_point)
+    if not all(isinstance(a, np.ndarray) for a in arrays):
+        raise _lib.LoftrHipError("model_cells_host: expected numpy arrays (GPU tensors go to model_cells)")
+    _model_shapes("model_cells_host", (("kp_offsets", "int64", 1, kp_offsets), ("keypoints", "float32", 2, keypoints),
+                                       ("kp_point", "int32", 1, kp_point)), lambda a: a.dtype.name)
+    K = keypoints.shape[0]
+    n_images = _model_geometry("model_cells_host", kp_offsets, gh, gw)
+    if tuple(keypoints.shape) != (K, 2) or kp_point.shape[0] != K:
+        raise _lib.LoftrHipError(f"model_cells_host: expected keypoints [K,2] and kp_point [K], got {tuple(keypoints.shape)}, {tuple(kp_point.shape)}")
+    a = [np.ascontiguousarray(x) for x in arrays]
+    cell, status = np.zeros(K, np.int32), C.c_int(0)
+    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
+    check(_lib.load().loftr_model_cells_host(ptr(a[0]), n_images, ptr(a[1]), ptr(a[2]), K, int(P), int(gh), int(gw), float(inv), ptr(cell),
+                                             C.cast(C.byref(status), C.c_void_p)),
+          "loftr_model_cells_host (kp_offsets must start at 0, end at K and ascend)")
+    return cell, status.value
+
+
+@_on_device
+def model_cells(kp_offsets, keypoints, kp_point, P, gh, gw, inv):
+    """loftr_model_cells on GPU tensors of the dtypes of model_cells_host -> (kp_cell [K] i32, status [1] i32), device tensors; nothing
+    is read back here."""
+    named = (("kp_offsets", "int64", 1, kp_offsets), ("keypoints", "float32", 2, keypoints), ("kp_point", "int32", 1, kp_point))
+    for name, _, _, a in named:
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the host form is model_cells_host)")
+    _model_shapes("model_cells", named, lambda a: str(a.dtype).replace("torch.", ""))
+    K = keypoints.shape[0]
+    n_images = _model_geometry("model_cells", kp_offsets, gh, gw)
+    if tuple(keypoints.shape) != (K, 2) or kp_point.shape[0] != K:
+        raise _lib.LoftrHipError(f"model_cells: expected keypoints [K,2] and kp_point [K], got {tuple(keypoints.shape)}, {tuple(kp_point.shape)}")
+    a = [x.contiguous() for x in (kp_offsets, keypoints, kp_point)]
+    cell = torch.empty(K, dtype=torch.int32, device=keypoints.device)
+    status = torch.empty(1, dtype=torch.int32, device=keypoints.device)
+    check(_lib.load().loftr_model_cells(_ptr(a[0]), n_images, _ptr(a[1]), _ptr(a[2]), K, int(P), int(gh), int(gw), float(inv), _ptr(cell),
+                                        _ptr(status), _stream()), "loftr_model_cells")
+    return cell, status
+
+
+def model_lookup_host(kp_offsets, kp_cell, kp_point, xyz, gh, gw, inv, kpts_db, kpts_q, conf, rows, mask, row_db, row_query, Q):
+    """loftr_model_lookup_host: the host routine that DEFINES the fused 2D-3D correspondences (include/loftr_hip.h) on numpy arrays:
+    the model (kp_offsets [n_images+1] i64, kp_cell / kp_point [K] i32, xyz [P,3] f32, grid), the matches (kpts_db / kpts_q [M,2] f32,
+    conf [M] f32, rows [M] i32 ascending, mask [M] u8 or None) and the rows (row_db / row_query [R] i32).
+    -> dict of numpy arrays of the bound size M (pts3d, kpts, q_ids, match, point, conf), q_offsets [Q+1] i64, match_reason [M] u8 and
+    counts [16] i64; the caller trims by counts[0]."""
+    import numpy as np
+    model, queries = (kp_offsets, kp_cell, kp_point, xyz), (kpts_db, kpts_q, conf, rows, mask, row_db, row_query)
+    if not all(a is None or isinstance(a, np.ndarray) for a in model + queries):
+        raise _lib.LoftrHipError("model_lookup_host: expected numpy arrays (GPU tensors go to model_lookup)")
+    _model_shapes("model_lookup_host", [s + (a,) for s, a in zip(_MODEL_ARGS + _QUERY_ARGS, model + queries)], lambda a: a.dtype.name)
+    sizes = _lookup_sizes("model_lookup_host", model, queries)
+    M, Q = sizes[3], int(Q)
+    if Q < 0:
+        raise _lib.LoftrHipError(f"model_lookup_host: Q must be >= 0, got {Q}")
+    model = [np.ascontiguousarray(a) for a in model]
+    queries = [None if a is None else np.ascontiguousarray(a) for a in queries]
+    out = {k: np.zeros((max(M, 1), w) if w else max(M, 1), dt) for k, w, dt in _MODEL_OUT}
+    out.update(q_offsets=np.zeros(Q + 1, np.int64), match_reason=np.zeros(M, np.uint8), counts=np.zeros(MODEL_COUNTS, np.int64))
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    md, st = _lookup_structs(model, sizes, gh, gw, inv, out, ptr)
+    check(_lib.load().loftr_model_lookup_host(C.byref(md), *[ptr(a) for a in queries[:5]], M, ptr(queries[5]), ptr(queries[6]), sizes[4], Q,
+                                              C.byref(st)),
+          "loftr_model_lookup_host (rows must ascend within [0, R), row_query within [0, Q) without descending, row_db within [0, n_images); "
+          "kp_offsets must start at 0, end at K and ascend)")
+    return out
+
+
+@_on_device
+def model_lookup(kp_offsets, kp_cell, kp_point, xyz, gh, gw, inv, kpts_db, kpts_q, conf, rows, mask, row_db, row_query, Q, timings=None):
+    """loftr_model_lookup: the lookup / fusion kernels (csrc/model_lookup_gpu.hip) on GPU tensors of the dtypes and shapes of
+    model_lookup_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: bad rows raise bits in
+    counts[3], which the caller reads once, with counts[0] = C to trim by.  timings: a list that receives (stage, ms) pairs (the call
+    then waits for the stream)."""
+    model, queries = (kp_offsets, kp_cell, kp_point, xyz), (kpts_db, kpts_q, conf, rows, mask, row_db, row_query)
+    for (name, _, _), a in zip(_MODEL_ARGS + _QUERY_ARGS, model + queries):
+        if a is not None and (not isinstance(a, torch.Tensor) or not a.is_cuda):
+            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the lookup kernels have no CPU fallback; the host routine is "
+                                     "model_lookup_host)")
+    _model_shapes("model_lookup", [s + (a,) for s, a in zip(_MODEL_ARGS + _QUERY_ARGS, model + queries)],
+                  lambda a: str(a.dtype).replace("torch.", ""))
+    sizes = _lookup_sizes("model_lookup", model, queries)
+    M, Q = sizes[3], int(Q)
+    if Q < 0:
+        raise _lib.LoftrHipError(f"model_lookup: Q must be >= 0, got {Q}")
+    dev = kp_offsets.device
+    model = [a.contiguous() for a in model]
+    queries = [None if a is None else a.contiguous() for a in queries]
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = {k: e((max(M, 1), w) if w else max(M, 1), getattr(torch, dt)) for k, w, dt in _MODEL_OUT}
+    out.update(q_offsets=e(Q + 1, torch.int64), match_reason=e(M, torch.uint8), counts=e(MODEL_COUNTS, torch.int64))
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_model_lookup_workspace_bytes(M, Q)), dtype=torch.uint8, device=dev)
+    md, st = _lookup_structs(model, sizes, gh, gw, inv, out, _ptr)
+    ms = (C.c_float * len(MODEL_STAGES))() if timings is not None else None
+    check(lib.loftr_model_lookup(C.byref(md), *[_ptr(a) for a in queries[:5]], M, _ptr(queries[5]), _ptr(queries[6]), sizes[4], Q, C.byref(st),
+                                 _ptr(ws), ws.numel(), C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_model_lookup")
+    if timings is not None:
+        timings.extend(zip(MODEL_STAGES, (float(v) for v in ms)))
+    return out
+
+
 # ---- training-mode glue of the backbone (csrc/train_glue.hip; resnet_fpn.py:22-40,66-77,110-116) ------------------------------------------
 def _dense4(t, name):
     """A 4-D fp32 GPU tensor [N,C,H,W] stored densely either NCHW or NHWC (channels_last: what the convolution nodes produce); returns
