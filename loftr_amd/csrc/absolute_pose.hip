@@ -26,7 +26,7 @@ namespace {
 
 using namespace absp;
 
-const PolarTable& table() { static const PolarTable t = polar_table(); return t; }
+const PolarTable& table() { static const PolarTable t = polar_table<4>(); return t; }
 
 // pts [n,8]: world point (3), pixel (2), unit bearing (3)
 long score(const Cam& cam, const double* R, const double* t, const double* pts, long n, double thr2, uint8_t* mask) {
@@ -37,12 +37,6 @@ long score(const Cam& cam, const double* R, const double* t, const double* pts, 
     cnt += in;
   }
   return cnt;
-}
-
-// the fixed pairwise tree over the 256 strided partials
-double tree(double* p) {
-  for (int st = kLanes / 2; st >= 1; st >>= 1) for (int k = 0; k < st; ++k) p[k] = p[k] + p[k + st];
-  return p[0];
 }
 
 // Gauss-Newton fit on the matches with in[i] != 0, from (R, t); the fit replaces them on success
@@ -105,10 +99,10 @@ extern "C" int loftr_estimate_absolute_pose(const float* pts3d, const float* kpt
   Rng rng(seed);
   double bestR[9] = {0}, bestT[3] = {0};
   long best = 0;
-  int max_iters = kIters, iters = max_iters;
+  int iters = kIters;
   for (int it = 0; it < iters; ++it) {
-    int idx[3];
-    draw_sample(rng, M, idx);
+    int idx[kSample];
+    draw_sample(rng, M, kSample, idx);
     double X[9], f[9], poses[kPose * kSol];
     for (int k = 0; k < 3; ++k) for (int c = 0; c < 3; ++c) { X[3 * k + c] = pts[8 * (size_t)idx[k] + c]; f[3 * k + c] = pts[8 * (size_t)idx[k] + 5 + c]; }
     const int ns = p3p(X, f, poses, tab);
@@ -119,13 +113,7 @@ extern "C" int loftr_estimate_absolute_pose(const float* pts3d, const float* kpt
         best = cnt;
         memcpy(bestR, Rs, sizeof(bestR));
         memcpy(bestT, ts, sizeof(bestT));
-        const double w = (double)cnt / (double)M;              // adaptive iteration count from the confidence
-        const double p_all = pow(w, 3.0);
-        if (p_all > 1 - 1e-12) iters = it + 1;
-        else if (p_all > 1e-12) {
-          const double need = log(1.0 - (double)conf) / log(1.0 - p_all);
-          if (need < iters) iters = need < it + 1 ? it + 1 : (int)ceil(need);
-        }
+        iters = adaptive_iters(cnt, M, kSample, conf, it, iters);
       }
     }
   }

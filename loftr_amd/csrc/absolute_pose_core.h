@@ -4,8 +4,7 @@
 // both, frexp / ldexp are exact, and the only libm values (cos / sin of the Aberth start angles) are tabulated on the host and handed
 // to the device.  No acos, cbrt or trigonometric function is evaluated on the shared path.
 //
-// The complex arithmetic, the Aberth-Ehrlich + Newton root finder (here up to degree 4) and the xorshift64* generator are restated
-// from geometry_core.h / pose.hip (same operations, same order); those files keep their own copies untouched.
+// The sampler, the complex arithmetic of the root finder (here up to degree 4) and the small vector helpers are ransac_core.h's.
 //
 // Minimal solver: Grunert's P3P in the form of Haralick, Lee, Ottenberg, Noelle, "Review and analysis of solutions of the three point
 // perspective pose estimation problem" (IJCV 1994).  With the camera-to-point distances s1, s2 = u s1, s3 = v s1, the law of cosines
@@ -15,9 +14,7 @@
 // Aberth + Newton routine, the distances are polished by Newton steps on the three cosine-law equations, and the rigid motion follows
 // from the orthonormal frames of the two point triples (no SVD).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
+#include "ransac_core.h"
 
 #pragma clang fp contract(off)
 
@@ -25,10 +22,10 @@
 
 namespace absp {
 
-constexpr int kIters = 1000;               // RANSAC iteration cap (loftr_estimate_pose: max_iters)
+using namespace ransac;
+
+constexpr int kSample = 3;
 constexpr int kSol = 4;                    // hypothesis slots per minimal sample
-constexpr int kRefitRounds = 4;            // the refit is repeated on the adopted model's inliers while it strictly gains inliers
-constexpr int kLanes = 256;                // strided partial sums of the refit: partial k takes matches i = k (mod 256), ascending
 constexpr int kGnIters = 5;                // Gauss-Newton steps of one fit (fixed: every bit is equal on both sides)
 constexpr int kSums = 27;                  // 21 upper-triangle entries of J^T J + 6 of J^T r
 // Degenerate samples (relative, scale-free; shared by host and device):
@@ -39,88 +36,7 @@ constexpr double kCoincident = 1e-7;
 // A polished solution is kept when each cosine-law equation holds to kResidual * (longest squared side).
 constexpr double kResidual = 1e-10;
 
-struct Rng {                                                     // xorshift64* (pose.hip)
-  uint64_t s;
-  ABS_HD explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 0x1234567ull) { if (!s) s = 1; }
-  ABS_HD uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
-  ABS_HD long below(long n) { return (long)(next() % (uint64_t)n); }
-};
-// the three distinct indices of one minimal sample (loftr_estimate_pose's duplicate rejection)
-ABS_HD void draw_sample(Rng& rng, long n, int* d) {
-  for (int k = 0; k < 3;) {
-    const int c = (int)rng.below(n);
-    bool dup = false;
-    for (int j = 0; j < k; ++j) dup = dup || d[j] == c;
-    if (!dup) d[k++] = c;
-  }
-}
-
-// ---- complex arithmetic as the host library computes it (geometry_core.h) -------------------------------------------------------
-struct cd { double re, im; };
-ABS_HD cd c_add(cd a, cd b) { return {a.re + b.re, a.im + b.im}; }
-ABS_HD cd c_sub(cd a, cd b) { return {a.re - b.re, a.im - b.im}; }
-ABS_HD cd c_mul(cd a, cd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-ABS_HD double c_abs(cd z) {                                      // libstdc++ __complex_abs
-  double x = z.re, y = z.im;
-  const double ax = fabs(x), ay = fabs(y);
-  const double s = ax < ay ? ay : ax;
-  if (s == 0.0) return s;
-  x /= s;
-  y /= s;
-  return s * sqrt(x * x + y * y);
-}
-ABS_HD double crt_logb(double x) {                               // compiler-rt logb
-  if (isnan(x)) return x;
-  if (isinf(x)) return INFINITY;
-  if (x == 0.0) return -INFINITY;
-  int e;
-  frexp(x, &e);
-  return (double)(e - 1);
-}
-ABS_HD cd c_div(cd num, cd den) {                                // compiler-rt __divdc3
-  double a = num.re, b = num.im, c = den.re, d = den.im;
-  int ilogbw = 0;
-  const double ac = fabs(c), ad = fabs(d);
-  const double mx = isnan(c) ? ad : (isnan(d) ? ac : (ac > ad ? ac : ad));
-  const double logbw = crt_logb(mx);
-  if (isfinite(logbw)) {
-    ilogbw = (int)logbw;
-    c = ldexp(c, -ilogbw);
-    d = ldexp(d, -ilogbw);
-  }
-  const double denom = c * c + d * d;
-  cd z{ldexp((a * c + b * d) / denom, -ilogbw), ldexp((b * c - a * d) / denom, -ilogbw)};
-  if (isnan(z.re) && isnan(z.im)) {
-    if (denom == 0.0 && (!isnan(a) || !isnan(b))) {
-      z.re = copysign(INFINITY, c) * a;
-      z.im = copysign(INFINITY, c) * b;
-    } else if ((isinf(a) || isinf(b)) && isfinite(c) && isfinite(d)) {
-      a = copysign(isinf(a) ? 1.0 : 0.0, a);
-      b = copysign(isinf(b) ? 1.0 : 0.0, b);
-      z.re = INFINITY * (a * c + b * d);
-      z.im = INFINITY * (b * c - a * d);
-    } else if (isinf(logbw) && logbw > 0.0 && isfinite(a) && isfinite(b)) {
-      c = copysign(isinf(c) ? 1.0 : 0.0, c);
-      d = copysign(isinf(d) ? 1.0 : 0.0, d);
-      z.re = 0.0 * (a * c + b * d);
-      z.im = 0.0 * (b * c - a * d);
-    }
-  }
-  return z;
-}
-
-// cos / sin of the Aberth start angles 2 pi i / n + 0.4, n = 1..4, from the host's libm
-struct PolarTable { double c[4][4], s[4][4]; };
-inline PolarTable polar_table() {                                // host only
-  PolarTable t{};
-  for (int n = 1; n <= 4; ++n)
-    for (int i = 0; i < n; ++i) {
-      const double theta = 2 * M_PI * i / n + 0.4;               // pose.hip real_roots: std::polar(rho, theta)
-      t.c[n - 1][i] = cos(theta);
-      t.s[n - 1][i] = sin(theta);
-    }
-  return t;
-}
+using PolarTable = ransac::PolarAngles<4>;    // Aberth start angles up to degree 4
 
 // Small arrays indexed by a run-time value: a select chain over constant indices instead of an address computation, so that the
 // device compiler keeps them in registers (same values, no arithmetic).
@@ -135,8 +51,8 @@ template <int N> struct Pick<N, 0> {
 template <int N> ABS_HD double get(const double (&a)[N], int i) { return Pick<N>::get(a, i); }
 template <int N> ABS_HD void put(double (&a)[N], int i, double v) { Pick<N>::put(a, i, v); }
 
-// pose.hip real_roots for a polynomial of degree <= 4 (ascending coefficients pin[0..5)): Aberth-Ehrlich + Newton polishing on the
-// real axis; the distinct real roots go to r[0..*nr)
+// pose_core.h's real_roots for a polynomial of degree <= 4 (ascending coefficients pin[0..5)), kept apart for its select-chain arrays,
+// which stay in registers: Aberth-Ehrlich + Newton polishing on the real axis; the distinct real roots go to r[0..*nr)
 ABS_HD void real_roots4(const double (&pin)[5], double (&r)[4], int* nr, const PolarTable& tab) {
   double p[5] = {pin[0], pin[1], pin[2], pin[3], pin[4]};
   int pn = 5;
@@ -160,7 +76,7 @@ ABS_HD void real_roots4(const double (&pin)[5], double (&r)[4], int* nr, const P
     put(zre, i, rho * get(tc, (n - 1) * 4 + i));
     put(zim, i, rho * get(ts, (n - 1) * 4 + i));
   }
-  const cd tiny{1e-300, 0};
+  const cd tiny{1e-300, 0}, one{1.0, 0.0};
   for (int it = 0; it < 200; ++it) {
     double change = 0;
     for (int i = 0; i < n; ++i) {
@@ -170,7 +86,7 @@ ABS_HD void real_roots4(const double (&pin)[5], double (&r)[4], int* nr, const P
       if (c_abs(f) < 1e-300) continue;
       const cd ratio = c_div(f, c_abs(df) > 1e-300 ? df : tiny);
       cd sum{0.0, 0.0};
-      for (int j = 0; j < n; ++j) if (j != i) { const cd d = c_sub(zi, cd{get(zre, j), get(zim, j)}); sum = c_add(sum, c_div(cd{1.0, 0.0}, c_abs(d) > 1e-300 ? d : tiny)); }
+      for (int j = 0; j < n; ++j) if (j != i) { const cd d = c_sub(zi, cd{get(zre, j), get(zim, j)}); sum = c_add(sum, c_div(one, c_abs(d) > 1e-300 ? d : tiny)); }
       const cd rs = c_mul(ratio, sum);
       const cd step = c_div(ratio, cd{-rs.re + 1.0, -rs.im});
       const cd zn = c_sub(zi, step);
@@ -199,13 +115,7 @@ ABS_HD void real_roots4(const double (&pin)[5], double (&r)[4], int* nr, const P
 
 // ---- small vectors ----------------------------------------------------------------------------------------------------------------
 ABS_HD double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-ABS_HD void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
 ABS_HD void sub3(const double* a, const double* b, double* c) { c[0] = a[0] - b[0]; c[1] = a[1] - b[1]; c[2] = a[2] - b[2]; }
-ABS_HD void mat3_mul(const double* a, const double* b, double* c) {
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) c[i * 3 + j] = a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j] + a[i * 3 + 2] * b[6 + j];
-}
 // right-handed orthonormal frame (e1, e2, e3 in rows) of the triangle A B C: e1 along AB, e3 along AB x AC
 ABS_HD bool triangle_frame(const double* A, const double* B, const double* C, double* e) {
   double ab[3], ac[3], n[3];

@@ -1,24 +1,20 @@
 // Batched absolute pose (P3P RANSAC + Gauss-Newton refit) on the GPU: loftr_estimate_absolute_pose (absolute_pose.hip, host code) for
 // every pair of a batch, with the same result -- same inlier count, same inlier mask, R and t equal after the float32 rounding -- for
-// the same seed.  The layout follows geometry_gpu.hip: the host loop's random stream does not depend on the scores, so all
-// 1000 minimal samples of a pair are drawn up front, solved and scored in parallel, and the sequential decision is replayed afterwards:
-//   1. abs_prep_kernel    (thread per match)    fp64 world point, pixel and unit bearing of every match, m_bids checked (range, grouping);
-//   2. abs_sample_kernel  (thread per pair)     pair offsets, the 1000 samples of Rng(seed) with the host's duplicate rejection;
-//   3. abs_solve_kernel   (thread per sample)   P3P: up to 4 poses per sample, appended to a per-pair work list of hypotheses;
-//   4. abs_score_kernel   (thread per hypothesis, 512-match tiles of the pair in LDS)  inlier counts;
-//   5. host replay of the RANSAC loop over the copied counts (strict `>`, the adaptive count with the host's own pow / log);
-//   6. abs_refit_kernel   (workgroup per pair)  mask of the best hypothesis, then the host's refit loop: the Gauss-Newton sums in the
-//                                               host's order (thread k = strided partial k, then the pairwise tree in LDS), the 6 x 6
-//                                               solve in thread 0, the fit scored, the adoption rule, again while the inlier set grows;
-//                                               mask / pose / count written.
+// the same seed.  The sequence is ransac_gpu.h's (all 1000 minimal samples of a pair drawn up front, solved and scored in parallel, the
+// sequential decision replayed on the host over the counts); this file holds the model's kernels:
+//   abs_prep_kernel    (thread per match)    fp64 world point, pixel and unit bearing of every match, m_bids checked;
+//   abs_solve_kernel   (thread per sample)   P3P: up to 4 poses per sample;
+//   AbsScore           the model's inlier test for the shared scorer;
+//   abs_refit_kernel   (workgroup per pair)  mask of the best hypothesis, then the host's refit loop: the Gauss-Newton sums in the
+//                                            host's order (thread k = strided partial k, then the pairwise tree in LDS), the 6 x 6
+//                                            solve in thread 0, the fit scored, the adoption rule, again while the inlier set grows;
+//                                            mask / pose / count written.
 // Identical decisions need identical arithmetic: every formula is absolute_pose_core.h's, compiled from the same text as the host
 // estimator's, fp64 without FMA contraction.  loftr_lift_keypoints (the first half of the reference's warp_kpts, fp32) is at the end.
 // Plain C++ throughout; all stores are ordinary vector stores.
 #include <math.h>
-#include <string.h>
-#include <vector>
-#include "common.h"
 #include "absolute_pose_core.h"
+#include "ransac_gpu.h"
 
 #pragma clang fp contract(off)
 
@@ -28,28 +24,15 @@ using namespace absp;
 
 constexpr int kHyp = kIters * kSol;          // hypothesis slots per pair
 constexpr int kPt = 8;                       // doubles per match: world point (3), pixel (2), unit bearing (3)
-constexpr int kScoreThreads = 256;
-constexpr int kScoreTile = 512;              // matches per LDS tile of the scorer (20 KiB)
-constexpr int kRefitChunk = 9;               // sums reduced per pass through the LDS tree (18 KiB)
-
-enum : int { kBadBid = 1, kUngrouped = 2 };  // status word bits (device-side findings)
-
-__device__ long lower_bound(const long* a, long n, long key) {
-  long lo = 0, hi = n;
-  while (lo < hi) { const long mid = lo + (hi - lo) / 2; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-// pair p's matches [start[p], start[p] + count) (a negative difference -- only with ungrouped m_bids -- counts as none)
-__device__ __forceinline__ long pair_count(const long* start, int p) { const long n = start[p + 1] - start[p]; return n > 0 ? n : 0; }
+constexpr Problem kProblem = {kSample, kSol, kPose, kPt};
 
 // grid ceil(M / 256) x 256: pts [M,8] in fp64, m_bids checked
 __global__ void abs_prep_kernel(const float* __restrict__ pts3d, const float* __restrict__ kpts, const long* __restrict__ m_bids, long M,
                                 const float* __restrict__ K, int P, double* __restrict__ pts, int* __restrict__ status) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
-  const long b = m_bids[i];
-  if (b < 0 || b >= P) { atomicOr(status, (int)kBadBid); return; }
-  if (i > 0 && m_bids[i - 1] > b) atomicOr(status, (int)kUngrouped);
+  const long b = checked_bid(m_bids, i, P, status);
+  if (b < 0) return;
   const Cam cam = cam_from_K(K + 9 * b);
   double* q = pts + kPt * i;
   double f[3];
@@ -58,38 +41,14 @@ __global__ void abs_prep_kernel(const float* __restrict__ pts3d, const float* __
   q[0] = pts3d[3 * i]; q[1] = pts3d[3 * i + 1]; q[2] = pts3d[3 * i + 2]; q[3] = u; q[4] = v; q[5] = f[0]; q[6] = f[1]; q[7] = f[2];
 }
 
-// grid ceil((P + 1) / 64) x 64: pair offsets, the kIters minimal samples (3 indices each) of every pair with >= 3 matches
-__global__ void abs_sample_kernel(const long* __restrict__ m_bids, long M, int P, unsigned seed, long* __restrict__ start,
-                                  int* __restrict__ idx, int* __restrict__ n_hyp) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p > P) return;
-  const long s0 = lower_bound(m_bids, M, p);
-  start[p] = s0;
-  if (p == P) return;
-  n_hyp[p] = 0;
-  const long n = lower_bound(m_bids, M, p + 1) - s0;
-  if (n < 3) return;
-  Rng rng(seed);
-  int* out = idx + (long)p * kIters * 3;
-  for (int it = 0; it < kIters; ++it) {
-    int d[3];
-    draw_sample(rng, n, d);
-    out[it * 3] = d[0]; out[it * 3 + 1] = d[1]; out[it * 3 + 2] = d[2];
-  }
-}
-
-// grid ceil(P * kIters / 64) x 64: one minimal sample per thread -> poses [P, kHyp, 12], counts [P, kHyp] = -1 (filled by the scorer
-// for the solutions), work list hyp [P, kHyp] of slot ids it * kSol + sol (any order), n_hyp [P]
+// one minimal sample per thread -> poses [P, kHyp, 12] (ransac_gpu.h: sample_slots, append_hypotheses)
 __global__ void __launch_bounds__(64) abs_solve_kernel(const double* __restrict__ pts, const long* __restrict__ start,
                                                        const int* __restrict__ idx, int P, PolarTable tab, double* __restrict__ poses,
                                                        int* __restrict__ counts, int* __restrict__ hyp, int* __restrict__ n_hyp,
                                                        const int* __restrict__ status) {
   const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (long)P * kIters || *status) return;
-  const int p = (int)(g / kIters), it = (int)(g % kIters);
-  int* cnt = counts + (long)p * kHyp + it * kSol;
-  for (int k = 0; k < kSol; ++k) cnt[k] = -1;
-  if (pair_count(start, p) < 3) return;
+  int p, it;
+  if (!sample_slots<kSol>(g, P, kSample, start, status, counts, &p, &it)) return;
   const double* q = pts + kPt * start[p];
   double X[9], f[9];
   for (int k = 0; k < 3; ++k) {
@@ -97,55 +56,16 @@ __global__ void __launch_bounds__(64) abs_solve_kernel(const double* __restrict_
     for (int c = 0; c < 3; ++c) { X[3 * k + c] = q[kPt * i + c]; f[3 * k + c] = q[kPt * i + 5 + c]; }
   }
   const int ns = p3p(X, f, poses + ((long)p * kHyp + it * kSol) * kPose, tab);   // the sample's kSol slots, filled in solver order
-  if (ns == 0) return;
-  const int base = atomicAdd(n_hyp + p, ns);
-  for (int k = 0; k < ns; ++k) hyp[(long)p * kHyp + base + k] = it * kSol + k;
+  append_hypotheses<kSol>(p, it, ns, hyp, n_hyp);
 }
 
-// grid (P, ceil(kHyp / 256)) x 256: thread = hypothesis of the pair's work list; the pair's matches stream through LDS
-__global__ void __launch_bounds__(kScoreThreads) abs_score_kernel(const double* __restrict__ pts, const long* __restrict__ start,
-                                                                 const float* __restrict__ K, double thr2, const double* __restrict__ poses,
-                                                                 const int* __restrict__ hyp, const int* __restrict__ n_hyp,
-                                                                 int* __restrict__ counts, const int* __restrict__ status) {
-  __shared__ double tile[kScoreTile][5];
-  const int p = blockIdx.x;
-  const int nh = n_hyp[p];
-  const int h = blockIdx.y * kScoreThreads + threadIdx.x;
-  if (*status || (int)blockIdx.y * kScoreThreads >= nh) return;           // (uniform over the block)
-  const bool valid = h < nh;
-  const int slot = valid ? hyp[(long)p * kHyp + h] : 0;
-  const Cam cam = cam_from_K(K + 9 * (long)p);
-  double m[kPose];
-  for (int i = 0; i < kPose; ++i) m[i] = valid ? poses[((long)p * kHyp + slot) * kPose + i] : 0.0;
-  const long s0 = start[p], n = pair_count(start, p);
-  int cnt = 0;
-  for (long b = 0; b < n; b += kScoreTile) {
-    const int nt = (int)(n - b < kScoreTile ? n - b : kScoreTile);
-    __syncthreads();
-    for (int j = threadIdx.x; j < nt; j += kScoreThreads) {
-      const double* q = pts + kPt * (s0 + b + j);
-      for (int c = 0; c < 5; ++c) tile[j][c] = q[c];
-    }
-    __syncthreads();
-    for (int j = 0; j < nt; ++j) cnt += is_inlier(cam, m, m + 9, tile[j], tile[j][3], tile[j][4], thr2);
-  }
-  if (valid) counts[(long)p * kHyp + slot] = cnt;
-}
-
-// the host's tree() over kLanes partials, N sums at a time: a[q] of thread k is partial k of sum q; out[0..N) in LDS
-template <int N>
-__device__ void block_tree(double (*red)[kLanes], const double* a, double* out) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  for (int q = 0; q < N; ++q) red[q][tid] = a[q];
-  __syncthreads();
-  for (int st = kLanes / 2; st >= 1; st >>= 1) {
-    if (tid < st) for (int q = 0; q < N; ++q) red[q][tid] = red[q][tid] + red[q][tid + st];
-    __syncthreads();
-  }
-  if (tid < N) out[tid] = red[tid][0];
-  __syncthreads();
-}
+struct AbsScore {                            // ransac_score_kernel's model; the tile holds world point and pixel
+  static constexpr int kSol = absp::kSol, kModelSize = kPose, kPt = ::kPt, kTilePt = 5;
+  struct Params { const float* K; double thr2; };
+  struct Ctx { Cam cam; double thr2; };
+  static __device__ Ctx context(const Params& a, int p) { return {cam_from_K(a.K + 9 * (long)p), a.thr2}; }
+  static __device__ bool is_inlier(const Ctx& c, const double* m, const double* q) { return absp::is_inlier(c.cam, m, m + 9, q, q[3], q[4], c.thr2); }
+};
 
 // grid P x kLanes: refit + final.  Pairs without a model (best[p] < 0): n_inliers = -1, pose and mask 0.
 __global__ void __launch_bounds__(kLanes) abs_refit_kernel(const double* __restrict__ pts, const long* __restrict__ start,
@@ -228,29 +148,6 @@ __global__ void __launch_bounds__(kLanes) abs_refit_kernel(const double* __restr
   for (long j = tid; j < n; j += kLanes) mask[s0 + j] = bits[s0 + j] & 1;
 }
 
-// workspace layout (byte offsets, 256-aligned)
-struct Layout { size_t status, start, counts, pts, idx, poses, hyp, n_hyp, best, bits, total; };
-Layout layout(long M, int P) {
-  Layout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
-  // status, start and counts are contiguous: the one device -> host copy of the replay
-  L.status = take(8);
-  L.start = L.status + 8;
-  o = align_up(L.start + sizeof(long) * ((size_t)P + 1), 8);
-  L.counts = o;
-  o = align_up(o + sizeof(int) * (size_t)P * kHyp, 256);
-  L.pts = take(sizeof(double) * kPt * (size_t)M);
-  L.idx = take(sizeof(int) * 3 * (size_t)P * kIters);
-  L.poses = take(sizeof(double) * kPose * (size_t)P * kHyp);
-  L.hyp = take(sizeof(int) * (size_t)P * kHyp);
-  L.n_hyp = take(sizeof(int) * (size_t)P);
-  L.best = take(sizeof(int) * (size_t)P);
-  L.bits = take((size_t)M);
-  L.total = o;
-  return L;
-}
-
 // grid ceil(M / 256) x 256.  fp32 as the reference's warp_kpts; no FMA contraction, so that a float32 restatement of the same
 // operations in the same order gives the same bits.
 __global__ void LOFTR_NO_PACKED_FP32 lift_keypoints_kernel(const float* __restrict__ kpts, const long* __restrict__ m_bids,
@@ -287,7 +184,7 @@ __global__ void LOFTR_NO_PACKED_FP32 lift_keypoints_kernel(const float* __restri
 
 extern "C" size_t loftr_estimate_absolute_pose_batched_workspace_bytes(long M, int P) {
   if (M < 0 || P < 0) return 0;
-  return layout(M, P).total;
+  return layout(M, P, kProblem).total;
 }
 
 extern "C" int loftr_estimate_absolute_pose_batched(const float* pts3d, const float* kpts, const long* m_bids, long M, const float* K, int P,
@@ -297,75 +194,20 @@ extern "C" int loftr_estimate_absolute_pose_batched(const float* pts3d, const fl
   if (P == 0) return M == 0 ? LOFTR_OK : LOFTR_ERR_BAD_ARG;             // every pair id would be out of range
   LOFTR_CHECK_ARG(K && R_out && t_out && n_inliers && ws);
   LOFTR_CHECK_ARG(M == 0 || (pts3d && kpts && m_bids && inliers_out));
-  if ((M + 255) / 256 >= (1L << 31) || M >= (1L << 31) || (long)P * kIters >= (1L << 31)) return LOFTR_ERR_UNSUPPORTED;
-  const Layout L = layout(M, P);
+  if (too_large(M, P)) return LOFTR_ERR_UNSUPPORTED;
+  const Layout L = layout(M, P, kProblem);
   if (ws_bytes < L.total) return LOFTR_ERR_WORKSPACE;
+  const Workspace W = workspace(ws, L);
   hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  int* status = (int*)(w + L.status);
-  long* start = (long*)(w + L.start);
-  int* counts = (int*)(w + L.counts);
-  double *pts = (double*)(w + L.pts), *poses = (double*)(w + L.poses);
-  int *idx = (int*)(w + L.idx), *hyp = (int*)(w + L.hyp), *n_hyp = (int*)(w + L.n_hyp), *best = (int*)(w + L.best);
-  uint8_t* bits = (uint8_t*)(w + L.bits);
+  static const PolarTable tab = polar_table<4>();
   const double thr2 = (double)thresh_px * (double)thresh_px;
-  if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-  if (M > 0) {
-    hipLaunchKernelGGL(abs_prep_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, pts3d, kpts, m_bids, M, K, P, pts, status);
-    LOFTR_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(abs_sample_kernel, dim3((unsigned)((P + 1 + 63) / 64)), dim3(64), 0, s, m_bids, M, P, seed, start, idx, n_hyp);
-  LOFTR_CHECK_LAUNCH();
-  static const PolarTable tab = polar_table();
-  hipLaunchKernelGGL(abs_solve_kernel, dim3((unsigned)(((long)P * kIters + 63) / 64)), dim3(64), 0, s, pts, start, idx, P, tab, poses, counts, hyp,
-                     n_hyp, status);
-  LOFTR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(abs_score_kernel, dim3((unsigned)P, (unsigned)((kHyp + kScoreThreads - 1) / kScoreThreads)), dim3(kScoreThreads), 0, s, pts,
-                     start, K, thr2, poses, hyp, n_hyp, counts, status);
-  LOFTR_CHECK_LAUNCH();
-  // ---- replay of the host loop (absolute_pose.hip loftr_estimate_absolute_pose) over the counts: one copy down, one copy up ----
-  const size_t down = L.counts + sizeof(int) * (size_t)P * kHyp - L.status;
-  std::vector<char> host(down);
-  if (hipMemcpyAsync(host.data(), w + L.status, down, hipMemcpyDeviceToHost, s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-  if (hipStreamSynchronize(s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-  int st;
-  memcpy(&st, host.data(), sizeof(int));
-  if (st) return LOFTR_ERR_BAD_ARG;                                     // m_bids out of [0, P) or not grouped by ascending pair
-  const long* h_start = (const long*)(host.data() + (L.start - L.status));
-  const int* h_counts = (const int*)(host.data() + (L.counts - L.status));
-  std::vector<int> h_best(P);
-  for (int p = 0; p < P; ++p) {
-    const long Mp = h_start[p + 1] - h_start[p];
-    h_best[p] = -1;
-    if (Mp < 3) continue;
-    const int* c = h_counts + (size_t)p * kHyp;
-    long bestn = 0;
-    int max_iters = kIters, iters = max_iters;
-    for (int it = 0; it < iters; ++it) {
-      for (int sol = 0; sol < kSol && c[it * kSol + sol] >= 0; ++sol) {
-        const long cnt = c[it * kSol + sol];
-        if (cnt > bestn) {
-          bestn = cnt;
-          h_best[p] = it * kSol + sol;
-          const double wr = (double)cnt / (double)Mp;
-          const double p_all = pow(wr, 3.0);
-          if (p_all > 1 - 1e-12) iters = it + 1;
-          else if (p_all > 1e-12) {
-            const double need = log(1.0 - (double)conf) / log(1.0 - p_all);
-            if (need < iters) iters = need < it + 1 ? it + 1 : (int)ceil(need);
-          }
-        }
-      }
-    }
-    if (bestn < 3) h_best[p] = -1;
-  }
-  if (hipMemcpyAsync(best, h_best.data(), sizeof(int) * P, hipMemcpyHostToDevice, s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-  hipLaunchKernelGGL(abs_refit_kernel, dim3((unsigned)P), dim3(kLanes), 0, s, pts, start, K, thr2, poses, best, bits, R_out, t_out, inliers_out,
-                     n_inliers);
-  LOFTR_CHECK_LAUNCH();
-  // h_best is pageable host memory that goes out of scope on return: wait for the stream rather than rely on the copy staging it
-  if (hipStreamSynchronize(s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-  return LOFTR_OK;
+  const AbsScore::Params prm = {K, thr2};
+  return run<kProblem.s>(
+      m_bids, M, P, kProblem, conf, seed, L, W, s,
+      [&](dim3 g, dim3 b) { hipLaunchKernelGGL(abs_prep_kernel, g, b, 0, s, pts3d, kpts, m_bids, M, K, P, W.pts, W.status); },
+      [&](dim3 g, dim3 b) { hipLaunchKernelGGL(abs_solve_kernel, g, b, 0, s, W.pts, W.start, W.idx, P, tab, W.models, W.counts, W.hyp, W.n_hyp, W.status); },
+      [&](dim3 g, dim3 b) { hipLaunchKernelGGL(ransac_score_kernel<AbsScore>, g, b, 0, s, W.pts, W.start, prm, W.models, W.hyp, W.n_hyp, W.counts, W.status); },
+      [&](dim3 g, dim3 b) { hipLaunchKernelGGL(abs_refit_kernel, g, b, 0, s, W.pts, W.start, K, thr2, W.models, W.best, W.bits, R_out, t_out, inliers_out, n_inliers); });
 }
 
 extern "C" int loftr_lift_keypoints(const float* kpts, const long* m_bids, long M, const float* depth, int dh, int dw, const float* K,

@@ -28,14 +28,7 @@ namespace {
 
 using namespace geo;
 
-struct Rng {                                                 // xorshift64* (pose.hip)
-  uint64_t s;
-  explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 0x1234567ull) { if (!s) s = 1; }
-  uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
-  long below(long n) { return (long)(next() % (uint64_t)n); }
-};
-
-const PolarTable& table() { static const PolarTable t = polar_table(); return t; }
+const PolarTable& table() { static const PolarTable t = polar_table<3>(); return t; }
 
 long score(int model, const double* m, const double* pts, long n, double thr2, uint8_t* mask) {
   long cnt = 0;
@@ -45,12 +38,6 @@ long score(int model, const double* m, const double* pts, long n, double thr2, u
     cnt += in;
   }
   return cnt;
-}
-
-// the fixed pairwise tree over the 256 strided partials
-double tree(double* p) {
-  for (int st = kLanes / 2; st >= 1; st >>= 1) for (int k = 0; k < st; ++k) p[k] = p[k] + p[k + st];
-  return p[0];
 }
 
 // least-squares fit on the matches with in[i] != 0 (cnt of them)
@@ -112,15 +99,10 @@ extern "C" int loftr_estimate_geometry(const float* kpts0, const float* kpts1, l
   Rng rng(seed);
   double bestM[9] = {0};
   long best = 0;
-  int max_iters = kIters, iters = max_iters;
+  int iters = kIters;
   for (int it = 0; it < iters; ++it) {
-    int idx[7];
-    for (int k = 0; k < s;) {
-      const int c = (int)rng.below(M);
-      bool dup = false;
-      for (int j = 0; j < k; ++j) dup = dup || idx[j] == c;
-      if (!dup) idx[k++] = c;
-    }
+    int idx[kMaxSample];
+    draw_sample(rng, M, s, idx);
     double x0[7], y0[7], x1[7], y1[7], mats[27];
     for (int k = 0; k < s; ++k) { x0[k] = pts[4 * idx[k]]; y0[k] = pts[4 * idx[k] + 1]; x1[k] = pts[4 * idx[k] + 2]; y1[k] = pts[4 * idx[k] + 3]; }
     const int ns = solve_minimal(model, x0, y0, x1, y1, mats, tab);
@@ -129,13 +111,7 @@ extern "C" int loftr_estimate_geometry(const float* kpts0, const float* kpts1, l
       if (cnt > best) {
         best = cnt;
         memcpy(bestM, mats + 9 * sol, sizeof(bestM));
-        const double w = (double)cnt / (double)M;            // adaptive iteration count from the confidence
-        const double p_all = pow(w, (double)s);
-        if (p_all > 1 - 1e-12) iters = it + 1;
-        else if (p_all > 1e-12) {
-          const double need = log(1.0 - (double)conf) / log(1.0 - p_all);
-          if (need < iters) iters = need < it + 1 ? it + 1 : (int)ceil(need);
-        }
+        iters = adaptive_iters(cnt, M, s, conf, it, iters);
       }
     }
   }

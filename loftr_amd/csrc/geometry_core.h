@@ -3,13 +3,9 @@
 // contraction, so that the two sides take identical decisions: IEEE + - * / and sqrt are correctly rounded on both, frexp / ldexp
 // are exact, and the only libm values (cos / sin of the Aberth start angles) are tabulated on the host and handed to the device.
 //
-// The small dense linear algebra (cyclic Jacobi, svd3), the complex arithmetic and the Aberth-Ehrlich root finder are restated
-// from pose.hip / pose_gpu.hip (same operations, same order; the root finder with the device file's complex arithmetic, which
-// DESIGN 11 pins bit for bit to the host library's).  pose.hip and pose_gpu.hip keep their own copies untouched.
+// The sampler, the small dense linear algebra (cyclic Jacobi, svd3) and the complex arithmetic of the root finder are ransac_core.h's.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
+#include "ransac_core.h"
 
 #pragma clang fp contract(off)
 
@@ -17,10 +13,8 @@
 
 namespace geo {
 
-constexpr int kIters = 1000;               // RANSAC iteration cap (loftr_estimate_pose: max_iters)
-// The least-squares refit is repeated on the adopted model's inliers while it strictly gains inliers, at most this many fits.
-constexpr int kRefitRounds = 4;
-constexpr int kLanes = 256;                // strided partial sums of the refit: partial k takes matches i = k (mod 256), ascending
+using namespace ransac;
+
 // A homography sample is rejected when a triple of its four points has |signed area| (twice the triangle's area, in the
 // Hartley-normalised frame of the four points: centroid 0, mean distance sqrt 2) below this, in either image.
 constexpr double kCollinearArea = 1e-3;
@@ -28,141 +22,10 @@ constexpr double kCollinearArea = 1e-3;
 GEO_HD int sample_size(int model) { return model == 0 ? 4 : 7; }
 GEO_HD int max_solutions(int model) { return model == 0 ? 1 : 3; }
 
-// ---- small dense linear algebra (pose.hip: jacobi_eig, mat3_mul, svd3) --------------------------------------------------------
-template <int n>
-GEO_HD void jacobi_eig(double* a, double* w, double* v) {
-  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) v[i * n + j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0;
-    for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) off += a[i * n + j] * a[i * n + j];
-    if (off < 1e-300) break;
-    for (int p = 0; p < n; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        const double apq = a[p * n + q];
-        if (fabs(apq) < 1e-300) continue;
-        const double theta = (a[q * n + q] - a[p * n + p]) / (2 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1));
-        const double c = 1 / sqrt(t * t + 1), s = t * c;
-        for (int k = 0; k < n; ++k) {
-          const double akp = a[k * n + p], akq = a[k * n + q];
-          a[k * n + p] = c * akp - s * akq; a[k * n + q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double apk = a[p * n + k], aqk = a[q * n + k];
-          a[p * n + k] = c * apk - s * aqk; a[q * n + k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double vkp = v[k * n + p], vkq = v[k * n + q];
-          v[k * n + p] = c * vkp - s * vkq; v[k * n + q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  for (int i = 0; i < n; ++i) w[i] = a[i * n + i];
-}
+using PolarTable = ransac::PolarAngles<3>;   // Aberth start angles up to degree 3
 
-GEO_HD void mat3_mul(const double* a, const double* b, double* c) {
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) c[i * 3 + j] = a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j] + a[i * 3 + 2] * b[6 + j];
-}
-GEO_HD double det3_rows(const double* r0, const double* r1, const double* r2) {
-  return r0[0] * (r1[1] * r2[2] - r1[2] * r2[1]) - r0[1] * (r1[0] * r2[2] - r1[2] * r2[0]) + r0[2] * (r1[0] * r2[1] - r1[1] * r2[0]);
-}
-
-// E = U diag(s) V^T via the eigen-decomposition of E^T E (s descending)
-GEO_HD void svd3(const double* E, double* U, double* s, double* V) {
-  double ete[9], w[3], v[9];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) ete[i * 3 + j] = E[i] * E[j] + E[3 + i] * E[3 + j] + E[6 + i] * E[6 + j];
-  jacobi_eig<3>(ete, w, v);
-  int o[3] = {0, 1, 2};
-  for (int i = 0; i < 3; ++i) for (int j = i + 1; j < 3; ++j) if (w[o[j]] > w[o[i]]) { int t = o[i]; o[i] = o[j]; o[j] = t; }
-  for (int k = 0; k < 3; ++k) {
-    s[k] = sqrt(w[o[k]] > 0 ? w[o[k]] : 0);
-    for (int i = 0; i < 3; ++i) V[i * 3 + k] = v[i * 3 + o[k]];
-  }
-  double u[3][3];
-  for (int k = 0; k < 2; ++k) {
-    for (int i = 0; i < 3; ++i) u[k][i] = E[i * 3] * V[k] + E[i * 3 + 1] * V[3 + k] + E[i * 3 + 2] * V[6 + k];
-    double nrm = sqrt(u[k][0] * u[k][0] + u[k][1] * u[k][1] + u[k][2] * u[k][2]);
-    if (nrm < 1e-300) nrm = 1;
-    for (int i = 0; i < 3; ++i) u[k][i] /= nrm;
-  }
-  double d = u[0][0] * u[1][0] + u[0][1] * u[1][1] + u[0][2] * u[1][2];
-  for (int i = 0; i < 3; ++i) u[1][i] -= d * u[0][i];
-  double nrm = sqrt(u[1][0] * u[1][0] + u[1][1] * u[1][1] + u[1][2] * u[1][2]);
-  if (nrm < 1e-300) nrm = 1;
-  for (int i = 0; i < 3; ++i) u[1][i] /= nrm;
-  u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1]; u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2]; u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
-  for (int k = 0; k < 3; ++k) for (int i = 0; i < 3; ++i) U[i * 3 + k] = u[k][i];
-}
-
-// ---- complex arithmetic as the host library computes it (pose_gpu.hip) ----------------------------------------------------------
-struct cd { double re, im; };
-GEO_HD cd c_add(cd a, cd b) { return {a.re + b.re, a.im + b.im}; }
-GEO_HD cd c_sub(cd a, cd b) { return {a.re - b.re, a.im - b.im}; }
-GEO_HD cd c_mul(cd a, cd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-GEO_HD double c_abs(cd z) {                                      // libstdc++ __complex_abs
-  double x = z.re, y = z.im;
-  const double ax = fabs(x), ay = fabs(y);
-  const double s = ax < ay ? ay : ax;
-  if (s == 0.0) return s;
-  x /= s;
-  y /= s;
-  return s * sqrt(x * x + y * y);
-}
-GEO_HD double crt_logb(double x) {                               // compiler-rt logb
-  if (isnan(x)) return x;
-  if (isinf(x)) return INFINITY;
-  if (x == 0.0) return -INFINITY;
-  int e;
-  frexp(x, &e);
-  return (double)(e - 1);
-}
-GEO_HD cd c_div(cd num, cd den) {                                // compiler-rt __divdc3
-  double a = num.re, b = num.im, c = den.re, d = den.im;
-  int ilogbw = 0;
-  const double ac = fabs(c), ad = fabs(d);
-  const double mx = isnan(c) ? ad : (isnan(d) ? ac : (ac > ad ? ac : ad));
-  const double logbw = crt_logb(mx);
-  if (isfinite(logbw)) {
-    ilogbw = (int)logbw;
-    c = ldexp(c, -ilogbw);
-    d = ldexp(d, -ilogbw);
-  }
-  const double denom = c * c + d * d;
-  cd z{ldexp((a * c + b * d) / denom, -ilogbw), ldexp((b * c - a * d) / denom, -ilogbw)};
-  if (isnan(z.re) && isnan(z.im)) {
-    if (denom == 0.0 && (!isnan(a) || !isnan(b))) {
-      z.re = copysign(INFINITY, c) * a;
-      z.im = copysign(INFINITY, c) * b;
-    } else if ((isinf(a) || isinf(b)) && isfinite(c) && isfinite(d)) {
-      a = copysign(isinf(a) ? 1.0 : 0.0, a);
-      b = copysign(isinf(b) ? 1.0 : 0.0, b);
-      z.re = INFINITY * (a * c + b * d);
-      z.im = INFINITY * (b * c - a * d);
-    } else if (isinf(logbw) && logbw > 0.0 && isfinite(a) && isfinite(b)) {
-      c = copysign(isinf(c) ? 1.0 : 0.0, c);
-      d = copysign(isinf(d) ? 1.0 : 0.0, d);
-      z.re = 0.0 * (a * c + b * d);
-      z.im = 0.0 * (b * c - a * d);
-    }
-  }
-  return z;
-}
-
-// cos / sin of the Aberth start angles 2 pi i / n + 0.4, n = 1..3, from the host's libm
-struct PolarTable { double c[3][3], s[3][3]; };
-inline PolarTable polar_table() {                                // host only
-  PolarTable t{};
-  for (int n = 1; n <= 3; ++n)
-    for (int i = 0; i < n; ++i) {
-      const double theta = 2 * M_PI * i / n + 0.4;               // pose.hip real_roots: std::polar(rho, theta)
-      t.c[n - 1][i] = cos(theta);
-      t.s[n - 1][i] = sin(theta);
-    }
-  return t;
-}
-
-// pose.hip real_roots for a polynomial of degree <= 3 (ascending coefficients pin[0..4)): Aberth-Ehrlich + Newton polishing on the
-// real axis; the distinct real roots go to r[0..*nr)
+// pose_core.h's real_roots for a polynomial of degree <= 3 (ascending coefficients pin[0..4)), kept apart for its arrays of that size,
+// which stay in registers: Aberth-Ehrlich + Newton polishing on the real axis; the distinct real roots go to r[0..*nr)
 GEO_HD void real_roots3(const double* pin, double* r, int* nr, const PolarTable& tab) {
   double p[4] = {pin[0], pin[1], pin[2], pin[3]};
   int pn = 4;
@@ -181,7 +44,7 @@ GEO_HD void real_roots3(const double* pin, double* r, int* nr, const PolarTable&
     const double rho = radius * (0.3 + 0.7 * (i + 1) / n);
     z[i] = {rho * tab.c[n - 1][i], rho * tab.s[n - 1][i]};
   }
-  const cd tiny{1e-300, 0};
+  const cd tiny{1e-300, 0}, one{1.0, 0.0};
   for (int it = 0; it < 200; ++it) {
     double change = 0;
     for (int i = 0; i < n; ++i) {
@@ -190,7 +53,7 @@ GEO_HD void real_roots3(const double* pin, double* r, int* nr, const PolarTable&
       if (c_abs(f) < 1e-300) continue;
       const cd ratio = c_div(f, c_abs(df) > 1e-300 ? df : tiny);
       cd sum{0.0, 0.0};
-      for (int j = 0; j < n; ++j) if (j != i) { const cd d = c_sub(z[i], z[j]); sum = c_add(sum, c_div(cd{1.0, 0.0}, c_abs(d) > 1e-300 ? d : tiny)); }
+      for (int j = 0; j < n; ++j) if (j != i) { const cd d = c_sub(z[i], z[j]); sum = c_add(sum, c_div(one, c_abs(d) > 1e-300 ? d : tiny)); }
       const cd rs = c_mul(ratio, sum);
       const cd step = c_div(ratio, cd{-rs.re + 1.0, -rs.im});
       z[i] = c_sub(z[i], step);
@@ -341,7 +204,7 @@ GEO_HD int solve_minimal(int model, const double* x0, const double* y0, const do
 
 // ---- residual test: is the correspondence within thr2 (squared pixels) of the model? --------------------------------------------
 // Homography: squared forward transfer error |x1 - pi(H x0)|^2; a non-positive third coordinate of H x0 is an outlier.
-// Fundamental: squared Sampson distance (pose.hip score(), on pixels).
+// Fundamental: squared Sampson distance (on pixels; `<=`, where the five-point estimator on normalised points has `<`).
 GEO_HD bool is_inlier(int model, const double* m, double x0, double y0, double x1, double y1, double thr2) {
   if (model == 0) {
     const double w = m[6] * x0 + m[7] * y0 + m[8];

@@ -92,12 +92,13 @@ def _ransac_fraction(p0, p1, K0, K1, R, t):
     return float(np.mean(r * r < thr * thr * (l[:, 0] ** 2 + l[:, 1] ** 2 + m[:, 0] ** 2 + m[:, 1] ** 2)))
 
 
-def _compare(pairs, got, seed):
+def _compare(pairs, got, seed, host=None):
+    """The batched result against the host estimator's, pair by pair (host: its results for `seed` where they are at hand)."""
     R, t, inl, n = (x.cpu().numpy() for x in got)
     bids = np.concatenate([np.full(len(p[0]), b) for b, p in enumerate(pairs)])
     stats = {"early": 0, "capped": 0, "none": 0}
     for b, (p0, p1, K0, K1) in enumerate(pairs):
-        ref = EV.estimate_pose_native(p0, p1, K0, K1, THR, conf=CONF, seed=seed)
+        ref = host[b] if host is not None else EV.estimate_pose_native(p0, p1, K0, K1, THR, conf=CONF, seed=seed)
         mask = inl[bids == b]
         if ref is None:
             assert n[b] == -1 and not mask.any() and not R[b].any() and not t[b].any(), (b, n[b])
