@@ -61,7 +61,8 @@ typedef enum {
  *     loftr_estimate_absolute_pose_batched_workspace_bytes, loftr_lift_keypoints), the keypoint atlas (loftr_atlas_*), triangulation
  *     of tracks (loftr_triangulate_tracks_host, loftr_triangulation_pairs, loftr_triangulate_tracks,
  *     loftr_triangulate_tracks_workspace_bytes), localisation against the triangulated model (loftr_model_cells_host,
- *     loftr_model_cells, loftr_model_lookup_host, loftr_model_lookup_workspace_bytes, loftr_model_lookup) */
+ *     loftr_model_cells, loftr_model_lookup_host, loftr_model_lookup_workspace_bytes, loftr_model_lookup), bundle adjustment of the
+ *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -844,6 +845,78 @@ size_t loftr_model_lookup_workspace_bytes(long M, long Q);
 int loftr_model_lookup(const LoftrModel* model, const float* kpts_db, const float* kpts_q, const float* conf, const int* rows,
                        const uint8_t* mask, long M, const int* row_db, const int* row_query, long R, long Q, const LoftrModelLookupOut* out,
                        void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
+/* ---- bundle adjustment of the triangulated model (csrc/bundle_core.h holds all the arithmetic and every per-item step) ------
+ * Joint refinement of camera poses (6 DoF, intrinsics fixed) and points over the pixel reprojection error: Levenberg-Marquardt, optional
+ * Huber loss, the point-eliminated Schur system solved by preconditioned conjugate gradients without forming it.
+ * loftr_bundle_adjust_host (csrc/bundle.hip, host memory) DEFINES the result, loftr_bundle_adjust (csrc/bundle_gpu.hip, device memory)
+ * reproduces it bit for bit, whatever the grid.
+ * Input: tracks in CSR form as for the triangulation -- offsets [T+1] i64, obs_image [N] i32, obs_xy [N,2] f32 -- plus obs_mask [N] u8,
+ *   xyz [T,3] f32, K [n,3,3] f64 (fx, skew, cx, fy, cy read), T_cam_from_world [n,4,4] f64, fixed [n] u8, and the observations grouped by
+ *   image: cam_offsets [n+1] i64 (0 first, N last, ascending), cam_obs [N] i32, the observation indices of image 0, then of image 1, ...,
+ *   strictly ascending within an image (the stable sort of obs_image).
+ * Arithmetic: fp64 without FMA contraction, + - * / sqrt only.
+ *   1. State.  A camera is a unit quaternion (w, x, y, z) and t.  The quaternion comes from the input R by Shepperd's method, branch on
+ *      the largest of trace, R00, R11, R22 (the first of equals), then divided by its norm.  A camera is VALID when fx, skew, cx, fy, cy,
+ *      the top 3 x 4 of its matrix and its quaternion are finite and fx, fy are not 0.  The rotation used for a valid camera that is not
+ *      fixed is R(q); for any other camera it is the input's R.  Points are fp64 copies of the f32 xyz.  A camera that is not free gets
+ *      its 16 input doubles back bit for bit, a point that is not active its 3 input floats.
+ *   2. Active set, fixed for the run.  An observation is active iff its mask byte is non-zero, its pixel is finite, its camera is valid,
+ *      its point is finite and Y_z > 0 at the start; a point with fewer than 2 such observations is inactive and so are its
+ *      observations.  A camera is free iff it is not fixed, valid, and has at least 1 active observation.
+ *   3. P = R X, Y = P + t, u = fx (Y0 / Y2) + skew (Y1 / Y2) + cx, v = fy (Y1 / Y2) + cy, r = (u, v) - obs.  With the perturbation
+ *      Y' = dR P + t + dt: A = dr/d(omega, dt) [2,6] with dY/domega = -[P]x, B = dr/dX = (dr/dY) R [2,3].
+ *   4. Huber: |r| = sqrt(ru^2 + rv^2); w = 1, rho = |r|^2 if huber_px is 0 or |r| <= huber_px, else w = huber_px / |r|,
+ *      rho = 2 huber_px |r| - huber_px^2.  A, B and r enter the normal equations multiplied by sqrt(w); the cost is the sum of rho.
+ *   5. Sums.  Per point (V = sum B^T B, g = sum B^T r, its shares of the cost and of sum |r|^2): sequentially over the track's active
+ *      observations in CSR order.  Per camera (U = sum A^T A, 21 entries; g_c = sum A^T r; the camera half of S p): osum64 over the
+ *      camera's list, element l being slot l of the list (an inactive slot adds nothing).  osum64: 64 accumulators start at +0;
+ *      accumulator l adds elements l, l + 64, ... ascending; then for s = 32, 16, ..., 1: a[l] = a[l] + a[l + s] for l < s; the result is
+ *      a[0].  osum (the cost over tracks, dot products over cameras): osum64 per chunk of 4096 elements, then osum of the chunk sums.
+ *      A dot product of camera vectors is 6 terms sequentially per camera (+0 for a camera that is not free), then osum over cameras.
+ *   6. Step.  The diagonals of U and V are multiplied by 1 + lambda (a zero diagonal becomes lambda).  V^-1 and the block-Jacobi
+ *      preconditioner U^-1 are L D L^T eliminations in index order without pivoting; a non-positive pivot rejects the step.  Right-hand
+ *      side b = -(g_c - sum A^T (B y_j)), y_j = V^-1 g_j.  S x = b by preconditioned conjugate gradients from x = 0 over the free
+ *      cameras; S p is evaluated as z_j = V^-1 sum B^T (A p_c) per point (over its active observations of free cameras), then
+ *      U p_c - sum A^T (B z_j) per camera.  Before each of the at most pcg_iters iterations the solve stops when
+ *      r.M^-1 r <= pcg_tol^2 r0.M^-1 r0, and after S p when p.S p is not greater than 0.  Points: dX_j = V^-1 (-(g_j + sum B^T (A x_c))).
+ *      With no free camera this is the per-point step.
+ *   7. Trial: q' = normalise((1, omega / 2) (x) q), t' = t + dt, X' = X + dX; a non-finite value rejects.  Accepted iff every active
+ *      observation keeps Y_z > 0 and cost' < cost; then lambda = max(lambda / 10, 1e-10), and the run stops as converged when
+ *      cost - cost' <= ftol cost'.  Rejected: lambda = 10 lambda, and the run stops as stalled when lambda > 1e10.  lambda starts at 1e-4;
+ *      A, B, U, V are evaluated again only after an accepted trial.  At most max_iters trials; none when there is no active observation
+ *      (status 3) or when the cost of the start is exactly 0 (converged).
+ * Output: T_out [n,4,4] f64 (R(q), t and the row 0 0 0 1 for a free camera), xyz_out [T,3] f32 (the fp64 point rounded once),
+ *   obs_active [N] u8, cam_free [n] u8, point_active [T] u8, counts [16] i64: [0] status -- 0 converged, 1 max_iters, 2 stalled,
+ *   3 nothing to adjust (no active observation) --, [1] error bits (1: an obs_image outside [0, n); 2: offsets that do not start at 0,
+ *   end at N and ascend; 4: cam_offsets / cam_obs that are not the stable grouping), [2] trials, [3] accepted trials, [4] conjugate
+ *   gradient iterations, [5] active observations, [6] active points, [7] free cameras, [8..12] the bits of five doubles: cost before,
+ *   cost after, rms pixel error over the active observations before and after, final lambda; [13..15] 0.
+ * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, huber_px or ftol negative or not finite, pcg_tol outside [0, 1),
+ *   max_iters outside [0, LOFTR_BUNDLE_MAX_ITERS], pcg_iters outside [1, LOFTR_BUNDLE_MAX_PCG]; the host routine also for the three
+ *   error bits (the kernels raise counts[1] instead, read nothing through the bad value, run no trial and leave the other outputs
+ *   undefined: they never wait for the device); LOFTR_ERR_UNSUPPORTED for T or N >= 2^31; LOFTR_ERR_WORKSPACE for a short workspace. */
+#define LOFTR_BUNDLE_MAX_ITERS 1000
+#define LOFTR_BUNDLE_MAX_PCG 200
+int loftr_bundle_adjust_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                             const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
+                             const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
+                             double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
+                             long* counts);
+/* The kernels: a fixed schedule of launches on the stream (max_iters trials of pcg_iters iterations); a kernel whose phase the host
+ * routine would not run returns at once on a flag in device memory.  No host synchronisation unless class_ms is given: NULL, or
+ * 2 * LOFTR_BUNDLE_CLASSES host floats that receive, per kernel class, the median GPU time of a launch and the total (events around
+ * every launch; the call then waits for the stream).  class_launches: NULL, or LOFTR_BUNDLE_CLASSES host longs, the launches issued.
+ * Classes: 0 setup, 1 linearise, 2 factor, 3 track half, 4 camera half, 5 osum, 6 update, 7 apply, 8 evaluate, 9 accept, 10 write.
+ * Workspace: loftr_bundle_adjust_workspace_bytes(T, N, n_images): 208 bytes per track, 4 per observation, about 960 per image; 0 for
+ * sizes out of range. */
+#define LOFTR_BUNDLE_CLASSES 11
+size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images);
+int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                        const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
+                        const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
+                        double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
+                        long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

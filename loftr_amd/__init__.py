@@ -8,4 +8,5 @@ from .loftr import LoFTR                                           # noqa: F401
 from .pairs import FeatureBank                                     # noqa: F401
 from .atlas import KeypointAtlas, SfmResult                       # noqa: F401
 from .triangulation import Points3D, triangulate_tracks           # noqa: F401
+from .bundle import BundleResult, bundle_adjust                   # noqa: F401
 from .localization import LocalizationModel, QueryLocalizer, QueryPoses   # noqa: F401

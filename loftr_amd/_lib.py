@@ -154,6 +154,11 @@ SIGNATURES = {
     "loftr_model_lookup_host": (_i, [C.POINTER(Model), _p, _p, _p, _p, _p, _l, _p, _p, _l, _l, C.POINTER(ModelLookupOut)]),
     "loftr_model_lookup_workspace_bytes": (_sz, [_l, _l]),
     "loftr_model_lookup": (_i, [C.POINTER(Model), _p, _p, _p, _p, _p, _l, _p, _p, _l, _l, C.POINTER(ModelLookupOut), _p, _sz, _p, _p]),
+    "loftr_bundle_adjust_host": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _i, _p, _p, C.c_double, _i, _i, C.c_double, C.c_double,
+                                      _p, _p, _p, _p, _p, _p]),
+    "loftr_bundle_adjust_workspace_bytes": (_sz, [_l, _l, _i]),
+    "loftr_bundle_adjust": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _i, _p, _p, C.c_double, _i, _i, C.c_double, C.c_double,
+                                 _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

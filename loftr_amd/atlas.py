@@ -99,6 +99,20 @@ class SfmResult:
         pts.offsets, pts.image, pts.keypoint = offsets, image, local
         return pts
 
+    def adjust(self, pts, K, T_cam_from_world, fixed=None, **kwargs):
+        """Bundle adjustment of the poses and of the points ``pts`` (a Points3D of ``triangulate`` on this result) over the observations
+        the triangulation kept (bundle.bundle_adjust) -> BundleResult on this result's device.  ``fixed`` and the keyword
+        arguments are bundle_adjust's; the intended loop is triangulate -> adjust -> triangulate(K, res.T_cam_from_world)."""
+        from .bundle import bundle_adjust
+        if pts.offsets is None:
+            raise ValueError("SfmResult.adjust: this Points3D carries no tracks (use SfmResult.triangulate)")
+        dev = self.keypoints.device
+        K, T = (torch.as_tensor(x).detach().to(dev, torch.float64) for x in (K, T_cam_from_world))
+        xy = self.keypoints[self.kp_offsets[pts.image] + pts.keypoint]
+        if fixed is not None:
+            fixed = torch.as_tensor(fixed).to(dev)
+        return bundle_adjust(pts.offsets, pts.image.to(torch.int32), xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **kwargs)
+
     def to_host(self):
         """dict of numpy arrays (plus 'stats')."""
         out = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}

@@ -1,0 +1,133 @@
+"""Bundle adjustment of the triangulated model: camera poses and points refined together over the reprojection error, on the device.
+
+The step between two triangulations: database poses that come from pairwise estimates, a coarse SfM run, SLAM or GPS / IMU priors are
+not exact, and the points triangulated from them carry the error into every localised query.  ``bundle_adjust`` minimises the pixel
+reprojection error over the poses (6 DoF, intrinsics fixed) and the points::
+
+    sfm = atlas.finalize()
+    pts = sfm.triangulate(K, T_cam_from_world)
+    res = sfm.adjust(pts, K, T_cam_from_world, fixed=known)                           # BundleResult, on the atlas's device
+    pts = sfm.triangulate(K, res.T_cam_from_world)                                    # the refined poses admit more observations
+
+The rule (include/loftr_hip.h): Levenberg-Marquardt with an optional Huber loss; the linear step is the point-eliminated
+Schur system, solved by preconditioned conjugate gradients without forming it; every sum has a defined order.  The host routine
+``loftr_bundle_adjust_host`` defines the result (CPU tensors / numpy arrays run it), the HIP kernels reproduce it bit for bit (GPU
+tensors run them; there is no silent fallback either way).
+"""
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import LoftrHipError
+
+_OUT = ("T_cam_from_world", "xyz", "obs_active", "cam_free", "point_active")
+_ARGS = ("offsets", "obs_image", "obs_xy", "obs_mask", "xyz", "K", "T_cam_from_world")
+
+
+class BundleResult:
+    """What ``bundle_adjust`` returns (tensors on the device of the input).
+
+    ``T_cam_from_world [n,4,4] f64`` (the input's bits for a camera that is not free), ``xyz [T,3] f32`` (the input's bits for a point
+    that is not active), ``obs_active [N] bool``, ``cam_free [n] bool``, ``point_active [T] bool``; ``cost_before`` / ``cost_after`` (the
+    sum of the loss over the active observations), ``rms_px_before`` / ``rms_px_after`` (root mean squared pixel error over them),
+    ``n_iters`` (trials), ``n_accepted``, ``n_pcg`` (conjugate-gradient iterations), ``status`` (a name of ``ops.BUNDLE_STATUS``:
+    converged, max_iters, stalled, nothing_to_adjust); ``stats``: dict of the counts."""
+
+    FIELDS = _OUT
+
+    def __init__(self, stats, **tensors):
+        self.stats = stats
+        for k in self.FIELDS:
+            setattr(self, k, tensors[k])
+        for k in ("cost_before", "cost_after", "rms_px_before", "rms_px_after", "n_iters", "n_accepted", "n_pcg", "status"):
+            setattr(self, k, stats[k])
+
+    def to_host(self):
+        """dict of numpy arrays (plus 'stats')."""
+        out = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}
+        out["stats"] = dict(self.stats)
+        return out
+
+
+def _integers(name, a):
+    dt = a.dtype if isinstance(a, torch.Tensor) else np.asarray(a).dtype
+    if (isinstance(dt, torch.dtype) and (dt.is_floating_point or dt == torch.bool)) or \
+            (not isinstance(dt, torch.dtype) and not np.issubdtype(dt, np.integer)):
+        raise ValueError(f"bundle_adjust: {name} must hold integers, got {dt}")
+
+
+def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed=None, huber_px=0.0, max_iters=30, pcg_iters=30,
+                  pcg_tol=1e-2, ftol=1e-9, timings=None):
+    """Refine poses and points over the reprojection error -> ``BundleResult``.
+
+    ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``; ``obs_mask [N]`` (bool or integers: which
+    observations to use, e.g. ``Points3D.obs_inlier``), ``xyz [T,3]`` the starting points (NaN: the point is left out), ``K [n,3,3]``,
+    ``T_cam_from_world [n,4,4]`` the starting poses.  CPU tensors or numpy arrays run the defining host routine; GPU tensors (all of them,
+    on one device) run the kernels.
+
+    ``fixed``: ``[n]`` bool, the cameras that keep their pose; ``None`` fixes image 0 only.  Fixing one camera removes six of the seven
+    gauge freedoms; what remains of the gauge, the scale included, is held only by the damping, so a caller who knows two poses should
+    fix both.  ``huber_px``: 0 for the squared loss, else the Huber radius in pixels.  ``max_iters`` trials at most, each solving its
+    step with at most ``pcg_iters`` conjugate-gradient iterations to the relative tolerance ``pcg_tol``; the run stops as converged when
+    an accepted trial lowers the cost by no more than ``ftol`` of it.  The active set is decided once, at the start; loop through
+    ``triangulate`` to renew it.  One readback of the 16 counts; bad ``obs_image`` / ``offsets`` raise ValueError."""
+    args = [offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world]
+    params = ops._ba_params("bundle_adjust", huber_px, max_iters, pcg_iters, pcg_tol, ftol)
+    gpu = [isinstance(a, torch.Tensor) and a.is_cuda for a in args]
+    fixed_gpu = isinstance(fixed, torch.Tensor) and fixed.is_cuda
+    if (any(gpu) and not all(gpu)) or (fixed is not None and fixed_gpu != all(gpu)):
+        where = [f"{n}: {'GPU' if g else 'CPU'}" for n, g in zip(_ARGS, gpu)] + ([f"fixed: {'GPU' if fixed_gpu else 'CPU'}"] if fixed is not None else [])
+        raise LoftrHipError("bundle_adjust: GPU and CPU arguments mixed (" + ", ".join(where) + "); there is no silent fallback: move them to one device")
+    for n, a in zip(_ARGS[:2], args[:2]):
+        _integers(n, a)
+    if all(gpu):
+        dev = args[0].device
+        dts = (torch.int64, torch.int32, torch.float32, None, torch.float32, torch.float64, torch.float64)
+        a = [x.detach() if dt is None else x.detach().to(dt) for x, dt in zip(args, dts)]
+        a[3] = (a[3] != 0).to(torch.uint8)
+        n = a[5].shape[0]
+        if fixed is None:
+            fixed = torch.zeros(n, dtype=torch.bool, device=dev)
+            fixed[:1] = True
+        fx = (fixed.detach() != 0).to(torch.uint8)
+        # the observations grouped by image: integer plumbing, a stable sort (bad image ids are caught by the kernels, so clamp here)
+        im = a[1].to(torch.int64)
+        cam_obs = torch.sort(im, stable=True).indices.to(torch.int32)
+        cam_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n > 0 and im.numel() and im.dim() == 1:
+            cam_offsets[1:] = torch.cumsum(torch.bincount(im.clamp(0, n - 1), minlength=n), 0)
+        out = ops.bundle_adjust(*a, fx, cam_offsets, cam_obs, *params, timings=timings)
+    else:
+        dts = (np.int64, np.int32, np.float32, None, np.float32, np.float64, np.float64)
+        host = lambda x: x.detach().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        a = [np.ascontiguousarray(host(x)) if dt is None else np.ascontiguousarray(host(x), dt) for x, dt in zip(args, dts)]
+        a[3] = (a[3] != 0).astype(np.uint8)
+        n = a[5].shape[0]
+        fx = np.zeros(n, np.uint8)
+        if fixed is None:
+            fx[:1] = 1
+        else:
+            fx = (host(fixed) != 0).astype(np.uint8)
+        if a[0].ndim == 1 and a[1].ndim == 1 and a[5].ndim == 3:         # the errors the kernels report through counts[1]
+            if a[1].size and (a[1].min() < 0 or a[1].max() >= n):
+                raise ValueError("bundle_adjust: " + ops.BUNDLE_ERRORS[0][1])
+            if a[0].size and (a[0][0] != 0 or a[0][-1] != a[1].shape[0] or (np.diff(a[0]) < 0).any()):
+                raise ValueError("bundle_adjust: " + ops.BUNDLE_ERRORS[1][1])
+        cam_obs = np.argsort(a[1], kind="stable").astype(np.int32)
+        cam_offsets = np.zeros(n + 1, np.int64)
+        if a[1].ndim == 1:
+            cam_offsets[1:] = np.cumsum(np.bincount(a[1], minlength=n)[:n])
+        out = {k: torch.from_numpy(v) for k, v in ops.bundle_adjust_host(*a, fx, cam_offsets, cam_obs, *params).items()}
+    counts = out["counts"].cpu()                                        # the one readback
+    reals = counts[8:13].view(torch.float64).tolist()
+    counts = counts.tolist()
+    for bit, text in ops.BUNDLE_ERRORS:
+        if counts[1] & bit:
+            raise ValueError(f"bundle_adjust: {text} (found on the device)")
+    stats = {"status": ops.BUNDLE_STATUS[counts[0]], "n_iters": counts[2], "n_accepted": counts[3], "n_pcg": counts[4],
+             "n_active_observations": counts[5], "n_active_points": counts[6], "n_free_cameras": counts[7],
+             "n_tracks": out["point_active"].numel(), "n_observations": out["obs_active"].numel(), "n_images": out["cam_free"].numel(),
+             "cost_before": reals[0], "cost_after": reals[1], "rms_px_before": reals[2], "rms_px_after": reals[3], "lambda": reals[4]}
+    for k in ("obs_active", "cam_free", "point_active"):
+        out[k] = out[k].view(torch.bool)
+    return BundleResult(stats, **{k: out[k] for k in _OUT})

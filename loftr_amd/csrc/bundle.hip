@@ -1,0 +1,160 @@
+// Bundle adjustment of the triangulated model (host code, double precision): Levenberg-Marquardt over camera poses (6 DoF, intrinsics
+// fixed) and points on the pixel reprojection error, optional Huber loss, the point-eliminated Schur system solved by preconditioned
+// conjugate gradients without forming it (the contract is in include/loftr_hip.h).  What Ceres / COLMAP's bundle adjuster is
+// used for after triangulation; neither is in this image, so this is a statement of the published method (Triggs et al., "Bundle
+// Adjustment -- A Modern Synthesis"; Agarwal et al., "Bundle Adjustment in the Large"), NOT of their source.  PARITY UNPINNED against them.
+// This function DEFINES the result: loftr_bundle_adjust (bundle_gpu.hip) reproduces it bit for bit, which is why all the arithmetic and
+// every per-item step live in bundle_core.h and why this file is only the sequence of phases and the order-defined sums.
+#include <stdint.h>
+#include <type_traits>
+#include <vector>
+#include "../../include/loftr_hip.h"
+#include "bundle_core.h"
+
+#pragma clang fp contract(off)
+
+using namespace ba;
+
+namespace {
+
+// osum64 of `count` elements of M values each: term(e, a) adds element e into the M accumulators a
+template <int M, class F> void osum64(long count, F term, double* out) {
+  double a[64][M];
+  for (int l = 0; l < 64; ++l) for (int m = 0; m < M; ++m) a[l][m] = 0.0;
+  for (long e = 0; e < count; ++e) term(e, a[e % 64]);
+  for (int s = 32; s >= 1; s >>= 1)
+    for (int l = 0; l < s; ++l) for (int m = 0; m < M; ++m) a[l][m] = a[l][m] + a[l + s][m];
+  for (int m = 0; m < M; ++m) out[m] = a[0][m];
+}
+// osum of v[0 .. count): osum64 per chunk of 4096, then osum of the chunk sums
+double osum(const double* v, long count) {
+  std::vector<double> cur(v, v + count), next;
+  for (;;) {
+    const long chunks = (long)((cur.size() + kChunk - 1) / kChunk);
+    next.assign((size_t)(chunks > 0 ? chunks : 1), 0.0);
+    for (long b = 0; b < (chunks > 0 ? chunks : 1); ++b) {
+      const long lo = b * kChunk, len = (long)cur.size() - lo < kChunk ? (long)cur.size() - lo : kChunk;
+      const double* src = cur.data() + lo;
+      osum64<1>(len > 0 ? len : 0, [&](long e, double* a) { a[0] = a[0] + src[e]; }, &next[(size_t)b]);
+    }
+    if (chunks <= 1) return next[0];
+    cur.swap(next);
+  }
+}
+
+}  // namespace
+
+extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                        const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
+                                        const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters,
+                                        double pcg_tol, double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
+                                        uint8_t* point_active, long* counts) {
+  if (!offsets || !cam_offsets || !counts || T < 0 || N < 0 || n_images < 0) return LOFTR_ERR_BAD_ARG;
+  if (T > 0 && (!xyz || !xyz_out || !point_active)) return LOFTR_ERR_BAD_ARG;
+  if (N > 0 && (!obs_image || !obs_xy || !obs_mask || !obs_active || !cam_obs)) return LOFTR_ERR_BAD_ARG;
+  if (n_images > 0 && (!K || !T_cam_from_world || !fixed || !T_out || !cam_free)) return LOFTR_ERR_BAD_ARG;
+  if (!(huber_px >= 0.0 && fin(huber_px) && ftol >= 0.0 && fin(ftol) && pcg_tol >= 0.0 && pcg_tol < 1.0)) return LOFTR_ERR_BAD_ARG;
+  if (max_iters < 0 || max_iters > LOFTR_BUNDLE_MAX_ITERS || pcg_iters < 1 || pcg_iters > LOFTR_BUNDLE_MAX_PCG) return LOFTR_ERR_BAD_ARG;
+  if (T >= (1L << 31) || N >= (1L << 31)) return LOFTR_ERR_UNSUPPORTED;
+  for (int i = 0; i < kCounts; ++i) counts[i] = 0;
+  if (T == 0 && N > 0) return LOFTR_ERR_BAD_ARG;
+  if (n_images == 0 && N > 0) return LOFTR_ERR_BAD_ARG;
+  Ctx c{};
+  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
+  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
+  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
+  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+  std::vector<char> ws(layout(c, nullptr), 0);
+  layout(c, ws.data());
+  Ctrl& s = *c.ctrl;
+  const long n = n_images;
+  ctrl_init(c);
+  for (long i = 0; i < n; ++i) cam_setup(c, i);
+  for (long t = 0; t < T; ++t) {
+    long cnt;
+    s.err |= track_setup(c, t, &cnt);
+    s.n_active_obs += (unsigned long long)cnt;
+    s.n_active_pts += cnt > 0;
+  }
+  if (s.err) return LOFTR_ERR_BAD_ARG;
+  for (long i = 0; i < n; ++i) {
+    long b, e, cnt = 0;
+    if (!group_range(c, i, &b, &e)) { s.err |= kBadGroups; continue; }
+    for (long k = b; k < e; ++k) {
+      bool active;
+      s.err |= group_check(c, i, b, k, &active);
+      cnt += active;
+    }
+    cam_free[i] = (uint8_t)(!fixed[i] && c.cam_valid[i] && cnt >= 1);
+    s.n_free += cam_free[i];
+  }
+  if (s.err) return LOFTR_ERR_BAD_ARG;
+
+  // a camera's osum64: element l is slot l of its list; an inactive slot adds nothing
+  auto cam_sum = [&](long i, auto tag, auto term, double* out) {
+    constexpr int M = decltype(tag)::value;
+    const long b = cam_offsets[i];
+    osum64<M>(cam_offsets[i + 1] - b, [&](long e, double* a) { const long o = cam_obs[b + e]; if (obs_active[o]) term(o, a); }, out);
+  };
+  auto evaluate = [&](int buf) {
+    bool ok = true;
+    for (long t = 0; t < T; ++t) ok = track_eval(c, buf, t) && ok;
+    return ok;
+  };
+  evaluate(0);
+  ctrl_feed(c, kActCost0, osum(c.part, T));
+  ctrl_feed(c, kActSq0, osum(c.part2, T));
+
+  for (int it = 0; it < max_iters && !s.done; ++it) {
+    const int cur = s.cur;
+    if (s.fresh) {
+      for (long t = 0; t < T; ++t) track_lin(c, cur, t);
+      for (long i = 0; i < n; ++i) {
+        if (!cam_free[i]) continue;
+        double a[27];
+        cam_sum(i, std::integral_constant<int, 27>{}, [&](long o, double* acc) { cam_lin_term(c, cur, o, acc); }, a);
+        for (int k = 0; k < 21; ++k) c.U[21 * i + k] = a[k];
+        for (int k = 0; k < 6; ++k) c.gc[6 * i + k] = a[21 + k];
+      }
+    }
+    const double lambda = s.lambda;
+    for (long t = 0; t < T; ++t) if (!track_factor(c, t, lambda)) s.bad_f = 1;
+    for (long i = 0; i < n; ++i) if (!cam_factor(c, i, lambda)) s.bad_f = 1;
+    auto camera_half = [&](int mode) {
+      for (long i = 0; i < n; ++i) {
+        double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (cam_free[i]) cam_sum(i, std::integral_constant<int, 6>{}, [&](long o, double* acc) { cam_half_term(c, cur, o, acc); }, a);
+        cam_half_finish(c, i, mode, lambda, a);
+      }
+    };
+    if (!s.bad_f) {
+      for (long t = 0; t < T; ++t) track_half(c, cur, t, 0, nullptr);
+      camera_half(0);
+      ctrl_feed(c, kActRz0, osum(c.part, n));
+      for (int pi = 0; pi < pcg_iters && !s.pcg_done; ++pi) {
+        for (long t = 0; t < T; ++t) track_half(c, cur, t, 1, c.p);
+        camera_half(1);
+        ctrl_feed(c, kActPsp, osum(c.part, n));
+        if (s.pcg_done) break;
+        for (long i = 0; i < n; ++i) cam_update1(c, i, s.alpha);
+        ctrl_feed(c, kActRz, osum(c.part, n));
+        if (s.pcg_done) break;
+        for (long i = 0; i < n; ++i) cam_update2(c, i, s.beta);
+      }
+      for (long i = 0; i < n; ++i) if (!cam_apply(c, cur, i)) s.bad_a = 1;
+      for (long t = 0; t < T; ++t) if (!track_half(c, cur, t, 2, c.x)) s.bad_a = 1;
+    }
+    if (!s.bad_f && !s.bad_a) {
+      if (!evaluate(1 - cur)) s.bad_e = 1;
+      if (!s.bad_e) {
+        ctrl_feed(c, kActCostT, osum(c.part, T));
+        ctrl_feed(c, kActSqT, osum(c.part2, T));
+      }
+    }
+    ctrl_accept(c);
+  }
+  for (long i = 0; i < n; ++i) cam_write(c, s.cur, i);
+  for (long t = 0; t < T; ++t) track_write(c, s.cur, t);
+  ctrl_write(c);
+  return LOFTR_OK;
+}

@@ -1,0 +1,325 @@
+// Bundle adjustment on the GPU: loftr_bundle_adjust_host (bundle.hip) with the same result bit for bit.  Every phase of
+// the host routine is one kernel here, every per-item step is bundle_core.h's, compiled from the same text, fp64 without FMA
+// contraction; what this file adds is only how a phase is spread over threads:
+//   a thread per track      setup, linearise, track half of S p, back substitution, evaluate (the sums of a track run sequentially in
+//                           that one thread, as §16's refit);
+//   a wave per camera       groups check, linearise, camera half of S p: lane l accumulates slots l, l + 64, ... of the camera's list
+//                           and the 64 lanes are folded 32, 16, ..., 1 with shuffles -- osum64 exactly as the host's 64-entry array;
+//   a wave per 4096 terms   osum over tracks or cameras, one launch per level; lane 0 of the last level hands the sum to ctrl_feed;
+//   a thread per camera     factor, the two updates of the conjugate gradients, apply;
+//   one thread              init, accept: the owner of lambda, the counters and the flags.
+// The whole run is a FIXED launch schedule on the caller's stream: max_iters trials of pcg_iters iterations each.  A kernel whose phase
+// the host routine would not run (the run has stopped, the conjugate gradients have stopped, the step is already rejected, an error bit
+// is up) returns at once on a flag in device memory; a flag is only ever read by kernels launched after the one that wrote it.  No
+// readback, no grid-wide barrier, no persistent kernel, no captured graph: a kernel boundary is the only device-wide ordering.
+// Floating-point values cross lanes only as exact copies (shuffles); atomics are integer only.  Plain C++, ordinary vector stores.
+#include <algorithm>
+#include <vector>
+#include "common.h"
+#include "bundle_core.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace ba;
+
+constexpr int kThreads = 256;
+enum : int { kSkipBadF = 1, kSkipBadA = 2, kSkipBadE = 4, kSkipPcg = 8, kNeedFresh = 16 };
+enum : int { kClsSetup = 0, kClsLinearise, kClsFactor, kClsTrackHalf, kClsCamHalf, kClsOsum, kClsUpdate, kClsApply, kClsEvaluate, kClsAccept,
+             kClsWrite, kClsCount };
+static_assert(kClsCount == LOFTR_BUNDLE_CLASSES, "kernel classes out of step with include/loftr_hip.h");
+
+__device__ __forceinline__ bool skipped(const Ctx& c, int flags) {
+  const Ctrl& s = *c.ctrl;
+  return s.done || s.err || ((flags & kSkipBadF) && s.bad_f) || ((flags & kSkipBadA) && s.bad_a) || ((flags & kSkipBadE) && s.bad_e) ||
+         ((flags & kSkipPcg) && s.pcg_done) || ((flags & kNeedFresh) && !s.fresh);
+}
+
+// osum64 of camera i's list over the 64 lanes of a wave: a [M] of lane 0 is the sum
+template <int M, class F> __device__ __forceinline__ void wave_osum64(const Ctx& c, long i, int lane, F term, double* a) {
+#pragma unroll
+  for (int m = 0; m < M; ++m) a[m] = 0.0;
+  const long b = c.cam_offsets[i], e = c.cam_offsets[i + 1];
+  for (long k = b + lane; k < e; k += 64) {
+    const long o = c.cam_obs[k];
+    if (c.obs_active[o]) term(o, a);
+  }
+  for (int s = 32; s >= 1; s >>= 1)
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const double v = __shfl_down(a[m], s, 64);
+      if (lane < s) a[m] = a[m] + v;
+    }
+}
+
+__global__ void ba_init_kernel(Ctx c) { ctrl_init(c); }
+
+// grid ceil(n / 256) x 256
+__global__ void __launch_bounds__(kThreads) ba_cam_setup_kernel(Ctx c) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i < c.n) cam_setup(c, i);
+}
+
+// grid ceil(T / 256) x 256
+__global__ void __launch_bounds__(kThreads) ba_track_setup_kernel(Ctx c) {
+  __shared__ unsigned s_cnt[3];                                          // active observations, active points, error bits
+  if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (t < c.T) {
+    long cnt;
+    const int err = track_setup(c, t, &cnt);
+    if (cnt) { atomicAdd(&s_cnt[0], (unsigned)cnt); atomicAdd(&s_cnt[1], 1u); }
+    if (err) atomicOr(&s_cnt[2], (unsigned)err);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_cnt[0]) atomicAdd(&c.ctrl->n_active_obs, (unsigned long long)s_cnt[0]);
+    if (s_cnt[1]) atomicAdd(&c.ctrl->n_active_pts, (unsigned long long)s_cnt[1]);
+    if (s_cnt[2]) atomicOr(&c.ctrl->err, (int)s_cnt[2]);
+  }
+}
+
+// a wave per camera, grid ceil(n / 4) x 256.  Reads the observation arrays only through checked indices, so it needs no flag.
+__global__ void __launch_bounds__(kThreads) ba_groups_kernel(Ctx c) {
+  const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (i >= c.n) return;
+  long b, e;
+  int err = 0, cnt = 0;
+  if (!group_range(c, i, &b, &e)) { err = kBadGroups; b = e = 0; }
+  for (long k = b + lane; k < e; k += 64) {
+    bool active;
+    err |= group_check(c, i, b, k, &active);
+    cnt += active;
+  }
+  for (int m = 32; m >= 1; m >>= 1) { err |= __shfl_xor(err, m, 64); cnt += __shfl_xor(cnt, m, 64); }
+  if (lane == 0) {
+    const bool fr = !c.fixed[i] && c.cam_valid[i] && cnt >= 1;
+    c.cam_free[i] = (uint8_t)fr;
+    if (fr) atomicAdd(&c.ctrl->n_free, 1ull);
+    if (err) atomicOr(&c.ctrl->err, err);
+  }
+}
+
+// grid ceil(T / 256) x 256; other = 0 evaluates the state, 1 the trial
+__global__ void __launch_bounds__(kThreads) ba_evaluate_kernel(Ctx c, int other, int flags) {
+  if (skipped(c, flags)) return;
+  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (t < c.T && !track_eval(c, c.ctrl->cur ^ other, t)) atomicOr(&c.ctrl->bad_e, 1);
+}
+
+// one level of an osum: a wave per chunk of 4096, grid ceil(count / 4096) (at least 1) x 64; action >= 0 on the last level
+__global__ void __launch_bounds__(64) ba_osum_kernel(Ctx c, const double* in, long count, double* out, int action, int flags) {
+  if (skipped(c, flags)) return;
+  const int lane = threadIdx.x;
+  const long lo = (long)blockIdx.x * kChunk, len = count - lo < kChunk ? count - lo : kChunk;
+  double a = 0.0;
+  for (long e = lane; e < len; e += 64) a = a + in[lo + e];
+  for (int s = 32; s >= 1; s >>= 1) {
+    const double v = __shfl_down(a, s, 64);
+    if (lane < s) a = a + v;
+  }
+  if (lane == 0) {
+    if (action >= 0) ctrl_feed(c, action, a);
+    else out[blockIdx.x] = a;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) ba_track_lin_kernel(Ctx c, int flags) {
+  if (skipped(c, flags)) return;
+  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (t < c.T) track_lin(c, c.ctrl->cur, t);
+}
+
+// a wave per camera, grid ceil(n / 4) x 256
+__global__ void __launch_bounds__(kThreads) ba_cam_lin_kernel(Ctx c, int flags) {
+  if (skipped(c, flags)) return;
+  const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64, cur = c.ctrl->cur;
+  if (i >= c.n || !c.cam_free[i]) return;
+  double a[27];
+  wave_osum64<27>(c, i, lane, [&](long o, double* acc) { cam_lin_term(c, cur, o, acc); }, a);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 21; ++k) c.U[21 * i + k] = a[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c.gc[6 * i + k] = a[21 + k];
+  }
+}
+
+// threads [0, T): tracks, [T, T + n): cameras; grid ceil((T + n) / 256) x 256
+__global__ void __launch_bounds__(kThreads) ba_factor_kernel(Ctx c, int flags) {
+  if (skipped(c, flags)) return;
+  const long id = (long)blockIdx.x * kThreads + threadIdx.x;
+  const double lambda = c.ctrl->lambda;
+  bool ok = true;
+  if (id < c.T) ok = track_factor(c, id, lambda);
+  else if (id < c.T + c.n) ok = cam_factor(c, id - c.T, lambda);
+  if (!ok) atomicOr(&c.ctrl->bad_f, 1);
+}
+
+// mode 0: z = Vd^-1 gp; mode 1: the track half of S p
+__global__ void __launch_bounds__(kThreads) ba_track_half_kernel(Ctx c, int mode, int flags) {
+  if (skipped(c, flags)) return;
+  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (t < c.T) track_half(c, c.ctrl->cur, t, mode, c.p);
+}
+
+// a wave per camera, grid ceil(n / 4) x 256.  mode 0: the right-hand side and the start of the conjugate gradients; mode 1: S p
+__global__ void __launch_bounds__(kThreads) ba_cam_half_kernel(Ctx c, int mode, int flags) {
+  if (skipped(c, flags)) return;
+  const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64, cur = c.ctrl->cur;
+  if (i >= c.n) return;
+  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (c.cam_free[i]) wave_osum64<6>(c, i, lane, [&](long o, double* acc) { cam_half_term(c, cur, o, acc); }, a);
+  if (lane == 0) cam_half_finish(c, i, mode, c.ctrl->lambda, a);
+}
+
+__global__ void __launch_bounds__(kThreads) ba_update_kernel(Ctx c, int which, int flags) {
+  if (skipped(c, flags)) return;
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= c.n) return;
+  if (which == 1) cam_update1(c, i, c.ctrl->alpha);
+  else cam_update2(c, i, c.ctrl->beta);
+}
+
+// threads [0, T): back substitution of the tracks, [T, T + n): the cameras' trial poses
+__global__ void __launch_bounds__(kThreads) ba_apply_kernel(Ctx c, int flags) {
+  if (skipped(c, flags)) return;
+  const long id = (long)blockIdx.x * kThreads + threadIdx.x;
+  const int cur = c.ctrl->cur;
+  bool ok = true;
+  if (id < c.T) ok = track_half(c, cur, id, 2, c.x);
+  else if (id < c.T + c.n) ok = cam_apply(c, cur, id - c.T);
+  if (!ok) atomicOr(&c.ctrl->bad_a, 1);
+}
+
+__global__ void ba_accept_kernel(Ctx c) { ctrl_accept(c); }
+
+// threads [0, T): points, [T, T + n): cameras; thread 0 also writes the counts.  Runs whatever the flags say.
+__global__ void __launch_bounds__(kThreads) ba_write_kernel(Ctx c) {
+  const long id = (long)blockIdx.x * kThreads + threadIdx.x;
+  const int cur = c.ctrl->cur;
+  if (!c.ctrl->err) {
+    if (id < c.T) track_write(c, cur, id);
+    else if (id < c.T + c.n) cam_write(c, cur, id - c.T);
+  }
+  if (id == 0) ctrl_write(c);
+}
+
+bool sizes_ok(long T, long N, int n) { return T >= 0 && N >= 0 && n >= 0 && T < (1L << 31) && N < (1L << 31); }
+
+}  // namespace
+
+extern "C" size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images) {
+  if (!sizes_ok(T, N, n_images)) return 0;
+  Ctx c{};
+  c.T = T; c.N = N; c.n = n_images;
+  return layout(c, nullptr);
+}
+
+extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                   const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
+                                   const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
+                                   double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
+                                   long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
+  LOFTR_CHECK_ARG(offsets && cam_offsets && counts && ws && T >= 0 && N >= 0 && n_images >= 0);
+  LOFTR_CHECK_ARG(T == 0 || (xyz && xyz_out && point_active));
+  LOFTR_CHECK_ARG(N == 0 || (obs_image && obs_xy && obs_mask && obs_active && cam_obs));
+  LOFTR_CHECK_ARG(n_images == 0 || (K && T_cam_from_world && fixed && T_out && cam_free));
+  LOFTR_CHECK_ARG(huber_px >= 0.0 && fin(huber_px) && ftol >= 0.0 && fin(ftol) && pcg_tol >= 0.0 && pcg_tol < 1.0);
+  LOFTR_CHECK_ARG(max_iters >= 0 && max_iters <= LOFTR_BUNDLE_MAX_ITERS && pcg_iters >= 1 && pcg_iters <= LOFTR_BUNDLE_MAX_PCG);
+  LOFTR_CHECK_ARG((T > 0 && n_images > 0) || N == 0);                  // observations outside every track or camera
+  if (!sizes_ok(T, N, n_images)) return LOFTR_ERR_UNSUPPORTED;
+  Ctx c{};
+  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
+  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
+  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
+  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+  if (ws_bytes < layout(c, nullptr)) return LOFTR_ERR_WORKSPACE;
+  layout(c, (char*)ws);
+  hipStream_t s = (hipStream_t)stream;
+  const long n = n_images;
+  const bool timed = class_ms != nullptr;
+  std::vector<hipEvent_t> ev;
+  std::vector<int> ev_cls;
+  long launches[kClsCount] = {0};
+  bool failed = false;
+  auto mark = [&]() {
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess || hipEventRecord(e, s) != hipSuccess) failed = true;
+    else ev.push_back(e);
+  };
+  auto after = [&](int cls) {
+    if (hipGetLastError() != hipSuccess) failed = true;
+    launches[cls] += 1;
+    if (timed && !failed) { mark(); ev_cls.push_back(cls); }
+  };
+  auto blocks = [](long items, long per) { return dim3((unsigned)(items > 0 ? (items + per - 1) / per : 1)); };
+  // osum of v[0 .. count) into ctrl_feed(action): one launch per level
+  auto osum = [&](const double* v, long count, int action, int flags) {
+    const double* in = v;
+    double* out = c.red;
+    for (;;) {
+      const long chunks = count > 0 ? (count + kChunk - 1) / kChunk : 1;
+      hipLaunchKernelGGL(ba_osum_kernel, dim3((unsigned)chunks), dim3(64), 0, s, c, in, count, out, chunks == 1 ? action : -1, flags);
+      after(kClsOsum);
+      if (chunks == 1) return;
+      in = out;
+      out = out == c.red ? c.red + ((std::max(T, n) + 1 + kChunk - 1) / kChunk) : c.red;
+      count = chunks;
+    }
+  };
+  if (timed) mark();
+  hipLaunchKernelGGL(ba_init_kernel, dim3(1), dim3(1), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_cam_setup_kernel, blocks(n, kThreads), dim3(kThreads), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_track_setup_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_groups_kernel, blocks(n, 4), dim3(kThreads), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 0, 0); after(kClsEvaluate);
+  osum(c.part, T, kActCost0, 0);
+  osum(c.part2, T, kActSq0, 0);
+  for (int it = 0; it < max_iters && !failed; ++it) {
+    hipLaunchKernelGGL(ba_track_lin_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
+    hipLaunchKernelGGL(ba_cam_lin_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
+    hipLaunchKernelGGL(ba_factor_kernel, blocks(T + n, kThreads), dim3(kThreads), 0, s, c, 0); after(kClsFactor);
+    hipLaunchKernelGGL(ba_track_half_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 0, kSkipBadF); after(kClsTrackHalf);
+    hipLaunchKernelGGL(ba_cam_half_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, 0, kSkipBadF); after(kClsCamHalf);
+    osum(c.part, n, kActRz0, kSkipBadF);
+    for (int pi = 0; pi < pcg_iters && !failed; ++pi) {
+      const int f = kSkipBadF | kSkipPcg;
+      hipLaunchKernelGGL(ba_track_half_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 1, f); after(kClsTrackHalf);
+      hipLaunchKernelGGL(ba_cam_half_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, 1, f); after(kClsCamHalf);
+      osum(c.part, n, kActPsp, f);
+      hipLaunchKernelGGL(ba_update_kernel, blocks(n, kThreads), dim3(kThreads), 0, s, c, 1, f); after(kClsUpdate);
+      osum(c.part, n, kActRz, f);
+      hipLaunchKernelGGL(ba_update_kernel, blocks(n, kThreads), dim3(kThreads), 0, s, c, 2, f); after(kClsUpdate);
+    }
+    hipLaunchKernelGGL(ba_apply_kernel, blocks(T + n, kThreads), dim3(kThreads), 0, s, c, kSkipBadF); after(kClsApply);
+    hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 1, kSkipBadF | kSkipBadA); after(kClsEvaluate);
+    osum(c.part, T, kActCostT, kSkipBadF | kSkipBadA | kSkipBadE);
+    osum(c.part2, T, kActSqT, kSkipBadF | kSkipBadA | kSkipBadE);
+    hipLaunchKernelGGL(ba_accept_kernel, dim3(1), dim3(1), 0, s, c); after(kClsAccept);
+  }
+  hipLaunchKernelGGL(ba_write_kernel, blocks(T + n, kThreads), dim3(kThreads), 0, s, c); after(kClsWrite);
+  if (class_launches) for (int k = 0; k < kClsCount; ++k) class_launches[k] = launches[k];
+  if (timed) {
+    if (hipStreamSynchronize(s) != hipSuccess) failed = true;
+    std::vector<float> ms[kClsCount];
+    for (size_t k = 0; k + 1 < ev.size() && !failed; ++k) {
+      float v = 0.f;
+      if (hipEventElapsedTime(&v, ev[k], ev[k + 1]) == hipSuccess) ms[ev_cls[k]].push_back(v);
+    }
+    for (int k = 0; k < kClsCount; ++k) {                             // per class: the median launch, then the total
+      std::sort(ms[k].begin(), ms[k].end());
+      float total = 0.f;
+      for (float v : ms[k]) total += v;
+      class_ms[2 * k] = ms[k].empty() ? 0.f : ms[k][ms[k].size() / 2];
+      class_ms[2 * k + 1] = total;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  return failed ? LOFTR_ERR_LAUNCH : LOFTR_OK;
+}

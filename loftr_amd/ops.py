@@ -1301,6 +1301,96 @@ def triangulate_tracks(offsets, obs_image, obs_xy, K, T_cam_from_world, thresh_p
     return out
 
 
+# ---- bundle adjustment of the triangulated model (csrc/bundle.hip, csrc/bundle_gpu.hip) -----------------------------------
+BUNDLE_COUNTS = 16
+BUNDLE_STATUS = ("converged", "max_iters", "stalled", "nothing_to_adjust")               # status codes 0..3 = counts[0]
+BUNDLE_ERRORS = ((1, "obs_image outside [0, n_images)"), (2, "offsets must start at 0, end at the number of observations and ascend"),
+                 (4, "cam_offsets / cam_obs are not the observations grouped by image in ascending order"))     # bits of counts[1]
+BUNDLE_CLASSES = ("setup", "linearise", "factor", "track_half", "camera_half", "osum", "update", "apply", "evaluate", "accept", "write")
+BUNDLE_MAX_ITERS, BUNDLE_MAX_PCG = 1000, 200
+_BA_ARGS = (("offsets", "int64", 1), ("obs_image", "int32", 1), ("obs_xy", "float32", 2), ("obs_mask", "uint8", 1), ("xyz", "float32", 2),
+            ("K", "float64", 3), ("T_cam_from_world", "float64", 3), ("fixed", "uint8", 1), ("cam_offsets", "int64", 1), ("cam_obs", "int32", 1))
+
+
+def _ba_shapes(what, arrays, dtype_of):
+    """Dtype and shape checks shared by the two bundle-adjustment wrappers -> (T, N, n_images)."""
+    for (name, dt, nd), a in zip(_BA_ARGS, arrays):
+        if dtype_of(a) != dt or a.ndim != nd:
+            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
+    offsets, obs_image, obs_xy, obs_mask, xyz, K, T, fixed, cam_offsets, cam_obs = arrays
+    N, n, nt = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
+    if nt < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (nt, 3) or tuple(K.shape) != (n, 3, 3) or \
+            tuple(T.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N:
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
+                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1] and cam_obs [N], got {[tuple(a.shape) for a in arrays]}")
+    return nt, N, n
+
+
+def _ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol):
+    import math
+    ok = all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in (huber_px, pcg_tol, ftol)) and \
+        all(isinstance(v, int) and not isinstance(v, bool) for v in (max_iters, pcg_iters))
+    if not (ok and huber_px >= 0 and ftol >= 0 and 0 <= pcg_tol < 1 and 0 <= max_iters <= BUNDLE_MAX_ITERS and 1 <= pcg_iters <= BUNDLE_MAX_PCG):
+        raise ValueError(f"{what}: huber_px and ftol must be finite and >= 0, pcg_tol in [0, 1), max_iters an integer in [0, {BUNDLE_MAX_ITERS}] and "
+                         f"pcg_iters an integer in [1, {BUNDLE_MAX_PCG}], got {huber_px}, {ftol}, {pcg_tol}, {max_iters}, {pcg_iters}")
+    return float(huber_px), int(max_iters), int(pcg_iters), float(pcg_tol), float(ftol)
+
+
+def bundle_adjust_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, huber_px, max_iters,
+                       pcg_iters, pcg_tol, ftol):
+    """loftr_bundle_adjust_host: the host routine that DEFINES the bundle adjustment (include/loftr_hip.h) on numpy arrays: offsets [T+1]
+    i64, obs_image [N] i32, obs_xy [N,2] f32, obs_mask [N] u8, xyz [T,3] f32, K [n,3,3] f64, T_cam_from_world [n,4,4] f64, fixed [n] u8,
+    cam_offsets [n+1] i64, cam_obs [N] i32.  -> dict of numpy arrays: T_cam_from_world [n,4,4] f64, xyz [T,3] f32, obs_active [N] u8,
+    cam_free [n] u8, point_active [T] u8, counts [16] i64."""
+    import numpy as np
+    arrays = (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs)
+    if not all(isinstance(a, np.ndarray) for a in arrays):
+        raise _lib.LoftrHipError("bundle_adjust_host: expected numpy arrays (GPU tensors go to bundle_adjust)")
+    T, N, n = _ba_shapes("bundle_adjust_host", arrays, lambda a: a.dtype.name)
+    params = _ba_params("bundle_adjust_host", huber_px, max_iters, pcg_iters, pcg_tol, ftol)
+    a = [np.ascontiguousarray(x) for x in arrays]
+    out = {"T_cam_from_world": np.zeros((n, 4, 4), np.float64), "xyz": np.zeros((T, 3), np.float32), "obs_active": np.zeros(N, np.uint8),
+           "cam_free": np.zeros(n, np.uint8), "point_active": np.zeros(T, np.uint8), "counts": np.zeros(BUNDLE_COUNTS, np.int64)}
+    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
+    check(_lib.load().loftr_bundle_adjust_host(ptr(a[0]), T, ptr(a[1]), ptr(a[2]), ptr(a[3]), N, ptr(a[4]), ptr(a[5]), ptr(a[6]), ptr(a[7]), n,
+                                               ptr(a[8]), ptr(a[9]), *params, *[ptr(out[k]) for k in out]),
+          "loftr_bundle_adjust_host (offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images); cam_offsets / cam_obs "
+          "must group the observations by image in ascending order)")
+    return out
+
+
+@_on_device
+def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, huber_px, max_iters, pcg_iters,
+                  pcg_tol, ftol, timings=None):
+    """loftr_bundle_adjust: the bundle-adjustment kernels (csrc/bundle_gpu.hip) on GPU tensors of the dtypes and shapes of
+    bundle_adjust_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in
+    counts[1], which the caller reads once.  timings: a dict that receives per kernel class (BUNDLE_CLASSES) the tuple
+    (median ms of a launch, total ms, launches issued); the call then waits for the stream."""
+    arrays = (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs)
+    for (name, _, _), a in zip(_BA_ARGS, arrays):
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the bundle-adjustment kernels have no CPU fallback; the host routine is "
+                                     "bundle_adjust_host)")
+    T, N, n = _ba_shapes("bundle_adjust", arrays, lambda a: str(a.dtype).replace("torch.", ""))
+    params = _ba_params("bundle_adjust", huber_px, max_iters, pcg_iters, pcg_tol, ftol)
+    dev = offsets.device
+    a = [x.contiguous() for x in arrays]
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    out = {"T_cam_from_world": z((n, 4, 4), torch.float64), "xyz": z((T, 3), torch.float32), "obs_active": z(N, torch.uint8),
+           "cam_free": z(n, torch.uint8), "point_active": z(T, torch.uint8), "counts": z(BUNDLE_COUNTS, torch.int64)}
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_bundle_adjust_workspace_bytes(T, N, n)), dtype=torch.uint8, device=dev)
+    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
+    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
+    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
+    check(lib.loftr_bundle_adjust(_ptr(a[0]), T, _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), N, _ptr(a[4]), _ptr(a[5]), _ptr(a[6]), _ptr(a[7]), n,
+                                  _ptr(a[8]), _ptr(a[9]), *params, *[_ptr(out[k]) for k in out], _ptr(ws), ws.numel(), cast(ms), cast(launches),
+                                  _stream()), "loftr_bundle_adjust")
+    if timings is not None:
+        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
+    return out
+
+
 # ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip; DESIGN §17) ------------------------
 MODEL_COUNTS = 16
 MODEL_REASONS = ("n_kept", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside", "n_no_keypoint", "n_no_point",

@@ -1,0 +1,140 @@
+#!/usr/bin/env python
+"""Bundle adjustment (loftr_amd/bundle.py, csrc/bundle_gpu.hip) on a MegaDepth-1500-shaped load.  One JSON line.
+
+    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--no-host] [--out FILE]
+
+Load: the track lengths of tools/micro/atlas_bench.py's synthetic atlas (1500 rows over 806 images), observations as in
+tools/micro/triangulation_bench.py without outliers (one exact camera per image, one 3D point per track, every observation in a random
+image, projected, 0.5 px of noise).  The start: every pose but those of images 0 and 1 (fixed) rotated by 1 degree about a random axis
+and its centre moved by N(0, 0.05) per axis, every point moved by N(0, 0.05).
+
+Reported: per kernel class the median device time over all launches of the class (those that returned at once on a stop flag
+included), the total and the launches issued (events around every launch inside loftr_bundle_adjust, one call after a warm-up); a lower
+bound of the launches that returned at once (from the counts: trials and conjugate-gradient iterations not run); the wall time of bundle_adjust with its one readback (median of 3 calls without events); trials,
+accepted trials and conjugate-gradient iterations; the host routine (loftr_bundle_adjust_host, one core) on the same input; and the
+assertion that every run's output tensors and counts equal the host routine's."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+from loftr_amd import BundleResult, KeypointAtlas, bundle_adjust         # noqa: E402
+from tools.micro.atlas_bench import DEV, HW, make_chunks                 # noqa: E402
+from tools.micro.triangulation_bench import rotations                    # noqa: E402
+
+
+def make_load(track_len, n_images, seed=0):
+    """-> (offsets, obs_image, obs_xy, obs_mask, xyz start, K, T start, fixed) on the device."""
+    rng = np.random.default_rng(seed)
+    R = rotations(rng, n_images, 20.0)
+    c = rng.uniform([-2, -1, -0.5], [2, 1, 0.5], (n_images, 3))
+    K = np.tile(np.eye(3), (n_images, 1, 1))
+    K[:, 0, 0] = K[:, 1, 1] = rng.uniform(450, 650, n_images)
+    K[:, 0, 2], K[:, 1, 2] = 320.0, 240.0
+    T = np.tile(np.eye(4), (n_images, 1, 1))
+    T[:, :3, :3] = R
+    T[:, :3, 3] = -(R @ c[:, :, None])[:, :, 0]
+    axis_turn = rotations_fixed(rng, n_images, 1.0) @ R
+    c0 = c + 0.05 * rng.standard_normal((n_images, 3))
+    T0 = T.copy()
+    T0[2:, :3, :3] = axis_turn[2:]
+    T0[2:, :3, 3] = -(axis_turn[2:] @ c0[2:, :, None])[:, :, 0]
+    K, T, T0 = (torch.from_numpy(a).to(DEV) for a in (K, T, T0))
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    lens = track_len.to(DEV, torch.int64)
+    n_tracks = lens.numel()
+    offsets = torch.zeros(n_tracks + 1, dtype=torch.int64, device=DEV)
+    offsets[1:] = torch.cumsum(lens, 0)
+    N = int(offsets[-1])
+    track = torch.repeat_interleave(torch.arange(n_tracks, device=DEV), lens)
+    lo, hi = torch.tensor([-2, -1.5, 3.0], device=DEV, dtype=torch.float64), torch.tensor([2, 1.5, 8.0], device=DEV, dtype=torch.float64)
+    X = lo + (hi - lo) * torch.rand(n_tracks, 3, device=DEV, dtype=torch.float64, generator=g)
+    image = torch.randint(0, n_images, (N,), device=DEV, generator=g)
+    p = torch.einsum("nij,nj->ni", K[image], torch.einsum("nij,nj->ni", T[image, :3, :3], X[track]) + T[image, :3, 3])
+    xy = p[:, :2] / p[:, 2:] + 0.5 * torch.randn(N, 2, device=DEV, dtype=torch.float64, generator=g)
+    xyz = (X + 0.05 * torch.randn(n_tracks, 3, device=DEV, dtype=torch.float64, generator=g)).to(torch.float32)
+    fixed = torch.zeros(n_images, dtype=torch.bool, device=DEV)
+    fixed[:2] = True
+    return offsets, image.to(torch.int32), xy.to(torch.float32), torch.ones(N, dtype=torch.bool, device=DEV), xyz, K, T0, fixed
+
+
+def rotations_fixed(rng, n, deg):
+    """Rotations by exactly `deg` degrees about random axes."""
+    axis = rng.standard_normal((n, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    A = np.zeros((n, 3, 3))
+    A[:, 0, 1], A[:, 0, 2], A[:, 1, 0], A[:, 1, 2], A[:, 2, 0], A[:, 2, 1] = -axis[:, 2], axis[:, 1], axis[:, 2], -axis[:, 0], -axis[:, 1], axis[:, 0]
+    t = np.radians(deg)
+    return np.eye(3) + np.sin(t) * A + (1 - np.cos(t)) * (A @ A)
+
+
+def same(a, b):
+    eq = lambda x, y: torch.equal(torch.isnan(x), torch.isnan(y)) and torch.equal(torch.nan_to_num(x, nan=0.0), torch.nan_to_num(y, nan=0.0))
+    return all(eq(getattr(a, k).cpu().double(), getattr(b, k).cpu().double()) for k in BundleResult.FIELDS) and a.stats == b.stats
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--rows", type=int, default=1500)
+    ap.add_argument("--matches", type=int, default=1000)
+    ap.add_argument("--max-iters", type=int, default=30)
+    ap.add_argument("--pcg-iters", type=int, default=30)
+    ap.add_argument("--huber", type=float, default=0.0)
+    ap.add_argument("--no-host", action="store_true", help="skip the host routine (and the equality assertion)")
+    ap.add_argument("--out", default=None, help="also append the JSON line to this file")
+    args = ap.parse_args()
+    pairs = np.load(os.path.join(ROOT, "tests", "golden", "pair_lists.npz"))["megadepth_pairs"][:args.rows].astype(np.int64)
+    n_images, chunks = make_chunks(pairs, args.matches)
+    atlas = KeypointAtlas(n_images, HW, 2.0, device=DEV)
+    for ids, data in chunks:
+        atlas.add(ids, data)
+    sfm = atlas.finalize(min_track_len=2)
+    lens = sfm.track_len[sfm.track_ok]
+    del atlas, chunks
+    *inputs, fixed = make_load(lens, n_images)
+    kw = dict(huber_px=args.huber, max_iters=args.max_iters, pcg_iters=args.pcg_iters)
+    out = {"workload": "bundle_megadepth1500_shape", "images": n_images, "tracks": int(lens.numel()), "observations": int(inputs[0][-1]),
+           "fixed_cameras": 2, **kw}
+    run = lambda timings=None: bundle_adjust(*inputs, fixed=fixed, timings=timings, **kw)
+    results = [run()]                                                   # warm-up (kernel load)
+    wall = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        results.append(run())
+        wall.append(1e3 * (time.perf_counter() - t))
+    timings = {}
+    results.append(run(timings))
+    res = results[-1]
+    out["wall_ms"] = round(float(np.median(wall)), 3)
+    out["class_median_ms"] = {k: round(v[0], 4) for k, v in timings.items()}
+    out["class_total_ms"] = {k: round(v[1], 3) for k, v in timings.items()}
+    out["class_launches"] = {k: v[2] for k, v in timings.items()}
+    issued = sum(v[2] for v in timings.values())
+    levels_t = 1 if lens.numel() <= 4096 else 2
+    per_pcg, per_trial = 6, 3 + 2 + 1 + 2 + 2 * levels_t + 1                # the launches of one iteration / of a trial without them
+    skipped = (args.max_iters - res.n_iters) * (per_trial + per_pcg * args.pcg_iters) + per_pcg * (res.n_iters * args.pcg_iters - res.n_pcg)
+    out["launches_issued"], out["launches_skipped_at_least"] = issued, int(skipped)
+    out["stats"] = res.stats
+    if not args.no_host:
+        t = time.perf_counter()
+        host = bundle_adjust(*[x.cpu() for x in inputs], fixed=fixed.cpu(), **kw)
+        out["host_routine_ms"] = round(1e3 * (time.perf_counter() - t), 1)
+        out["identical_to_host"] = bool(all(same(r, host) for r in results))
+        assert out["identical_to_host"], "a GPU run differs from the host routine"
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
