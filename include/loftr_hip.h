@@ -62,7 +62,8 @@ typedef enum {
  *     of tracks (loftr_triangulate_tracks_host, loftr_triangulation_pairs, loftr_triangulate_tracks,
  *     loftr_triangulate_tracks_workspace_bytes), localisation against the triangulated model (loftr_model_cells_host,
  *     loftr_model_cells, loftr_model_lookup_host, loftr_model_lookup_workspace_bytes, loftr_model_lookup), bundle adjustment of the
- *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust) */
+ *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust), the correspondence
+ *     table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes, loftr_register_corr) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -917,6 +918,46 @@ int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const
                         const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
                         double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
                         long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream);
+
+/* ---- correspondence table of the images without a pose (csrc/register_core.h holds every per-item step) -------------------
+ * The 2D-3D correspondences that the tracks give the images that have no pose yet, gathered per image in a defined order: the input of
+ * one batched absolute-pose call (loftr_estimate_absolute_pose_batched) that registers them.  Integer work and bit copies only.
+ * loftr_register_corr_host (csrc/register.hip, host memory) DEFINES the result, loftr_register_corr (csrc/register_gpu.hip, device
+ * memory) reproduces it bit for bit.
+ * Input: tracks in CSR form as for the bundle adjustment -- offsets [T+1] i64, obs_image [N] i32, obs_xy [N,2] f32 --, xyz [T,3] f32 and
+ *   status [T] u8 of the triangulation (0 = ok), posed [n] u8, the observations grouped by image -- cam_offsets [n+1] i64, cam_obs [N] i32,
+ *   the stable sort of obs_image, checked here as there -- and min_corr >= 4.
+ *   1. Observation o of track j is a correspondence iff posed[obs_image[o]] == 0, status[j] == 0, the three floats of xyz[j] are finite
+ *      and the two floats of obs_xy[o] are finite (NaN fails).
+ *   2. n_corr[i] = the correspondences in image i's list; 0 for a posed image.
+ *   3. Image i is a candidate iff it is not posed and n_corr[i] >= min_corr.  Candidates are numbered in ascending image id:
+ *      cand_rank [n] i32 (-1 otherwise), cand_image [P] i32.
+ *   4. The table holds the correspondences of the candidates only: candidates in ascending rank, within a candidate the order of its
+ *      cam_obs list (ascending observation index).  corr_xyz [C,3] f32 and corr_xy [C,2] f32 are bit copies, corr_bid [C] i64 is the rank,
+ *      corr_obs [C] i32 the observation index, cand_offsets [P+1] i64 the candidates' row ranges.
+ *   5. counts [8] i64: [0] C, [1] P, [2] error bits (1: an obs_image outside [0, n); 2: offsets that do not start at 0, end at N and
+ *      ascend; 4: cam_offsets / cam_obs that are not the stable grouping), [3] unposed images, [4] unposed images with at least one
+ *      correspondence, [5] correspondences including those of non-candidates, [6] the largest n_corr, [7] 0.
+ * Output buffers are sized by the bounds: n_corr, cand_rank, cand_image [n]; cand_offsets [n+1]; corr_* [N] rows; rows past P / C are
+ *   not written.
+ * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, min_corr < 4, observations without a track or an image; the host
+ *   routine also for the three error bits (the kernels raise counts[2] instead, read nothing through the bad value, write C = P = 0 and
+ *   nothing else); LOFTR_ERR_UNSUPPORTED for T or N >= 2^31; LOFTR_ERR_WORKSPACE for a short workspace. */
+int loftr_register_corr_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, long N, const float* xyz,
+                             const uint8_t* status, const uint8_t* posed, int n_images, const long* cam_offsets, const int* cam_obs,
+                             int min_corr, int* n_corr, int* cand_rank, int* cand_image, long* cand_offsets, float* corr_xyz, float* corr_xy,
+                             long* corr_bid, int* corr_obs, long* counts);
+/* The kernels: four launches on the stream (0 flags per track, 1 counts per image, 2 ranks and offsets -- one workgroup that walks the
+ * images in blocks of LOFTR_REGISTER_RANK_BLOCK --, 3 rows per candidate).  No host synchronisation unless stage_ms is given: NULL, or
+ * LOFTR_REGISTER_STAGES host floats that receive the GPU time of each launch (the call then waits for the stream).
+ * Workspace: loftr_register_corr_workspace_bytes(T, N, n_images): 5 bytes per observation, 4 per image; 0 for sizes out of range. */
+#define LOFTR_REGISTER_STAGES 4
+#define LOFTR_REGISTER_RANK_BLOCK 256
+size_t loftr_register_corr_workspace_bytes(long T, long N, int n_images);
+int loftr_register_corr(const long* offsets, long T, const int* obs_image, const float* obs_xy, long N, const float* xyz,
+                        const uint8_t* status, const uint8_t* posed, int n_images, const long* cam_offsets, const int* cam_obs,
+                        int min_corr, int* n_corr, int* cand_rank, int* cand_image, long* cand_offsets, float* corr_xyz, float* corr_xy,
+                        long* corr_bid, int* corr_obs, long* counts, void* ws, size_t ws_bytes, float* stage_ms, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

@@ -159,6 +159,9 @@ SIGNATURES = {
     "loftr_bundle_adjust_workspace_bytes": (_sz, [_l, _l, _i]),
     "loftr_bundle_adjust": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _i, _p, _p, C.c_double, _i, _i, C.c_double, C.c_double,
                                  _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
+    "loftr_register_corr_host": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "loftr_register_corr_workspace_bytes": (_sz, [_l, _l, _i]),
+    "loftr_register_corr": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

@@ -83,10 +83,13 @@ class SfmResult:
         offsets[1:] = torch.cumsum(counts, 0)
         return offsets, image, kp - self.kp_offsets[image]
 
-    def triangulate(self, K, T_cam_from_world, thresh_px=4.0, min_angle_deg=1.5, consistent_only=True, group=0):
+    def triangulate(self, K, T_cam_from_world, thresh_px=4.0, min_angle_deg=1.5, consistent_only=True, group=0, posed=None):
         """One 3D point per track from the images' poses (triangulation.triangulate_tracks) -> Points3D on this result's
         device, with the CSR arrays of ``tracks(consistent_only)`` attached (``offsets``, ``image``, ``keypoint``).
-        K [n_images,3,3], T_cam_from_world [n_images,4,4] (float32 or float64, tensors or arrays; moved to the device)."""
+        K [n_images,3,3], T_cam_from_world [n_images,4,4] (float32 or float64, tensors or arrays; moved to the device).
+        posed: None, or [n_images] bool / integers: only the observations of these images are triangulated and the poses of the others
+        are never read (registration.triangulate_posed); the result stays aligned with the full tracks, ``obs_inlier`` is
+        false at the observations of unposed images and a track with fewer than 2 posed observations is too_short."""
         from .triangulation import triangulate_tracks
         dev = self.keypoints.device
         K, T = (torch.as_tensor(x).detach().to(dev, torch.float64) for x in (K, T_cam_from_world))
@@ -95,9 +98,93 @@ class SfmResult:
             raise ValueError(f"SfmResult.triangulate: expected K [{n},3,3] and T_cam_from_world [{n},4,4], got {tuple(K.shape)}, {tuple(T.shape)}")
         offsets, image, local = self.tracks(consistent_only)
         xy = self.keypoints[self.kp_offsets[image] + local]
-        pts = triangulate_tracks(offsets, image.to(torch.int32), xy, K, T, thresh_px=thresh_px, min_angle_deg=min_angle_deg, group=group)
+        if posed is None:
+            pts = triangulate_tracks(offsets, image.to(torch.int32), xy, K, T, thresh_px=thresh_px, min_angle_deg=min_angle_deg, group=group)
+        else:
+            from .registration import triangulate_posed
+            pts = triangulate_posed(offsets, image.to(torch.int32), xy, K, T, posed, thresh_px=thresh_px, min_angle_deg=min_angle_deg, group=group)
         pts.offsets, pts.image, pts.keypoint = offsets, image, local
         return pts
+
+    def register(self, pts, K, T_cam_from_world, posed, **kwargs):
+        """Resect the images without a pose from the points ``pts`` (a Points3D of ``triangulate`` on this result) that their tracks
+        reach (registration.register_images) -> Registration on this result's device.  ``posed`` [n_images] and the keyword
+        arguments are register_images'."""
+        from .registration import register_images
+        if pts.offsets is None:
+            raise ValueError("SfmResult.register: this Points3D carries no tracks (use SfmResult.triangulate)")
+        dev = self.keypoints.device
+        K, T = (torch.as_tensor(x).detach().to(dev, torch.float64) for x in (K, T_cam_from_world))
+        xy = self.keypoints[self.kp_offsets[pts.image] + pts.keypoint]
+        return register_images(pts.offsets, pts.image.to(torch.int32), xy, pts.xyz, pts.status, K, T, torch.as_tensor(posed).to(dev), **kwargs)
+
+    def pairwise_poses(self, K, thresh_px=4.0, conf=0.99999, seed=0):
+        """Five-point poses of ALL rows from the kept matches: one ``ops.estimate_poses`` call on a GPU result, a loop over
+        ``evaluation.estimate_pose_native`` on a CPU one (the same result for one seed).
+        -> (R [R,3,3] f32, t [R,3] f32 with x_b = R x_a + t, n_inliers [R] i64, -1 without a model), on this result's device."""
+        dev = self.keypoints.device
+        n_rows = self.row_offsets.numel() - 1
+        K32 = torch.as_tensor(K).detach().to(dev, torch.float32)
+        row = torch.repeat_interleave(torch.arange(n_rows, device=dev), self.row_offsets[1:] - self.row_offsets[:-1])
+        ims = self.row_images.to(torch.int64)
+        m = self.matches.to(torch.int64)
+        k0 = self.keypoints[self.kp_offsets[ims[row, 0]] + m[:, 0]].contiguous()
+        k1 = self.keypoints[self.kp_offsets[ims[row, 1]] + m[:, 1]].contiguous()
+        K0, K1 = K32[ims[:, 0]].contiguous(), K32[ims[:, 1]].contiguous()
+        if dev.type == "cuda":
+            R, t, _, ninl = ops.estimate_poses(k0, k1, row, K0, K1, thresh_px, conf, seed)
+            return R, t, ninl
+        from .evaluation import estimate_pose_native
+        R, t, ninl = torch.zeros(n_rows, 3, 3), torch.zeros(n_rows, 3), torch.full((n_rows,), -1, dtype=torch.int64)
+        off = self.row_offsets.tolist()
+        for r in range(n_rows):
+            sl = slice(off[r], off[r + 1])
+            est = estimate_pose_native(k0[sl].numpy(), k1[sl].numpy(), K0[r].numpy(), K1[r].numpy(), thresh_px, conf, seed)
+            if est is not None:
+                R[r], t[r], ninl[r] = torch.from_numpy(est[0]).float(), torch.from_numpy(est[1]).float(), int(est[2].sum())
+        return R, t, ninl
+
+    def reconstruct(self, K, init_row=None, init_candidates=8, thresh_px=4.0, pose_conf=0.99999, consistent_only=True, **kwargs):
+        """Poses of the images and points of the tracks from intrinsics alone (registration.reconstruct_tracks) ->
+        Reconstruction on this result's device, its ``points`` carrying the CSR arrays as ``triangulate`` attaches them.
+        The initial pair is row ``init_row`` with its five-point pose (``pairwise_poses`` at ``thresh_px``).  With ``init_row=None``:
+        of the ``init_candidates`` rows with the most five-point inliers (ties to the earliest row), the one whose two images alone
+        triangulate the most points (ties to the earliest row); the selection is integer and order-defined.  ``thresh_px`` is also the
+        triangulation's and the registration's threshold; the other keyword arguments are reconstruct_tracks'."""
+        from .registration import reconstruct_tracks, triangulate_posed
+        dev = self.keypoints.device
+        n = self.kp_offsets.numel() - 1
+        K = torch.as_tensor(K).detach().to(dev, torch.float64)
+        if tuple(K.shape) != (n, 3, 3):
+            raise ValueError(f"SfmResult.reconstruct: expected K [{n},3,3], got {tuple(K.shape)}")
+        R, t, ninl = self.pairwise_poses(K, thresh_px, pose_conf, kwargs.get("seed", 0))
+        ninl_host, rows = ninl.cpu().tolist(), self.row_images.cpu().tolist()
+        offsets, image, local = self.tracks(consistent_only)
+        obs_image, xy = image.to(torch.int32), self.keypoints[self.kp_offsets[image] + local]
+        if init_row is None:
+            order = sorted((r for r in range(len(rows)) if ninl_host[r] >= 0), key=lambda r: (-ninl_host[r], r))[:max(int(init_candidates), 0)]
+            if not order:
+                raise ValueError(f"SfmResult.reconstruct: no row has a five-point model (inlier counts of the {len(rows)} rows: {ninl_host})")
+            n_ok = []
+            for r in sorted(order):
+                a, b = rows[r]
+                Tb, tb = torch.eye(4, dtype=torch.float64), t[r].cpu().to(torch.float64)       # on the host: one arithmetic for both devices
+                Tb[:3, :3], Tb[:3, 3] = R[r].cpu().to(torch.float64), tb / torch.linalg.norm(tb)
+                T = torch.eye(4, dtype=torch.float64, device=dev).repeat(n, 1, 1)
+                T[b] = Tb.to(dev)
+                posed = torch.zeros(n, dtype=torch.bool, device=dev)
+                posed[a] = posed[b] = True
+                n_ok.append((-triangulate_posed(offsets, obs_image, xy, K, T, posed, thresh_px, kwargs.get("min_angle_deg", 1.5)).stats["n_ok"], r))
+            init_row = min(n_ok)[1]
+        init_row = int(init_row)
+        if not 0 <= init_row < len(rows) or ninl_host[init_row] < 0:
+            raise ValueError(f"SfmResult.reconstruct: row {init_row} has no five-point model (rows: {len(rows)}, inliers: "
+                             f"{ninl_host[init_row] if 0 <= init_row < len(rows) else None})")
+        a, b = rows[init_row]
+        rec = reconstruct_tracks(offsets, obs_image, xy, K, (a, b, R[init_row], t[init_row]), thresh_px=thresh_px, **kwargs)
+        rec.points.offsets, rec.points.image, rec.points.keypoint = offsets, image, local
+        rec.stats["init_row"], rec.stats["pair_inliers"] = init_row, ninl_host
+        return rec
 
     def adjust(self, pts, K, T_cam_from_world, fixed=None, **kwargs):
         """Bundle adjustment of the poses and of the points ``pts`` (a Points3D of ``triangulate`` on this result) over the observations

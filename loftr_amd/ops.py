@@ -1391,6 +1391,85 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     return out
 
 
+# ---- correspondence table of the images without a pose (csrc/register.hip, csrc/register_gpu.hip) --------------------------
+REGISTER_COUNTS = 8
+REGISTER_STAGES = ("track", "count", "rank", "write")
+REGISTER_RANK_BLOCK = 256
+REGISTER_MIN_CORR = 4
+REGISTER_ERRORS = BUNDLE_ERRORS                                                          # bits of counts[2]
+_REG_ARGS = (("offsets", "int64", 1), ("obs_image", "int32", 1), ("obs_xy", "float32", 2), ("xyz", "float32", 2), ("status", "uint8", 1),
+             ("posed", "uint8", 1), ("cam_offsets", "int64", 1), ("cam_obs", "int32", 1))
+_REG_OUT = (("n_corr", "n", (), "int32"), ("cand_rank", "n", (), "int32"), ("cand_image", "n", (), "int32"), ("cand_offsets", "n1", (), "int64"),
+            ("corr_xyz", "N", (3,), "float32"), ("corr_xy", "N", (2,), "float32"), ("corr_bid", "N", (), "int64"), ("corr_obs", "N", (), "int32"))
+
+
+def _reg_shapes(what, arrays, dtype_of, min_corr):
+    """Dtype and shape checks shared by the two wrappers of the correspondence table -> (T, N, n_images)."""
+    for (name, dt, nd), a in zip(_REG_ARGS, arrays):
+        if dtype_of(a) != dt or a.ndim != nd:
+            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
+    offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs = arrays
+    N, n, nt = obs_image.shape[0], posed.shape[0], offsets.shape[0] - 1
+    if nt < 0 or tuple(obs_xy.shape) != (N, 2) or tuple(xyz.shape) != (nt, 3) or status.shape[0] != nt or cam_offsets.shape[0] != n + 1 or \
+            cam_obs.shape[0] != N:
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], xyz [T,3], status [T], posed [n], "
+                                 f"cam_offsets [n+1] and cam_obs [N], got {[tuple(a.shape) for a in arrays]}")
+    if not isinstance(min_corr, int) or isinstance(min_corr, bool) or min_corr < REGISTER_MIN_CORR:
+        raise ValueError(f"{what}: min_corr must be an integer >= {REGISTER_MIN_CORR}, got {min_corr}")
+    return nt, N, n
+
+
+def register_corr_host(offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs, min_corr):
+    """loftr_register_corr_host: the host routine that DEFINES the correspondence table of the unposed images (include/loftr_hip.h) on
+    numpy arrays: offsets [T+1] i64, obs_image [N] i32, obs_xy [N,2] f32, xyz [T,3] f32, status [T] u8, posed [n] u8, cam_offsets [n+1]
+    i64, cam_obs [N] i32.  -> dict of numpy arrays sized by the bounds (n_corr, cand_rank, cand_image [n] i32, cand_offsets [n+1] i64,
+    corr_xyz [N,3] f32, corr_xy [N,2] f32, corr_bid [N] i64, corr_obs [N] i32; rows past counts[1] / counts[0] are zero) and counts [8]
+    i64."""
+    import numpy as np
+    arrays = (offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs)
+    if not all(isinstance(a, np.ndarray) for a in arrays):
+        raise _lib.LoftrHipError("register_corr_host: expected numpy arrays (GPU tensors go to register_corr)")
+    T, N, n = _reg_shapes("register_corr_host", arrays, lambda a: a.dtype.name, min_corr)
+    a = [np.ascontiguousarray(x) for x in arrays]
+    size = {"n": n, "n1": n + 1, "N": N}
+    out = {k: np.zeros((size[s],) + tail, dt) for k, s, tail, dt in _REG_OUT}
+    out["counts"] = np.zeros(REGISTER_COUNTS, np.int64)
+    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
+    check(_lib.load().loftr_register_corr_host(ptr(a[0]), T, ptr(a[1]), ptr(a[2]), N, ptr(a[3]), ptr(a[4]), ptr(a[5]), n, ptr(a[6]), ptr(a[7]),
+                                               int(min_corr), *[ptr(out[k]) for k in out]),
+          "loftr_register_corr_host (offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images); cam_offsets / cam_obs "
+          "must group the observations by image in ascending order)")
+    return out
+
+
+@_on_device
+def register_corr(offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs, min_corr, timings=None):
+    """loftr_register_corr: the kernels of the correspondence table (csrc/register_gpu.hip) on GPU tensors of the dtypes and shapes of
+    register_corr_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in
+    counts[2], C and P in counts[0] and counts[1], which the caller reads once.  timings: a list that receives (stage, ms) pairs (the
+    call then waits for the stream)."""
+    arrays = (offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs)
+    for (name, _, _), a in zip(_REG_ARGS, arrays):
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the correspondence-table kernels have no CPU fallback; the host routine "
+                                     "is register_corr_host)")
+    T, N, n = _reg_shapes("register_corr", arrays, lambda a: str(a.dtype).replace("torch.", ""), min_corr)
+    dev = offsets.device
+    a = [x.contiguous() for x in arrays]
+    size = {"n": n, "n1": n + 1, "N": N}
+    out = {k: torch.zeros((size[s],) + tail, dtype=getattr(torch, dt), device=dev) for k, s, tail, dt in _REG_OUT}
+    out["counts"] = torch.zeros(REGISTER_COUNTS, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_register_corr_workspace_bytes(T, N, n)), dtype=torch.uint8, device=dev)
+    ms = (C.c_float * len(REGISTER_STAGES))() if timings is not None else None
+    check(lib.loftr_register_corr(_ptr(a[0]), T, _ptr(a[1]), _ptr(a[2]), N, _ptr(a[3]), _ptr(a[4]), _ptr(a[5]), n, _ptr(a[6]), _ptr(a[7]),
+                                  int(min_corr), *[_ptr(out[k]) for k in out], _ptr(ws), ws.numel(),
+                                  C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_register_corr")
+    if timings is not None:
+        timings.extend(zip(REGISTER_STAGES, (float(v) for v in ms)))
+    return out
+
+
 # ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip; DESIGN §17) ------------------------
 MODEL_COUNTS = 16
 MODEL_REASONS = ("n_kept", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside", "n_no_keypoint", "n_no_point",

@@ -1,0 +1,293 @@
+"""Image registration and incremental reconstruction from atlas tracks: the step that gives the images without a pose one, on the device.
+
+``triangulate`` needs a pose for every image it uses and ``ops.estimate_poses`` only gives pairwise ones.  What joins them is the loop
+of incremental structure from motion: triangulate from the images that have a pose, adjust, resect the images that do not from the 2D-3D
+correspondences the tracks give them, repeat::
+
+    sfm = atlas.finalize()
+    rec = sfm.reconstruct(K)                                  # Reconstruction: poses of every image that could be registered, points
+    pts = rec.points                                          # the final Points3D, ready for LocalizationModel
+
+or piece by piece::
+
+    pts = sfm.triangulate(K, T, posed=posed)                  # tolerates images without a pose
+    reg = sfm.register(pts, K, T, posed, min_corr=15, min_inliers=15)          # Registration: poses of the newly registered images
+
+The rule of the correspondence table (include/loftr_hip.h) is integer work and bit copies in a defined order: the host
+routine ``loftr_register_corr_host`` defines it (CPU tensors / numpy arrays run it), the HIP kernels reproduce it bit for bit (GPU
+tensors run them; there is no silent fallback either way).  The poses come from the batched P3P RANSAC of §14, one call for all
+candidates, which is pinned bit for bit host against device as well; so are the triangulation (§16) and the bundle adjustment (§18), and
+the whole chain therefore gives the same poses on both sides.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import LoftrHipError
+
+_ARGS = ("offsets", "obs_image", "obs_xy", "xyz", "status", "K", "T_cam_from_world", "posed")
+_TABLE = ("cand_image", "cand_offsets", "corr_xyz", "corr_xy", "corr_obs")
+
+
+class Registration:
+    """What ``register_images`` returns (tensors on the device of the input).
+
+    ``T_cam_from_world [n,4,4] f64`` (the input's bits for an image that was not registered in this call), ``registered [n] bool``,
+    ``posed [n] bool`` (the input or registered), ``n_corr [n] i32`` (correspondences per unposed image), ``n_inliers [n] i64`` (-1
+    where the image is not a candidate or has no model); the table of the ``P`` candidates: ``cand_image [P] i32``, ``cand_offsets
+    [P+1] i64``, ``corr_xyz [C,3] f32``, ``corr_xy [C,2] f32``, ``corr_obs [C] i32`` (observation index), ``corr_inlier [C] bool``;
+    ``stats``: dict of the counts."""
+
+    FIELDS = ("T_cam_from_world", "registered", "posed", "n_corr", "n_inliers") + _TABLE + ("corr_inlier",)
+
+    def __init__(self, stats, **tensors):
+        self.stats = stats
+        for k in self.FIELDS:
+            setattr(self, k, tensors[k])
+
+    def to_host(self):
+        """dict of numpy arrays (plus 'stats')."""
+        out = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}
+        out["stats"] = dict(self.stats)
+        return out
+
+
+class Reconstruction:
+    """What ``reconstruct_tracks`` returns: ``T_cam_from_world [n,4,4] f64`` (NaN for an image that never got a pose), ``posed [n]
+    bool``, ``round_registered [n] i32`` (the round in which the image got its pose; 0 for the initial pair; -1 for never), ``points``
+    (the final ``Points3D``), ``bundle`` (the final ``BundleResult``), ``stats`` (dict; ``stats['rounds']`` holds the per-round counts)."""
+
+    def __init__(self, T_cam_from_world, posed, round_registered, points, bundle, stats):
+        self.T_cam_from_world, self.posed, self.round_registered = T_cam_from_world, posed, round_registered
+        self.points, self.bundle, self.stats = points, bundle, stats
+
+
+def _integers(what, name, a):
+    dt = a.dtype if isinstance(a, torch.Tensor) else np.asarray(a).dtype
+    if (isinstance(dt, torch.dtype) and (dt.is_floating_point or dt == torch.bool)) or \
+            (not isinstance(dt, torch.dtype) and not np.issubdtype(dt, np.integer)):
+        raise ValueError(f"{what}: {name} must hold integers, got {dt}")
+
+
+def _one_device(what, names, args):
+    """True when every argument is a GPU tensor, False when none is; mixed is an error."""
+    gpu = [isinstance(a, torch.Tensor) and a.is_cuda for a in args]
+    if any(gpu) and not all(gpu):
+        raise LoftrHipError(f"{what}: GPU and CPU arguments mixed (" + ", ".join(f"{n}: {'GPU' if g else 'CPU'}" for n, g in zip(names, gpu))
+                            + "); there is no silent fallback: move them to one device")
+    return all(gpu)
+
+
+def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed, min_corr=15, min_inliers=15, thresh_px=4.0,
+                    conf=0.999, seed=0, timings=None):
+    """Resect the images that have no pose from the points their tracks already have -> ``Registration``.
+
+    ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``; ``xyz [T,3]`` and ``status [T]`` of a
+    ``Points3D``; ``K [n,3,3]``; ``T_cam_from_world [n,4,4]`` (the poses of unposed images are never read); ``posed [n]`` (bool or
+    integers).  CPU tensors or numpy arrays run the defining host routine and a loop over ``evaluation.estimate_absolute_pose_native``;
+    GPU tensors (all of them, on one device) run the kernels and ONE ``ops.estimate_absolute_poses`` call over all candidates: the same
+    result for one seed.
+
+    An unposed image with at least ``min_corr`` (>= 4) correspondences is a candidate; a candidate whose estimate has at least
+    ``min_inliers`` inliers at ``thresh_px`` pixels is registered: its pose is the estimator's f32 ``R``, ``t`` as float64.  One
+    readback of the 8 counts; bad ``obs_image`` / ``offsets`` raise ValueError.  timings: a list that receives (stage, ms) pairs of the
+    GPU stages."""
+    what = "register_images"
+    args = [offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed]
+    gpu = _one_device(what, _ARGS, args)
+    for name, a in zip(_ARGS[:2], args[:2]):
+        _integers(what, name, a)
+    if not (isinstance(min_inliers, int) and not isinstance(min_inliers, bool) and math.isfinite(thresh_px) and thresh_px >= 0):
+        raise ValueError(f"{what}: min_inliers must be an integer and thresh_px >= 0, got {min_inliers}, {thresh_px}")
+    if gpu:
+        dev = args[0].device
+        dts = (torch.int64, torch.int32, torch.float32, torch.float32, torch.uint8, torch.float32, torch.float64, None)
+        a = [x.detach() if dt is None else x.detach().to(dt) for x, dt in zip(args, dts)]
+        a[7] = (a[7] != 0).to(torch.uint8)
+    else:
+        dev = torch.device("cpu")
+        dts = (np.int64, np.int32, np.float32, np.float32, np.uint8, np.float32, np.float64, None)
+        host = lambda x: x.detach().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        a = [np.ascontiguousarray(host(x)) if dt is None else np.ascontiguousarray(host(x), dt) for x, dt in zip(args, dts)]
+        a[7] = (a[7] != 0).astype(np.uint8)
+    n = a[7].shape[0] if a[7].ndim == 1 else -1
+    if a[5].ndim != 3 or tuple(a[5].shape) != (n, 3, 3) or tuple(a[6].shape) != (n, 4, 4):
+        raise LoftrHipError(f"{what}: expected K [n,3,3], T_cam_from_world [n,4,4] and posed [n], got {tuple(a[5].shape)}, {tuple(a[6].shape)}, "
+                            f"{tuple(a[7].shape)}")
+    if gpu:
+        # the observations grouped by image: integer plumbing, a stable sort (bad image ids are caught by the kernels, so clamp here)
+        im = a[1].to(torch.int64)
+        cam_obs = torch.sort(im, stable=True).indices.to(torch.int32)
+        cam_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n > 0 and im.numel() and im.dim() == 1:
+            cam_offsets[1:] = torch.cumsum(torch.bincount(im.clamp(0, n - 1), minlength=n), 0)
+        out = ops.register_corr(a[0], a[1], a[2], a[3], a[4], a[7], cam_offsets, cam_obs, min_corr, timings=timings)
+    else:
+        if a[0].ndim == 1 and a[1].ndim == 1:                            # the errors the kernels report through counts[2]
+            if a[1].size and (a[1].min() < 0 or a[1].max() >= n):
+                raise ValueError(f"{what}: " + ops.REGISTER_ERRORS[0][1])
+            if a[0].size and (a[0][0] != 0 or a[0][-1] != a[1].shape[0] or (np.diff(a[0]) < 0).any()):
+                raise ValueError(f"{what}: " + ops.REGISTER_ERRORS[1][1])
+        cam_obs = np.argsort(a[1], kind="stable").astype(np.int32)
+        cam_offsets = np.zeros(n + 1, np.int64)
+        if a[1].ndim == 1:
+            cam_offsets[1:] = np.cumsum(np.bincount(a[1], minlength=n)[:n])
+        out = {k: torch.from_numpy(v) for k, v in ops.register_corr_host(a[0], a[1], a[2], a[3], a[4], a[7], cam_offsets, cam_obs, min_corr).items()}
+        a = [torch.from_numpy(x) for x in a]
+    counts = out["counts"].cpu().tolist()                               # the one readback
+    for bit, text in ops.REGISTER_ERRORS:
+        if counts[2] & bit:
+            raise ValueError(f"{what}: {text} (found on the device)")
+    C, P = counts[0], counts[1]
+    cand = out["cand_image"][:P]
+    cand64 = cand.to(torch.int64)
+    table = {"cand_image": cand, "cand_offsets": out["cand_offsets"][:P + 1], "corr_xyz": out["corr_xyz"][:C], "corr_xy": out["corr_xy"][:C],
+             "corr_obs": out["corr_obs"][:C]}
+    Kc = a[5][cand64].contiguous()
+    if P == 0:
+        R, t = torch.zeros(0, 3, 3, device=dev), torch.zeros(0, 3, device=dev)
+        inl, ninl = torch.zeros(0, dtype=torch.bool, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+    elif gpu:
+        R, t, inl, ninl = ops.estimate_absolute_poses(table["corr_xyz"], table["corr_xy"], out["corr_bid"][:C], Kc, thresh_px, conf, seed)
+    else:
+        from .evaluation import estimate_absolute_pose_native
+        R, t = torch.zeros(P, 3, 3), torch.zeros(P, 3)
+        inl, ninl = torch.zeros(C, dtype=torch.bool), torch.full((P,), -1, dtype=torch.int64)
+        off = table["cand_offsets"].tolist()
+        for p in range(P):
+            sl = slice(off[p], off[p + 1])
+            est = estimate_absolute_pose_native(table["corr_xyz"][sl].numpy(), table["corr_xy"][sl].numpy(), Kc[p].numpy(), thresh_px, conf, seed)
+            if est is not None:
+                R[p], t[p] = torch.from_numpy(est[0]).float(), torch.from_numpy(est[1]).float()
+                inl[sl] = torch.from_numpy(est[2])
+                ninl[p] = int(est[2].sum())
+    ok = ninl >= min_inliers                                            # [P]; a candidate is one image: no two writes meet below
+    T_new = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
+    T_new[:, :3, :3], T_new[:, :3, 3], T_new[:, 3, 3] = R.to(torch.float64), t.to(torch.float64), 1.0
+    T_out = a[6].clone()
+    T_out[cand64] = torch.where(ok[:, None, None], T_new, a[6][cand64])
+    registered = torch.zeros(n, dtype=torch.bool, device=dev)
+    registered[cand64] = ok
+    n_inliers = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    n_inliers[cand64] = ninl
+    stats = {"n_correspondences": C, "n_candidates": P, "n_unposed": counts[3], "n_unposed_with_correspondences": counts[4],
+             "n_correspondences_all": counts[5], "max_n_corr": counts[6], "n_images": n, "n_tracks": a[3].shape[0],
+             "n_observations": a[1].shape[0]}
+    return Registration(stats, T_cam_from_world=T_out, registered=registered, posed=(a[7] != 0) | registered, n_corr=out["n_corr"],
+                        n_inliers=n_inliers, corr_inlier=inl, **table)
+
+
+def triangulate_posed(offsets, obs_image, obs_xy, K, T_cam_from_world, posed, thresh_px=4.0, min_angle_deg=1.5, group=0):
+    """``triangulate_tracks`` over the observations of the posed images only -> ``Points3D`` aligned with the FULL tracks: the CSR is
+    filtered in torch (integer plumbing; a track keeps its row, so a track with fewer than 2 posed observations is ``too_short``), the
+    poses of unposed images are never read, and ``obs_inlier`` is scattered back to the full observation order (false at the
+    observations of unposed images).  Torch tensors on one device."""
+    from .triangulation import triangulate_tracks
+    dev = offsets.device
+    posed = torch.as_tensor(posed).to(dev) != 0
+    n, N, nt = K.shape[0], obs_image.shape[0], offsets.numel() - 1
+    if tuple(posed.shape) != (n,):
+        raise ValueError(f"triangulate: expected posed [{n}], got {tuple(posed.shape)}")
+    image = obs_image.to(torch.int64)
+    if n > 0:                                                          # an image id out of range stays in: triangulate_tracks reports it
+        kept = torch.nonzero(posed[image.clamp(0, n - 1)] | (image < 0) | (image >= n)).reshape(-1)
+    else:
+        kept = torch.arange(N, device=dev)
+    track = torch.repeat_interleave(torch.arange(nt, device=dev), offsets[1:] - offsets[:-1])
+    sub = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
+    sub[1:] = torch.cumsum(torch.bincount(track[kept], minlength=nt), 0)
+    T = torch.as_tensor(T_cam_from_world).to(dev, torch.float64)
+    T = torch.where(posed[:, None, None], T, torch.eye(4, dtype=torch.float64, device=dev).expand(n, 4, 4))
+    pts = triangulate_tracks(sub, obs_image[kept].to(torch.int32), obs_xy[kept], K, T, thresh_px=thresh_px, min_angle_deg=min_angle_deg, group=group)
+    full = torch.zeros(N, dtype=torch.bool, device=dev)
+    full[kept] = pts.obs_inlier
+    pts.obs_inlier = full
+    pts.stats["n_observations"], pts.stats["n_posed_observations"] = N, int(kept.numel())
+    return pts
+
+
+def _tensors(what, names, args):
+    out = [a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a)) for a in args]
+    _one_device(what, names, out)
+    return [a.detach() for a in out]
+
+
+def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=None, min_angle_deg=1.5, **register_kw):
+    """Incremental reconstruction from tracks and an initial pair -> ``Reconstruction``.
+
+    ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``, ``K [n,3,3]``; tensors on one device (GPU:
+    the kernels; CPU: the host routines; the same result) or numpy arrays.  ``init`` = ``(a, b, R [3,3], t [3])`` with
+    ``x_b = R x_a + t``, e.g. a five-point estimate: ``T[a] = I``, ``T[b] = [R | t / |t|]``; every other pose starts as NaN.
+
+    A round is: triangulate over the posed images, ``bundle_adjust`` with image ``a`` fixed (``ba``: keyword arguments for
+    ``bundle_adjust``; ``ba['fixed_extra']``: a ``[n]`` mask of further fixed images), triangulate again with the adjusted poses,
+    ``register_images`` (``register_kw``: its keyword arguments; ``thresh_px`` is also the triangulation's threshold).  The loop stops
+    when a round registers nothing, when every image is posed, or after ``max_rounds``; then one more triangulate -> adjust ->
+    triangulate.  An image is registered once: its pose changes afterwards only through the bundle adjustment.
+
+    Only image ``a`` is fixed, which removes six of the seven gauge freedoms: the scale, set by ``|t| = 1`` at the start, is held only
+    by the damping of the bundle adjustment and may drift slowly; fix ``b`` as well (``fixed_extra``) to pin it."""
+    from .bundle import bundle_adjust
+    what = "reconstruct_tracks"
+    offsets, obs_image, obs_xy, K = _tensors(what, ("offsets", "obs_image", "obs_xy", "K"), (offsets, obs_image, obs_xy, K))
+    _integers(what, "offsets", offsets)
+    _integers(what, "obs_image", obs_image)
+    dev = offsets.device
+    offsets, obs_image, obs_xy, K = offsets.to(torch.int64), obs_image.to(torch.int32), obs_xy.to(torch.float32), K.to(torch.float64)
+    if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3):
+        raise LoftrHipError(f"{what}: expected K [n,3,3], got {tuple(K.shape)}")
+    n = K.shape[0]
+    a, b, R, t = init
+    a, b = int(a), int(b)
+    R = torch.as_tensor(np.asarray(R.cpu() if isinstance(R, torch.Tensor) else R, np.float64)).reshape(3, 3)
+    t = torch.as_tensor(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, np.float64)).reshape(3)
+    if a == b or not (0 <= a < n and 0 <= b < n):
+        raise ValueError(f"{what}: the initial pair must be two different images in [0, {n}), got a = {a}, b = {b}")
+    norm = float(torch.linalg.norm(t))
+    if not (bool(torch.isfinite(R).all()) and math.isfinite(norm) and norm > 0 and float(torch.linalg.det(R)) > 0):
+        raise ValueError(f"{what}: init holds no relative pose (a refused five-point or P3P model returns zeros): det R = "
+                         f"{float(torch.linalg.det(R))}, |t| = {norm}")
+    ba = dict(ba or {})
+    fixed = torch.zeros(n, dtype=torch.bool, device=dev)
+    fixed[a] = True
+    extra = ba.pop("fixed_extra", None)
+    if extra is not None:
+        fixed |= torch.as_tensor(extra).to(dev) != 0
+    if "fixed" in ba:
+        raise ValueError(f"{what}: image a is the fixed one; name further fixed images in ba['fixed_extra']")
+    thresh_px = register_kw.get("thresh_px", 4.0)
+    T = torch.full((n, 4, 4), float("nan"), dtype=torch.float64, device=dev)
+    T[a] = torch.eye(4, dtype=torch.float64)
+    Tb = torch.eye(4, dtype=torch.float64)
+    Tb[:3, :3], Tb[:3, 3] = R, t / norm
+    T[b] = Tb
+    posed = torch.zeros(n, dtype=torch.bool, device=dev)
+    posed[a] = posed[b] = True
+    round_registered = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    round_registered[a] = round_registered[b] = 0
+    rounds = []
+
+    def refine(T, posed, first=False):
+        pts = triangulate_posed(offsets, obs_image, obs_xy, K, T, posed, thresh_px, min_angle_deg)
+        if first and pts.stats["n_ok"] == 0:
+            raise ValueError(f"{what}: the initial pair ({a}, {b}) triangulates nothing: {pts.stats['n_posed_observations']} observations in "
+                             f"{pts.stats['n_tracks']} tracks, statuses {[pts.stats['n_' + s] for s in ops.TRI_STATUS]}")
+        res = bundle_adjust(offsets, obs_image, obs_xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **ba)
+        return triangulate_posed(offsets, obs_image, obs_xy, K, res.T_cam_from_world, posed, thresh_px, min_angle_deg), res
+
+    for r in range(1, int(max_rounds) + 1):
+        pts, res = refine(T, posed, first=r == 1)
+        reg = register_images(offsets, obs_image, obs_xy, pts.xyz, pts.status, K, res.T_cam_from_world, posed, **register_kw)
+        n_new, n_posed = torch.stack([reg.registered.sum(), reg.posed.sum()]).tolist()
+        round_registered[reg.registered] = r
+        T, posed = reg.T_cam_from_world, reg.posed
+        rounds.append({"round": r, "n_points": pts.stats["n_ok"], "rms_px_after": res.rms_px_after, "n_candidates": reg.stats["n_candidates"],
+                       "n_registered": n_new, "n_posed": n_posed})
+        if n_new == 0 or n_posed == n:
+            break
+    pts, res = refine(T, posed, first=not rounds)
+    stats = {"rounds": rounds, "n_rounds": len(rounds), "n_images": n, "n_posed": int(posed.sum()), "n_points": pts.stats["n_ok"],
+             "rms_px_after": res.rms_px_after, "init": (a, b)}
+    return Reconstruction(res.T_cam_from_world, posed, round_registered, pts, res, stats)
