@@ -338,7 +338,9 @@ __device__ __forceinline__ void encoder_x_body(const Args& a, const int seq, con
         }
       }
       den += swap32(den);
-      const float z = a.v_length * __builtin_amdgcn_rcpf(den + a.attn_eps);
+      // den == 0: the source mask of the sequence is all zero (Ksum = 0) or this token is masked.  The reference's message is exactly 0 there (KV = 0,
+      // linear_attention.py:37-45); z = S / eps would put Q' beyond fp16 (inf x P = 0 -> NaN in the merge, which the ReLU of mlp.0 then turns into 0).
+      const float z = den == 0.f ? 0.f : a.v_length * __builtin_amdgcn_rcpf(den + a.attn_eps);
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] *= z;
       pack_panel(v, qh, ql);

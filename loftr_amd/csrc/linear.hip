@@ -156,9 +156,10 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& p, f32x16 (&acc)[C
         half_sum16(den);
 #pragma unroll
 #ifdef LOFTR_EPI_OLD
-        for (int r = 0; r < 16; ++r) v[r] *= p.v_length / (den[r] + p.eps);
+        for (int r = 0; r < 16; ++r) v[r] *= den[r] == 0.f ? 0.f : p.v_length / (den[r] + p.eps);
 #else
-        for (int r = 0; r < 16; ++r) v[r] *= p.v_length * __builtin_amdgcn_rcpf(den[r] + p.eps);   // 1 / (Q . Ksum + eps), :44 -- v_rcp_f32 (1 ulp) instead of the ten-instruction IEEE division
+        // (den == 0: all-zero source mask or masked row -- the reference's message is exactly 0, and S / eps does not fit fp16: encoder_fused.hip)
+        for (int r = 0; r < 16; ++r) v[r] *= den[r] == 0.f ? 0.f : p.v_length * __builtin_amdgcn_rcpf(den[r] + p.eps);   // 1 / (Q . Ksum + eps), :44 -- v_rcp_f32 (1 ulp) instead of the ten-instruction IEEE division
 #endif
         uint32_t w[16];
         sp_words16(v, e.odd, w);
