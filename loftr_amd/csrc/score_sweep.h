@@ -410,6 +410,12 @@ __global__ __launch_bounds__(512, 2) void score_sweep_kernel(Args a) {
   // in the in-order VMEM queue): pass A one partial store; pass B four conf stores + one partial store.  Panels that
   // take the scalar-store tail path are followed by a full drain instead.
   constexpr int ST = PASS == 0 ? 1 : PASS == 2 ? 4 : (SWEEP_PROBE_NOSTORE ? 1 : SWEEP_PROBE_COAL ? 17 : 5);
+  // A wave that writes no conf / score rows issues fewer: only the column partial (pass B), nothing (pass 2).  That is every wave of
+  // a pass B without conf_matrix, and the waves of a partial last row block that hold no valid row (their stores are skipped as a
+  // whole: exec == 0).  Counting ST for them would let such a wave pass the barrier with its own k-group of panel p still in flight.
+  constexpr int ST_BARE = PASS == 1 ? 1 : 0;
+  const bool bare_wave = PASS >= 1 && __builtin_amdgcn_readfirstlane(
+      (PASS == 1 && a.conf == nullptr) || !(rows_full || rb * BR + wave * 32 < L));        // wave-uniform
   f32x16 acc0, acc1;
   bool drain = false;                              // block-uniform: the previous period issued an unknown number of stores
   for (int p = 0; p < np; ++p) {
@@ -419,6 +425,7 @@ __global__ __launch_bounds__(512, 2) void score_sweep_kernel(Args a) {
     if (!dead) {
     if (drain || p + 1 >= np) LOFTR_WAITCNT_VM(0);
     else if (p < 2) LOFTR_WAITCNT_VM(DMA_PER_WAVE);
+    else if (bare_wave) LOFTR_WAITCNT_VM(DMA_PER_WAVE + ST_BARE);
     else LOFTR_WAITCNT_VM(DMA_PER_WAVE + ST);
     if (!SWEEP_PROBE_NOBAR) __builtin_amdgcn_s_barrier();   // ... for every wave; and every wave is past the MFMAs of panel p-2
     if (p + 2 < np && !SWEEP_PROBE_NODMA) SWEEP_ISSUE(p + 2);
