@@ -17,8 +17,7 @@ tensors run them; there is no silent fallback either way).
 import numpy as np
 import torch
 
-from . import ops
-from ._lib import LoftrHipError
+from . import _tracks, ops
 
 _OUT = ("T_cam_from_world", "xyz", "obs_active", "cam_free", "point_active")
 _ARGS = ("offsets", "obs_image", "obs_xy", "obs_mask", "xyz", "K", "T_cam_from_world")
@@ -49,13 +48,6 @@ class BundleResult:
         return out
 
 
-def _integers(name, a):
-    dt = a.dtype if isinstance(a, torch.Tensor) else np.asarray(a).dtype
-    if (isinstance(dt, torch.dtype) and (dt.is_floating_point or dt == torch.bool)) or \
-            (not isinstance(dt, torch.dtype) and not np.issubdtype(dt, np.integer)):
-        raise ValueError(f"bundle_adjust: {name} must hold integers, got {dt}")
-
-
 def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed=None, huber_px=0.0, max_iters=30, pcg_iters=30,
                   pcg_tol=1e-2, ftol=1e-9, timings=None):
     """Refine poses and points over the reprojection error -> ``BundleResult``.
@@ -71,16 +63,13 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     step with at most ``pcg_iters`` conjugate-gradient iterations to the relative tolerance ``pcg_tol``; the run stops as converged when
     an accepted trial lowers the cost by no more than ``ftol`` of it.  The active set is decided once, at the start; loop through
     ``triangulate`` to renew it.  One readback of the 16 counts; bad ``obs_image`` / ``offsets`` raise ValueError."""
+    what = "bundle_adjust"
     args = [offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world]
-    params = ops._ba_params("bundle_adjust", huber_px, max_iters, pcg_iters, pcg_tol, ftol)
-    gpu = [isinstance(a, torch.Tensor) and a.is_cuda for a in args]
-    fixed_gpu = isinstance(fixed, torch.Tensor) and fixed.is_cuda
-    if (any(gpu) and not all(gpu)) or (fixed is not None and fixed_gpu != all(gpu)):
-        where = [f"{n}: {'GPU' if g else 'CPU'}" for n, g in zip(_ARGS, gpu)] + ([f"fixed: {'GPU' if fixed_gpu else 'CPU'}"] if fixed is not None else [])
-        raise LoftrHipError("bundle_adjust: GPU and CPU arguments mixed (" + ", ".join(where) + "); there is no silent fallback: move them to one device")
+    params = ops._ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol)
+    gpu = _tracks.one_device(what, _ARGS + ("fixed",), args + ([] if fixed is None else [fixed]))   # ("fixed" is named only when given)
     for n, a in zip(_ARGS[:2], args[:2]):
-        _integers(n, a)
-    if all(gpu):
+        _tracks.integers(what, n, a)
+    if gpu:
         dev = args[0].device
         dts = (torch.int64, torch.int32, torch.float32, None, torch.float32, torch.float64, torch.float64)
         a = [x.detach() if dt is None else x.detach().to(dt) for x, dt in zip(args, dts)]
@@ -90,13 +79,7 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             fixed = torch.zeros(n, dtype=torch.bool, device=dev)
             fixed[:1] = True
         fx = (fixed.detach() != 0).to(torch.uint8)
-        # the observations grouped by image: integer plumbing, a stable sort (bad image ids are caught by the kernels, so clamp here)
-        im = a[1].to(torch.int64)
-        cam_obs = torch.sort(im, stable=True).indices.to(torch.int32)
-        cam_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        if n > 0 and im.numel() and im.dim() == 1:
-            cam_offsets[1:] = torch.cumsum(torch.bincount(im.clamp(0, n - 1), minlength=n), 0)
-        out = ops.bundle_adjust(*a, fx, cam_offsets, cam_obs, *params, timings=timings)
+        out = ops.bundle_adjust(*a, fx, *_tracks.group_by_image(a[1], n), *params, timings=timings)
     else:
         dts = (np.int64, np.int32, np.float32, None, np.float32, np.float64, np.float64)
         host = lambda x: x.detach().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
@@ -109,21 +92,13 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
         else:
             fx = (host(fixed) != 0).astype(np.uint8)
         if a[0].ndim == 1 and a[1].ndim == 1 and a[5].ndim == 3:         # the errors the kernels report through counts[1]
-            if a[1].size and (a[1].min() < 0 or a[1].max() >= n):
-                raise ValueError("bundle_adjust: " + ops.BUNDLE_ERRORS[0][1])
-            if a[0].size and (a[0][0] != 0 or a[0][-1] != a[1].shape[0] or (np.diff(a[0]) < 0).any()):
-                raise ValueError("bundle_adjust: " + ops.BUNDLE_ERRORS[1][1])
-        cam_obs = np.argsort(a[1], kind="stable").astype(np.int32)
-        cam_offsets = np.zeros(n + 1, np.int64)
-        if a[1].ndim == 1:
-            cam_offsets[1:] = np.cumsum(np.bincount(a[1], minlength=n)[:n])
-        out = {k: torch.from_numpy(v) for k, v in ops.bundle_adjust_host(*a, fx, cam_offsets, cam_obs, *params).items()}
+            _tracks.check_host(what, a[0], a[1], n)
+        out = ops.bundle_adjust_host(*a, fx, *_tracks.group_by_image(a[1], n), *params)
+        out = {k: torch.from_numpy(v) for k, v in out.items()}
     counts = out["counts"].cpu()                                        # the one readback
     reals = counts[8:13].view(torch.float64).tolist()
     counts = counts.tolist()
-    for bit, text in ops.BUNDLE_ERRORS:
-        if counts[1] & bit:
-            raise ValueError(f"bundle_adjust: {text} (found on the device)")
+    _tracks.raise_error_bits(what, counts[1])
     stats = {"status": ops.BUNDLE_STATUS[counts[0]], "n_iters": counts[2], "n_accepted": counts[3], "n_pcg": counts[4],
              "n_active_observations": counts[5], "n_active_points": counts[6], "n_free_cameras": counts[7],
              "n_tracks": out["point_active"].numel(), "n_observations": out["obs_active"].numel(), "n_images": out["cam_free"].numel(),

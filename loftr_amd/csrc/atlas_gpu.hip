@@ -10,136 +10,17 @@
 //   mutual best          a match is kept when it is the table's winner on both sides; count -> scan -> write matches and row offsets
 //   tracks               union-find over the kept matches (larger root hooked under the smaller by atomicCAS, path halving),
 //                        flatten + lengths + table[(label, image)] counts, same-image flags, flag -> scan -> number
-// The one u32 scan (reduce / scan / downsweep over per-block counts) serves the cells, the keep flags and the track flags.
+// The one u32 scan (scan.hip: reduce / scan / downsweep over per-block counts) serves the cells, the keep flags and the track flags;
+// it, the block helpers and the table are compact_gpu.h's.
 #include <algorithm>
-#include <vector>
-#include "common.h"
-#include "atlas_core.h"
+#include "compact_gpu.h"
+#include "stage_timer.h"
+#include "tracks_core.h"
 
 namespace {
 
 using namespace atlas;
-typedef unsigned long long u64;
-
-constexpr int kBlock = 256;                 // threads per block of every kernel here
-constexpr int kWaves = kBlock / 64;
-constexpr int kScanItems = 4;               // elements per thread of the scan kernels: 1024 per block
-
-// ---- block-level helpers (every thread of the block must call them) ----------------------------------------------------------------
-// rank of this thread among the threads of the block with flag set, and the block's total
-__device__ __forceinline__ unsigned block_rank(bool flag, unsigned* total) {
-  __shared__ unsigned wsum[kWaves];
-  const u64 b = __ballot(flag);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) wsum[w] = (unsigned)__popcll(b);
-  __syncthreads();
-  unsigned off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) {
-    if (i < w) off += wsum[i];
-    tot += wsum[i];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
-}
-
-// exclusive prefix sum of v over the block, and the block's total
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* total) {
-  __shared__ unsigned wsum[kWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  unsigned off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) {
-    if (i < w) off += wsum[i];
-    tot += wsum[i];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + inc - v;
-}
-
-// ---- the u32 scan: data[0, n) <- its exclusive prefix sums, *total <- the sum --------------------------------------------------------
-__global__ void scan_reduce_kernel(const unsigned* __restrict__ data, long n, unsigned* __restrict__ partials) {
-  const long base = ((long)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
-  unsigned v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) v += base + j < n ? data[base + j] : 0u;
-  unsigned tot;
-  block_excl_scan(v, &tot);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
-}
-// one block: partials[0, nb) <- exclusive prefix sums
-__global__ void scan_partials_kernel(unsigned* __restrict__ partials, long nb, long* __restrict__ total) {
-  unsigned carry = 0;
-  for (long base = 0; base < nb; base += kBlock) {
-    const long i = base + threadIdx.x;
-    const unsigned v = i < nb ? partials[i] : 0u;
-    unsigned tot;
-    const unsigned ex = block_excl_scan(v, &tot);
-    if (i < nb) partials[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = (long)carry;
-}
-__global__ void scan_down_kernel(unsigned* __restrict__ data, long n, const unsigned* __restrict__ partials) {
-  const long base = ((long)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
-  unsigned x[kScanItems], v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    x[j] = base + j < n ? data[base + j] : 0u;
-    v += x[j];
-  }
-  unsigned tot;
-  unsigned run = partials[blockIdx.x] + block_excl_scan(v, &tot);
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    if (base + j < n) data[base + j] = run;
-    run += x[j];
-  }
-}
-
-inline long blocks_of(long n) { return (n + kBlock - 1) / kBlock; }
-inline long scan_blocks(long n) { return (n + (long)kBlock * kScanItems - 1) / ((long)kBlock * kScanItems); }
-
-int scan_u32(unsigned* data, long n, unsigned* partials, long* total, hipStream_t s) {
-  const long nb = scan_blocks(n);
-  hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, data, n, partials);
-  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kBlock), 0, s, partials, nb, total);
-  hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, data, n, partials);
-  LOFTR_CHECK_LAUNCH();
-  return LOFTR_OK;
-}
-
-// ---- the open-addressing table (keys / vals [cap] u64, cap a power of two at load <= 0.5, zero = empty) ---------------------------
-// slot of `key`, claimed if absent.  The probe ends: the table always holds an empty slot.
-__device__ __forceinline__ u64 table_claim(u64* __restrict__ keys, u64 mask, u64 key) {
-  u64 h = hash64(key) & mask;
-  for (;;) {
-    const u64 prev = atomicCAS(&keys[h], 0ull, key);
-    if (prev == 0ull || prev == key) return h;
-    h = (h + 1) & mask;
-  }
-}
-// value of `key` in a table that a previous kernel filled; 0 if absent
-__device__ __forceinline__ u64 table_find(const u64* __restrict__ keys, const u64* __restrict__ vals, u64 mask, u64 key) {
-  u64 h = hash64(key) & mask;
-  for (u64 n = 0; n <= mask; ++n) {
-    const u64 k = keys[h];
-    if (k == key) return vals[h];
-    if (k == 0ull) return 0ull;
-    h = (h + 1) & mask;
-  }
-  return 0ull;
-}
+using namespace compact;
 
 // ---- observe ---------------------------------------------------------------------------------------------------------------------
 __global__ void atlas_observe_kernel(const float* __restrict__ kpts0, const float* __restrict__ kpts1, const float* __restrict__ conf,
@@ -352,7 +233,7 @@ Layout layout(long M, long G) {
   const long Kb = keypoint_bound(M, G);
   const long nb = std::max(blocks_of(G), std::max(blocks_of(M), blocks_of(Kb)));
   size_t o = 0;
-  auto take = [&o](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
+  auto take = [&o](size_t bytes) { return tracks::carve(&o, bytes); };
   L.block_counts = take(sizeof(unsigned) * (size_t)nb);
   L.partials = take(sizeof(unsigned) * (size_t)scan_blocks(nb));
   L.mk = take(sizeof(int) * 2 * (size_t)M);
@@ -419,82 +300,62 @@ extern "C" int loftr_atlas_finalize(u64* grid, const float* obs_xy, const int* o
   const u64 mask = L.cap - 1;
   long* counts = out->counts;
 
-  std::vector<hipEvent_t> ev;
-  auto mark = [&]() {                                                   // stage boundaries, only when the caller asked for timings
-    if (!stage_ms) return true;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return false;
-    ev.push_back(e);
-    return hipEventRecord(e, s) == hipSuccess;
-  };
-  auto fail = [&](int code) { for (hipEvent_t e : ev) (void)hipEventDestroy(e); return code; };
-#define ATLAS_TRY(expr) do { if ((expr) != hipSuccess) return fail(LOFTR_ERR_LAUNCH); } while (0)
-#define ATLAS_LAUNCHED() do { if (hipGetLastError() != hipSuccess) return fail(LOFTR_ERR_LAUNCH); } while (0)
-#define ATLAS_MARK() do { if (!mark()) return fail(LOFTR_ERR_LAUNCH); } while (0)
+  StageTimer timer(stage_ms, LOFTR_ATLAS_STAGES, s);                    // stage boundaries, only when the caller asked for timings
+  auto zero = [s](void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, s) == hipSuccess; };
 
-  ATLAS_TRY(hipMemsetAsync(counts, 0, sizeof(long) * kCounts, s));
-  ATLAS_TRY(hipMemsetAsync(out->kp_offsets, 0, sizeof(long) * ((size_t)n_images + 1), s));
-  ATLAS_TRY(hipMemsetAsync(out->row_offsets, 0, sizeof(long) * ((size_t)R + 1), s));
-  if (status) ATLAS_TRY(hipMemcpyAsync(counts + kCountStatus, status, sizeof(int), hipMemcpyDeviceToDevice, s));   // the low half of the zeroed slot
-  ATLAS_MARK();
+  if (!zero(counts, sizeof(long) * kCounts) || !zero(out->kp_offsets, sizeof(long) * ((size_t)n_images + 1)) ||
+      !zero(out->row_offsets, sizeof(long) * ((size_t)R + 1)))
+    return LOFTR_ERR_LAUNCH;
+  if (status && hipMemcpyAsync(counts + kCountStatus, status, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)   // the low half of the zeroed slot
+    return LOFTR_ERR_LAUNCH;
+  timer.mark();
   // ---- compact
   if (G > 0 && M > 0) {
     const long nb = blocks_of(G);
     hipLaunchKernelGGL(atlas_count_cells_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, grid, G, block_counts);
-    ATLAS_LAUNCHED();
-    if (scan_u32(block_counts, nb, partials, counts + kCountK, s) != LOFTR_OK) return fail(LOFTR_ERR_LAUNCH);
+    LOFTR_CHECK_LAUNCH();
+    if (scan_u32(block_counts, nb, partials, counts + kCountK, s) != LOFTR_OK) return LOFTR_ERR_LAUNCH;
     hipLaunchKernelGGL(atlas_write_keypoints_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, grid, G, block_counts, cpi, n_images, obs_xy, m_conf,
                        out->keypoints, out->score, out->n_obs, out->kp_offsets, kp_image, parent, len, bad);
-    ATLAS_LAUNCHED();
+    LOFTR_CHECK_LAUNCH();
   }
-  ATLAS_MARK();
+  timer.mark();
   if (M > 0) {
     const unsigned nbm = (unsigned)blocks_of(M), nbk = (unsigned)blocks_of(Kb);
     // ---- resolve
-    ATLAS_TRY(hipMemsetAsync(keys, 0, sizeof(u64) * L.cap, s));
-    ATLAS_TRY(hipMemsetAsync(vals, 0, sizeof(u64) * L.cap, s));
+    if (!zero(keys, sizeof(u64) * L.cap) || !zero(vals, sizeof(u64) * L.cap)) return LOFTR_ERR_LAUNCH;
     hipLaunchKernelGGL(atlas_resolve_kernel, dim3(nbm), dim3(kBlock), 0, s, M, obs_cell, m_conf, m_row, m_reason, grid, mk, out->n_obs, keys, vals,
                        mask, (u64*)counts);
-    ATLAS_LAUNCHED();
-    ATLAS_MARK();
+    LOFTR_CHECK_LAUNCH();
+    timer.mark();
     // ---- mutual best
     hipLaunchKernelGGL(atlas_keep_kernel, dim3(nbm), dim3(kBlock), 0, s, M, mk, m_conf, m_row, keys, vals, mask, keep, block_counts);
-    ATLAS_LAUNCHED();
-    if (scan_u32(block_counts, nbm, partials, counts + kCountMk, s) != LOFTR_OK) return fail(LOFTR_ERR_LAUNCH);
-    ATLAS_MARK();
+    LOFTR_CHECK_LAUNCH();
+    if (scan_u32(block_counts, nbm, partials, counts + kCountMk, s) != LOFTR_OK) return LOFTR_ERR_LAUNCH;
+    timer.mark();
     hipLaunchKernelGGL(atlas_write_matches_kernel, dim3(nbm), dim3(kBlock), 0, s, M, R, keep, block_counts, mk, m_conf, m_row, kp_image,
                        out->kp_offsets, out->matches, out->match_conf, out->row_offsets);
-    ATLAS_LAUNCHED();
-    ATLAS_MARK();
+    LOFTR_CHECK_LAUNCH();
+    timer.mark();
     // ---- tracks
     hipLaunchKernelGGL(atlas_union_kernel, dim3(nbm), dim3(kBlock), 0, s, M, keep, mk, parent);
-    ATLAS_LAUNCHED();
-    ATLAS_MARK();
-    ATLAS_TRY(hipMemsetAsync(keys, 0, sizeof(u64) * L.cap, s));
-    ATLAS_TRY(hipMemsetAsync(vals, 0, sizeof(u64) * L.cap, s));
+    LOFTR_CHECK_LAUNCH();
+    timer.mark();
+    if (!zero(keys, sizeof(u64) * L.cap) || !zero(vals, sizeof(u64) * L.cap)) return LOFTR_ERR_LAUNCH;
     const long* Kp = counts + kCountK;
     hipLaunchKernelGGL(atlas_label_kernel, dim3(nbk), dim3(kBlock), 0, s, Kp, parent, kp_image, label, len, keys, vals, mask);
-    ATLAS_LAUNCHED();
-    ATLAS_MARK();
+    LOFTR_CHECK_LAUNCH();
+    timer.mark();
     hipLaunchKernelGGL(atlas_flag_tracks_kernel, dim3(nbk), dim3(kBlock), 0, s, Kp, label, len, kp_image, keys, vals, mask, min_track_len, bad,
                        block_counts);
-    ATLAS_LAUNCHED();
-    if (scan_u32(block_counts, nbk, partials, counts + kCountT, s) != LOFTR_OK) return fail(LOFTR_ERR_LAUNCH);
+    LOFTR_CHECK_LAUNCH();
+    if (scan_u32(block_counts, nbk, partials, counts + kCountT, s) != LOFTR_OK) return LOFTR_ERR_LAUNCH;
     hipLaunchKernelGGL(atlas_number_tracks_kernel, dim3(nbk), dim3(kBlock), 0, s, Kp, label, len, bad, block_counts, min_track_len, number,
                        out->track_len, out->track_ok);
-    ATLAS_LAUNCHED();
+    LOFTR_CHECK_LAUNCH();
     hipLaunchKernelGGL(atlas_track_id_kernel, dim3(nbk), dim3(kBlock), 0, s, Kp, label, len, number, min_track_len, out->track_id);
-    ATLAS_LAUNCHED();
-    ATLAS_MARK();
+    LOFTR_CHECK_LAUNCH();
+    timer.mark();
   }
-  if (stage_ms) {
-    for (int i = 0; i < LOFTR_ATLAS_STAGES; ++i) stage_ms[i] = 0.f;
-    ATLAS_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i + 1 < ev.size() && i < LOFTR_ATLAS_STAGES; ++i) ATLAS_TRY(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
-    fail(LOFTR_OK);                                                     // (destroys the events)
-  }
-#undef ATLAS_TRY
-#undef ATLAS_LAUNCHED
-#undef ATLAS_MARK
-  return LOFTR_OK;
+  return timer.finish();
 }

@@ -1,8 +1,8 @@
 // Bundle adjustment of the triangulated model: the arithmetic and the per-item steps shared by the host routine (bundle.hip) and the GPU
 // kernels (bundle_gpu.hip).  As in triangulate_core.h, every function here is compiled for both sides from this one text, fp64, without
 // FMA contraction, and uses + - * / and sqrt only (correctly rounded on both sides), so that host and device take identical decisions and
-// produce identical bits.  The rule is stated in include/loftr_hip.h and DESIGN §18; self-contained on purpose (no include of the other
-// *_core.h files).
+// produce identical bits.  The rule is stated in include/loftr_hip.h and DESIGN §18; the checks of the track table, its error bits and
+// the carving step of the workspace are tracks_core.h's.
 //
 // The run is a sequence of PHASES; a phase is a loop over tracks, over cameras or one single step, and a phase boundary is the only
 // ordering (a kernel boundary on the device, the end of a loop on the host).  Every per-item step below reads only what earlier phases
@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "tracks_core.h"
 
 #pragma clang fp contract(off)
 
@@ -24,7 +25,10 @@ constexpr int kChunk = 4096;               // osum: osum64 per chunk of 4096, th
 constexpr double kLambda0 = 1e-4, kLambdaMin = 1e-10, kLambdaMax = 1e10;
 
 enum : int { kConverged = 0, kMaxIters = 1, kStalled = 2, kNothing = 3 };
-enum : int { kBadImage = 1, kBadOffsets = 2, kBadGroups = 4 };                   // error bits (counts[1])
+using tracks::kBadImage;                   // error bits (counts[1])
+using tracks::kBadOffsets;
+using tracks::kBadGroups;
+using tracks::sizes_ok;
 enum : int { kActPsp = 0, kActRz0, kActRz, kActCost0, kActSq0, kActCostT, kActSqT };   // what the last level of an osum feeds
 
 BA_HD bool fin(double x) { return fabs(x) <= 1.7976931348623157e308; }        // false for NaN and the infinities
@@ -57,12 +61,11 @@ struct Ctx {
   Ctrl* ctrl;
 };
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 // carves the workspace; base may be null (then only the size counts) -> bytes
 inline size_t layout(Ctx& c, char* base) {
   const size_t T = (size_t)c.T, n = (size_t)c.n, N = (size_t)c.N, m = (T > n ? T : n) + 1, ch = (m + kChunk - 1) / kChunk;
   size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += up256(bytes ? bytes : 1); return p; };
+  auto take = [&](size_t bytes) { const size_t at = tracks::carve(&off, bytes ? bytes : 1); return base ? base + at : nullptr; };
   c.ctrl = (Ctrl*)take(sizeof(Ctrl));
   c.tab = (double*)take(8 * 2 * n * kTab); c.quat = (double*)take(8 * 2 * n * 4); c.X = (double*)take(8 * 2 * T * 3);
   c.V = (double*)take(8 * T * 6); c.gp = (double*)take(8 * T * 3); c.Vf = (double*)take(8 * T * 6); c.z = (double*)take(8 * T * 3);
@@ -185,8 +188,8 @@ BA_HD void obs_terms(const Ctx& c, int buf, long o, long t, double* A, double* B
 // both states and its input bits to the output -> error bits; *n_act = active observations of the track
 BA_HD int track_setup(const Ctx& c, long t, long* n_act) {
   *n_act = 0;
-  const long b = c.offsets[t], e = c.offsets[t + 1];
-  if (b < 0 || e < b || e > c.N || (t == 0 && b != 0) || (t == c.T - 1 && e != c.N)) return kBadOffsets;
+  long b, e;
+  if (!tracks::span(c.offsets, c.T, c.N, t, &b, &e)) return kBadOffsets;
   const uint32_t* src = (const uint32_t*)(c.xyz_in + 3 * t);
   uint32_t* dst = (uint32_t*)(c.xyz_out + 3 * t);
   double X[3];
@@ -197,7 +200,7 @@ BA_HD int track_setup(const Ctx& c, long t, long* n_act) {
     X_of(c, 1, t)[k] = X[k];
   }
   const bool pt = fin(X[0]) && fin(X[1]) && fin(X[2]);
-  for (long o = b; o < e; ++o) if (c.image[o] < 0 || c.image[o] >= c.n) return kBadImage;
+  if (!tracks::images_ok(c.image, b, e, c.n)) return kBadImage;
   long cnt = 0;
   for (long o = b; o < e; ++o) {
     const int im = c.image[o];
@@ -221,17 +224,12 @@ BA_HD int track_setup(const Ctx& c, long t, long* n_act) {
 // phase "camera groups": slot k of camera i's list; -> error bits, *active = the observation is active.  Reads nothing through a bad value.
 BA_HD int group_check(const Ctx& c, long i, long b, long k, bool* active) {
   *active = false;
-  const int o = c.cam_obs[k];
-  if (o < 0 || o >= c.N) return kBadGroups;
-  if (c.image[o] != i) return kBadGroups;
-  if (k > b && !(c.cam_obs[k - 1] < o)) return kBadGroups;
+  int o;
+  if (tracks::group_slot(c.cam_obs, c.image, c.N, i, b, k, &o)) return kBadGroups;
   *active = c.obs_active[o] != 0;
   return 0;
 }
-BA_HD bool group_range(const Ctx& c, long i, long* b, long* e) {
-  *b = c.cam_offsets[i]; *e = c.cam_offsets[i + 1];
-  return !(*b < 0 || *e < *b || *e > c.N || (i == 0 && *b != 0) || (i == c.n - 1 && *e != c.N));
-}
+BA_HD bool group_range(const Ctx& c, long i, long* b, long* e) { return tracks::span(c.cam_offsets, c.n, c.N, i, b, e); }
 
 // ---- rule 6: fixed-order elimination, M x M, no pivoting --------------------------------------------------------------------------------
 // a: upper triangle row-major (M (M + 1) / 2); f: d [M] then the strict lower triangle of L row-major; false on a non-positive pivot.

@@ -210,8 +210,6 @@ __global__ void __launch_bounds__(kThreads) ba_write_kernel(Ctx c) {
   if (id == 0) ctrl_write(c);
 }
 
-bool sizes_ok(long T, long N, int n) { return T >= 0 && N >= 0 && n >= 0 && T < (1L << 31) && N < (1L << 31); }
-
 }  // namespace
 
 extern "C" size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images) {

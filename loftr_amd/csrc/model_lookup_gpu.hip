@@ -10,138 +10,18 @@
 //            and query: the queries of a wave's matches ascend)
 //   scans    block counts -> offsets and C; query counts -> q_offsets
 //   write    the compacted correspondences in match order, q_offsets widened to int64
-// The u32 scan and the table restate those of atlas_gpu.hip, which keeps its own in an anonymous namespace.
+// The u32 scan (scan.hip), the block helpers and the table are compact_gpu.h's, shared with atlas_gpu.hip.
 #include <algorithm>
-#include <vector>
-#include "common.h"
+#include "compact_gpu.h"
+#include "stage_timer.h"
+#include "tracks_core.h"
 #include "model_lookup_core.h"
 
 namespace {
 
 using namespace model_lookup;
-using atlas::hash64;
+using namespace compact;
 using atlas::pack;
-typedef unsigned long long u64;
-
-constexpr int kBlock = 256;                 // threads per block of every kernel here
-constexpr int kWaves = kBlock / 64;
-constexpr int kScanItems = 4;               // elements per thread of the scan kernels: 1024 per block
-
-// ---- block-level helpers (every thread of the block must call them) ----------------------------------------------------------------
-// rank of this thread among the threads of the block with flag set, and the block's total
-__device__ __forceinline__ unsigned block_rank(bool flag, unsigned* total) {
-  __shared__ unsigned wsum[kWaves];
-  const u64 b = __ballot(flag);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) wsum[w] = (unsigned)__popcll(b);
-  __syncthreads();
-  unsigned off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) {
-    if (i < w) off += wsum[i];
-    tot += wsum[i];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
-}
-
-// exclusive prefix sum of v over the block, and the block's total
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* total) {
-  __shared__ unsigned wsum[kWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  unsigned off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) {
-    if (i < w) off += wsum[i];
-    tot += wsum[i];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + inc - v;
-}
-
-// ---- the u32 scan: data[0, n) <- its exclusive prefix sums, *total <- the sum --------------------------------------------------------
-__global__ void model_scan_reduce_kernel(const unsigned* __restrict__ data, long n, unsigned* __restrict__ partials) {
-  const long base = ((long)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
-  unsigned v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) v += base + j < n ? data[base + j] : 0u;
-  unsigned tot;
-  block_excl_scan(v, &tot);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
-}
-// one block: partials[0, nb) <- exclusive prefix sums
-__global__ void model_scan_partials_kernel(unsigned* __restrict__ partials, long nb, long* __restrict__ total) {
-  unsigned carry = 0;
-  for (long base = 0; base < nb; base += kBlock) {
-    const long i = base + threadIdx.x;
-    const unsigned v = i < nb ? partials[i] : 0u;
-    unsigned tot;
-    const unsigned ex = block_excl_scan(v, &tot);
-    if (i < nb) partials[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = (long)carry;
-}
-__global__ void model_scan_down_kernel(unsigned* __restrict__ data, long n, const unsigned* __restrict__ partials) {
-  const long base = ((long)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
-  unsigned x[kScanItems], v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    x[j] = base + j < n ? data[base + j] : 0u;
-    v += x[j];
-  }
-  unsigned tot;
-  unsigned run = partials[blockIdx.x] + block_excl_scan(v, &tot);
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    if (base + j < n) data[base + j] = run;
-    run += x[j];
-  }
-}
-
-inline long blocks_of(long n) { return (n + kBlock - 1) / kBlock; }
-inline long scan_blocks(long n) { return (n + (long)kBlock * kScanItems - 1) / ((long)kBlock * kScanItems); }
-
-// n > 0
-bool scan_u32(unsigned* data, long n, unsigned* partials, long* total, hipStream_t s) {
-  const long nb = scan_blocks(n);
-  hipLaunchKernelGGL(model_scan_reduce_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, data, n, partials);
-  hipLaunchKernelGGL(model_scan_partials_kernel, dim3(1), dim3(kBlock), 0, s, partials, nb, total);
-  hipLaunchKernelGGL(model_scan_down_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, data, n, partials);
-  return hipGetLastError() == hipSuccess;
-}
-
-// ---- the open-addressing table (keys / vals [cap] u64, cap a power of two at load <= 0.5, zero = empty) ---------------------------
-// slot of `key`, claimed if absent.  The probe ends: the table always holds an empty slot.
-__device__ __forceinline__ u64 table_claim(u64* __restrict__ keys, u64 mask, u64 key) {
-  u64 h = hash64(key) & mask;
-  for (;;) {
-    const u64 prev = atomicCAS(&keys[h], 0ull, key);
-    if (prev == 0ull || prev == key) return h;
-    h = (h + 1) & mask;
-  }
-}
-// value of `key` in a table that a previous kernel filled; 0 if absent
-__device__ __forceinline__ u64 table_find(const u64* __restrict__ keys, const u64* __restrict__ vals, u64 mask, u64 key) {
-  u64 h = hash64(key) & mask;
-  for (u64 n = 0; n <= mask; ++n) {
-    const u64 k = keys[h];
-    if (k == key) return vals[h];
-    if (k == 0ull) return 0ull;
-    h = (h + 1) & mask;
-  }
-  return 0ull;
-}
 
 // one integer atomicAdd per wave for the lanes with flag set (every lane of the wave must call it)
 __device__ __forceinline__ void wave_count(bool flag, u64* __restrict__ slot) {
@@ -289,7 +169,7 @@ struct Layout {
 Layout layout(long M, long Q) {
   Layout L;
   size_t o = 0;
-  auto take = [&o](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
+  auto take = [&o](size_t bytes) { return tracks::carve(&o, bytes); };
   L.block_counts = take(sizeof(unsigned) * (size_t)blocks_of(M));
   L.partials = take(sizeof(unsigned) * (size_t)scan_blocks(blocks_of(M)));
   L.q_counts = take(sizeof(unsigned) * (size_t)Q);
@@ -357,59 +237,36 @@ extern "C" int loftr_model_lookup(const LoftrModel* model, const float* kpts_db,
   const u64 tmask = L.cap - 1;
   long* counts = out->counts;
 
-  std::vector<hipEvent_t> ev;
-  auto mark = [&]() {                                                   // stage boundaries, only when the caller asked for timings
-    if (!stage_ms) return true;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return false;
-    ev.push_back(e);
-    return hipEventRecord(e, s) == hipSuccess;
-  };
-  auto fail = [&](int code) { for (hipEvent_t e : ev) (void)hipEventDestroy(e); return code; };
-#define MODEL_TRY(expr) do { if ((expr) != hipSuccess) return fail(LOFTR_ERR_LAUNCH); } while (0)
-#define MODEL_LAUNCHED() do { if (hipGetLastError() != hipSuccess) return fail(LOFTR_ERR_LAUNCH); } while (0)
-#define MODEL_MARK() do { if (!mark()) return fail(LOFTR_ERR_LAUNCH); } while (0)
+  StageTimer timer(stage_ms, LOFTR_MODEL_LOOKUP_STAGES, s);             // stage boundaries, only when the caller asked for timings
+  auto zero = [s](void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, s) == hipSuccess; };
 
-  MODEL_TRY(hipMemsetAsync(counts, 0, sizeof(long) * kCounts, s));
-  MODEL_TRY(hipMemsetAsync(out->q_offsets, 0, sizeof(long) * ((size_t)Q + 1), s));
-  MODEL_MARK();
+  if (!zero(counts, sizeof(long) * kCounts) || !zero(out->q_offsets, sizeof(long) * ((size_t)Q + 1))) return LOFTR_ERR_LAUNCH;
+  timer.mark();
   const long nbm = blocks_of(M);
   // ---- lookup (the row checks run even without a match)
-  if (M > 0) {
-    MODEL_TRY(hipMemsetAsync(keys, 0, sizeof(u64) * L.cap, s));
-    MODEL_TRY(hipMemsetAsync(vals, 0, sizeof(u64) * L.cap, s));
-  }
-  if (Q > 0) MODEL_TRY(hipMemsetAsync(q_counts, 0, sizeof(unsigned) * (size_t)Q, s));
+  if (M > 0 && (!zero(keys, sizeof(u64) * L.cap) || !zero(vals, sizeof(u64) * L.cap))) return LOFTR_ERR_LAUNCH;
+  if (Q > 0 && !zero(q_counts, sizeof(unsigned) * (size_t)Q)) return LOFTR_ERR_LAUNCH;
   if (std::max(M, R) > 0) {
     hipLaunchKernelGGL(model_lookup_kernel, dim3((unsigned)blocks_of(std::max(M, R))), dim3(kBlock), 0, s, model->kp_offsets, model->kp_cell,
                        model->kp_point, K, P, n_images, gh, gw, model->inv, kpts_db, kpts_q, conf, rows, mask, M, row_db, row_query, R, Q, m_point,
                        m_query, out->match_reason, keys, vals, tmask, (u64*)counts);
-    MODEL_LAUNCHED();
+    LOFTR_CHECK_LAUNCH();
   }
-  MODEL_MARK();
+  timer.mark();
   if (M > 0) {
     // ---- keep
     hipLaunchKernelGGL(model_keep_kernel, dim3((unsigned)nbm), dim3(kBlock), 0, s, M, m_point, m_query, conf, keys, vals, tmask, out->match_reason,
                        block_counts, q_counts, (u64*)counts);
-    MODEL_LAUNCHED();
-    if (!scan_u32(block_counts, nbm, partials, counts + kCountC, s)) return fail(LOFTR_ERR_LAUNCH);
-    if (Q > 0 && !scan_u32(q_counts, Q, q_partials, q_total, s)) return fail(LOFTR_ERR_LAUNCH);
-    MODEL_MARK();
+    LOFTR_CHECK_LAUNCH();
+    if (scan_u32(block_counts, nbm, partials, counts + kCountC, s) != LOFTR_OK) return LOFTR_ERR_LAUNCH;
+    if (Q > 0 && scan_u32(q_counts, Q, q_partials, q_total, s) != LOFTR_OK) return LOFTR_ERR_LAUNCH;
+    timer.mark();
     // ---- write
     hipLaunchKernelGGL(model_write_kernel, dim3((unsigned)blocks_of(std::max(M, Q + 1))), dim3(kBlock), 0, s, M, Q, out->match_reason,
                        block_counts, q_counts, counts, m_point, m_query, model->xyz, kpts_q, conf, out->pts3d, out->kpts, out->q_ids, out->match,
                        out->point, out->conf, out->q_offsets);
-    MODEL_LAUNCHED();
-    MODEL_MARK();
+    LOFTR_CHECK_LAUNCH();
+    timer.mark();
   }
-  if (stage_ms) {
-    for (int i = 0; i < LOFTR_MODEL_LOOKUP_STAGES; ++i) stage_ms[i] = 0.f;
-    MODEL_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i + 1 < ev.size() && i < LOFTR_MODEL_LOOKUP_STAGES; ++i) MODEL_TRY(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
-    fail(LOFTR_OK);                                                     // (destroys the events)
-  }
-#undef MODEL_TRY
-#undef MODEL_LAUNCHED
-#undef MODEL_MARK
-  return LOFTR_OK;
+  return timer.finish();
 }

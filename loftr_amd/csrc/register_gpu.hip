@@ -11,6 +11,8 @@
 // two kernels and only read by the last two.  Plain C++, ordinary vector stores.
 #include "common.h"
 #include "register_core.h"
+#include "stage_timer.h"
+#include "tracks_core.h"
 
 namespace {
 
@@ -135,12 +137,10 @@ __global__ void __launch_bounds__(kThreads) reg_write_kernel(Ctx c) {
   }
 }
 
-bool sizes_ok(long T, long N, int n) { return T >= 0 && N >= 0 && n >= 0 && T < (1L << 31) && N < (1L << 31); }
-
 }  // namespace
 
 extern "C" size_t loftr_register_corr_workspace_bytes(long T, long N, int n_images) {
-  if (!sizes_ok(T, N, n_images)) return 0;
+  if (!tracks::sizes_ok(T, N, n_images)) return 0;
   Ctx c{};
   c.T = T; c.N = N; c.n = n_images;
   return layout(c, nullptr);
@@ -157,7 +157,7 @@ extern "C" int loftr_register_corr(const long* offsets, long T, const int* obs_i
   LOFTR_CHECK_ARG(n_images == 0 || (posed && n_corr && cand_rank && cand_image));
   LOFTR_CHECK_ARG(min_corr >= kMinCorr);
   LOFTR_CHECK_ARG((T > 0 && n_images > 0) || N == 0);                            // observations outside every track or image
-  if (!sizes_ok(T, N, n_images)) return LOFTR_ERR_UNSUPPORTED;
+  if (!tracks::sizes_ok(T, N, n_images)) return LOFTR_ERR_UNSUPPORTED;
   Ctx c{};
   c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.N = N; c.xyz = xyz; c.status = status; c.posed = posed; c.n = n_images;
   c.cam_offsets = cam_offsets; c.cam_obs = cam_obs; c.min_corr = min_corr;
@@ -166,32 +166,19 @@ extern "C" int loftr_register_corr(const long* offsets, long T, const int* obs_i
   if (ws_bytes < layout(c, nullptr)) return LOFTR_ERR_WORKSPACE;
   layout(c, (char*)ws);
   hipStream_t s = (hipStream_t)stream;
-  hipEvent_t ev[LOFTR_REGISTER_STAGES + 1];
-  int n_ev = 0;
+  StageTimer timer(stage_ms, LOFTR_REGISTER_STAGES, s);
   bool failed = false;
-  auto mark = [&]() {
-    if (!stage_ms || failed) return;
-    if (hipEventCreate(&ev[n_ev]) != hipSuccess) { failed = true; return; }
-    if (hipEventRecord(ev[n_ev++], s) != hipSuccess) failed = true;
-  };
   auto after = [&]() {
     if (hipGetLastError() != hipSuccess) failed = true;
-    mark();
+    timer.mark();
   };
   auto blocks = [](long items, long per) { return dim3((unsigned)(items > 0 ? (items + per - 1) / per : 1)); };
   if (hipMemsetAsync(c.err, 0, sizeof(int), s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-  mark();
+  timer.mark();
   hipLaunchKernelGGL(reg_track_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c); after();
   hipLaunchKernelGGL(reg_count_kernel, blocks(n_images, kThreads / 64), dim3(kThreads), 0, s, c); after();
   hipLaunchKernelGGL(reg_rank_kernel, dim3(1), dim3(kRankBlock), 0, s, c); after();
   hipLaunchKernelGGL(reg_write_kernel, blocks(n_images, kThreads / 64), dim3(kThreads), 0, s, c); after();
-  if (stage_ms) {
-    if (hipStreamSynchronize(s) != hipSuccess) failed = true;
-    for (int k = 0; k < LOFTR_REGISTER_STAGES; ++k) {
-      stage_ms[k] = 0.f;
-      if (!failed && k + 1 < n_ev && hipEventElapsedTime(&stage_ms[k], ev[k], ev[k + 1]) != hipSuccess) failed = true;
-    }
-    for (int k = 0; k < n_ev; ++k) (void)hipEventDestroy(ev[k]);
-  }
-  return failed ? LOFTR_ERR_LAUNCH : LOFTR_OK;
+  const int timed = timer.finish();
+  return failed ? LOFTR_ERR_LAUNCH : timed;
 }

@@ -37,9 +37,9 @@ extern "C" int loftr_triangulate_tracks_host(const long* offsets, long T, const 
   if (!(thresh_px >= 0.0 && cos_min_angle >= -1.0 && cos_min_angle <= 1.0)) return LOFTR_ERR_BAD_ARG;
   if (T >= (1L << 31) || N >= (1L << 31)) return LOFTR_ERR_UNSUPPORTED;
   for (int i = 0; i < kCounts; ++i) counts[i] = 0;
-  if (offsets[0] != 0 || offsets[T] != N) return LOFTR_ERR_BAD_ARG;
-  for (long t = 0; t < T; ++t) if (offsets[t + 1] < offsets[t]) return LOFTR_ERR_BAD_ARG;
-  for (long k = 0; k < N; ++k) if (obs_image[k] < 0 || obs_image[k] >= n_images) return LOFTR_ERR_BAD_ARG;
+  if (T == 0 && (offsets[0] != 0 || N != 0)) return LOFTR_ERR_BAD_ARG;
+  for (long t = 0, b, e; t < T; ++t)
+    if (!tracks::span(offsets, T, N, t, &b, &e) || !tracks::images_ok(obs_image, b, e, n_images)) return LOFTR_ERR_BAD_ARG;
   std::vector<double> tab((size_t)kCam * (size_t)n_images);
   for (int i = 0; i < n_images; ++i) cam_table(K + 9 * (size_t)i, T_cam_from_world + 16 * (size_t)i, &tab[(size_t)kCam * i]);
   const Obs o{tab.data(), obs_image, obs_xy, thresh_px * thresh_px, cos_min_angle};

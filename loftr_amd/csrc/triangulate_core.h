@@ -1,14 +1,15 @@
 // Triangulation of atlas tracks from known camera poses: the arithmetic shared by the host routine (triangulate.hip) and the GPU
 // kernels (triangulate_gpu.hip).  As in absolute_pose_core.h, every function here is compiled for both sides from this one text, fp64,
 // without FMA contraction, and uses + - * / and sqrt only (correctly rounded on both sides), so that host and device take identical
-// decisions and produce identical bits.  The rule is stated in include/loftr_hip.h and DESIGN §16; self-contained on purpose (no
-// include of the other *_core.h files).
+// decisions and produce identical bits.  The rule is stated in include/loftr_hip.h and DESIGN §16; the checks of the track table and
+// its error bits are tracks_core.h's.
 //
 // Every rejection below is written as "unless (x > y)" rather than "if (x <= y)": a NaN (a non-finite pixel, a zero ray) then rejects.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "tracks_core.h"
 
 #pragma clang fp contract(off)
 
@@ -24,7 +25,8 @@ constexpr int kCounts = 8;                 // counts[0..4]: tracks per status, [
 constexpr double kParallel = 1e-12;        // den <= kParallel * a * c: the two rays are parallel
 
 enum : int { kOk = 0, kTooShort = 1, kNoHypothesis = 2, kSmallAngle = 3, kBadCamera = 4 };
-enum : int { kBadImage = 1, kBadOffsets = 2 };        // error bits (counts[5])
+using tracks::kBadImage;                   // error bits (counts[5])
+using tracks::kBadOffsets;
 
 TRI_HD bool fin(double x) { return fabs(x) <= 1.7976931348623157e308; }       // false for NaN and the infinities
 TRI_HD double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }

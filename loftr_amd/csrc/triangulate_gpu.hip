@@ -16,6 +16,7 @@
 // Plain C++ throughout; all stores are ordinary vector stores.
 #include "common.h"
 #include "triangulate_core.h"
+#include "stage_timer.h"
 
 #pragma clang fp contract(off)
 
@@ -72,8 +73,8 @@ __global__ void __launch_bounds__(kThreads) tri_solve_kernel(Args a, int cls) {
   long o0 = 0, L = 0;
   int err = 0;
   if (live) {                                                          // offsets: 0 first, N last, ascending, inside [0, N]
-    const long b = a.offsets[t], e = a.offsets[t + 1];
-    if (b < 0 || e < b || e > a.N || (t == 0 && b != 0) || (t == a.T - 1 && e != a.N)) { err = kBadOffsets; live = false; }
+    long b, e;
+    if (!tracks::span(a.offsets, a.T, a.N, t, &b, &e)) { err = kBadOffsets; live = false; }
     else { o0 = b; L = e - b; }
   }
   if (live && cls) live = (cls == 1) == (L <= kShortMax);
@@ -157,32 +158,25 @@ extern "C" int loftr_triangulate_tracks(const long* offsets, long T, const int* 
   if (ws_bytes < table_bytes(n_images)) return LOFTR_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   double* tab = (double*)ws;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  auto tick = [&](int i) { if (stage_ms) (void)hipEventRecord(ev[i], s); };
-  if (stage_ms) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) return LOFTR_ERR_LAUNCH;
+  StageTimer timer(stage_ms, LOFTR_TRIANGULATE_STAGES, s);
   if (hipMemsetAsync(counts, 0, sizeof(long) * kCounts, s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-  tick(0);
+  timer.mark();
   if (n_images > 0) {
     hipLaunchKernelGGL(tri_camera_kernel, dim3((unsigned)((n_images + 63) / 64)), dim3(64), 0, s, K, T_cam_from_world, n_images, tab);
     LOFTR_CHECK_LAUNCH();
   }
-  tick(1);
+  timer.mark();
   const Args a{offsets, T, obs_image, obs_xy, N, n_images, tab, thresh_px * thresh_px, cos_min_angle,
                Out{xyz, n_inliers, rms_px, tri_cos, status}, obs_inlier, (unsigned long long*)counts};
   if (T > 0 && group != 64) {
     hipLaunchKernelGGL(tri_solve_kernel<8>, dim3((unsigned)((T + 31) / 32)), dim3(kThreads), 0, s, a, group == 0 ? 1 : 0);
     LOFTR_CHECK_LAUNCH();
   }
-  tick(2);
+  timer.mark();
   if (T > 0 && group != 8) {
     hipLaunchKernelGGL(tri_solve_kernel<64>, dim3((unsigned)((T + 3) / 4)), dim3(kThreads), 0, s, a, group == 0 ? 2 : 0);
     LOFTR_CHECK_LAUNCH();
   }
-  tick(3);
-  if (stage_ms) {
-    if (hipStreamSynchronize(s) != hipSuccess) return LOFTR_ERR_LAUNCH;
-    for (int i = 0; i < LOFTR_TRIANGULATE_STAGES; ++i) if (hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]) != hipSuccess) stage_ms[i] = 0.f;
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
-  return LOFTR_OK;
+  timer.mark();
+  return timer.finish();
 }

@@ -1129,6 +1129,110 @@ def lift_keypoints(kpts, m_bids, depth, K, T=None):
     return out, valid.view(torch.bool)
 
 
+# ---- the two sides of a routine pair -------------------------------------------------------------------------------------------------
+# The SfM routines below come in pairs: loftr_<name>_host on numpy arrays DEFINES the result, loftr_<name> reproduces it on GPU tensors.
+# A pair shares one body, written against a backend that supplies what differs: how an array that belongs to the other side is refused,
+# how a dtype is named, a pointer taken, an output allocated, and which of the two C entry points is called with which trailing arguments.
+class _Host:
+    @staticmethod
+    def refuse(what, names, arrays, hint):
+        import numpy as np
+        if not all(isinstance(a, np.ndarray) for a in arrays):
+            raise _lib.LoftrHipError(f"{what}: expected numpy arrays (GPU tensors go to {hint})")
+
+    @staticmethod
+    def dtype_of(a):
+        return a.dtype.name
+
+    @staticmethod
+    def ptr(a):
+        return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+    @staticmethod
+    def contiguous(a):
+        import numpy as np
+        return None if a is None else np.ascontiguousarray(a)
+
+    @staticmethod
+    def zeros(shape, dt, like):
+        import numpy as np
+        return np.zeros(shape, dt)
+
+    empty = zeros                                                                        # (the host routines' outputs start as zeros)
+
+    @staticmethod
+    def call(name, args, why, like, ws=None, extra=(), tail=()):
+        check(getattr(_lib.load(), f"loftr_{name}_host")(*args), f"loftr_{name}_host ({why})")
+
+
+class _Gpu:
+    @staticmethod
+    def refuse(what, names, arrays, hint):
+        for name, a in zip(names, arrays):
+            if not isinstance(a, torch.Tensor) or not a.is_cuda:
+                raise _lib.LoftrHipError(f"{name}: expected a GPU tensor ({hint})")
+
+    @staticmethod
+    def dtype_of(a):
+        return str(a.dtype).replace("torch.", "")
+
+    ptr = staticmethod(_ptr)
+
+    @staticmethod
+    def contiguous(a):
+        return None if a is None else a.contiguous()
+
+    @staticmethod
+    def zeros(shape, dt, like):
+        return torch.zeros(shape, dtype=getattr(torch, dt), device=like.device)
+
+    @staticmethod
+    def empty(shape, dt, like):
+        return torch.empty(shape, dtype=getattr(torch, dt), device=like.device)
+
+    @staticmethod
+    def call(name, args, why, like, ws=None, extra=(), tail=()):
+        """args: what both entry points take; extra: what only the kernels take before the workspace; ws: the arguments of
+        loftr_<name>_workspace_bytes (None: no workspace); tail: the timing arguments before the stream."""
+        lib = _lib.load()
+        if ws is not None:
+            buf = torch.empty(max(1, getattr(lib, f"loftr_{name}_workspace_bytes")(*ws)), dtype=torch.uint8, device=like.device)
+            extra = (*extra, _ptr(buf), buf.numel())
+        check(getattr(lib, f"loftr_{name}")(*args, *extra, *tail, _stream()), f"loftr_{name}")
+
+
+def _check_args(B, what, hint, spec, arrays):
+    """Arrays of the right side, then the (name, dtype, ndim) table `spec` against them."""
+    B.refuse(what, [s[0] for s in spec], arrays, hint)
+    for (name, dt, nd), a in zip(spec, arrays):
+        if B.dtype_of(a) != dt or a.ndim != nd:
+            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {B.dtype_of(a)} {tuple(a.shape)}")
+
+
+def _outputs(B, table, size, counts, like):
+    """Zeroed outputs of a (name, size key, trailing shape, dtype) table, and counts [counts] i64 last."""
+    out = {k: B.zeros((size[s],) + tail, dt, like) for k, s, tail, dt in table}
+    out["counts"] = B.zeros(counts, "int64", like)
+    return out
+
+
+class _StageMs:
+    """The stage-timing buffer of one call: `arg` goes to the entry point (None without timings), report() appends (stage, ms) pairs."""
+
+    def __init__(self, timings, stages):
+        self.timings, self.stages = timings, stages
+        self.buf = (C.c_float * len(stages))() if timings is not None else None
+        self.arg = C.cast(self.buf, C.c_void_p) if timings is not None else None
+
+    def report(self):
+        if self.timings is not None:
+            self.timings.extend(zip(self.stages, (float(v) for v in self.buf)))
+
+
+_TABLE_RULES = ("offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images); cam_offsets / cam_obs "
+                "must group the observations by image in ascending order")
+
+
 # ---- keypoint atlas (csrc/atlas.hip, csrc/atlas_gpu.hip; DESIGN §15) -----------------------------------------------------------------
 ATLAS_COUNTS = 16
 ATLAS_REASONS = ("n_valid", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside")     # counts[4 + reason]
@@ -1157,7 +1261,7 @@ def atlas_host(kpts0, kpts1, conf, rows, mask, row_images, n_images, gh, gw, inv
            "n_obs": np.zeros(Kb, np.int32), "row_offsets": np.zeros(R + 1, np.int64), "matches": np.zeros((max(M, 1), 2), np.int32),
            "match_conf": np.zeros(max(M, 1), np.float32), "track_id": np.full(Kb, -1, np.int32), "track_len": np.zeros(Kb, np.int32),
            "track_ok": np.zeros(Kb, np.uint8), "counts": np.zeros(ATLAS_COUNTS, np.int64)}
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    ptr = _Host.ptr
     st = _atlas_out(out, ptr)
     check(_lib.load().loftr_atlas_host(ptr(k0), ptr(k1), ptr(c), ptr(r), ptr(mk), M, ptr(ri), R, int(n_images), int(gh), int(gw), float(inv),
                                        int(min_track_len), C.byref(st)),
@@ -1213,12 +1317,11 @@ def atlas_finalize(grid, obs_xy, obs_cell, m_conf, m_row, m_reason, status, M, R
     lib = _lib.load()
     ws = torch.empty(max(1, lib.loftr_atlas_finalize_workspace_bytes(M, int(n_images), int(gh), int(gw))), dtype=torch.uint8, device=dev)
     st = _atlas_out(out, _ptr)
-    ms = (C.c_float * len(ATLAS_STAGES))() if timings is not None else None
+    ms = _StageMs(timings, ATLAS_STAGES)
     check(lib.loftr_atlas_finalize(_ptr(grid), _ptr(obs_xy), _ptr(obs_cell), _ptr(m_conf), _ptr(m_row), _ptr(m_reason), M, R, int(n_images),
                                    int(gh), int(gw), int(min_track_len), _ptr(status), C.byref(st), _ptr(ws), ws.numel(),
-                                   C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_atlas_finalize")
-    if timings is not None:
-        timings.extend(zip(ATLAS_STAGES, (float(v) for v in ms)))
+                                   ms.arg, _stream()), "loftr_atlas_finalize")
+    ms.report()
     return out
 
 
@@ -1227,19 +1330,8 @@ TRI_COUNTS = 8
 TRI_STATUS = ("ok", "too_short", "no_hypothesis", "small_angle", "bad_camera")            # status codes 0..4 = counts[0..4]
 TRI_STAGES = ("camera_table", "solve_8", "solve_64")
 _TRI_ARGS = (("offsets", "int64", 1), ("obs_image", "int32", 1), ("obs_xy", "float32", 2), ("K", "float64", 3), ("T_cam_from_world", "float64", 3))
-
-
-def _tri_shapes(what, arrays, dtype_of):
-    """Dtype and shape checks shared by the two triangulation wrappers -> (T, N, n_images)."""
-    for (name, dt, nd), a in zip(_TRI_ARGS, arrays):
-        if dtype_of(a) != dt or a.ndim != nd:
-            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
-    offsets, obs_image, obs_xy, K, T = arrays
-    N, n = obs_image.shape[0], K.shape[0]
-    if offsets.shape[0] < 1 or tuple(obs_xy.shape) != (N, 2) or tuple(K.shape) != (n, 3, 3) or tuple(T.shape) != (n, 4, 4):
-        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], K [n,3,3] and T_cam_from_world [n,4,4], got "
-                                 f"{[tuple(a.shape) for a in arrays]}")
-    return offsets.shape[0] - 1, N, n
+_TRI_OUT = (("xyz", "T", (3,), "float32"), ("n_inliers", "T", (), "int32"), ("rms_px", "T", (), "float32"), ("tri_cos", "T", (), "float32"),
+            ("status", "T", (), "uint8"), ("obs_inlier", "N", (), "uint8"))
 
 
 def triangulation_pairs(L):
@@ -1249,26 +1341,33 @@ def triangulation_pairs(L):
     return [(buf[2 * h], buf[2 * h + 1]) for h in range(n.value)]
 
 
+def _triangulate_tracks(B, what, hint, arrays, thresh_px, cos_min_angle, group, timings):
+    _check_args(B, what, hint, _TRI_ARGS, arrays)
+    offsets, obs_image, obs_xy, K, Tc = arrays
+    N, n, T = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
+    if T < 0 or tuple(obs_xy.shape) != (N, 2) or tuple(K.shape) != (n, 3, 3) or tuple(Tc.shape) != (n, 4, 4):
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], K [n,3,3] and T_cam_from_world [n,4,4], got "
+                                 f"{[tuple(a.shape) for a in arrays]}")
+    if int(group) not in (0, 8, 64):
+        raise _lib.LoftrHipError(f"{what}: group must be 0, 8 or 64, got {group}")
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _TRI_OUT, {"T": T, "N": N}, TRI_COUNTS, offsets)
+    ms = _StageMs(timings, TRI_STAGES)
+    B.call("triangulate_tracks", (a[0], T, a[1], a[2], N, a[3], a[4], n, float(thresh_px), float(cos_min_angle), *[B.ptr(out[k]) for k in out]),
+           "offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images)", offsets, ws=(T, N, n), extra=(int(group),),
+           tail=(ms.arg,))
+    ms.report()
+    return out
+
+
 def triangulate_tracks_host(offsets, obs_image, obs_xy, K, T_cam_from_world, thresh_px, cos_min_angle):
     """loftr_triangulate_tracks_host: the host routine that DEFINES the triangulation (include/loftr_hip.h) on numpy arrays:
     offsets [T+1] i64, obs_image [N] i32, obs_xy [N,2] f32, K [n,3,3] f64, T_cam_from_world [n,4,4] f64.
     -> dict of numpy arrays: xyz [T,3] f32, n_inliers [T] i32, rms_px [T] f32, tri_cos [T] f32, status [T] u8, obs_inlier [N] u8,
     counts [8] i64."""
-    import numpy as np
-    arrays = (offsets, obs_image, obs_xy, K, T_cam_from_world)
-    if not all(isinstance(a, np.ndarray) for a in arrays):
-        raise _lib.LoftrHipError("triangulate_tracks_host: expected numpy arrays (GPU tensors go to triangulate_tracks)")
-    T, N, n = _tri_shapes("triangulate_tracks_host", arrays, lambda a: a.dtype.name)
-    arrays = [np.ascontiguousarray(a) for a in arrays]
-    out = {"xyz": np.zeros((T, 3), np.float32), "n_inliers": np.zeros(T, np.int32), "rms_px": np.zeros(T, np.float32),
-           "tri_cos": np.zeros(T, np.float32), "status": np.zeros(T, np.uint8), "obs_inlier": np.zeros(N, np.uint8),
-           "counts": np.zeros(TRI_COUNTS, np.int64)}
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-    a = arrays
-    check(_lib.load().loftr_triangulate_tracks_host(ptr(a[0]), T, ptr(a[1]), ptr(a[2]), N, ptr(a[3]), ptr(a[4]), n, float(thresh_px),
-                                                    float(cos_min_angle), *[ptr(out[k]) for k in out]),
-          "loftr_triangulate_tracks_host (offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images))")
-    return out
+    return _triangulate_tracks(_Host, "triangulate_tracks_host", "triangulate_tracks", (offsets, obs_image, obs_xy, K, T_cam_from_world),
+                               thresh_px, cos_min_angle, 0, None)
 
 
 @_on_device
@@ -1277,28 +1376,9 @@ def triangulate_tracks(offsets, obs_image, obs_xy, K, T_cam_from_world, thresh_p
     triangulate_tracks_host; the same result bit for bit, whatever group (0, 8 or 64) is.  -> dict of device tensors; nothing is read
     back here: bad offsets / obs_image raise bits in counts[5], which the caller reads once.  timings: a list that receives
     (stage, ms) pairs (the call then waits for the stream)."""
-    arrays = (offsets, obs_image, obs_xy, K, T_cam_from_world)
-    for (name, _, _), a in zip(_TRI_ARGS, arrays):
-        if not isinstance(a, torch.Tensor) or not a.is_cuda:
-            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the triangulation kernels have no CPU fallback; the host routine is "
-                                     "triangulate_tracks_host)")
-    T, N, n = _tri_shapes("triangulate_tracks", arrays, lambda a: str(a.dtype).replace("torch.", ""))
-    if int(group) not in (0, 8, 64):
-        raise _lib.LoftrHipError(f"triangulate_tracks: group must be 0, 8 or 64, got {group}")
-    dev = offsets.device
-    a = [x.contiguous() for x in arrays]
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-    out = {"xyz": z((T, 3), torch.float32), "n_inliers": z(T, torch.int32), "rms_px": z(T, torch.float32), "tri_cos": z(T, torch.float32),
-           "status": z(T, torch.uint8), "obs_inlier": z(N, torch.uint8), "counts": z(TRI_COUNTS, torch.int64)}
-    lib = _lib.load()
-    ws = torch.empty(max(1, lib.loftr_triangulate_tracks_workspace_bytes(T, N, n)), dtype=torch.uint8, device=dev)
-    ms = (C.c_float * len(TRI_STAGES))() if timings is not None else None
-    check(lib.loftr_triangulate_tracks(_ptr(a[0]), T, _ptr(a[1]), _ptr(a[2]), N, _ptr(a[3]), _ptr(a[4]), n, float(thresh_px), float(cos_min_angle),
-                                       *[_ptr(out[k]) for k in out], int(group), _ptr(ws), ws.numel(),
-                                       C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_triangulate_tracks")
-    if timings is not None:
-        timings.extend(zip(TRI_STAGES, (float(v) for v in ms)))
-    return out
+    return _triangulate_tracks(_Gpu, "triangulate_tracks", "the triangulation kernels have no CPU fallback; the host routine is "
+                               "triangulate_tracks_host", (offsets, obs_image, obs_xy, K, T_cam_from_world), thresh_px, cos_min_angle, group,
+                               timings)
 
 
 # ---- bundle adjustment of the triangulated model (csrc/bundle.hip, csrc/bundle_gpu.hip; DESIGN §18) -----------------------------------
@@ -1310,20 +1390,8 @@ BUNDLE_CLASSES = ("setup", "linearise", "factor", "track_half", "camera_half", "
 BUNDLE_MAX_ITERS, BUNDLE_MAX_PCG = 1000, 200
 _BA_ARGS = (("offsets", "int64", 1), ("obs_image", "int32", 1), ("obs_xy", "float32", 2), ("obs_mask", "uint8", 1), ("xyz", "float32", 2),
             ("K", "float64", 3), ("T_cam_from_world", "float64", 3), ("fixed", "uint8", 1), ("cam_offsets", "int64", 1), ("cam_obs", "int32", 1))
-
-
-def _ba_shapes(what, arrays, dtype_of):
-    """Dtype and shape checks shared by the two bundle-adjustment wrappers -> (T, N, n_images)."""
-    for (name, dt, nd), a in zip(_BA_ARGS, arrays):
-        if dtype_of(a) != dt or a.ndim != nd:
-            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
-    offsets, obs_image, obs_xy, obs_mask, xyz, K, T, fixed, cam_offsets, cam_obs = arrays
-    N, n, nt = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
-    if nt < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (nt, 3) or tuple(K.shape) != (n, 3, 3) or \
-            tuple(T.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N:
-        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
-                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1] and cam_obs [N], got {[tuple(a.shape) for a in arrays]}")
-    return nt, N, n
+_BA_OUT = (("T_cam_from_world", "n", (4, 4), "float64"), ("xyz", "T", (3,), "float32"), ("obs_active", "N", (), "uint8"),
+           ("cam_free", "n", (), "uint8"), ("point_active", "T", (), "uint8"))
 
 
 def _ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol):
@@ -1336,27 +1404,38 @@ def _ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol):
     return float(huber_px), int(max_iters), int(pcg_iters), float(pcg_tol), float(ftol)
 
 
+def _bundle_adjust(B, what, hint, arrays, params, timings):
+    _check_args(B, what, hint, _BA_ARGS, arrays)
+    offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs = arrays
+    N, n, T = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
+    if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or tuple(K.shape) != (n, 3, 3) or \
+            tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N:
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
+                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1] and cam_obs [N], got {[tuple(a.shape) for a in arrays]}")
+    params = _ba_params(what, *params)
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _BA_OUT, {"T": T, "N": N, "n": n}, BUNDLE_COUNTS, offsets)
+    # per kernel class, not per stage: the median launch and the total, and the launches issued
+    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
+    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
+    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
+    B.call("bundle_adjust", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], n, a[8], a[9], *params, *[B.ptr(out[k]) for k in out]),
+           _TABLE_RULES, offsets, ws=(T, N, n), tail=(cast(ms), cast(launches)))
+    if timings is not None:
+        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
+    return out
+
+
 def bundle_adjust_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, huber_px, max_iters,
                        pcg_iters, pcg_tol, ftol):
     """loftr_bundle_adjust_host: the host routine that DEFINES the bundle adjustment (include/loftr_hip.h) on numpy arrays: offsets [T+1]
     i64, obs_image [N] i32, obs_xy [N,2] f32, obs_mask [N] u8, xyz [T,3] f32, K [n,3,3] f64, T_cam_from_world [n,4,4] f64, fixed [n] u8,
     cam_offsets [n+1] i64, cam_obs [N] i32.  -> dict of numpy arrays: T_cam_from_world [n,4,4] f64, xyz [T,3] f32, obs_active [N] u8,
     cam_free [n] u8, point_active [T] u8, counts [16] i64."""
-    import numpy as np
-    arrays = (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs)
-    if not all(isinstance(a, np.ndarray) for a in arrays):
-        raise _lib.LoftrHipError("bundle_adjust_host: expected numpy arrays (GPU tensors go to bundle_adjust)")
-    T, N, n = _ba_shapes("bundle_adjust_host", arrays, lambda a: a.dtype.name)
-    params = _ba_params("bundle_adjust_host", huber_px, max_iters, pcg_iters, pcg_tol, ftol)
-    a = [np.ascontiguousarray(x) for x in arrays]
-    out = {"T_cam_from_world": np.zeros((n, 4, 4), np.float64), "xyz": np.zeros((T, 3), np.float32), "obs_active": np.zeros(N, np.uint8),
-           "cam_free": np.zeros(n, np.uint8), "point_active": np.zeros(T, np.uint8), "counts": np.zeros(BUNDLE_COUNTS, np.int64)}
-    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
-    check(_lib.load().loftr_bundle_adjust_host(ptr(a[0]), T, ptr(a[1]), ptr(a[2]), ptr(a[3]), N, ptr(a[4]), ptr(a[5]), ptr(a[6]), ptr(a[7]), n,
-                                               ptr(a[8]), ptr(a[9]), *params, *[ptr(out[k]) for k in out]),
-          "loftr_bundle_adjust_host (offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images); cam_offsets / cam_obs "
-          "must group the observations by image in ascending order)")
-    return out
+    return _bundle_adjust(_Host, "bundle_adjust_host", "bundle_adjust",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), None)
 
 
 @_on_device
@@ -1366,29 +1445,9 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     bundle_adjust_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in
     counts[1], which the caller reads once.  timings: a dict that receives per kernel class (BUNDLE_CLASSES) the tuple
     (median ms of a launch, total ms, launches issued); the call then waits for the stream."""
-    arrays = (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs)
-    for (name, _, _), a in zip(_BA_ARGS, arrays):
-        if not isinstance(a, torch.Tensor) or not a.is_cuda:
-            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the bundle-adjustment kernels have no CPU fallback; the host routine is "
-                                     "bundle_adjust_host)")
-    T, N, n = _ba_shapes("bundle_adjust", arrays, lambda a: str(a.dtype).replace("torch.", ""))
-    params = _ba_params("bundle_adjust", huber_px, max_iters, pcg_iters, pcg_tol, ftol)
-    dev = offsets.device
-    a = [x.contiguous() for x in arrays]
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-    out = {"T_cam_from_world": z((n, 4, 4), torch.float64), "xyz": z((T, 3), torch.float32), "obs_active": z(N, torch.uint8),
-           "cam_free": z(n, torch.uint8), "point_active": z(T, torch.uint8), "counts": z(BUNDLE_COUNTS, torch.int64)}
-    lib = _lib.load()
-    ws = torch.empty(max(1, lib.loftr_bundle_adjust_workspace_bytes(T, N, n)), dtype=torch.uint8, device=dev)
-    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
-    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
-    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
-    check(lib.loftr_bundle_adjust(_ptr(a[0]), T, _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), N, _ptr(a[4]), _ptr(a[5]), _ptr(a[6]), _ptr(a[7]), n,
-                                  _ptr(a[8]), _ptr(a[9]), *params, *[_ptr(out[k]) for k in out], _ptr(ws), ws.numel(), cast(ms), cast(launches),
-                                  _stream()), "loftr_bundle_adjust")
-    if timings is not None:
-        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
-    return out
+    return _bundle_adjust(_Gpu, "bundle_adjust", "the bundle-adjustment kernels have no CPU fallback; the host routine is bundle_adjust_host",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), timings)
 
 
 # ---- correspondence table of the images without a pose (csrc/register.hip, csrc/register_gpu.hip; DESIGN §19) --------------------------
@@ -1403,20 +1462,24 @@ _REG_OUT = (("n_corr", "n", (), "int32"), ("cand_rank", "n", (), "int32"), ("can
             ("corr_xyz", "N", (3,), "float32"), ("corr_xy", "N", (2,), "float32"), ("corr_bid", "N", (), "int64"), ("corr_obs", "N", (), "int32"))
 
 
-def _reg_shapes(what, arrays, dtype_of, min_corr):
-    """Dtype and shape checks shared by the two wrappers of the correspondence table -> (T, N, n_images)."""
-    for (name, dt, nd), a in zip(_REG_ARGS, arrays):
-        if dtype_of(a) != dt or a.ndim != nd:
-            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
+def _register_corr(B, what, hint, arrays, min_corr, timings):
+    _check_args(B, what, hint, _REG_ARGS, arrays)
     offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs = arrays
-    N, n, nt = obs_image.shape[0], posed.shape[0], offsets.shape[0] - 1
-    if nt < 0 or tuple(obs_xy.shape) != (N, 2) or tuple(xyz.shape) != (nt, 3) or status.shape[0] != nt or cam_offsets.shape[0] != n + 1 or \
+    N, n, T = obs_image.shape[0], posed.shape[0], offsets.shape[0] - 1
+    if T < 0 or tuple(obs_xy.shape) != (N, 2) or tuple(xyz.shape) != (T, 3) or status.shape[0] != T or cam_offsets.shape[0] != n + 1 or \
             cam_obs.shape[0] != N:
         raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], xyz [T,3], status [T], posed [n], "
                                  f"cam_offsets [n+1] and cam_obs [N], got {[tuple(a.shape) for a in arrays]}")
     if not isinstance(min_corr, int) or isinstance(min_corr, bool) or min_corr < REGISTER_MIN_CORR:
         raise ValueError(f"{what}: min_corr must be an integer >= {REGISTER_MIN_CORR}, got {min_corr}")
-    return nt, N, n
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _REG_OUT, {"n": n, "n1": n + 1, "N": N}, REGISTER_COUNTS, offsets)
+    ms = _StageMs(timings, REGISTER_STAGES)
+    B.call("register_corr", (a[0], T, a[1], a[2], N, a[3], a[4], a[5], n, a[6], a[7], int(min_corr), *[B.ptr(out[k]) for k in out]),
+           _TABLE_RULES, offsets, ws=(T, N, n), tail=(ms.arg,))
+    ms.report()
+    return out
 
 
 def register_corr_host(offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs, min_corr):
@@ -1425,21 +1488,8 @@ def register_corr_host(offsets, obs_image, obs_xy, xyz, status, posed, cam_offse
     i64, cam_obs [N] i32.  -> dict of numpy arrays sized by the bounds (n_corr, cand_rank, cand_image [n] i32, cand_offsets [n+1] i64,
     corr_xyz [N,3] f32, corr_xy [N,2] f32, corr_bid [N] i64, corr_obs [N] i32; rows past counts[1] / counts[0] are zero) and counts [8]
     i64."""
-    import numpy as np
-    arrays = (offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs)
-    if not all(isinstance(a, np.ndarray) for a in arrays):
-        raise _lib.LoftrHipError("register_corr_host: expected numpy arrays (GPU tensors go to register_corr)")
-    T, N, n = _reg_shapes("register_corr_host", arrays, lambda a: a.dtype.name, min_corr)
-    a = [np.ascontiguousarray(x) for x in arrays]
-    size = {"n": n, "n1": n + 1, "N": N}
-    out = {k: np.zeros((size[s],) + tail, dt) for k, s, tail, dt in _REG_OUT}
-    out["counts"] = np.zeros(REGISTER_COUNTS, np.int64)
-    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
-    check(_lib.load().loftr_register_corr_host(ptr(a[0]), T, ptr(a[1]), ptr(a[2]), N, ptr(a[3]), ptr(a[4]), ptr(a[5]), n, ptr(a[6]), ptr(a[7]),
-                                               int(min_corr), *[ptr(out[k]) for k in out]),
-          "loftr_register_corr_host (offsets must start at 0, end at N and ascend; obs_image must lie in [0, n_images); cam_offsets / cam_obs "
-          "must group the observations by image in ascending order)")
-    return out
+    return _register_corr(_Host, "register_corr_host", "register_corr", (offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs),
+                          min_corr, None)
 
 
 @_on_device
@@ -1448,26 +1498,8 @@ def register_corr(offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, c
     register_corr_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in
     counts[2], C and P in counts[0] and counts[1], which the caller reads once.  timings: a list that receives (stage, ms) pairs (the
     call then waits for the stream)."""
-    arrays = (offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs)
-    for (name, _, _), a in zip(_REG_ARGS, arrays):
-        if not isinstance(a, torch.Tensor) or not a.is_cuda:
-            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the correspondence-table kernels have no CPU fallback; the host routine "
-                                     "is register_corr_host)")
-    T, N, n = _reg_shapes("register_corr", arrays, lambda a: str(a.dtype).replace("torch.", ""), min_corr)
-    dev = offsets.device
-    a = [x.contiguous() for x in arrays]
-    size = {"n": n, "n1": n + 1, "N": N}
-    out = {k: torch.zeros((size[s],) + tail, dtype=getattr(torch, dt), device=dev) for k, s, tail, dt in _REG_OUT}
-    out["counts"] = torch.zeros(REGISTER_COUNTS, dtype=torch.int64, device=dev)
-    lib = _lib.load()
-    ws = torch.empty(max(1, lib.loftr_register_corr_workspace_bytes(T, N, n)), dtype=torch.uint8, device=dev)
-    ms = (C.c_float * len(REGISTER_STAGES))() if timings is not None else None
-    check(lib.loftr_register_corr(_ptr(a[0]), T, _ptr(a[1]), _ptr(a[2]), N, _ptr(a[3]), _ptr(a[4]), _ptr(a[5]), n, _ptr(a[6]), _ptr(a[7]),
-                                  int(min_corr), *[_ptr(out[k]) for k in out], _ptr(ws), ws.numel(),
-                                  C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_register_corr")
-    if timings is not None:
-        timings.extend(zip(REGISTER_STAGES, (float(v) for v in ms)))
-    return out
+    return _register_corr(_Gpu, "register_corr", "the correspondence-table kernels have no CPU fallback; the host routine is register_corr_host",
+                          (offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs), min_corr, timings)
 
 
 # ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip; DESIGN §17) ------------------------
@@ -1478,6 +1510,7 @@ MODEL_STATUS = ((1, "rows outside [0, R)"), (2, "rows that do not ascend"), (4, 
                 (8, "row_db outside [0, n_images)"), (16, "keypoints outside the grid, or cells that do not ascend strictly within an image"),
                 (32, "kp_point outside [-1, P)"))
 MODEL_STAGES = ("lookup", "keep", "write")
+_CELLS_ARGS = (("kp_offsets", "int64", 1), ("keypoints", "float32", 2), ("kp_point", "int32", 1))
 _MODEL_ARGS = (("kp_offsets", "int64", 1), ("kp_cell", "int32", 1), ("kp_point", "int32", 1), ("xyz", "float32", 2))
 _QUERY_ARGS = (("kpts_db", "float32", 2), ("kpts_q", "float32", 2), ("conf", "float32", 1), ("rows", "int32", 1), ("mask", "uint8", 1),
                ("row_db", "int32", 1), ("row_query", "int32", 1))
@@ -1485,21 +1518,40 @@ _MODEL_OUT = (("pts3d", 3, "float32"), ("kpts", 2, "float32"), ("q_ids", 0, "int
               ("conf", 0, "float32"))
 
 
-def _model_shapes(what, named, dtype_of):
-    """Dtype and shape checks shared by the model wrappers; named: (name, dtype, ndim, array) tuples."""
-    for name, dt, nd, a in named:
-        if a is not None and (dtype_of(a) != dt or a.ndim != nd):
-            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} with {nd} dimension(s), got {dtype_of(a)} {tuple(a.shape)}")
-
-
-def _model_geometry(what, kp_offsets, gh, gw):
+def _model_cells(B, what, hint, arrays, P, gh, gw, inv):
+    """-> (kp_cell [K] i32, status [1] i32) of the backend's kind"""
+    _check_args(B, what, hint, _CELLS_ARGS, arrays)
+    kp_offsets, keypoints, kp_point = arrays
+    K = keypoints.shape[0]
     if kp_offsets.shape[0] < 1 or min(int(gh), int(gw)) < 0:
         raise _lib.LoftrHipError(f"{what}: expected kp_offsets [n_images+1] and a grid of gh x gw >= 0 cells, got {tuple(kp_offsets.shape)}, {gh} x {gw}")
-    return kp_offsets.shape[0] - 1
+    if tuple(keypoints.shape) != (K, 2) or kp_point.shape[0] != K:
+        raise _lib.LoftrHipError(f"{what}: expected keypoints [K,2] and kp_point [K], got {tuple(keypoints.shape)}, {tuple(kp_point.shape)}")
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    cell, status = B.empty(K, "int32", keypoints), B.empty(1, "int32", keypoints)
+    B.call("model_cells", (a[0], kp_offsets.shape[0] - 1, a[1], a[2], K, int(P), int(gh), int(gw), float(inv), B.ptr(cell), B.ptr(status)),
+           "kp_offsets must start at 0, end at K and ascend", keypoints)
+    return cell, status
 
 
-def _lookup_sizes(what, model, queries):
-    """(n_images, K, P, M, R) after the shape checks of one lookup; model = (kp_offsets, kp_cell, kp_point, xyz), queries in _QUERY_ARGS order."""
+def model_cells_host(kp_offsets, keypoints, kp_point, P, gh, gw, inv):
+    """loftr_model_cells_host on numpy arrays: kp_offsets [n_images+1] i64, keypoints [K,2] f32, kp_point [K] i32 -> (kp_cell [K] i32,
+    status bits: 16 cells not strictly ascending within an image or outside the grid, 32 kp_point outside [-1, P))."""
+    cell, status = _model_cells(_Host, "model_cells_host", "model_cells", (kp_offsets, keypoints, kp_point), P, gh, gw, inv)
+    return cell, int(status[0])
+
+
+@_on_device
+def model_cells(kp_offsets, keypoints, kp_point, P, gh, gw, inv):
+    """loftr_model_cells on GPU tensors of the dtypes of model_cells_host -> (kp_cell [K] i32, status [1] i32), device tensors; nothing
+    is read back here."""
+    return _model_cells(_Gpu, "model_cells", "the host form is model_cells_host", (kp_offsets, keypoints, kp_point), P, gh, gw, inv)
+
+
+def _model_lookup(B, what, hint, model, gh, gw, inv, queries, Q, timings):
+    given = [(s, a) for s, a in zip(_MODEL_ARGS + _QUERY_ARGS, model + queries) if a is not None]          # (mask may be None)
+    _check_args(B, what, hint, [s for s, _ in given], [a for _, a in given])
     kp_offsets, kp_cell, kp_point, xyz = model
     kd, kq, c, rows, mask, row_db, row_query = queries
     K, P, M, R = kp_cell.shape[0], xyz.shape[0], kd.shape[0], row_db.shape[0]
@@ -1510,57 +1562,23 @@ def _lookup_sizes(what, model, queries):
             (mask is not None and mask.shape[0] != M) or row_query.shape[0] != R:
         raise _lib.LoftrHipError(f"{what}: expected kpts_db / kpts_q [M,2], conf / rows / mask [M] and row_db / row_query [R], got "
                                  f"{[None if a is None else tuple(a.shape) for a in queries]}")
-    return kp_offsets.shape[0] - 1, K, P, M, R
-
-
-def _lookup_structs(model, sizes, gh, gw, inv, out, ptr):
-    n_images, K, P, _, _ = sizes
-    md = _lib.Model(kp_offsets=ptr(model[0]), kp_cell=ptr(model[1]), kp_point=ptr(model[2]), xyz=ptr(model[3]), K=K, P=P, n_images=n_images,
-                    gh=int(gh), gw=int(gw), inv=float(inv))
-    return md, _lib.ModelLookupOut(**{k: ptr(out[k]) for k, _ in _lib.ModelLookupOut._fields_})
-
-
-def model_cells_host(kp_offsets, keypoints, kp_point, P, gh, gw, inv):
-    """loftr_model_cells_host on numpy arrays: kp_offsets [n_images+1] i64, keypoints [K,2] f32, kp_point [K] i32 -> (kp_cell [K] i32,
-    status bits: 16 cells not strictly ascending within an image or outside the grid, 32 kp_point outside [-1, P))."""
-    import numpy as np
-    arrays = (kp_offsets, keypoints, kp_point)
-    if not all(isinstance(a, np.ndarray) for a in arrays):
-        raise _lib.LoftrHipError("model_cells_host: expected numpy arrays (GPU tensors go to model_cells)")
-    _model_shapes("model_cells_host", (("kp_offsets", "int64", 1, kp_offsets), ("keypoints", "float32", 2, keypoints),
-                                       ("kp_point", "int32", 1, kp_point)), lambda a: a.dtype.name)
-    K = keypoints.shape[0]
-    n_images = _model_geometry("model_cells_host", kp_offsets, gh, gw)
-    if tuple(keypoints.shape) != (K, 2) or kp_point.shape[0] != K:
-        raise _lib.LoftrHipError(f"model_cells_host: expected keypoints [K,2] and kp_point [K], got {tuple(keypoints.shape)}, {tuple(kp_point.shape)}")
-    a = [np.ascontiguousarray(x) for x in arrays]
-    cell, status = np.zeros(K, np.int32), C.c_int(0)
-    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
-    check(_lib.load().loftr_model_cells_host(ptr(a[0]), n_images, ptr(a[1]), ptr(a[2]), K, int(P), int(gh), int(gw), float(inv), ptr(cell),
-                                             C.cast(C.byref(status), C.c_void_p)),
-          "loftr_model_cells_host (kp_offsets must start at 0, end at K and ascend)")
-    return cell, status.value
-
-
-@_on_device
-def model_cells(kp_offsets, keypoints, kp_point, P, gh, gw, inv):
-    """loftr_model_cells on GPU tensors of the dtypes of model_cells_host -> (kp_cell [K] i32, status [1] i32), device tensors; nothing
-    is read back here."""
-    named = (("kp_offsets", "int64", 1, kp_offsets), ("keypoints", "float32", 2, keypoints), ("kp_point", "int32", 1, kp_point))
-    for name, _, _, a in named:
-        if not isinstance(a, torch.Tensor) or not a.is_cuda:
-            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the host form is model_cells_host)")
-    _model_shapes("model_cells", named, lambda a: str(a.dtype).replace("torch.", ""))
-    K = keypoints.shape[0]
-    n_images = _model_geometry("model_cells", kp_offsets, gh, gw)
-    if tuple(keypoints.shape) != (K, 2) or kp_point.shape[0] != K:
-        raise _lib.LoftrHipError(f"model_cells: expected keypoints [K,2] and kp_point [K], got {tuple(keypoints.shape)}, {tuple(kp_point.shape)}")
-    a = [x.contiguous() for x in (kp_offsets, keypoints, kp_point)]
-    cell = torch.empty(K, dtype=torch.int32, device=keypoints.device)
-    status = torch.empty(1, dtype=torch.int32, device=keypoints.device)
-    check(_lib.load().loftr_model_cells(_ptr(a[0]), n_images, _ptr(a[1]), _ptr(a[2]), K, int(P), int(gh), int(gw), float(inv), _ptr(cell),
-                                        _ptr(status), _stream()), "loftr_model_cells")
-    return cell, status
+    Q = int(Q)
+    if Q < 0:
+        raise _lib.LoftrHipError(f"{what}: Q must be >= 0, got {Q}")
+    model, queries = [B.contiguous(a) for a in model], [B.contiguous(a) for a in queries]  # (held until the call has returned)
+    m, q = [B.ptr(a) for a in model], [B.ptr(a) for a in queries]
+    out = {k: B.empty((max(M, 1), w) if w else max(M, 1), dt, kp_offsets) for k, w, dt in _MODEL_OUT}
+    out.update(q_offsets=B.empty(Q + 1, "int64", kp_offsets), match_reason=B.empty(M, "uint8", kp_offsets),
+               counts=B.empty(MODEL_COUNTS, "int64", kp_offsets))
+    md = _lib.Model(kp_offsets=m[0], kp_cell=m[1], kp_point=m[2], xyz=m[3], K=K, P=P, n_images=kp_offsets.shape[0] - 1, gh=int(gh), gw=int(gw),
+                    inv=float(inv))
+    st = _lib.ModelLookupOut(**{k: B.ptr(out[k]) for k, _ in _lib.ModelLookupOut._fields_})
+    ms = _StageMs(timings, MODEL_STAGES)
+    B.call("model_lookup", (C.byref(md), *q[:5], M, q[5], q[6], R, Q, C.byref(st)),
+           "rows must ascend within [0, R), row_query within [0, Q) without descending, row_db within [0, n_images); "
+           "kp_offsets must start at 0, end at K and ascend", kp_offsets, ws=(M, Q), tail=(ms.arg,))
+    ms.report()
+    return out
 
 
 def model_lookup_host(kp_offsets, kp_cell, kp_point, xyz, gh, gw, inv, kpts_db, kpts_q, conf, rows, mask, row_db, row_query, Q):
@@ -1569,26 +1587,8 @@ def model_lookup_host(kp_offsets, kp_cell, kp_point, xyz, gh, gw, inv, kpts_db, 
     conf [M] f32, rows [M] i32 ascending, mask [M] u8 or None) and the rows (row_db / row_query [R] i32).
     -> dict of numpy arrays of the bound size M (pts3d, kpts, q_ids, match, point, conf), q_offsets [Q+1] i64, match_reason [M] u8 and
     counts [16] i64; the caller trims by counts[0]."""
-    import numpy as np
-    model, queries = (kp_offsets, kp_cell, kp_point, xyz), (kpts_db, kpts_q, conf, rows, mask, row_db, row_query)
-    if not all(a is None or isinstance(a, np.ndarray) for a in model + queries):
-        raise _lib.LoftrHipError("model_lookup_host: expected numpy arrays (GPU tensors go to model_lookup)")
-    _model_shapes("model_lookup_host", [s + (a,) for s, a in zip(_MODEL_ARGS + _QUERY_ARGS, model + queries)], lambda a: a.dtype.name)
-    sizes = _lookup_sizes("model_lookup_host", model, queries)
-    M, Q = sizes[3], int(Q)
-    if Q < 0:
-        raise _lib.LoftrHipError(f"model_lookup_host: Q must be >= 0, got {Q}")
-    model = [np.ascontiguousarray(a) for a in model]
-    queries = [None if a is None else np.ascontiguousarray(a) for a in queries]
-    out = {k: np.zeros((max(M, 1), w) if w else max(M, 1), dt) for k, w, dt in _MODEL_OUT}
-    out.update(q_offsets=np.zeros(Q + 1, np.int64), match_reason=np.zeros(M, np.uint8), counts=np.zeros(MODEL_COUNTS, np.int64))
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    md, st = _lookup_structs(model, sizes, gh, gw, inv, out, ptr)
-    check(_lib.load().loftr_model_lookup_host(C.byref(md), *[ptr(a) for a in queries[:5]], M, ptr(queries[5]), ptr(queries[6]), sizes[4], Q,
-                                              C.byref(st)),
-          "loftr_model_lookup_host (rows must ascend within [0, R), row_query within [0, Q) without descending, row_db within [0, n_images); "
-          "kp_offsets must start at 0, end at K and ascend)")
-    return out
+    return _model_lookup(_Host, "model_lookup_host", "model_lookup", (kp_offsets, kp_cell, kp_point, xyz), gh, gw, inv,
+                         (kpts_db, kpts_q, conf, rows, mask, row_db, row_query), Q, None)
 
 
 @_on_device
@@ -1597,32 +1597,8 @@ def model_lookup(kp_offsets, kp_cell, kp_point, xyz, gh, gw, inv, kpts_db, kpts_
     model_lookup_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: bad rows raise bits in
     counts[3], which the caller reads once, with counts[0] = C to trim by.  timings: a list that receives (stage, ms) pairs (the call
     then waits for the stream)."""
-    model, queries = (kp_offsets, kp_cell, kp_point, xyz), (kpts_db, kpts_q, conf, rows, mask, row_db, row_query)
-    for (name, _, _), a in zip(_MODEL_ARGS + _QUERY_ARGS, model + queries):
-        if a is not None and (not isinstance(a, torch.Tensor) or not a.is_cuda):
-            raise _lib.LoftrHipError(f"{name}: expected a GPU tensor (the lookup kernels have no CPU fallback; the host routine is "
-                                     "model_lookup_host)")
-    _model_shapes("model_lookup", [s + (a,) for s, a in zip(_MODEL_ARGS + _QUERY_ARGS, model + queries)],
-                  lambda a: str(a.dtype).replace("torch.", ""))
-    sizes = _lookup_sizes("model_lookup", model, queries)
-    M, Q = sizes[3], int(Q)
-    if Q < 0:
-        raise _lib.LoftrHipError(f"model_lookup: Q must be >= 0, got {Q}")
-    dev = kp_offsets.device
-    model = [a.contiguous() for a in model]
-    queries = [None if a is None else a.contiguous() for a in queries]
-    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-    out = {k: e((max(M, 1), w) if w else max(M, 1), getattr(torch, dt)) for k, w, dt in _MODEL_OUT}
-    out.update(q_offsets=e(Q + 1, torch.int64), match_reason=e(M, torch.uint8), counts=e(MODEL_COUNTS, torch.int64))
-    lib = _lib.load()
-    ws = torch.empty(max(1, lib.loftr_model_lookup_workspace_bytes(M, Q)), dtype=torch.uint8, device=dev)
-    md, st = _lookup_structs(model, sizes, gh, gw, inv, out, _ptr)
-    ms = (C.c_float * len(MODEL_STAGES))() if timings is not None else None
-    check(lib.loftr_model_lookup(C.byref(md), *[_ptr(a) for a in queries[:5]], M, _ptr(queries[5]), _ptr(queries[6]), sizes[4], Q, C.byref(st),
-                                 _ptr(ws), ws.numel(), C.cast(ms, C.c_void_p) if ms is not None else None, _stream()), "loftr_model_lookup")
-    if timings is not None:
-        timings.extend(zip(MODEL_STAGES, (float(v) for v in ms)))
-    return out
+    return _model_lookup(_Gpu, "model_lookup", "the lookup kernels have no CPU fallback; the host routine is model_lookup_host",
+                         (kp_offsets, kp_cell, kp_point, xyz), gh, gw, inv, (kpts_db, kpts_q, conf, rows, mask, row_db, row_query), Q, timings)
 
 
 # ---- training-mode glue of the backbone (csrc/train_glue.hip; resnet_fpn.py:22-40,66-77,110-116) ------------------------------------------

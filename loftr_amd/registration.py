@@ -24,7 +24,7 @@ import math
 import numpy as np
 import torch
 
-from . import ops
+from . import _tracks, ops
 from ._lib import LoftrHipError
 
 _ARGS = ("offsets", "obs_image", "obs_xy", "xyz", "status", "K", "T_cam_from_world", "posed")
@@ -64,22 +64,6 @@ class Reconstruction:
         self.points, self.bundle, self.stats = points, bundle, stats
 
 
-def _integers(what, name, a):
-    dt = a.dtype if isinstance(a, torch.Tensor) else np.asarray(a).dtype
-    if (isinstance(dt, torch.dtype) and (dt.is_floating_point or dt == torch.bool)) or \
-            (not isinstance(dt, torch.dtype) and not np.issubdtype(dt, np.integer)):
-        raise ValueError(f"{what}: {name} must hold integers, got {dt}")
-
-
-def _one_device(what, names, args):
-    """True when every argument is a GPU tensor, False when none is; mixed is an error."""
-    gpu = [isinstance(a, torch.Tensor) and a.is_cuda for a in args]
-    if any(gpu) and not all(gpu):
-        raise LoftrHipError(f"{what}: GPU and CPU arguments mixed (" + ", ".join(f"{n}: {'GPU' if g else 'CPU'}" for n, g in zip(names, gpu))
-                            + "); there is no silent fallback: move them to one device")
-    return all(gpu)
-
-
 def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed, min_corr=15, min_inliers=15, thresh_px=4.0,
                     conf=0.999, seed=0, timings=None):
     """Resect the images that have no pose from the points their tracks already have -> ``Registration``.
@@ -96,9 +80,9 @@ def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world
     GPU stages."""
     what = "register_images"
     args = [offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed]
-    gpu = _one_device(what, _ARGS, args)
+    gpu = _tracks.one_device(what, _ARGS, args)
     for name, a in zip(_ARGS[:2], args[:2]):
-        _integers(what, name, a)
+        _tracks.integers(what, name, a)
     if not (isinstance(min_inliers, int) and not isinstance(min_inliers, bool) and math.isfinite(thresh_px) and thresh_px >= 0):
         raise ValueError(f"{what}: min_inliers must be an integer and thresh_px >= 0, got {min_inliers}, {thresh_px}")
     if gpu:
@@ -117,29 +101,15 @@ def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world
         raise LoftrHipError(f"{what}: expected K [n,3,3], T_cam_from_world [n,4,4] and posed [n], got {tuple(a[5].shape)}, {tuple(a[6].shape)}, "
                             f"{tuple(a[7].shape)}")
     if gpu:
-        # the observations grouped by image: integer plumbing, a stable sort (bad image ids are caught by the kernels, so clamp here)
-        im = a[1].to(torch.int64)
-        cam_obs = torch.sort(im, stable=True).indices.to(torch.int32)
-        cam_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        if n > 0 and im.numel() and im.dim() == 1:
-            cam_offsets[1:] = torch.cumsum(torch.bincount(im.clamp(0, n - 1), minlength=n), 0)
-        out = ops.register_corr(a[0], a[1], a[2], a[3], a[4], a[7], cam_offsets, cam_obs, min_corr, timings=timings)
+        out = ops.register_corr(a[0], a[1], a[2], a[3], a[4], a[7], *_tracks.group_by_image(a[1], n), min_corr, timings=timings)
     else:
         if a[0].ndim == 1 and a[1].ndim == 1:                            # the errors the kernels report through counts[2]
-            if a[1].size and (a[1].min() < 0 or a[1].max() >= n):
-                raise ValueError(f"{what}: " + ops.REGISTER_ERRORS[0][1])
-            if a[0].size and (a[0][0] != 0 or a[0][-1] != a[1].shape[0] or (np.diff(a[0]) < 0).any()):
-                raise ValueError(f"{what}: " + ops.REGISTER_ERRORS[1][1])
-        cam_obs = np.argsort(a[1], kind="stable").astype(np.int32)
-        cam_offsets = np.zeros(n + 1, np.int64)
-        if a[1].ndim == 1:
-            cam_offsets[1:] = np.cumsum(np.bincount(a[1], minlength=n)[:n])
-        out = {k: torch.from_numpy(v) for k, v in ops.register_corr_host(a[0], a[1], a[2], a[3], a[4], a[7], cam_offsets, cam_obs, min_corr).items()}
+            _tracks.check_host(what, a[0], a[1], n)
+        out = ops.register_corr_host(a[0], a[1], a[2], a[3], a[4], a[7], *_tracks.group_by_image(a[1], n), min_corr)
+        out = {k: torch.from_numpy(v) for k, v in out.items()}
         a = [torch.from_numpy(x) for x in a]
     counts = out["counts"].cpu().tolist()                               # the one readback
-    for bit, text in ops.REGISTER_ERRORS:
-        if counts[2] & bit:
-            raise ValueError(f"{what}: {text} (found on the device)")
+    _tracks.raise_error_bits(what, counts[2])
     C, P = counts[0], counts[1]
     cand = out["cand_image"][:P]
     cand64 = cand.to(torch.int64)
@@ -210,7 +180,7 @@ def triangulate_posed(offsets, obs_image, obs_xy, K, T_cam_from_world, posed, th
 
 def _tensors(what, names, args):
     out = [a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a)) for a in args]
-    _one_device(what, names, out)
+    _tracks.one_device(what, names, out)
     return [a.detach() for a in out]
 
 
@@ -232,8 +202,8 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     from .bundle import bundle_adjust
     what = "reconstruct_tracks"
     offsets, obs_image, obs_xy, K = _tensors(what, ("offsets", "obs_image", "obs_xy", "K"), (offsets, obs_image, obs_xy, K))
-    _integers(what, "offsets", offsets)
-    _integers(what, "obs_image", obs_image)
+    _tracks.integers(what, "offsets", offsets)
+    _tracks.integers(what, "obs_image", obs_image)
     dev = offsets.device
     offsets, obs_image, obs_xy, K = offsets.to(torch.int64), obs_image.to(torch.int32), obs_xy.to(torch.float32), K.to(torch.float64)
     if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3):

@@ -18,12 +18,9 @@ import math
 import numpy as np
 import torch
 
-from . import ops
-from ._lib import LoftrHipError
+from . import _tracks, ops
 
 _OUT = ("xyz", "n_inliers", "rms_px", "tri_cos", "status", "obs_inlier")
-_BAD_IMAGE = "triangulate_tracks: obs_image outside [0, n_images)"
-_BAD_OFFSETS = "triangulate_tracks: offsets must start at 0, end at the number of observations and ascend"
 
 
 class Points3D:
@@ -80,39 +77,27 @@ def triangulate_tracks(offsets, obs_image, obs_xy, K, T_cam_from_world, thresh_p
     routine; GPU tensors (all of them, on one device) run the kernels.  ``thresh_px``: inlier threshold; ``min_angle_deg``: the smallest
     accepted triangulation angle; ``group``: 0, 8 or 64 lanes per track on the GPU (a tuning knob: the result does not depend on it).
     One readback of the 8 counts; bad ``obs_image`` / ``offsets`` raise ValueError."""
-    names = ("offsets", "obs_image", "obs_xy", "K", "T_cam_from_world")
+    what, names = "triangulate_tracks", ("offsets", "obs_image", "obs_xy", "K", "T_cam_from_world")
     args = (offsets, obs_image, obs_xy, K, T_cam_from_world)
     if not (math.isfinite(thresh_px) and thresh_px >= 0 and math.isfinite(min_angle_deg) and 0 <= min_angle_deg <= 180):
         raise ValueError(f"triangulate_tracks: thresh_px must be >= 0 and min_angle_deg in [0, 180], got {thresh_px}, {min_angle_deg}")
     if group not in (0, 8, 64):
         raise ValueError(f"triangulate_tracks: group must be 0, 8 or 64, got {group}")
     cos_min = math.cos(math.radians(float(min_angle_deg)))              # the host's libm, once: no trigonometry in the shared core
-    gpu = [isinstance(a, torch.Tensor) and a.is_cuda for a in args]
-    if any(gpu) and not all(gpu):
-        raise LoftrHipError("triangulate_tracks: GPU and CPU arguments mixed (" + ", ".join(f"{n}: {'GPU' if g else 'CPU'}" for n, g in zip(names, gpu))
-                            + "); there is no silent fallback: move them to one device")
+    gpu = _tracks.one_device(what, names, args)
     for n, a in zip(names[:2], args[:2]):
-        dt = a.dtype if isinstance(a, torch.Tensor) else np.asarray(a).dtype
-        if (isinstance(dt, torch.dtype) and (dt.is_floating_point or dt == torch.bool)) or \
-                (not isinstance(dt, torch.dtype) and not np.issubdtype(dt, np.integer)):
-            raise ValueError(f"triangulate_tracks: {n} must hold integers, got {dt}")
-    if all(gpu):
+        _tracks.integers(what, n, a)
+    if gpu:
         dts = (torch.int64, torch.int32, torch.float32, torch.float64, torch.float64)
         out = ops.triangulate_tracks(*[a.detach().to(dt) for a, dt in zip(args, dts)], float(thresh_px), cos_min, group=group, timings=timings)
     else:
         dts = (np.int64, np.int32, np.float32, np.float64, np.float64)
         a = [np.ascontiguousarray(x.detach().numpy() if isinstance(x, torch.Tensor) else x, dt) for x, dt in zip(args, dts)]
         if a[0].ndim == 1 and a[1].ndim == 1 and a[3].ndim == 3:         # the errors the kernels report through counts[5]
-            if a[1].size and (a[1].min() < 0 or a[1].max() >= a[3].shape[0]):
-                raise ValueError(_BAD_IMAGE)
-            if a[0].size and (a[0][0] != 0 or a[0][-1] != a[1].shape[0] or (np.diff(a[0]) < 0).any()):
-                raise ValueError(_BAD_OFFSETS)
+            _tracks.check_host(what, a[0], a[1], a[3].shape[0])
         out = {k: torch.from_numpy(v) for k, v in ops.triangulate_tracks_host(*a, float(thresh_px), cos_min).items()}
     counts = out["counts"].cpu().tolist()                               # the one readback
-    if counts[5] & 1:
-        raise ValueError(_BAD_IMAGE + " (found on the device)")
-    if counts[5] & 2:
-        raise ValueError(_BAD_OFFSETS + " (found on the device)")
+    _tracks.raise_error_bits(what, counts[5])
     stats = {"n_tracks": out["status"].numel(), "n_observations": out["obs_inlier"].numel(), "n_inlier_observations": counts[6]}
     stats.update({"n_" + name: counts[i] for i, name in enumerate(ops.TRI_STATUS)})
     out["obs_inlier"] = out["obs_inlier"].view(torch.bool)
