@@ -572,7 +572,7 @@ __global__ __launch_bounds__(256) void scatter_kernel(ScatterParams sp, const in
   sp.out.mkpts1_c[dst * 2 + 1] = (float)(j / g.w1c) * s1y;
 }
 
-#include "sinkhorn.h"         // Sinkhorn: iteration / finalize kernels (row-streaming and round-1 forms), prefilter, dustbins
+#include "sinkhorn.h"         // Sinkhorn: iteration / finalize kernels (row-streaming and separate-kernel forms), prefilter, dustbins
 #include "dual_softmax_bwd.h" // dual-softmax backward: the streaming passes after the recomputed statistics / scores
 #include "sinkhorn_bwd.h"     // Sinkhorn backward: reverse mode through the unrolled iterations
 
@@ -788,11 +788,11 @@ namespace {
 #ifndef OT_WIDE_NT_FINAL
 #define OT_WIDE_NT_FINAL 1024
 #endif
-struct OtPlan { bool rowstream, fused, wide, aligned; int wgs, rpws, wgp, rpw, cpt; };
+struct OtPlan { bool rowstream, wide, aligned; int wgs, rpws; };
 OtPlan ot_plan(const Geometry& g) {
   OtPlan p{};
   // row-streaming passes (otp::ot_pass_kernel): at most 5 x 1024 columns incl. the dustbin with 256 threads (indoor), 6 x 2048 with
-  // 512 (outdoor 105 x 105); rows of any alignment
+  // 512 (outdoor 105 x 105); rows of any alignment.  Wider rows: the separate row / column kernels and ot_finalize_kernel.
   p.rowstream = g.S + 1 <= 4 * 512 * 6;
   p.wide = g.S + 1 > 4 * 256 * 5;
   p.aligned = (g.S & 3) == 0;
@@ -805,15 +805,6 @@ OtPlan ot_plan(const Geometry& g) {
     p.rpws = ceil_div(ceil_div(g.L, wgs), R) * R;
     p.wgs = ceil_div(g.L, p.rpws);
   }
-  // fused iteration (one pass over Z): up to 19 x 256 (indoor) / 44 x 256 (outdoor 840 x 840) columns incl. the dustbin
-  p.cpt = ceil_div(g.S + 1, 256);
-  p.fused = p.cpt <= 44;
-  int wgp = 512 / (g.N > 0 ? g.N : 1);                     // ~2 workgroups per CU over the batch
-  wgp = wgp < 1 ? 1 : (wgp > OT_RCH ? OT_RCH : wgp);       // the partial buffer holds OT_RCH rows per column
-  if (wgp > ceil_div(g.L, 4)) wgp = ceil_div(g.L, 4);
-  int rpw = ceil_div(g.L, wgp);
-  p.rpw = ceil_div(rpw, 4) * 4;
-  p.wgp = ceil_div(g.L, p.rpw);
   return p;
 }
 // one row-streaming pass in the variant the plan names
@@ -842,10 +833,6 @@ void ot_iterate(const Geometry& g, const OtPlan& pl, float* z, const MatchWs& w,
     if (pl.rowstream) {
       ot_pass_launch<false>(pl, g, st, z, bin_score, norm, w.ot_v, w.ot_u, w.ot_part, nullptr, nullptr, nullptr, nullptr, nullptr);
       hipLaunchKernelGGL(ot_col_merge2_kernel, dim3(ceil_div((int)cols, 256)), dim3(256), 0, st, w.ot_part, g, bin_score, norm, pl.wgs, w.ot_u, w.ot_v);
-    } else if (pl.fused) {
-      if (pl.cpt <= 19) hipLaunchKernelGGL((ot_iter_kernel<19, 4>), dim3(pl.wgp, g.N), dim3(256), 0, st, z, g, bin_score, norm, w.ot_v, w.ot_u, w.ot_part, pl.rpw);
-      else hipLaunchKernelGGL((ot_iter_kernel<44, 2>), dim3(pl.wgp, g.N), dim3(256), 0, st, z, g, bin_score, norm, w.ot_v, w.ot_u, w.ot_part, pl.rpw);
-      hipLaunchKernelGGL(ot_col_merge2_kernel, dim3(ceil_div((int)cols, 256)), dim3(256), 0, st, w.ot_part, g, bin_score, norm, pl.wgp, w.ot_u, w.ot_v);
     } else {
       hipLaunchKernelGGL(ot_row_lse_kernel, dim3(ceil_div(g.L + 1, 4), g.N), dim3(256), 0, st, z, g, bin_score, norm, w.ot_v, w.ot_u);
       hipLaunchKernelGGL(ot_col_part_kernel, dim3(ceil_div(g.S + 1, 64), OT_RCH, g.N), dim3(256), 0, st, z, g, bin_score, w.ot_u, w.ot_part);

@@ -262,10 +262,12 @@ def test_single_encoder_layer_vs_oracle(C, L, S, masked):
                                                          ((5, 7), (75, 91), 256, True, False), ((6, 6), (72, 96), 256, False, True),
                                                          ((4, 5), (105, 105), 256, False, False)])
 def test_sinkhorn_paths_vs_oracle(hw0, hw1, C, masked, prefilter):
-    """Sinkhorn coarse matching against the numpy oracle on the shapes the goldens do not reach: rows that are not
-    16-byte aligned (S % 4 != 0: unaligned 16-byte groups and a ragged last group in the row-streaming passes), another
-    descriptor width (tiled score store), masks on unequal grids, and rows wider than 5119 columns (the 512-thread variant
-    of the passes: the outdoor 105 x 105 grid and an aligned one)."""
+    """Sinkhorn coarse matching against the numpy oracle in float32 on a few shapes off the goldens: rows that are not
+    16-byte aligned, another descriptor width (tiled score store: the one thing only this test reaches), masks on unequal
+    grids, and rows wider than 5119 columns.  A smoke test of those paths, not their pin: TOL_CONF is absolute (at
+    conf ~ 1 / (L S) a row or column sum may lose a term unseen), one id may flip, and the dustbins are left out under
+    masks.  The passes' column-group, row-range and dispatch edges (rows wider than 12287 columns included), the
+    dustbins and the prefilter are held to float64 by tests/test_hip_sinkhorn_edges.py."""
     import torch
     from oracle import loftr_oracle as O
     from loftr_amd import ops
