@@ -62,8 +62,10 @@ typedef enum {
  *     of tracks (loftr_triangulate_tracks_host, loftr_triangulation_pairs, loftr_triangulate_tracks,
  *     loftr_triangulate_tracks_workspace_bytes), localisation against the triangulated model (loftr_model_cells_host,
  *     loftr_model_cells, loftr_model_lookup_host, loftr_model_lookup_workspace_bytes, loftr_model_lookup), bundle adjustment of the
- *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust), the correspondence
- *     table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes, loftr_register_corr) */
+ *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust; with per-image focal
+ *     refinement loftr_bundle_adjust_focal_host, loftr_bundle_adjust_focal_workspace_bytes, loftr_bundle_adjust_focal), the
+ *     correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
+ *     loftr_register_corr) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -918,6 +920,42 @@ int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const
                         const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
                         double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
                         long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream);
+
+/* ---- bundle adjustment with per-image focal refinement -------------------------------------------------------------------
+ * The rule above with a camera block of 7 parameters instead of 6; everything not named here is that rule unchanged.
+ * loftr_bundle_adjust_focal_host DEFINES the result, loftr_bundle_adjust_focal reproduces it bit for bit.
+ *   Parameter.  One scalar per camera, a relative focal step delta: the trial is fx' = fx (1 + delta), skew' = skew (1 + delta),
+ *      fy' = fy (1 + delta); cx and cy stay fixed.
+ *   Jacobian.  The seventh column of A is sqrt(w) (fx a + skew b, fy b) with a = Y0 / Y2, b = Y1 / Y2, evaluated from the current
+ *      state's intrinsics like the other six columns; + - * / sqrt only, fp64, contraction off.
+ *   Which cameras.  Camera i REFINES ITS FOCAL iff it is free (rule 2), refine_focal[i] != 0 and it has at least min_focal_obs (>= 1)
+ *      active observations.  Any other camera has a zero seventh column, so its delta is exactly 0, and its K comes back bit for bit.
+ *      A fixed camera refines nothing.
+ *   Block sizes.  Camera blocks are 7 x 7: U has 28 entries, g_c has 7, a dot product of camera vectors has 7 terms, sequential; the
+ *      camera osum64 of the linearisation carries 35 accumulators per lane.  Sums, tree orders and flags are rule 5's.
+ *   Bounds.  focal_lo < 1 < focal_hi, finite.  A trial is rejected, like a non-finite value in rule 7, when for a refining camera fx'
+ *      or fy' is not finite, or fx' / fx_in or fy' / fy_in is not strictly inside (focal_lo, focal_hi) (fx_in, fy_in: the input K's).
+ * Input added: refine_focal [n] u8, min_focal_obs, focal_lo, focal_hi.  Output added: K_out [n,3,3] f64 (the input's bits for a camera
+ *   that does not refine; else fx, skew, cx, fy, cy of the final state and the other four entries copied), cam_focal [n] u8, and
+ *   counts[13] = the number of refining cameras.
+ * Status: as above; LOFTR_ERR_BAD_ARG also for min_focal_obs < 1, bounds that are not finite or do not straddle 1, and null
+ *   refine_focal / K_out / cam_focal with n_images > 0.  Workspace: loftr_bundle_adjust_focal_workspace_bytes (about 1100 bytes per image).
+ * Out of scope: intrinsics shared between images (they couple camera blocks, so U stops being block diagonal), principal point and
+ *   distortion, focal refinement of a fixed-pose camera, focal priors.  PARITY UNPINNED against Ceres / COLMAP. */
+int loftr_bundle_adjust_focal_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                   const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                   const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs, double huber_px,
+                                   int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs, double focal_lo,
+                                   double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
+                                   uint8_t* point_active, double* K_out, uint8_t* cam_focal, long* counts);
+size_t loftr_bundle_adjust_focal_workspace_bytes(long T, long N, int n_images);
+int loftr_bundle_adjust_focal(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                              const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                              const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs, double huber_px,
+                              int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs, double focal_lo, double focal_hi,
+                              double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out,
+                              uint8_t* cam_focal, long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches,
+                              void* stream);
 
 /* ---- correspondence table of the images without a pose (csrc/register_core.h holds every per-item step) -------------------
  * The 2D-3D correspondences that the tracks give the images that have no pose yet, gathered per image in a defined order: the input of

@@ -189,7 +189,8 @@ class SfmResult:
     def adjust(self, pts, K, T_cam_from_world, fixed=None, **kwargs):
         """Bundle adjustment of the poses and of the points ``pts`` (a Points3D of ``triangulate`` on this result) over the observations
         the triangulation kept (bundle.bundle_adjust) -> BundleResult on this result's device.  ``fixed`` and the keyword
-        arguments are bundle_adjust's; the intended loop is triangulate -> adjust -> triangulate(K, res.T_cam_from_world)."""
+        arguments are bundle_adjust's; the intended loop is triangulate -> adjust -> triangulate(K, res.T_cam_from_world).  With
+        ``refine_focal`` (True or an [n] mask) the focal lengths are refined as well and the loop goes on with ``res.K``."""
         from .bundle import bundle_adjust
         if pts.offsets is None:
             raise ValueError("SfmResult.adjust: this Points3D carries no tracks (use SfmResult.triangulate)")
@@ -198,6 +199,8 @@ class SfmResult:
         xy = self.keypoints[self.kp_offsets[pts.image] + pts.keypoint]
         if fixed is not None:
             fixed = torch.as_tensor(fixed).to(dev)
+        if kwargs.get("refine_focal") is not None and kwargs["refine_focal"] is not True:
+            kwargs["refine_focal"] = torch.as_tensor(kwargs["refine_focal"]).to(dev)
         return bundle_adjust(pts.offsets, pts.image.to(torch.int32), xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **kwargs)
 
     def to_host(self):

@@ -13,6 +13,12 @@ The rule (include/loftr_hip.h): Levenberg-Marquardt with an optiona
 Schur system, solved by preconditioned conjugate gradients without forming it; every sum has a defined order.  The host routine
 ``loftr_bundle_adjust_host`` defines the result (CPU tensors / numpy arrays run it), the HIP kernels reproduce it bit for bit (GPU
 tensors run them; there is no silent fallback either way).
+
+Where the focal lengths are guesses (internet photos, EXIF), ``refine_focal`` adds one relative focal step per image to its six pose
+parameters (DESIGN §18.1; ``loftr_bundle_adjust_focal_host`` and its kernels); the result then carries ``K``::
+
+    res = sfm.adjust(pts, K, T_cam_from_world, fixed=known, refine_focal=True)
+    pts = sfm.triangulate(res.K, res.T_cam_from_world)
 """
 import numpy as np
 import torch
@@ -20,6 +26,7 @@ import torch
 from . import _tracks, ops
 
 _OUT = ("T_cam_from_world", "xyz", "obs_active", "cam_free", "point_active")
+_OUT_FOCAL = ("K", "cam_focal")
 _ARGS = ("offsets", "obs_image", "obs_xy", "obs_mask", "xyz", "K", "T_cam_from_world")
 
 
@@ -30,12 +37,17 @@ class BundleResult:
     that is not active), ``obs_active [N] bool``, ``cam_free [n] bool``, ``point_active [T] bool``; ``cost_before`` / ``cost_after`` (the
     sum of the loss over the active observations), ``rms_px_before`` / ``rms_px_after`` (root mean squared pixel error over them),
     ``n_iters`` (trials), ``n_accepted``, ``n_pcg`` (conjugate-gradient iterations), ``status`` (a name of ``ops.BUNDLE_STATUS``:
-    converged, max_iters, stalled, nothing_to_adjust); ``stats``: dict of the counts."""
+    converged, max_iters, stalled, nothing_to_adjust); ``stats``: dict of the counts.
+
+    A call with ``refine_focal`` also carries ``K [n,3,3] f64`` (the input's bits for a camera that does not refine its focal),
+    ``cam_focal [n] bool`` and ``stats['n_focal_cameras']``; ``FIELDS`` of that result names them too."""
 
     FIELDS = _OUT
 
     def __init__(self, stats, **tensors):
         self.stats = stats
+        if "K" in tensors:                                               # a call with refine_focal: K and cam_focal as well
+            self.FIELDS = _OUT + _OUT_FOCAL
         for k in self.FIELDS:
             setattr(self, k, tensors[k])
         for k in ("cost_before", "cost_after", "rms_px_before", "rms_px_after", "n_iters", "n_accepted", "n_pcg", "status"):
@@ -49,7 +61,7 @@ class BundleResult:
 
 
 def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed=None, huber_px=0.0, max_iters=30, pcg_iters=30,
-                  pcg_tol=1e-2, ftol=1e-9, timings=None):
+                  pcg_tol=1e-2, ftol=1e-9, timings=None, refine_focal=None, min_focal_obs=20, focal_bounds=(0.5, 2.0)):
     """Refine poses and points over the reprojection error -> ``BundleResult``.
 
     ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``; ``obs_mask [N]`` (bool or integers: which
@@ -62,11 +74,33 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     fix both.  ``huber_px``: 0 for the squared loss, else the Huber radius in pixels.  ``max_iters`` trials at most, each solving its
     step with at most ``pcg_iters`` conjugate-gradient iterations to the relative tolerance ``pcg_tol``; the run stops as converged when
     an accepted trial lowers the cost by no more than ``ftol`` of it.  The active set is decided once, at the start; loop through
-    ``triangulate`` to renew it.  One readback of the 16 counts; bad ``obs_image`` / ``offsets`` raise ValueError."""
+    ``triangulate`` to renew it.  One readback of the 16 counts; bad ``obs_image`` / ``offsets`` raise ValueError.
+
+    ``refine_focal``: ``None`` keeps every ``K`` as given (the call above, unchanged); ``True`` or an ``[n]`` mask lets
+    those images refine one relative focal step each -- fx, skew and fy scale together, cx and cy stay -- next to their pose.  An image
+    refines only if it is free and has at least ``min_focal_obs`` active observations; a trial that takes a focal outside
+    ``focal_bounds = (lo, hi)`` times its input value is rejected.  The result then carries ``K``, ``cam_focal`` and
+    ``stats['n_focal_cameras']``.  Intrinsics shared between images, principal point, distortion and focal priors are not modelled."""
     what = "bundle_adjust"
     args = [offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world]
     params = ops._ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol)
+    focal = None
+    if refine_focal is not None:
+        if not (isinstance(focal_bounds, (tuple, list)) and len(focal_bounds) == 2):
+            raise ValueError(f"{what}: focal_bounds must be a pair (lo, hi), got {focal_bounds!r}")
+        focal = ops._ba_focal_params(what, min_focal_obs, *focal_bounds)
+        if refine_focal is False:
+            raise ValueError(f"{what}: refine_focal must be None, True or an [n] mask")
     gpu = _tracks.one_device(what, _ARGS + ("fixed",), args + ([] if fixed is None else [fixed]))   # ("fixed" is named only when given)
+    if focal is not None and refine_focal is not True:
+        on_gpu = isinstance(refine_focal, torch.Tensor) and refine_focal.is_cuda
+        if on_gpu != gpu or (gpu and refine_focal.device != args[0].device):
+            raise ValueError(f"{what}: refine_focal is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no "
+                             "silent fallback: move it to their device")
+        if not on_gpu:
+            refine_focal = refine_focal.detach().numpy() if isinstance(refine_focal, torch.Tensor) else np.asarray(refine_focal)
+        if tuple(refine_focal.shape) != (len(K),):
+            raise ValueError(f"{what}: refine_focal must be None, True or a mask of shape ({len(K)},), got {tuple(refine_focal.shape)}")
     for n, a in zip(_ARGS[:2], args[:2]):
         _tracks.integers(what, n, a)
     if gpu:
@@ -79,7 +113,11 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             fixed = torch.zeros(n, dtype=torch.bool, device=dev)
             fixed[:1] = True
         fx = (fixed.detach() != 0).to(torch.uint8)
-        out = ops.bundle_adjust(*a, fx, *_tracks.group_by_image(a[1], n), *params, timings=timings)
+        if focal is None:
+            out = ops.bundle_adjust(*a, fx, *_tracks.group_by_image(a[1], n), *params, timings=timings)
+        else:
+            rf = torch.ones(n, dtype=torch.uint8, device=dev) if refine_focal is True else (refine_focal.detach() != 0).to(torch.uint8)
+            out = ops.bundle_adjust_focal(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal, timings=timings)
     else:
         dts = (np.int64, np.int32, np.float32, None, np.float32, np.float64, np.float64)
         host = lambda x: x.detach().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
@@ -93,7 +131,11 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             fx = (host(fixed) != 0).astype(np.uint8)
         if a[0].ndim == 1 and a[1].ndim == 1 and a[5].ndim == 3:         # the errors the kernels report through counts[1]
             _tracks.check_host(what, a[0], a[1], n)
-        out = ops.bundle_adjust_host(*a, fx, *_tracks.group_by_image(a[1], n), *params)
+        if focal is None:
+            out = ops.bundle_adjust_host(*a, fx, *_tracks.group_by_image(a[1], n), *params)
+        else:
+            rf = np.ones(n, np.uint8) if refine_focal is True else (refine_focal != 0).astype(np.uint8)
+            out = ops.bundle_adjust_focal_host(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal)
         out = {k: torch.from_numpy(v) for k, v in out.items()}
     counts = out["counts"].cpu()                                        # the one readback
     reals = counts[8:13].view(torch.float64).tolist()
@@ -105,4 +147,8 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
              "cost_before": reals[0], "cost_after": reals[1], "rms_px_before": reals[2], "rms_px_after": reals[3], "lambda": reals[4]}
     for k in ("obs_active", "cam_free", "point_active"):
         out[k] = out[k].view(torch.bool)
-    return BundleResult(stats, **{k: out[k] for k in _OUT})
+    if focal is None:
+        return BundleResult(stats, **{k: out[k] for k in _OUT})
+    stats["n_focal_cameras"] = counts[13]
+    out["cam_focal"] = out["cam_focal"].view(torch.bool)
+    return BundleResult(stats, **{k: out[k] for k in _OUT + _OUT_FOCAL})

@@ -1,10 +1,12 @@
-// Bundle adjustment of the triangulated model (host code, double precision): Levenberg-Marquardt over camera poses (6 DoF, intrinsics
-// fixed) and points on the pixel reprojection error, optional Huber loss, the point-eliminated Schur system solved by preconditioned
-// conjugate gradients without forming it (the contract is in include/loftr_hip.h).  What Ceres / COLMAP's bundle adjuster is
-// used for after triangulation; neither is in this image, so this is a statement of the published method (Triggs et al., "Bundle
-// Adjustment -- A Modern Synthesis"; Agarwal et al., "Bundle Adjustment in the Large"), NOT of their source.  PARITY UNPINNED against them.
-// This function DEFINES the result: loftr_bundle_adjust (bundle_gpu.hip) reproduces it bit for bit, which is why all the arithmetic and
-// every per-item step live in bundle_core.h and why this file is only the sequence of phases and the order-defined sums.
+// Bundle adjustment of the triangulated model (host code, double precision): Levenberg-Marquardt over camera poses (6 DoF; intrinsics
+// fixed, or with §18.1 one relative focal step per camera) and points on the pixel reprojection error, optional Huber loss, the
+// point-eliminated Schur system solved by preconditioned conjugate gradients without forming it (the contract is in
+// include/loftr_hip.h).  What Ceres / COLMAP's bundle adjuster is used for after triangulation; neither is in this image, so this is a
+// statement of the published method (Triggs et al., "Bundle Adjustment -- A Modern Synthesis"; Agarwal et al., "Bundle Adjustment in
+// the Large"), NOT of their source.  PARITY UNPINNED against them.
+// These functions DEFINE the result: loftr_bundle_adjust / loftr_bundle_adjust_focal (bundle_gpu.hip) reproduce it bit for bit, which is
+// why all the arithmetic and every per-item step live in bundle_core.h and why this file is only the sequence of phases and the
+// order-defined sums.  The sequence is one template on the width M of the camera block: 6 (poses) or 7 (poses and focal).
 #include <stdint.h>
 #include <type_traits>
 #include <vector>
@@ -42,13 +44,11 @@ double osum(const double* v, long count) {
   }
 }
 
-}  // namespace
-
-extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
-                                        const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
-                                        const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters,
-                                        double pcg_tol, double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
-                                        uint8_t* point_active, long* counts) {
+// the argument checks of both entry points -> LOFTR_OK when the run may start (counts are zero then)
+int check_args(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N, const float* xyz,
+               const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images, const long* cam_offsets,
+               const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol, double* T_out, float* xyz_out,
+               uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, long* counts) {
   if (!offsets || !cam_offsets || !counts || T < 0 || N < 0 || n_images < 0) return LOFTR_ERR_BAD_ARG;
   if (T > 0 && (!xyz || !xyz_out || !point_active)) return LOFTR_ERR_BAD_ARG;
   if (N > 0 && (!obs_image || !obs_xy || !obs_mask || !obs_active || !cam_obs)) return LOFTR_ERR_BAD_ARG;
@@ -59,17 +59,25 @@ extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* 
   for (int i = 0; i < kCounts; ++i) counts[i] = 0;
   if (T == 0 && N > 0) return LOFTR_ERR_BAD_ARG;
   if (n_images == 0 && N > 0) return LOFTR_ERR_BAD_ARG;
-  Ctx c{};
-  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
-  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
-  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
-  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
-  std::vector<char> ws(layout(c, nullptr), 0);
-  layout(c, ws.data());
+  return LOFTR_OK;
+}
+
+// the sequence of phases; c holds the problem and the result
+template <int M> int run(CtxT<M>& c, int max_iters, int pcg_iters) {
+  constexpr int kU = kTri<M>;
+  const long T = c.T, n = c.n;
+  const long* cam_offsets = c.cam_offsets;
+  const int* cam_obs = c.cam_obs;
+  const uint8_t *fixed = c.fixed, *obs_active = c.obs_active;
+  uint8_t* cam_free = c.cam_free;
+  std::vector<char> ws(layout<M>(c, nullptr), 0);
+  layout<M>(c, ws.data());
   Ctrl& s = *c.ctrl;
-  const long n = n_images;
   ctrl_init(c);
-  for (long i = 0; i < n; ++i) cam_setup(c, i);
+  for (long i = 0; i < n; ++i) {
+    cam_setup(c, i);
+    if constexpr (M == 7) cam_setup_focal(c, i);
+  }
   for (long t = 0; t < T; ++t) {
     long cnt;
     s.err |= track_setup(c, t, &cnt);
@@ -78,6 +86,7 @@ extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* 
   }
   if (s.err) return LOFTR_ERR_BAD_ARG;
   for (long i = 0; i < n; ++i) {
+    if constexpr (M == 7) c.cam_focal[i] = 0;
     long b, e, cnt = 0;
     if (!group_range(c, i, &b, &e)) { s.err |= kBadGroups; continue; }
     for (long k = b; k < e; ++k) {
@@ -87,14 +96,18 @@ extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* 
     }
     cam_free[i] = (uint8_t)(!fixed[i] && c.cam_valid[i] && cnt >= 1);
     s.n_free += cam_free[i];
+    if constexpr (M == 7) {
+      c.cam_focal[i] = (uint8_t)cam_focal_rule(c, i, cam_free[i] != 0, cnt);
+      s.n_focal += c.cam_focal[i];
+    }
   }
   if (s.err) return LOFTR_ERR_BAD_ARG;
 
   // a camera's osum64: element l is slot l of its list; an inactive slot adds nothing
   auto cam_sum = [&](long i, auto tag, auto term, double* out) {
-    constexpr int M = decltype(tag)::value;
+    constexpr int W = decltype(tag)::value;
     const long b = cam_offsets[i];
-    osum64<M>(cam_offsets[i + 1] - b, [&](long e, double* a) { const long o = cam_obs[b + e]; if (obs_active[o]) term(o, a); }, out);
+    osum64<W>(cam_offsets[i + 1] - b, [&](long e, double* a) { const long o = cam_obs[b + e]; if (obs_active[o]) term(o, a); }, out);
   };
   auto evaluate = [&](int buf) {
     bool ok = true;
@@ -108,41 +121,42 @@ extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* 
   for (int it = 0; it < max_iters && !s.done; ++it) {
     const int cur = s.cur;
     if (s.fresh) {
-      for (long t = 0; t < T; ++t) track_lin(c, cur, t);
+      for (long t = 0; t < T; ++t) track_lin<M>(c, cur, t);
       for (long i = 0; i < n; ++i) {
         if (!cam_free[i]) continue;
-        double a[27];
-        cam_sum(i, std::integral_constant<int, 27>{}, [&](long o, double* acc) { cam_lin_term(c, cur, o, acc); }, a);
-        for (int k = 0; k < 21; ++k) c.U[21 * i + k] = a[k];
-        for (int k = 0; k < 6; ++k) c.gc[6 * i + k] = a[21 + k];
+        double a[kU + M];
+        cam_sum(i, std::integral_constant<int, kU + M>{}, [&](long o, double* acc) { cam_lin_term<M>(c, cur, o, acc); }, a);
+        for (int k = 0; k < kU; ++k) c.U[kU * i + k] = a[k];
+        for (int k = 0; k < M; ++k) c.gc[M * i + k] = a[kU + k];
       }
     }
     const double lambda = s.lambda;
     for (long t = 0; t < T; ++t) if (!track_factor(c, t, lambda)) s.bad_f = 1;
-    for (long i = 0; i < n; ++i) if (!cam_factor(c, i, lambda)) s.bad_f = 1;
+    for (long i = 0; i < n; ++i) if (!cam_factor<M>(c, i, lambda)) s.bad_f = 1;
     auto camera_half = [&](int mode) {
       for (long i = 0; i < n; ++i) {
-        double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (cam_free[i]) cam_sum(i, std::integral_constant<int, 6>{}, [&](long o, double* acc) { cam_half_term(c, cur, o, acc); }, a);
-        cam_half_finish(c, i, mode, lambda, a);
+        double a[M];
+        for (int k = 0; k < M; ++k) a[k] = 0.0;
+        if (cam_free[i]) cam_sum(i, std::integral_constant<int, M>{}, [&](long o, double* acc) { cam_half_term<M>(c, cur, o, acc); }, a);
+        cam_half_finish<M>(c, i, mode, lambda, a);
       }
     };
     if (!s.bad_f) {
-      for (long t = 0; t < T; ++t) track_half(c, cur, t, 0, nullptr);
+      for (long t = 0; t < T; ++t) track_half<M>(c, cur, t, 0, nullptr);
       camera_half(0);
       ctrl_feed(c, kActRz0, osum(c.part, n));
       for (int pi = 0; pi < pcg_iters && !s.pcg_done; ++pi) {
-        for (long t = 0; t < T; ++t) track_half(c, cur, t, 1, c.p);
+        for (long t = 0; t < T; ++t) track_half<M>(c, cur, t, 1, c.p);
         camera_half(1);
         ctrl_feed(c, kActPsp, osum(c.part, n));
         if (s.pcg_done) break;
-        for (long i = 0; i < n; ++i) cam_update1(c, i, s.alpha);
+        for (long i = 0; i < n; ++i) cam_update1<M>(c, i, s.alpha);
         ctrl_feed(c, kActRz, osum(c.part, n));
         if (s.pcg_done) break;
-        for (long i = 0; i < n; ++i) cam_update2(c, i, s.beta);
+        for (long i = 0; i < n; ++i) cam_update2<M>(c, i, s.beta);
       }
-      for (long i = 0; i < n; ++i) if (!cam_apply(c, cur, i)) s.bad_a = 1;
-      for (long t = 0; t < T; ++t) if (!track_half(c, cur, t, 2, c.x)) s.bad_a = 1;
+      for (long i = 0; i < n; ++i) if (!cam_apply<M>(c, cur, i)) s.bad_a = 1;
+      for (long t = 0; t < T; ++t) if (!track_half<M>(c, cur, t, 2, c.x)) s.bad_a = 1;
     }
     if (!s.bad_f && !s.bad_a) {
       if (!evaluate(1 - cur)) s.bad_e = 1;
@@ -153,8 +167,47 @@ extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* 
     }
     ctrl_accept(c);
   }
-  for (long i = 0; i < n; ++i) cam_write(c, s.cur, i);
+  for (long i = 0; i < n; ++i) cam_write<M>(c, s.cur, i);
   for (long t = 0; t < T; ++t) track_write(c, s.cur, t);
-  ctrl_write(c);
+  ctrl_write<M>(c);
   return LOFTR_OK;
+}
+
+}  // namespace
+
+extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                        const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
+                                        const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters,
+                                        double pcg_tol, double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
+                                        uint8_t* point_active, long* counts) {
+  const int st = check_args(offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs,
+                            huber_px, max_iters, pcg_iters, pcg_tol, ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts);
+  if (st != LOFTR_OK) return st;
+  Ctx c{};
+  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
+  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
+  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
+  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+  return run<6>(c, max_iters, pcg_iters);
+}
+
+extern "C" int loftr_bundle_adjust_focal_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
+                                              long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                              const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                              double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs,
+                                              double focal_lo, double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
+                                              uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, long* counts) {
+  if (n_images > 0 && (!refine_focal || !K_out || !cam_focal)) return LOFTR_ERR_BAD_ARG;
+  if (!(min_focal_obs >= 1 && fin(focal_lo) && fin(focal_hi) && focal_lo < 1.0 && 1.0 < focal_hi)) return LOFTR_ERR_BAD_ARG;
+  const int st = check_args(offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs,
+                            huber_px, max_iters, pcg_iters, pcg_tol, ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts);
+  if (st != LOFTR_OK) return st;
+  Ctx7 c{};
+  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
+  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
+  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
+  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+  c.refine_focal = refine_focal; c.min_focal_obs = min_focal_obs; c.focal_lo = focal_lo; c.focal_hi = focal_hi;
+  c.K_out = K_out; c.cam_focal = cam_focal;
+  return run<7>(c, max_iters, pcg_iters);
 }

@@ -35,7 +35,7 @@ BA_HD bool fin(double x) { return fabs(x) <= 1.7976931348623157e308; }        //
 
 // what one thread owns: damping, counters, flags and the scalars of the conjugate gradients
 struct Ctrl {
-  int done, err, bad_f, bad_a, bad_e, pcg_done, fresh, cur, status, n_iters, n_accepted, pad;   // bad_*: raised in the factor / apply / evaluate phase
+  int done, err, bad_f, bad_a, bad_e, pcg_done, fresh, cur, status, n_iters, n_accepted, n_focal;   // bad_*: raised in the factor / apply / evaluate phase
   long long n_pcg;
   unsigned long long n_active_obs, n_active_pts, n_free;
   double lambda, cost, sq, cost_t, sq_t, cost0, sq0, rz, rz0, psp, alpha, beta;
@@ -53,25 +53,36 @@ struct Ctx {
   // the workspace (layout(): the same on both sides)
   double *tab, *quat, *X;                   // [2][n][17], [2][n][4], [2][T][3]: the state and the trial, told apart by ctrl->cur
   double *V, *gp, *Vf, *z;                  // [T][6] sum B^T B, [T][3] sum B^T r, [T][6] factor of the damped V, [T][3] track half
-  double *U, *gc, *Uf;                      // [n][21] sum A^T A, [n][6] sum A^T r, [n][21] factor of the damped U
-  double *x, *r, *zc, *p, *Sp;              // [n][6] each: conjugate gradients over the cameras
+  double *U, *gc, *Uf;                      // [n][21] sum A^T A, [n][6] sum A^T r, [n][21] factor of the damped U  (28, 7, 28 when M = 7)
+  double *x, *r, *zc, *p, *Sp;              // [n][M] each: conjugate gradients over the cameras
   double *part, *part2, *red;               // [max(T, n)] x 2 terms of an osum, [2][ceil(max / 4096)] its chunk sums
   int* obs_track;                           // [N]
   uint8_t* cam_valid;                       // [n]
   Ctrl* ctrl;
 };
 
+// §18.1, focal refinement: the camera block is M = 7 wide (the seventh parameter is the relative focal step) and the problem carries the
+// extra inputs and outputs.  Every step that touches the camera block is a template on M; M = 6 is the fixed-intrinsics rule.
+struct Ctx7 : Ctx {
+  const uint8_t* refine_focal; int min_focal_obs; double focal_lo, focal_hi;
+  double* K_out; uint8_t* cam_focal;
+};
+template <int M> struct CtxOf { using type = Ctx; };
+template <> struct CtxOf<7> { using type = Ctx7; };
+template <int M> using CtxT = typename CtxOf<M>::type;
+template <int M> constexpr int kTri = M * (M + 1) / 2;      // entries of the upper triangle of a camera block: 21 or 28
+
 // carves the workspace; base may be null (then only the size counts) -> bytes
-inline size_t layout(Ctx& c, char* base) {
+template <int M> inline size_t layout(Ctx& c, char* base) {
   const size_t T = (size_t)c.T, n = (size_t)c.n, N = (size_t)c.N, m = (T > n ? T : n) + 1, ch = (m + kChunk - 1) / kChunk;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = tracks::carve(&off, bytes ? bytes : 1); return base ? base + at : nullptr; };
   c.ctrl = (Ctrl*)take(sizeof(Ctrl));
   c.tab = (double*)take(8 * 2 * n * kTab); c.quat = (double*)take(8 * 2 * n * 4); c.X = (double*)take(8 * 2 * T * 3);
   c.V = (double*)take(8 * T * 6); c.gp = (double*)take(8 * T * 3); c.Vf = (double*)take(8 * T * 6); c.z = (double*)take(8 * T * 3);
-  c.U = (double*)take(8 * n * 21); c.gc = (double*)take(8 * n * 6); c.Uf = (double*)take(8 * n * 21);
-  c.x = (double*)take(8 * n * 6); c.r = (double*)take(8 * n * 6); c.zc = (double*)take(8 * n * 6); c.p = (double*)take(8 * n * 6);
-  c.Sp = (double*)take(8 * n * 6);
+  c.U = (double*)take(8 * n * kTri<M>); c.gc = (double*)take(8 * n * M); c.Uf = (double*)take(8 * n * kTri<M>);
+  c.x = (double*)take(8 * n * M); c.r = (double*)take(8 * n * M); c.zc = (double*)take(8 * n * M); c.p = (double*)take(8 * n * M);
+  c.Sp = (double*)take(8 * n * M);
   c.part = (double*)take(8 * m); c.part2 = (double*)take(8 * m); c.red = (double*)take(8 * 2 * ch);
   c.obs_track = (int*)take(4 * N); c.cam_valid = (uint8_t*)take(n);
   return off;
@@ -134,6 +145,17 @@ BA_HD void cam_setup(const Ctx& c, long i) {
   for (int k = 0; k < 16; ++k) dst[k] = src[k];
 }
 
+// ... and with focal refinement: the output intrinsics start as the input's bits
+BA_HD void cam_setup_focal(const Ctx7& c, long i) {
+  const uint64_t* src = (const uint64_t*)(c.K + 9 * i);
+  uint64_t* dst = (uint64_t*)(c.K_out + 9 * i);
+  for (int k = 0; k < 9; ++k) dst[k] = src[k];
+}
+// phase "camera groups", the last step of a camera with cnt active observations: does it refine its focal?
+BA_HD bool cam_focal_rule(const Ctx7& c, long i, bool is_free, long cnt) {
+  return is_free && c.refine_focal[i] != 0 && cnt >= (long)c.min_focal_obs;
+}
+
 // ---- rule 3: residual and Jacobians ----------------------------------------------------------------------------------------------------
 // P = R X, Y = P + t -> Y_z > 0
 BA_HD bool transform(const double* cam, const double* X, double* P, double* Y) {
@@ -158,28 +180,39 @@ BA_HD void loss(const double* r, double huber, double* sw, double* rho, double* 
   }
   *sw = 1.0; *rho = s;
 }
-// A [2,6] = sw dr/d(omega, dt), B [2,3] = sw dr/dX
-BA_HD void jacobians(const double* cam, const double* P, const double* Y, double sw, double* A, double* B) {
+// A [2,M] = sw dr/d(omega, dt[, delta]), B [2,3] = sw dr/dX.  M = 7: the last column is sw (fx a + skew b, fy b) for a camera that
+// refines its focal (`focal`) and zero for any other.
+template <int M> BA_HD void jacobians(const double* cam, const double* P, const double* Y, double sw, bool focal, double* A, double* B) {
   const double fx = cam[12], sk = cam[13], fy = cam[15];
   const double du[3] = {sw * (fx / Y[2]), sw * (sk / Y[2]), sw * -(((fx * Y[0] + sk * Y[1]) / Y[2]) / Y[2])};
   const double dv[3] = {0.0, sw * (fy / Y[2]), sw * -(((fy * Y[1]) / Y[2]) / Y[2])};
   A[0] = du[2] * P[1] - du[1] * P[2]; A[1] = du[0] * P[2] - du[2] * P[0]; A[2] = du[1] * P[0] - du[0] * P[1];
   A[3] = du[0]; A[4] = du[1]; A[5] = du[2];
-  A[6] = dv[2] * P[1] - dv[1] * P[2]; A[7] = -(dv[2] * P[0]); A[8] = dv[1] * P[0];
-  A[9] = 0.0; A[10] = dv[1]; A[11] = dv[2];
+  A[M] = dv[2] * P[1] - dv[1] * P[2]; A[M + 1] = -(dv[2] * P[0]); A[M + 2] = dv[1] * P[0];
+  A[M + 3] = 0.0; A[M + 4] = dv[1]; A[M + 5] = dv[2];
+  if constexpr (M == 7) {
+    if (focal) {
+      const double a = Y[0] / Y[2], b = Y[1] / Y[2];
+      A[6] = sw * (fx * a + sk * b); A[M + 6] = sw * (fy * b);
+    } else {
+      A[6] = 0.0; A[M + 6] = 0.0;
+    }
+  }
   for (int k = 0; k < 3; ++k) {
     B[k] = (du[0] * cam[k] + du[1] * cam[3 + k]) + du[2] * cam[6 + k];
     B[3 + k] = dv[1] * cam[3 + k] + dv[2] * cam[6 + k];
   }
 }
 // the weighted A, B and residual rs of observation o of track t at state `buf`
-BA_HD void obs_terms(const Ctx& c, int buf, long o, long t, double* A, double* B, double* rs) {
+template <int M> BA_HD void obs_terms(const CtxT<M>& c, int buf, long o, long t, double* A, double* B, double* rs) {
   const double *cam = tab_of(c, buf, c.image[o]), *X = X_of(c, buf, t);
+  bool focal = false;
+  if constexpr (M == 7) focal = c.cam_focal[c.image[o]] != 0;
   double P[3], Y[3], r[2], sw, rho, sq;
   transform(cam, X, P, Y);
   residual(cam, Y, (double)c.xy[2 * o], (double)c.xy[2 * o + 1], r);
   loss(r, c.huber, &sw, &rho, &sq);
-  jacobians(cam, P, Y, sw, A, B);
+  jacobians<M>(cam, P, Y, sw, focal, A, B);
   rs[0] = sw * r[0]; rs[1] = sw * r[1];
 }
 
@@ -280,22 +313,22 @@ template <int M> BA_HD void solve(const double* f, const double* b, double* x) {
 #pragma unroll
   for (int i = 0; i < M; ++i) x[i] = y[i];
 }
-BA_HD double dot6(const double* a, const double* b) {
+template <int M> BA_HD double dotm(const double* a, const double* b) {
   double s = a[0] * b[0];
 #pragma unroll
-  for (int k = 1; k < 6; ++k) s = s + a[k] * b[k];
+  for (int k = 1; k < M; ++k) s = s + a[k] * b[k];
   return s;
 }
 
 // ---- rule 5: the sums ----------------------------------------------------------------------------------------------------------------
 // phase "linearise tracks", per track: V = sum B^T B (upper triangle), gp = sum B^T rs, sequentially over the active observations
-BA_HD void track_lin(const Ctx& c, int buf, long t) {
+template <int M> BA_HD void track_lin(const CtxT<M>& c, int buf, long t) {
   double V[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
   if (c.point_active[t])
     for (long o = c.offsets[t]; o < c.offsets[t + 1]; ++o) {
       if (!c.obs_active[o]) continue;
-      double A[12], B[6], rs[2];
-      obs_terms(c, buf, o, t, A, B, rs);
+      double A[2 * M], B[6], rs[2];
+      obs_terms<M>(c, buf, o, t, A, B, rs);
       V[0] = V[0] + (B[0] * B[0] + B[3] * B[3]); V[1] = V[1] + (B[0] * B[1] + B[3] * B[4]); V[2] = V[2] + (B[0] * B[2] + B[3] * B[5]);
       V[3] = V[3] + (B[1] * B[1] + B[4] * B[4]); V[4] = V[4] + (B[1] * B[2] + B[4] * B[5]); V[5] = V[5] + (B[2] * B[2] + B[5] * B[5]);
       for (int k = 0; k < 3; ++k) g[k] = g[k] + (B[k] * rs[0] + B[3 + k] * rs[1]);
@@ -304,16 +337,17 @@ BA_HD void track_lin(const Ctx& c, int buf, long t) {
   for (int k = 0; k < 3; ++k) c.gp[3 * t + k] = g[k];
 }
 // phase "linearise cameras", one element of a camera's osum64: a [27] += (A^T A upper triangle [21], A^T rs [6]) of observation o
-BA_HD void cam_lin_term(const Ctx& c, int buf, long o, double* a) {
-  double A[12], B[6], rs[2];
-  obs_terms(c, buf, o, c.obs_track[o], A, B, rs);
+// (a [35], 28 and 7 when M = 7)
+template <int M> BA_HD void cam_lin_term(const CtxT<M>& c, int buf, long o, double* a) {
+  double A[2 * M], B[6], rs[2];
+  obs_terms<M>(c, buf, o, c.obs_track[o], A, B, rs);
   int m = 0;
 #pragma unroll
-  for (int i = 0; i < 6; ++i)
+  for (int i = 0; i < M; ++i)
 #pragma unroll
-    for (int j = i; j < 6; ++j) { a[m] = a[m] + (A[i] * A[j] + A[6 + i] * A[6 + j]); ++m; }
+    for (int j = i; j < M; ++j) { a[m] = a[m] + (A[i] * A[j] + A[M + i] * A[M + j]); ++m; }
 #pragma unroll
-  for (int i = 0; i < 6; ++i) a[21 + i] = a[21 + i] + (A[i] * rs[0] + A[6 + i] * rs[1]);
+  for (int i = 0; i < M; ++i) a[kTri<M> + i] = a[kTri<M> + i] + (A[i] * rs[0] + A[M + i] * rs[1]);
 }
 
 // ---- rule 6: the step ------------------------------------------------------------------------------------------------------------------
@@ -325,27 +359,27 @@ BA_HD bool track_factor(const Ctx& c, long t, double lambda) {
   for (int k = 0; k < 6; ++k) c.Vf[6 * t + k] = f[k];
   return ok;
 }
-BA_HD bool cam_factor(const Ctx& c, long i, double lambda) {
+template <int M> BA_HD bool cam_factor(const Ctx& c, long i, double lambda) {
   if (!c.cam_free[i]) return true;
-  double f[21];
-  const bool ok = factor<6>(c.U + 21 * i, lambda, f);
+  double f[kTri<M>];
+  const bool ok = factor<M>(c.U + kTri<M> * i, lambda, f);
 #pragma unroll
-  for (int k = 0; k < 21; ++k) c.Uf[21 * i + k] = f[k];
+  for (int k = 0; k < kTri<M>; ++k) c.Uf[kTri<M> * i + k] = f[k];
   return ok;
 }
 // phase "track half", per track.  mode 0: z = Vd^-1 gp.  mode 1: z = Vd^-1 sum B^T (A vec_c) over the active observations of free
 // cameras, sequentially.  mode 2 (back substitution): dX = Vd^-1 (-(gp + sum B^T (A vec_c))), trial X' = X + dX -> false when not finite.
-BA_HD bool track_half(const Ctx& c, int buf, long t, int mode, const double* vec) {
+template <int M> BA_HD bool track_half(const CtxT<M>& c, int buf, long t, int mode, const double* vec) {
   if (!c.point_active[t]) return true;
   double s[3] = {0.0, 0.0, 0.0}, z[3];
   if (mode != 0)
     for (long o = c.offsets[t]; o < c.offsets[t + 1]; ++o) {
       const int im = c.image[o];
       if (!c.obs_active[o] || !c.cam_free[im]) continue;
-      double A[12], B[6], rs[2];
-      obs_terms(c, buf, o, t, A, B, rs);
-      const double* v = vec + 6 * (long)im;
-      const double eu = dot6(A, v), ev = dot6(A + 6, v);
+      double A[2 * M], B[6], rs[2];
+      obs_terms<M>(c, buf, o, t, A, B, rs);
+      const double* v = vec + M * (long)im;
+      const double eu = dotm<M>(A, v), ev = dotm<M>(A + M, v);
       for (int k = 0; k < 3; ++k) s[k] = s[k] + (B[k] * eu + B[3 + k] * ev);
     }
   if (mode == 0) for (int k = 0; k < 3; ++k) s[k] = c.gp[3 * t + k];
@@ -364,74 +398,76 @@ BA_HD bool track_half(const Ctx& c, int buf, long t, int mode, const double* vec
   return ok;
 }
 // phase "camera half", one element of a camera's osum64: a [6] += A^T (B z_j) of observation o
-BA_HD void cam_half_term(const Ctx& c, int buf, long o, double* a) {
-  double A[12], B[6], rs[2];
+template <int M> BA_HD void cam_half_term(const CtxT<M>& c, int buf, long o, double* a) {
+  double A[2 * M], B[6], rs[2];
   const long t = c.obs_track[o];
-  obs_terms(c, buf, o, t, A, B, rs);
+  obs_terms<M>(c, buf, o, t, A, B, rs);
   const double* z = c.z + 3 * t;
   const double eu = (B[0] * z[0] + B[1] * z[1]) + B[2] * z[2], ev = (B[3] * z[0] + B[4] * z[1]) + B[5] * z[2];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) a[k] = a[k] + (A[k] * eu + A[6 + k] * ev);
+  for (int k = 0; k < M; ++k) a[k] = a[k] + (A[k] * eu + A[M + k] * ev);
 }
 // ... and what follows the sum a [6] of free camera i.  mode 0 (right-hand side): b = -(gc - a); x = 0, r = b, zc = M^-1 r, p = zc,
 // part = r . zc.  mode 1: Sp = Ud p - a, part = p . Sp.  A camera that is not free has part = +0.
-BA_HD void cam_half_finish(const Ctx& c, long i, int mode, double lambda, const double* a) {
+template <int M> BA_HD void cam_half_finish(const Ctx& c, long i, int mode, double lambda, const double* a) {
   if (!c.cam_free[i]) { c.part[i] = 0.0; return; }
-  double *x = c.x + 6 * i, *r = c.r + 6 * i, *zc = c.zc + 6 * i, *p = c.p + 6 * i, *Sp = c.Sp + 6 * i;
+  double *x = c.x + M * i, *r = c.r + M * i, *zc = c.zc + M * i, *p = c.p + M * i, *Sp = c.Sp + M * i;
   if (mode == 0) {
-    double b[6], zz[6];
+    double b[M], zz[M];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) { b[k] = -(c.gc[6 * i + k] - a[k]); x[k] = 0.0; r[k] = b[k]; }
-    solve<6>(c.Uf + 21 * i, b, zz);
+    for (int k = 0; k < M; ++k) { b[k] = -(c.gc[M * i + k] - a[k]); x[k] = 0.0; r[k] = b[k]; }
+    solve<M>(c.Uf + kTri<M> * i, b, zz);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) { zc[k] = zz[k]; p[k] = zz[k]; }
-    c.part[i] = dot6(b, zz);
+    for (int k = 0; k < M; ++k) { zc[k] = zz[k]; p[k] = zz[k]; }
+    c.part[i] = dotm<M>(b, zz);
     return;
   }
-  const double* U = c.U + 21 * i;
-  double pv[6], sp[6];
+  const double* U = c.U + kTri<M> * i;
+  double pv[M], sp[M];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) pv[k] = p[k];
+  for (int k = 0; k < M; ++k) pv[k] = p[k];
 #pragma unroll
-  for (int row = 0; row < 6; ++row) {
+  for (int row = 0; row < M; ++row) {
     double s = 0.0;
 #pragma unroll
-    for (int col = 0; col < 6; ++col) {
+    for (int col = 0; col < M; ++col) {
       const int lo = row < col ? row : col, hi = row < col ? col : row;
-      const double u = U[lo * 6 - lo * (lo - 1) / 2 + (hi - lo)];
+      const double u = U[lo * M - lo * (lo - 1) / 2 + (hi - lo)];
       s = s + (row == col ? damped(u, lambda) : u) * pv[col];
     }
     sp[row] = s - a[row];
     Sp[row] = sp[row];
   }
-  c.part[i] = dot6(pv, sp);
+  c.part[i] = dotm<M>(pv, sp);
 }
 // phase "update 1", per free camera: x += alpha p, r -= alpha Sp, zc = M^-1 r, part = r . zc
-BA_HD void cam_update1(const Ctx& c, long i, double alpha) {
+template <int M> BA_HD void cam_update1(const Ctx& c, long i, double alpha) {
   if (!c.cam_free[i]) { c.part[i] = 0.0; return; }
-  double r[6], zz[6];
+  double r[M], zz[M];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    c.x[6 * i + k] = c.x[6 * i + k] + alpha * c.p[6 * i + k];
-    r[k] = c.r[6 * i + k] - alpha * c.Sp[6 * i + k];
-    c.r[6 * i + k] = r[k];
+  for (int k = 0; k < M; ++k) {
+    c.x[M * i + k] = c.x[M * i + k] + alpha * c.p[M * i + k];
+    r[k] = c.r[M * i + k] - alpha * c.Sp[M * i + k];
+    c.r[M * i + k] = r[k];
   }
-  solve<6>(c.Uf + 21 * i, r, zz);
+  solve<M>(c.Uf + kTri<M> * i, r, zz);
 #pragma unroll
-  for (int k = 0; k < 6; ++k) c.zc[6 * i + k] = zz[k];
-  c.part[i] = dot6(r, zz);
+  for (int k = 0; k < M; ++k) c.zc[M * i + k] = zz[k];
+  c.part[i] = dotm<M>(r, zz);
 }
 // phase "update 2", per free camera: p = zc + beta p
-BA_HD void cam_update2(const Ctx& c, long i, double beta) {
+template <int M> BA_HD void cam_update2(const Ctx& c, long i, double beta) {
   if (!c.cam_free[i]) return;
-  for (int k = 0; k < 6; ++k) c.p[6 * i + k] = c.zc[6 * i + k] + beta * c.p[6 * i + k];
+  for (int k = 0; k < M; ++k) c.p[M * i + k] = c.zc[M * i + k] + beta * c.p[M * i + k];
 }
 
 // ---- rule 7: the trial -----------------------------------------------------------------------------------------------------------------
 // phase "apply", per free camera: q' = normalise((1, omega / 2) (x) q), t' = t + dt into the other state -> false when not finite
-BA_HD bool cam_apply(const Ctx& c, int buf, long i) {
+// M = 7, a camera that refines its focal: fx' = fx (1 + delta), skew' = skew (1 + delta), fy' = fy (1 + delta) -> false as well when
+// fx' or fy' is not finite or fx' / fx_in or fy' / fy_in is not strictly inside (focal_lo, focal_hi); a NaN fails every test
+template <int M> BA_HD bool cam_apply(const CtxT<M>& c, int buf, long i) {
   if (!c.cam_free[i]) return true;
-  const double *d = c.x + 6 * i, *q = quat_of(c, buf, i), *tab = tab_of(c, buf, i);
+  const double *d = c.x + M * i,*q = quat_of(c, buf, i), *tab = tab_of(c, buf, i);
   double *q2 = quat_of(c, 1 - buf, i), *tab2 = tab_of(c, 1 - buf, i);
   const double a = 0.5 * d[0], b = 0.5 * d[1], e = 0.5 * d[2];
   double w = ((q[0] - a * q[1]) - b * q[2]) - e * q[3];
@@ -448,6 +484,15 @@ BA_HD bool cam_apply(const Ctx& c, int buf, long i) {
   for (int k = 0; k < 3; ++k) {
     tab2[9 + k] = tab[9 + k] + d[3 + k];
     ok = ok && fin(tab2[9 + k]);
+  }
+  if constexpr (M == 7) {
+    if (c.cam_focal[i]) {
+      const double s = 1.0 + d[6];
+      const double fx = tab[12] * s, sk = tab[13] * s, fy = tab[15] * s;
+      tab2[12] = fx; tab2[13] = sk; tab2[15] = fy;
+      const double rx = fx / c.K[9 * i], ry = fy / c.K[9 * i + 4];
+      ok = ok && fin(fx) && fin(fy) && rx > c.focal_lo && rx < c.focal_hi && ry > c.focal_lo && ry < c.focal_hi;
+    }
   }
   return ok;
 }
@@ -475,7 +520,7 @@ BA_HD bool track_eval(const Ctx& c, int buf, long t) {
 // ---- the single steps (one thread) -----------------------------------------------------------------------------------------------------
 BA_HD void ctrl_init(const Ctx& c) {
   Ctrl& s = *c.ctrl;
-  s.done = s.err = s.bad_f = s.bad_a = s.bad_e = s.pcg_done = s.cur = s.n_iters = s.n_accepted = s.pad = 0;
+  s.done = s.err = s.bad_f = s.bad_a = s.bad_e = s.pcg_done = s.cur = s.n_iters = s.n_accepted = s.n_focal = 0;
   s.fresh = 1;
   s.status = kMaxIters;
   s.n_pcg = 0;
@@ -522,7 +567,7 @@ BA_HD void ctrl_accept(const Ctx& c) {
   s.pcg_done = 0;
 }
 // phase "write": the outputs of a free camera / an active point from the final state
-BA_HD void cam_write(const Ctx& c, int buf, long i) {
+template <int M> BA_HD void cam_write(const CtxT<M>& c, int buf, long i) {
   if (!c.cam_free[i]) return;
   const double* tab = tab_of(c, buf, i);
   double* T = c.T_out + 16 * i;
@@ -531,13 +576,19 @@ BA_HD void cam_write(const Ctx& c, int buf, long i) {
     T[4 * r + 3] = tab[9 + r];
   }
   T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
+  if constexpr (M == 7) {
+    if (c.cam_focal[i]) {                    // the other four entries keep the input's bits (cam_setup_focal)
+      double* K = c.K_out + 9 * i;
+      K[0] = tab[12]; K[1] = tab[13]; K[2] = tab[14]; K[4] = tab[15]; K[5] = tab[16];
+    }
+  }
 }
 BA_HD void track_write(const Ctx& c, int buf, long t) {
   if (!c.point_active[t]) return;
   for (int k = 0; k < 3; ++k) c.xyz_out[3 * t + k] = (float)X_of(c, buf, t)[k];
 }
 BA_HD long bits_of(double v) { union { double d; long l; } u; u.d = v; return u.l; }
-BA_HD void ctrl_write(const Ctx& c) {
+template <int M> BA_HD void ctrl_write(const Ctx& c) {
   const Ctrl& s = *c.ctrl;
   long* k = c.counts;
   const double na = (double)s.n_active_obs;
@@ -546,6 +597,7 @@ BA_HD void ctrl_write(const Ctx& c) {
   k[8] = bits_of(s.cost0); k[9] = bits_of(s.cost);
   k[10] = bits_of(s.n_active_obs ? sqrt(s.sq0 / na) : 0.0); k[11] = bits_of(s.n_active_obs ? sqrt(s.sq / na) : 0.0);
   k[12] = bits_of(s.lambda); k[13] = 0; k[14] = 0; k[15] = 0;
+  if constexpr (M == 7) k[13] = s.n_focal;   // cameras that refine their focal
 }
 
 }  // namespace ba

@@ -56,9 +56,12 @@ template <int M, class F> __device__ __forceinline__ void wave_osum64(const Ctx&
 __global__ void ba_init_kernel(Ctx c) { ctrl_init(c); }
 
 // grid ceil(n / 256) x 256
-__global__ void __launch_bounds__(kThreads) ba_cam_setup_kernel(Ctx c) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_cam_setup_kernel(CtxT<M> c) {
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i < c.n) cam_setup(c, i);
+  if (i < c.n) {
+    cam_setup(c, i);
+    if constexpr (M == 7) cam_setup_focal(c, i);
+  }
 }
 
 // grid ceil(T / 256) x 256
@@ -82,7 +85,7 @@ __global__ void __launch_bounds__(kThreads) ba_track_setup_kernel(Ctx c) {
 }
 
 // a wave per camera, grid ceil(n / 4) x 256.  Reads the observation arrays only through checked indices, so it needs no flag.
-__global__ void __launch_bounds__(kThreads) ba_groups_kernel(Ctx c) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_groups_kernel(CtxT<M> c) {
   const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
   const int lane = threadIdx.x % 64;
   if (i >= c.n) return;
@@ -100,6 +103,11 @@ __global__ void __launch_bounds__(kThreads) ba_groups_kernel(Ctx c) {
     c.cam_free[i] = (uint8_t)fr;
     if (fr) atomicAdd(&c.ctrl->n_free, 1ull);
     if (err) atomicOr(&c.ctrl->err, err);
+    if constexpr (M == 7) {
+      const bool fo = cam_focal_rule(c, i, fr, cnt);
+      c.cam_focal[i] = (uint8_t)fo;
+      if (fo) atomicAdd(&c.ctrl->n_focal, 1);
+    }
   }
 }
 
@@ -127,103 +135,97 @@ __global__ void __launch_bounds__(64) ba_osum_kernel(Ctx c, const double* in, lo
   }
 }
 
-__global__ void __launch_bounds__(kThreads) ba_track_lin_kernel(Ctx c, int flags) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_track_lin_kernel(CtxT<M> c, int flags) {
   if (skipped(c, flags)) return;
   const long t = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (t < c.T) track_lin(c, c.ctrl->cur, t);
+  if (t < c.T) track_lin<M>(c, c.ctrl->cur, t);
 }
 
 // a wave per camera, grid ceil(n / 4) x 256
-__global__ void __launch_bounds__(kThreads) ba_cam_lin_kernel(Ctx c, int flags) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_cam_lin_kernel(CtxT<M> c, int flags) {
   if (skipped(c, flags)) return;
   const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
   const int lane = threadIdx.x % 64, cur = c.ctrl->cur;
   if (i >= c.n || !c.cam_free[i]) return;
-  double a[27];
-  wave_osum64<27>(c, i, lane, [&](long o, double* acc) { cam_lin_term(c, cur, o, acc); }, a);
+  constexpr int kU = kTri<M>;
+  double a[kU + M];
+  wave_osum64<kU + M>(c, i, lane, [&](long o, double* acc) { cam_lin_term<M>(c, cur, o, acc); }, a);
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 21; ++k) c.U[21 * i + k] = a[k];
+    for (int k = 0; k < kU; ++k) c.U[kU * i + k] = a[k];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) c.gc[6 * i + k] = a[21 + k];
+    for (int k = 0; k < M; ++k) c.gc[M * i + k] = a[kU + k];
   }
 }
 
 // threads [0, T): tracks, [T, T + n): cameras; grid ceil((T + n) / 256) x 256
-__global__ void __launch_bounds__(kThreads) ba_factor_kernel(Ctx c, int flags) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_factor_kernel(Ctx c, int flags) {
   if (skipped(c, flags)) return;
   const long id = (long)blockIdx.x * kThreads + threadIdx.x;
   const double lambda = c.ctrl->lambda;
   bool ok = true;
   if (id < c.T) ok = track_factor(c, id, lambda);
-  else if (id < c.T + c.n) ok = cam_factor(c, id - c.T, lambda);
+  else if (id < c.T + c.n) ok = cam_factor<M>(c, id - c.T, lambda);
   if (!ok) atomicOr(&c.ctrl->bad_f, 1);
 }
 
 // mode 0: z = Vd^-1 gp; mode 1: the track half of S p
-__global__ void __launch_bounds__(kThreads) ba_track_half_kernel(Ctx c, int mode, int flags) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_track_half_kernel(CtxT<M> c, int mode, int flags) {
   if (skipped(c, flags)) return;
   const long t = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (t < c.T) track_half(c, c.ctrl->cur, t, mode, c.p);
+  if (t < c.T) track_half<M>(c, c.ctrl->cur, t, mode, c.p);
 }
 
 // a wave per camera, grid ceil(n / 4) x 256.  mode 0: the right-hand side and the start of the conjugate gradients; mode 1: S p
-__global__ void __launch_bounds__(kThreads) ba_cam_half_kernel(Ctx c, int mode, int flags) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_cam_half_kernel(CtxT<M> c, int mode, int flags) {
   if (skipped(c, flags)) return;
   const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
   const int lane = threadIdx.x % 64, cur = c.ctrl->cur;
   if (i >= c.n) return;
-  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (c.cam_free[i]) wave_osum64<6>(c, i, lane, [&](long o, double* acc) { cam_half_term(c, cur, o, acc); }, a);
-  if (lane == 0) cam_half_finish(c, i, mode, c.ctrl->lambda, a);
+  double a[M];
+#pragma unroll
+  for (int k = 0; k < M; ++k) a[k] = 0.0;
+  if (c.cam_free[i]) wave_osum64<M>(c, i, lane, [&](long o, double* acc) { cam_half_term<M>(c, cur, o, acc); }, a);
+  if (lane == 0) cam_half_finish<M>(c, i, mode, c.ctrl->lambda, a);
 }
 
-__global__ void __launch_bounds__(kThreads) ba_update_kernel(Ctx c, int which, int flags) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_update_kernel(Ctx c, int which, int flags) {
   if (skipped(c, flags)) return;
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= c.n) return;
-  if (which == 1) cam_update1(c, i, c.ctrl->alpha);
-  else cam_update2(c, i, c.ctrl->beta);
+  if (which == 1) cam_update1<M>(c, i, c.ctrl->alpha);
+  else cam_update2<M>(c, i, c.ctrl->beta);
 }
 
 // threads [0, T): back substitution of the tracks, [T, T + n): the cameras' trial poses
-__global__ void __launch_bounds__(kThreads) ba_apply_kernel(Ctx c, int flags) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_apply_kernel(CtxT<M> c, int flags) {
   if (skipped(c, flags)) return;
   const long id = (long)blockIdx.x * kThreads + threadIdx.x;
   const int cur = c.ctrl->cur;
   bool ok = true;
-  if (id < c.T) ok = track_half(c, cur, id, 2, c.x);
-  else if (id < c.T + c.n) ok = cam_apply(c, cur, id - c.T);
+  if (id < c.T) ok = track_half<M>(c, cur, id, 2, c.x);
+  else if (id < c.T + c.n) ok = cam_apply<M>(c, cur, id - c.T);
   if (!ok) atomicOr(&c.ctrl->bad_a, 1);
 }
 
 __global__ void ba_accept_kernel(Ctx c) { ctrl_accept(c); }
 
 // threads [0, T): points, [T, T + n): cameras; thread 0 also writes the counts.  Runs whatever the flags say.
-__global__ void __launch_bounds__(kThreads) ba_write_kernel(Ctx c) {
+template <int M> __global__ void __launch_bounds__(kThreads) ba_write_kernel(CtxT<M> c) {
   const long id = (long)blockIdx.x * kThreads + threadIdx.x;
   const int cur = c.ctrl->cur;
   if (!c.ctrl->err) {
     if (id < c.T) track_write(c, cur, id);
-    else if (id < c.T + c.n) cam_write(c, cur, id - c.T);
+    else if (id < c.T + c.n) cam_write<M>(c, cur, id - c.T);
   }
-  if (id == 0) ctrl_write(c);
+  if (id == 0) ctrl_write<M>(c);
 }
 
-}  // namespace
-
-extern "C" size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images) {
-  if (!sizes_ok(T, N, n_images)) return 0;
-  Ctx c{};
-  c.T = T; c.N = N; c.n = n_images;
-  return layout(c, nullptr);
-}
-
-extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
-                                   const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
-                                   const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
-                                   double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
-                                   long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
+// the argument checks of both entry points
+int check_args(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N, const float* xyz,
+               const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images, const long* cam_offsets,
+               const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol, double* T_out, float* xyz_out,
+               uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, long* counts, void* ws) {
   LOFTR_CHECK_ARG(offsets && cam_offsets && counts && ws && T >= 0 && N >= 0 && n_images >= 0);
   LOFTR_CHECK_ARG(T == 0 || (xyz && xyz_out && point_active));
   LOFTR_CHECK_ARG(N == 0 || (obs_image && obs_xy && obs_mask && obs_active && cam_obs));
@@ -232,15 +234,16 @@ extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_i
   LOFTR_CHECK_ARG(max_iters >= 0 && max_iters <= LOFTR_BUNDLE_MAX_ITERS && pcg_iters >= 1 && pcg_iters <= LOFTR_BUNDLE_MAX_PCG);
   LOFTR_CHECK_ARG((T > 0 && n_images > 0) || N == 0);                  // observations outside every track or camera
   if (!sizes_ok(T, N, n_images)) return LOFTR_ERR_UNSUPPORTED;
-  Ctx c{};
-  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
-  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
-  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
-  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
-  if (ws_bytes < layout(c, nullptr)) return LOFTR_ERR_WORKSPACE;
-  layout(c, (char*)ws);
+  return LOFTR_OK;
+}
+
+// the fixed launch schedule; c holds the problem and the result
+template <int M> int run(CtxT<M>& c, int max_iters, int pcg_iters, void* ws, size_t ws_bytes, float* class_ms, long* class_launches,
+                         void* stream) {
+  if (ws_bytes < layout<M>(c, nullptr)) return LOFTR_ERR_WORKSPACE;
+  layout<M>(c, (char*)ws);
   hipStream_t s = (hipStream_t)stream;
-  const long n = n_images;
+  const long n = c.n, T = c.T;
   const bool timed = class_ms != nullptr;
   std::vector<hipEvent_t> ev;
   std::vector<int> ev_cls;
@@ -257,13 +260,14 @@ extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_i
     if (timed && !failed) { mark(); ev_cls.push_back(cls); }
   };
   auto blocks = [](long items, long per) { return dim3((unsigned)(items > 0 ? (items + per - 1) / per : 1)); };
+  const Ctx& b = c;                                                     // what the kernels without a camera block take
   // osum of v[0 .. count) into ctrl_feed(action): one launch per level
   auto osum = [&](const double* v, long count, int action, int flags) {
     const double* in = v;
     double* out = c.red;
     for (;;) {
       const long chunks = count > 0 ? (count + kChunk - 1) / kChunk : 1;
-      hipLaunchKernelGGL(ba_osum_kernel, dim3((unsigned)chunks), dim3(64), 0, s, c, in, count, out, chunks == 1 ? action : -1, flags);
+      hipLaunchKernelGGL(ba_osum_kernel, dim3((unsigned)chunks), dim3(64), 0, s, b, in, count, out, chunks == 1 ? action : -1, flags);
       after(kClsOsum);
       if (chunks == 1) return;
       in = out;
@@ -272,36 +276,36 @@ extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_i
     }
   };
   if (timed) mark();
-  hipLaunchKernelGGL(ba_init_kernel, dim3(1), dim3(1), 0, s, c); after(kClsSetup);
-  hipLaunchKernelGGL(ba_cam_setup_kernel, blocks(n, kThreads), dim3(kThreads), 0, s, c); after(kClsSetup);
-  hipLaunchKernelGGL(ba_track_setup_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c); after(kClsSetup);
-  hipLaunchKernelGGL(ba_groups_kernel, blocks(n, 4), dim3(kThreads), 0, s, c); after(kClsSetup);
-  hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 0, 0); after(kClsEvaluate);
+  hipLaunchKernelGGL(ba_init_kernel, dim3(1), dim3(1), 0, s, b); after(kClsSetup);
+  hipLaunchKernelGGL(ba_cam_setup_kernel<M>, blocks(n, kThreads), dim3(kThreads), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_track_setup_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, b); after(kClsSetup);
+  hipLaunchKernelGGL(ba_groups_kernel<M>, blocks(n, 4), dim3(kThreads), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, b, 0, 0); after(kClsEvaluate);
   osum(c.part, T, kActCost0, 0);
   osum(c.part2, T, kActSq0, 0);
   for (int it = 0; it < max_iters && !failed; ++it) {
-    hipLaunchKernelGGL(ba_track_lin_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
-    hipLaunchKernelGGL(ba_cam_lin_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
-    hipLaunchKernelGGL(ba_factor_kernel, blocks(T + n, kThreads), dim3(kThreads), 0, s, c, 0); after(kClsFactor);
-    hipLaunchKernelGGL(ba_track_half_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 0, kSkipBadF); after(kClsTrackHalf);
-    hipLaunchKernelGGL(ba_cam_half_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, 0, kSkipBadF); after(kClsCamHalf);
+    hipLaunchKernelGGL(ba_track_lin_kernel<M>, blocks(T, kThreads), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
+    hipLaunchKernelGGL(ba_cam_lin_kernel<M>, blocks(n, 4), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
+    hipLaunchKernelGGL(ba_factor_kernel<M>, blocks(T + n, kThreads), dim3(kThreads), 0, s, b, 0); after(kClsFactor);
+    hipLaunchKernelGGL(ba_track_half_kernel<M>, blocks(T, kThreads), dim3(kThreads), 0, s, c, 0, kSkipBadF); after(kClsTrackHalf);
+    hipLaunchKernelGGL(ba_cam_half_kernel<M>, blocks(n, 4), dim3(kThreads), 0, s, c, 0, kSkipBadF); after(kClsCamHalf);
     osum(c.part, n, kActRz0, kSkipBadF);
     for (int pi = 0; pi < pcg_iters && !failed; ++pi) {
       const int f = kSkipBadF | kSkipPcg;
-      hipLaunchKernelGGL(ba_track_half_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 1, f); after(kClsTrackHalf);
-      hipLaunchKernelGGL(ba_cam_half_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, 1, f); after(kClsCamHalf);
+      hipLaunchKernelGGL(ba_track_half_kernel<M>, blocks(T, kThreads), dim3(kThreads), 0, s, c, 1, f); after(kClsTrackHalf);
+      hipLaunchKernelGGL(ba_cam_half_kernel<M>, blocks(n, 4), dim3(kThreads), 0, s, c, 1, f); after(kClsCamHalf);
       osum(c.part, n, kActPsp, f);
-      hipLaunchKernelGGL(ba_update_kernel, blocks(n, kThreads), dim3(kThreads), 0, s, c, 1, f); after(kClsUpdate);
+      hipLaunchKernelGGL(ba_update_kernel<M>, blocks(n, kThreads), dim3(kThreads), 0, s, b, 1, f); after(kClsUpdate);
       osum(c.part, n, kActRz, f);
-      hipLaunchKernelGGL(ba_update_kernel, blocks(n, kThreads), dim3(kThreads), 0, s, c, 2, f); after(kClsUpdate);
+      hipLaunchKernelGGL(ba_update_kernel<M>, blocks(n, kThreads), dim3(kThreads), 0, s, b, 2, f); after(kClsUpdate);
     }
-    hipLaunchKernelGGL(ba_apply_kernel, blocks(T + n, kThreads), dim3(kThreads), 0, s, c, kSkipBadF); after(kClsApply);
-    hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 1, kSkipBadF | kSkipBadA); after(kClsEvaluate);
+    hipLaunchKernelGGL(ba_apply_kernel<M>, blocks(T + n, kThreads), dim3(kThreads), 0, s, c, kSkipBadF); after(kClsApply);
+    hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, b, 1, kSkipBadF | kSkipBadA); after(kClsEvaluate);
     osum(c.part, T, kActCostT, kSkipBadF | kSkipBadA | kSkipBadE);
     osum(c.part2, T, kActSqT, kSkipBadF | kSkipBadA | kSkipBadE);
-    hipLaunchKernelGGL(ba_accept_kernel, dim3(1), dim3(1), 0, s, c); after(kClsAccept);
+    hipLaunchKernelGGL(ba_accept_kernel, dim3(1), dim3(1), 0, s, b); after(kClsAccept);
   }
-  hipLaunchKernelGGL(ba_write_kernel, blocks(T + n, kThreads), dim3(kThreads), 0, s, c); after(kClsWrite);
+  hipLaunchKernelGGL(ba_write_kernel<M>, blocks(T + n, kThreads), dim3(kThreads), 0, s, c); after(kClsWrite);
   if (class_launches) for (int k = 0; k < kClsCount; ++k) class_launches[k] = launches[k];
   if (timed) {
     if (hipStreamSynchronize(s) != hipSuccess) failed = true;
@@ -320,4 +324,58 @@ extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_i
     for (auto& e : ev) (void)hipEventDestroy(e);
   }
   return failed ? LOFTR_ERR_LAUNCH : LOFTR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images) {
+  if (!sizes_ok(T, N, n_images)) return 0;
+  Ctx c{};
+  c.T = T; c.N = N; c.n = n_images;
+  return layout<6>(c, nullptr);
+}
+
+extern "C" size_t loftr_bundle_adjust_focal_workspace_bytes(long T, long N, int n_images) {
+  if (!sizes_ok(T, N, n_images)) return 0;
+  Ctx c{};
+  c.T = T; c.N = N; c.n = n_images;
+  return layout<7>(c, nullptr);
+}
+
+extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                   const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
+                                   const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
+                                   double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
+                                   long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
+  const int st = check_args(offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs,
+                            huber_px, max_iters, pcg_iters, pcg_tol, ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts, ws);
+  if (st != LOFTR_OK) return st;
+  Ctx c{};
+  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
+  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
+  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
+  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+  return run<6>(c, max_iters, pcg_iters, ws, ws_bytes, class_ms, class_launches, stream);
+}
+
+extern "C" int loftr_bundle_adjust_focal(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
+                                         long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                         const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                         double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs,
+                                         double focal_lo, double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
+                                         uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, long* counts, void* ws,
+                                         size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
+  LOFTR_CHECK_ARG(n_images <= 0 || (refine_focal && K_out && cam_focal));
+  LOFTR_CHECK_ARG(min_focal_obs >= 1 && fin(focal_lo) && fin(focal_hi) && focal_lo < 1.0 && 1.0 < focal_hi);
+  const int st = check_args(offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs,
+                            huber_px, max_iters, pcg_iters, pcg_tol, ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts, ws);
+  if (st != LOFTR_OK) return st;
+  Ctx7 c{};
+  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
+  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
+  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
+  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+  c.refine_focal = refine_focal; c.min_focal_obs = min_focal_obs; c.focal_lo = focal_lo; c.focal_hi = focal_hi;
+  c.K_out = K_out; c.cam_focal = cam_focal;
+  return run<7>(c, max_iters, pcg_iters, ws, ws_bytes, class_ms, class_launches, stream);
 }

@@ -1438,6 +1438,66 @@ def bundle_adjust_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_
                           (huber_px, max_iters, pcg_iters, pcg_tol, ftol), None)
 
 
+def _ba_focal_params(what, min_focal_obs, focal_lo, focal_hi):
+    import math
+    ok = isinstance(min_focal_obs, int) and not isinstance(min_focal_obs, bool) and \
+        all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (focal_lo, focal_hi))
+    if not (ok and min_focal_obs >= 1 and math.isfinite(focal_lo) and math.isfinite(focal_hi) and focal_lo < 1 < focal_hi):
+        raise ValueError(f"{what}: min_focal_obs must be an integer >= 1 and the focal bounds finite with lo < 1 < hi, got {min_focal_obs}, "
+                         f"{focal_lo}, {focal_hi}")
+    return int(min_focal_obs), float(focal_lo), float(focal_hi)
+
+
+def _bundle_adjust_focal(B, what, hint, arrays, params, focal, timings):
+    """The body of the focal pair: _bundle_adjust with refine_focal [n] u8 after fixed, (min_focal_obs, focal_lo, focal_hi)
+    after the parameters, and K [n,3,3] f64 and cam_focal [n] u8 after the outputs."""
+    _check_args(B, what, hint, _BA_ARGS + (("refine_focal", "uint8", 1),), arrays)
+    offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs, refine = arrays
+    N, n, T = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
+    if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or tuple(K.shape) != (n, 3, 3) or \
+            tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N or \
+            refine.shape[0] != n:
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
+                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1], cam_obs [N] and refine_focal [n], got "
+                                 f"{[tuple(a.shape) for a in arrays]}")
+    params = _ba_params(what, *params)
+    focal = _ba_focal_params(what, *focal)
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _BA_OUT + (("K", "n", (3, 3), "float64"), ("cam_focal", "n", (), "uint8")), {"T": T, "N": N, "n": n}, BUNDLE_COUNTS,
+                   offsets)
+    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
+    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
+    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
+    B.call("bundle_adjust_focal", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], a[10], n, a[8], a[9], *params, *focal,
+                                   *[B.ptr(out[k]) for k in out]),
+           _TABLE_RULES, offsets, ws=(T, N, n), tail=(cast(ms), cast(launches)))
+    if timings is not None:
+        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
+    return out
+
+
+def bundle_adjust_focal_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                             huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi):
+    """loftr_bundle_adjust_focal_host: the host routine that DEFINES the bundle adjustment with focal refinement (include/loftr_hip.h;
+    DESIGN §18.1) on numpy arrays: those of bundle_adjust_host plus refine_focal [n] u8.  -> its dict plus K [n,3,3] f64 and
+    cam_focal [n] u8; counts[13] is the number of cameras that refine their focal."""
+    return _bundle_adjust_focal(_Host, "bundle_adjust_focal_host", "bundle_adjust_focal",
+                                (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal),
+                                (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None)
+
+
+@_on_device
+def bundle_adjust_focal(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, huber_px,
+                        max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi, timings=None):
+    """loftr_bundle_adjust_focal: the kernels of the 7-wide camera block (csrc/bundle_gpu.hip) on GPU tensors; the same result as
+    bundle_adjust_focal_host bit for bit, the same launch schedule, timing classes and single readback as bundle_adjust."""
+    return _bundle_adjust_focal(_Gpu, "bundle_adjust_focal",
+                                "the bundle-adjustment kernels have no CPU fallback; the host routine is bundle_adjust_focal_host",
+                                (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal),
+                                (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
+
+
 @_on_device
 def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, huber_px, max_iters, pcg_iters,
                   pcg_tol, ftol, timings=None):

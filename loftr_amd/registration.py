@@ -57,11 +57,12 @@ class Registration:
 class Reconstruction:
     """What ``reconstruct_tracks`` returns: ``T_cam_from_world [n,4,4] f64`` (NaN for an image that never got a pose), ``posed [n]
     bool``, ``round_registered [n] i32`` (the round in which the image got its pose; 0 for the initial pair; -1 for never), ``points``
-    (the final ``Points3D``), ``bundle`` (the final ``BundleResult``), ``stats`` (dict; ``stats['rounds']`` holds the per-round counts)."""
+    (the final ``Points3D``), ``bundle`` (the final ``BundleResult``), ``stats`` (dict; ``stats['rounds']`` holds the per-round counts),
+    ``K [n,3,3] f64`` (the final intrinsics: the input's for an image that never refined its focal)."""
 
-    def __init__(self, T_cam_from_world, posed, round_registered, points, bundle, stats):
+    def __init__(self, T_cam_from_world, posed, round_registered, points, bundle, stats, K=None):
         self.T_cam_from_world, self.posed, self.round_registered = T_cam_from_world, posed, round_registered
-        self.points, self.bundle, self.stats = points, bundle, stats
+        self.points, self.bundle, self.stats, self.K = points, bundle, stats, K
 
 
 def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed, min_corr=15, min_inliers=15, thresh_px=4.0,
@@ -198,7 +199,11 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     triangulate.  An image is registered once: its pose changes afterwards only through the bundle adjustment.
 
     Only image ``a`` is fixed, which removes six of the seven gauge freedoms: the scale, set by ``|t| = 1`` at the start, is held only
-    by the damping of the bundle adjustment and may drift slowly; fix ``b`` as well (``fixed_extra``) to pin it."""
+    by the damping of the bundle adjustment and may drift slowly; fix ``b`` as well (``fixed_extra``) to pin it.
+
+    With ``ba={'refine_focal': True}`` (or an ``[n]`` mask) every adjustment also refines the focal of the posed images
+    named, and every step after an adjustment -- the triangulations, ``register_images``, the next adjustment -- uses the intrinsics it
+    returned; ``Reconstruction.K`` holds the last.  The focal bounds of an adjustment are relative to the intrinsics it was given."""
     from .bundle import bundle_adjust
     what = "reconstruct_tracks"
     offsets, obs_image, obs_xy, K = _tensors(what, ("offsets", "obs_image", "obs_xy", "K"), (offsets, obs_image, obs_xy, K))
@@ -227,6 +232,9 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
         fixed |= torch.as_tensor(extra).to(dev) != 0
     if "fixed" in ba:
         raise ValueError(f"{what}: image a is the fixed one; name further fixed images in ba['fixed_extra']")
+    if ba.get("refine_focal") is not None and ba["refine_focal"] is not True:
+        ba["refine_focal"] = torch.as_tensor(np.asarray(ba["refine_focal"].cpu() if isinstance(ba["refine_focal"], torch.Tensor)
+                                                        else ba["refine_focal"])).to(dev)
     thresh_px = register_kw.get("thresh_px", 4.0)
     T = torch.full((n, 4, 4), float("nan"), dtype=torch.float64, device=dev)
     T[a] = torch.eye(4, dtype=torch.float64)
@@ -239,16 +247,18 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     round_registered[a] = round_registered[b] = 0
     rounds = []
 
-    def refine(T, posed, first=False):
+    def refine(T, posed, K, first=False):
+        """-> (points of the adjusted poses, the adjustment, the intrinsics that hold from here on)"""
         pts = triangulate_posed(offsets, obs_image, obs_xy, K, T, posed, thresh_px, min_angle_deg)
         if first and pts.stats["n_ok"] == 0:
             raise ValueError(f"{what}: the initial pair ({a}, {b}) triangulates nothing: {pts.stats['n_posed_observations']} observations in "
                              f"{pts.stats['n_tracks']} tracks, statuses {[pts.stats['n_' + s] for s in ops.TRI_STATUS]}")
         res = bundle_adjust(offsets, obs_image, obs_xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **ba)
-        return triangulate_posed(offsets, obs_image, obs_xy, K, res.T_cam_from_world, posed, thresh_px, min_angle_deg), res
+        K = getattr(res, "K", K)                                        # (a result without refine_focal carries no K)
+        return triangulate_posed(offsets, obs_image, obs_xy, K, res.T_cam_from_world, posed, thresh_px, min_angle_deg), res, K
 
     for r in range(1, int(max_rounds) + 1):
-        pts, res = refine(T, posed, first=r == 1)
+        pts, res, K = refine(T, posed, K, first=r == 1)
         reg = register_images(offsets, obs_image, obs_xy, pts.xyz, pts.status, K, res.T_cam_from_world, posed, **register_kw)
         n_new, n_posed = torch.stack([reg.registered.sum(), reg.posed.sum()]).tolist()
         round_registered[reg.registered] = r
@@ -257,7 +267,7 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
                        "n_registered": n_new, "n_posed": n_posed})
         if n_new == 0 or n_posed == n:
             break
-    pts, res = refine(T, posed, first=not rounds)
+    pts, res, K = refine(T, posed, K, first=not rounds)
     stats = {"rounds": rounds, "n_rounds": len(rounds), "n_images": n, "n_posed": int(posed.sum()), "n_points": pts.stats["n_ok"],
              "rms_px_after": res.rms_px_after, "init": (a, b)}
-    return Reconstruction(res.T_cam_from_world, posed, round_registered, pts, res, stats)
+    return Reconstruction(res.T_cam_from_world, posed, round_registered, pts, res, stats, K)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Bundle adjustment (loftr_amd/bundle.py, csrc/bundle_gpu.hip) on a MegaDepth-1500-shaped load.  One JSON line.
 
-    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--no-host] [--out FILE]
+    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--refine-focal] [--no-host] [--out FILE]
 
 Load: the track lengths of tools/micro/atlas_bench.py's synthetic atlas (1500 rows over 806 images), observations as in
 tools/micro/triangulation_bench.py without outliers (one exact camera per image, one 3D point per track, every observation in a random
@@ -12,7 +12,9 @@ Reported: per kernel class the median device time over all launches of the class
 included), the total and the launches issued (events around every launch inside loftr_bundle_adjust, one call after a warm-up); a lower
 bound of the launches that returned at once (from the counts: trials and conjugate-gradient iterations not run); the wall time of bundle_adjust with its one readback (median of 3 calls without events); trials,
 accepted trials and conjugate-gradient iterations; the host routine (loftr_bundle_adjust_host, one core) on the same input; and the
-assertion that every run's output tensors and counts equal the host routine's."""
+assertion that every run's output tensors and counts equal the host routine's.  With --refine-focal the focal of every
+free camera starts 4-10 % off and the line holds two such legs on that load: "fixed_intrinsics" (the 6-wide kernels) and "refine_focal"
+(the 7-wide kernels, refine_focal=True), with the largest relative focal error before and after."""
 import argparse
 import json
 import os
@@ -77,31 +79,23 @@ def rotations_fixed(rng, n, deg):
 
 def same(a, b):
     eq = lambda x, y: torch.equal(torch.isnan(x), torch.isnan(y)) and torch.equal(torch.nan_to_num(x, nan=0.0), torch.nan_to_num(y, nan=0.0))
-    return all(eq(getattr(a, k).cpu().double(), getattr(b, k).cpu().double()) for k in BundleResult.FIELDS) and a.stats == b.stats
+    return a.FIELDS == b.FIELDS and all(eq(getattr(a, k).cpu().double(), getattr(b, k).cpu().double()) for k in a.FIELDS) and a.stats == b.stats
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--rows", type=int, default=1500)
-    ap.add_argument("--matches", type=int, default=1000)
-    ap.add_argument("--max-iters", type=int, default=30)
-    ap.add_argument("--pcg-iters", type=int, default=30)
-    ap.add_argument("--huber", type=float, default=0.0)
-    ap.add_argument("--no-host", action="store_true", help="skip the host routine (and the equality assertion)")
-    ap.add_argument("--out", default=None, help="also append the JSON line to this file")
-    args = ap.parse_args()
-    pairs = np.load(os.path.join(ROOT, "tests", "golden", "pair_lists.npz"))["megadepth_pairs"][:args.rows].astype(np.int64)
-    n_images, chunks = make_chunks(pairs, args.matches)
-    atlas = KeypointAtlas(n_images, HW, 2.0, device=DEV)
-    for ids, data in chunks:
-        atlas.add(ids, data)
-    sfm = atlas.finalize(min_track_len=2)
-    lens = sfm.track_len[sfm.track_ok]
-    del atlas, chunks
-    *inputs, fixed = make_load(lens, n_images)
-    kw = dict(huber_px=args.huber, max_iters=args.max_iters, pcg_iters=args.pcg_iters)
-    out = {"workload": "bundle_megadepth1500_shape", "images": n_images, "tracks": int(lens.numel()), "observations": int(inputs[0][-1]),
-           "fixed_cameras": 2, **kw}
+def detune(K, fixed, seed=5):
+    """K with fx, skew and fy of every camera that is not fixed multiplied by 1 +- U(0.04, 0.10)."""
+    rng = np.random.default_rng(seed)
+    n = K.shape[0]
+    fac = torch.from_numpy(1 + rng.choice([-1, 1], n) * rng.uniform(0.04, 0.10, n)).to(K.device)
+    fac = torch.where(fixed, torch.ones_like(fac), fac)
+    K = K.clone()
+    K[:, 0, 0], K[:, 0, 1], K[:, 1, 1] = K[:, 0, 0] * fac, K[:, 0, 1] * fac, K[:, 1, 1] * fac
+    return K
+
+
+def leg(inputs, fixed, kw, n_tracks, args):
+    """One timed leg: a warm-up, 3 timed calls, one call with events, the host routine and the equality assertion -> dict."""
+    out = {}
     run = lambda timings=None: bundle_adjust(*inputs, fixed=fixed, timings=timings, **kw)
     results = [run()]                                                   # warm-up (kernel load)
     wall = []
@@ -118,17 +112,56 @@ def main():
     out["class_total_ms"] = {k: round(v[1], 3) for k, v in timings.items()}
     out["class_launches"] = {k: v[2] for k, v in timings.items()}
     issued = sum(v[2] for v in timings.values())
-    levels_t = 1 if lens.numel() <= 4096 else 2
+    levels_t = 1 if n_tracks <= 4096 else 2
     per_pcg, per_trial = 6, 3 + 2 + 1 + 2 + 2 * levels_t + 1                # the launches of one iteration / of a trial without them
     skipped = (args.max_iters - res.n_iters) * (per_trial + per_pcg * args.pcg_iters) + per_pcg * (res.n_iters * args.pcg_iters - res.n_pcg)
     out["launches_issued"], out["launches_skipped_at_least"] = issued, int(skipped)
     out["stats"] = res.stats
     if not args.no_host:
         t = time.perf_counter()
-        host = bundle_adjust(*[x.cpu() for x in inputs], fixed=fixed.cpu(), **kw)
+        host_kw = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in kw.items()}
+        host = bundle_adjust(*[x.cpu() for x in inputs], fixed=fixed.cpu(), **host_kw)
         out["host_routine_ms"] = round(1e3 * (time.perf_counter() - t), 1)
         out["identical_to_host"] = bool(all(same(r, host) for r in results))
         assert out["identical_to_host"], "a GPU run differs from the host routine"
+    return out, res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--rows", type=int, default=1500)
+    ap.add_argument("--matches", type=int, default=1000)
+    ap.add_argument("--max-iters", type=int, default=30)
+    ap.add_argument("--pcg-iters", type=int, default=30)
+    ap.add_argument("--huber", type=float, default=0.0)
+    ap.add_argument("--refine-focal", action="store_true",
+                    help="the focal of every free camera off by 4-10 %%: a fixed-intrinsics leg and a refine_focal=True leg on that load")
+    ap.add_argument("--no-host", action="store_true", help="skip the host routine (and the equality assertion)")
+    ap.add_argument("--out", default=None, help="also append the JSON line to this file")
+    args = ap.parse_args()
+    pairs = np.load(os.path.join(ROOT, "tests", "golden", "pair_lists.npz"))["megadepth_pairs"][:args.rows].astype(np.int64)
+    n_images, chunks = make_chunks(pairs, args.matches)
+    atlas = KeypointAtlas(n_images, HW, 2.0, device=DEV)
+    for ids, data in chunks:
+        atlas.add(ids, data)
+    sfm = atlas.finalize(min_track_len=2)
+    lens = sfm.track_len[sfm.track_ok]
+    del atlas, chunks
+    *inputs, fixed = make_load(lens, n_images)
+    kw = dict(huber_px=args.huber, max_iters=args.max_iters, pcg_iters=args.pcg_iters)
+    out = {"workload": "bundle_megadepth1500_shape", "images": n_images, "tracks": int(lens.numel()), "observations": int(inputs[0][-1]),
+           "fixed_cameras": 2, **kw}
+    if not args.refine_focal:
+        out.update(leg(inputs, fixed, kw, lens.numel(), args)[0])
+    else:
+        K_true = inputs[5]
+        inputs[5] = detune(K_true, fixed)
+        err = lambda K: float(((K[:, 0, 0] / K_true[:, 0, 0] - 1).abs()[~fixed]).max())
+        out["workload"] += "_focal_off_4_to_10_percent"
+        out["focal_error_before"] = round(err(inputs[5]), 5)
+        out["fixed_intrinsics"], _ = leg(inputs, fixed, kw, lens.numel(), args)
+        out["refine_focal"], res = leg(inputs, fixed, dict(kw, refine_focal=True), lens.numel(), args)
+        out["focal_error_after"] = round(err(res.K), 5)
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:
