@@ -314,28 +314,33 @@ class FinePreprocess(nn.Module):
             if p.dim() > 1:
                 nn.init.kaiming_normal_(p, mode="fan_out", nonlinearity="relu")
 
-    def forward(self, feat_f0, feat_f1, feat_c0, feat_c1, data):
+    def _begin(self, data, device):
+        """What every form of the forward starts with: sets data["W"]; returns the window geometry (hw0_c, hw1_c, W, stride) the ops
+        take, the weight keywords, and the empty result when there is no match (else None)."""
         W = self.W
         stride = data["hw0_f"][0] // data["hw0_c"][0]
         data.update({"W": W})
+        empty = None
         if data["b_ids"].shape[0] == 0:
-            feat0 = torch.empty(0, self.W ** 2, self.d_model_f, device=feat_f0.device)
-            feat1 = torch.empty(0, self.W ** 2, self.d_model_f, device=feat_f0.device)
-            return feat0, feat1
+            empty = tuple(torch.empty(0, W ** 2, self.d_model_f, device=device) for _ in range(2))
         kw = {}
         if self.cat_c_feat:
             kw = dict(down_w=self.down_proj.weight, down_b=self.down_proj.bias,
                       merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
+        return (tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride), kw, empty
+
+    def forward(self, feat_f0, feat_f1, feat_c0, feat_c1, data):
+        geo, kw, empty = self._begin(data, feat_f0.device)
+        if empty is not None:
+            return empty
         wants = autograd.wants_grad(feat_f0, feat_f1, feat_c0, feat_c1, *self.parameters())
         if wants and self.training and not self.cat_c_feat:
             # no silent graph cut (advisor, round 4): the backward of the window gather alone (fine_concat_coarse_feat=False) is not built
             raise ops._lib.LoftrHipError("FinePreprocess: gradients requested with fine_concat_coarse_feat=False, whose backward is not "
                                          "implemented (csrc/fine_bwd.hip covers the reference's default, True)")
         if self.training and self.cat_c_feat and wants:
-            return autograd.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, (data["b_ids"], data["i_ids"], data["j_ids"]),
-                                            (tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride), **kw)
-        return ops.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
-                                   tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride, **kw)
+            return autograd.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, (data["b_ids"], data["i_ids"], data["j_ids"]), geo, **kw)
+        return ops.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"], *geo, **kw)
 
     def forward_windows(self, h_sp0, h_sp1, cin, conv, dense_fn, fine_head, feat_c0, feat_c1, data):
         """Inference forward from the INPUTS of the fine head's last convolution `conv` (SP [N, H, W, ceil32(cin)] per image batch): the
@@ -351,13 +356,8 @@ class FinePreprocess(nn.Module):
                 return self.forward(h_sp0, h_sp1, feat_c0, feat_c1, data)
             return self.forward(dense_fn(h_sp0), dense_fn(h_sp1), feat_c0, feat_c1, data)
         self.last_head = "windows"
-        W = self.W
-        stride = data["hw0_f"][0] // data["hw0_c"][0]
-        data.update({"W": W})
-        return ops.fine_preprocess_windows(h_sp0, h_sp1, cin, conv, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
-                                           tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride,
-                                           down_w=self.down_proj.weight, down_b=self.down_proj.bias,
-                                           merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
+        geo, kw, _ = self._begin(data, h_sp0.device)
+        return ops.fine_preprocess_windows(h_sp0, h_sp1, cin, conv, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"], *geo, **kw)
 
     def forward_windows2(self, t_sp0, t_sp1, cin, head, first_fn, dense_fn, fine_head, feat_c0, feat_c1, data):
         """Inference forward from the INPUTS of the fine head `head` (conv, BN, LeakyReLU, conv; SP [N, H, W, ceil32(cin)] per image
@@ -379,29 +379,17 @@ class FinePreprocess(nn.Module):
                 h_sp0, h_sp1 = first_fn(t_sp0), first_fn(t_sp1)
             return self.forward_windows(h_sp0, h_sp1, head[0].out_channels, head[3], dense_fn, fine_head, feat_c0, feat_c1, data)
         self.last_head = self.last_head_first = "windows"
-        W = self.W
-        stride = data["hw0_f"][0] // data["hw0_c"][0]
-        data.update({"W": W})
+        geo, kw, _ = self._begin(data, t_sp0.device)
         return ops.fine_preprocess_windows2(t_sp0, t_sp1, cin, head[0], head[1], head[3], feat_c0, feat_c1, data["b_ids"], data["i_ids"],
-                                            data["j_ids"], tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride,
-                                            down_w=self.down_proj.weight, down_b=self.down_proj.bias,
-                                            merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
+                                            data["j_ids"], *geo, **kw)
 
     def forward_gather(self, bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data):
         """Inference forward with the fine maps of pair b read from bank_f0[slot0[b]] / bank_f1[slot1[b]] (LoFTR.match_pairs)."""
-        W = self.W
-        stride = data["hw0_f"][0] // data["hw0_c"][0]
-        data.update({"W": W})
-        if data["b_ids"].shape[0] == 0:
-            feat0 = torch.empty(0, self.W ** 2, self.d_model_f, device=bank_f0.device)
-            feat1 = torch.empty(0, self.W ** 2, self.d_model_f, device=bank_f0.device)
-            return feat0, feat1
-        kw = {}
-        if self.cat_c_feat:
-            kw = dict(down_w=self.down_proj.weight, down_b=self.down_proj.bias,
-                      merge_w=self.merge_feat.weight, merge_b=self.merge_feat.bias)
+        geo, kw, empty = self._begin(data, bank_f0.device)
+        if empty is not None:
+            return empty
         return ops.fine_preprocess_gather(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
-                                          tuple(data["hw0_c"]), tuple(data["hw1_c"]), W, stride, **kw)
+                                          *geo, **kw)
 
 
 class FineMatching(nn.Module):

@@ -430,6 +430,27 @@ def _fmap(t):
     return FMap(t.data_ptr(), sn, sc, sh, sw, t.shape[2], t.shape[3])
 
 
+def _id_ptrs(b_ids, i_ids, j_ids):
+    return [_ptr(_need(t, n, torch.int64)) for t, n in ((b_ids, "b_ids"), (i_ids, "i_ids"), (j_ids, "j_ids"))]
+
+
+def _fine_preprocess_call(entry, source, dev, Cf, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride, lin, extra=()):
+    """What the four forms of fine_preprocess share: the [2 M, W*W, Cf] result, the empty return, the workspace and the arguments
+    from the coarse features to the stream.  `source`: the entry point's leading arguments (where the windows come from), `extra`:
+    those between the workspace and the stream; `lin`: (down_w, down_b, merge_w, merge_b).  The callers have checked feat_c0 / feat_c1."""
+    M = b_ids.shape[0]
+    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)     # one buffer: the fine transformer
+    out0, out1 = out[:M], out[M:]                                            # runs on it in place (no torch.cat)
+    if M == 0:
+        return out0, out1
+    lib = _lib.load()
+    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
+    check(getattr(lib, entry)(*source, _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[2],
+                              *_id_ptrs(b_ids, i_ids, j_ids), M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf, *map(_ptr, lin),
+                              _ptr(out0), _ptr(out1), _ptr(ws), ws.numel(), *extra, _stream()), entry)
+    return out0, out1
+
+
 @_on_device
 def fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride,
                     down_w=None, down_b=None, merge_w=None, merge_b=None):
@@ -438,23 +459,9 @@ def fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0
         if not t.is_cuda or t.dtype != torch.float32:
             raise _lib.LoftrHipError(f"{n}: expected a float32 GPU tensor")
     _need(feat_c0, "feat_c0"); _need(feat_c1, "feat_c1")
-    M = b_ids.shape[0]
-    Cf = feat_f0.shape[1]
-    dev = feat_f0.device
-    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)     # one buffer: the fine transformer
-    out0, out1 = out[:M], out[M:]                                            # runs on it in place (no torch.cat)
-    if M == 0:
-        return out0, out1
-    lib = _lib.load()
-    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
     f0, f1 = _fmap(feat_f0), _fmap(feat_f1)
-    check(lib.loftr_fine_preprocess(C.byref(f0), C.byref(f1), _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1],
-                                    feat_c1.shape[1], feat_c0.shape[2], _ptr(_need(b_ids, "b_ids", torch.int64)),
-                                    _ptr(_need(i_ids, "i_ids", torch.int64)), _ptr(_need(j_ids, "j_ids", torch.int64)),
-                                    M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf, _ptr(down_w), _ptr(down_b),
-                                    _ptr(merge_w), _ptr(merge_b), _ptr(out0), _ptr(out1), _ptr(ws), ws.numel(),
-                                    _stream()), "loftr_fine_preprocess")
-    return out0, out1
+    return _fine_preprocess_call("loftr_fine_preprocess", (C.byref(f0), C.byref(f1)), feat_f0.device, feat_f0.shape[1], feat_c0, feat_c1,
+                                 b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride, (down_w, down_b, merge_w, merge_b))
 
 
 # ---- the fine head at matched windows only (csrc/window_head.hip) -------------------------------------------------------
@@ -478,24 +485,26 @@ def window_head_supported(W, Cin, Cout, h_sp0, h_sp1):
             and h_sp0.numel() < 2 ** 31)
 
 
-def _window_head_common(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids):
-    for t, n in ((h_sp0, "h_sp0"), (h_sp1, "h_sp1")):
+def _window_conv_inputs(maps, Cin, conv, bn, b_ids, i_ids, j_ids):
+    """The input check of every window kernel: `maps` = ((SP map of image0, its name), (of image1, its name)), or () where the input
+    is no pair of maps; `conv` (with `bn` folded in) 3x3 / stride 1 / pad 1 on Cin channels; the three id vectors.
+    Returns (Cout, the prepared filter, the ids' pointers)."""
+    for t, n in maps:
         if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 4:
             raise _lib.LoftrHipError(f"{n}: expected a contiguous int32 (SP) GPU tensor [N, H, W, Cp]")
-    if h_sp0.shape != h_sp1.shape or h_sp0.shape[3] != ceil32(Cin):
-        raise _lib.LoftrHipError(f"window head: SP maps {tuple(h_sp0.shape)} / {tuple(h_sp1.shape)} for {Cin} channels")
+    if maps and (maps[0][0].shape != maps[1][0].shape or maps[0][0].shape[3] != ceil32(Cin)):
+        raise _lib.LoftrHipError(f"window head: SP maps {tuple(maps[0][0].shape)} / {tuple(maps[1][0].shape)} for {Cin} channels")
     Cout, Cin_w, KH, KW = conv.weight.shape
     if (Cin_w, KH, KW) != (Cin, 3, 3) or conv.stride[0] != 1 or conv.padding[0] != 1:
         raise _lib.LoftrHipError("window head: a 3x3 / stride-1 / pad-1 convolution expected")
-    ids = [_ptr(_need(t, n, torch.int64)) for t, n in ((b_ids, "b_ids"), (i_ids, "i_ids"), (j_ids, "j_ids"))]
-    return Cout, _prepared_conv(conv, None), ids
+    return Cout, _prepared_conv(conv, bn), _id_ptrs(b_ids, i_ids, j_ids)
 
 
 @_on_device
 def window_head(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride):
     """The W x W windows of conv(h) at the matched cells, without the map: (win0, win1) int32 SP [M, W*W, 128] -- bit for bit the
     window tiles loftr_fine_preprocess gathers from the dense convolution's fp32 output."""
-    Cout, prepared, ids = _window_head_common(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids)
+    Cout, prepared, ids = _window_conv_inputs(((h_sp0, "h_sp0"), (h_sp1, "h_sp1")), Cin, conv, None, b_ids, i_ids, j_ids)
     M = b_ids.shape[0]
     win = torch.empty(2, M, W * W, ceil32(Cout), dtype=torch.int32, device=h_sp0.device)
     if M:
@@ -512,23 +521,12 @@ def fine_preprocess_windows(h_sp0, h_sp1, Cin, conv, feat_c0, feat_c1, b_ids, i_
     """fine_preprocess with the fine head's last convolution `conv` evaluated at the matched windows only: h_sp0 / h_sp1 are that
     convolution's inputs (SP [N, H, W, ceil32(Cin)]) for the image0 / image1 batch.  Same results, bit for bit, as fine_preprocess on
     the dense maps conv_bn_act(h, Cin, conv) gives."""
-    Cf, prepared, ids = _window_head_common(h_sp0, h_sp1, Cin, conv, b_ids, i_ids, j_ids)
+    Cf, prepared, _ = _window_conv_inputs(((h_sp0, "h_sp0"), (h_sp1, "h_sp1")), Cin, conv, None, b_ids, i_ids, j_ids)
     _need(feat_c0, "feat_c0"); _need(feat_c1, "feat_c1")
-    M = b_ids.shape[0]
-    dev = h_sp0.device
-    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)
-    out0, out1 = out[:M], out[M:]
-    if M == 0:
-        return out0, out1
-    lib = _lib.load()
-    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
     N, H, Wm, _ = h_sp0.shape
-    check(lib.loftr_fine_preprocess_window_head(_ptr(h_sp0), _ptr(h_sp1), N, H, Wm, Cin, _ptr(prepared), prepared.numel(),
-                                                _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[2],
-                                                *ids, M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf, _ptr(down_w), _ptr(down_b),
-                                                _ptr(merge_w), _ptr(merge_b), _ptr(out0), _ptr(out1), _ptr(ws), ws.numel(),
-                                                _stream()), "loftr_fine_preprocess_window_head")
-    return out0, out1
+    return _fine_preprocess_call("loftr_fine_preprocess_window_head",
+                                 (_ptr(h_sp0), _ptr(h_sp1), N, H, Wm, Cin, _ptr(prepared), prepared.numel()), h_sp0.device, Cf,
+                                 feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride, (down_w, down_b, merge_w, merge_b))
 
 
 # ---- both convolutions of the fine head at matched windows only (csrc/window_head_first.hip) -----------------------------
@@ -554,25 +552,12 @@ def window_head_first_supported(W, Cin, conv0, conv1, t_sp0, t_sp1, M):
             and conv1.in_channels == 196 and 2 * M * 49 * 224 < 2 ** 31)
 
 
-def _window_head_first_common(t_sp0, t_sp1, Cin, conv, bn, b_ids, i_ids, j_ids):
-    for t, n in ((t_sp0, "t_sp0"), (t_sp1, "t_sp1")):
-        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 4:
-            raise _lib.LoftrHipError(f"{n}: expected a contiguous int32 (SP) GPU tensor [N, H, W, Cp]")
-    if t_sp0.shape != t_sp1.shape or t_sp0.shape[3] != ceil32(Cin):
-        raise _lib.LoftrHipError(f"window head: SP maps {tuple(t_sp0.shape)} / {tuple(t_sp1.shape)} for {Cin} channels")
-    Cout, Cin_w, KH, KW = conv.weight.shape
-    if (Cin_w, KH, KW) != (Cin, 3, 3) or conv.stride[0] != 1 or conv.padding[0] != 1:
-        raise _lib.LoftrHipError("window head: a 3x3 / stride-1 / pad-1 convolution expected")
-    ids = [_ptr(_need(t, n, torch.int64)) for t, n in ((b_ids, "b_ids"), (i_ids, "i_ids"), (j_ids, "j_ids"))]
-    return Cout, _prepared_conv(conv, bn), ids
-
-
 @_on_device
 def window_head_first(t_sp0, t_sp1, Cin, conv, bn, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride):
     """act(bn(conv(t))) (LeakyReLU 0.01: the fine head's first layer) at the 7 x 7 neighbourhoods of the matched W x W windows, without
     the map: int32 SP [2 M, 49, ceil32(Cout)], window side * M + m, row py * 7 + px -- bit for bit the dense layer's SP rows
     conv_bn_act(t, Cin, conv, bn, act=2) at those pixels, zeros outside the map."""
-    Cout, prepared, ids = _window_head_first_common(t_sp0, t_sp1, Cin, conv, bn, b_ids, i_ids, j_ids)
+    Cout, prepared, ids = _window_conv_inputs(((t_sp0, "t_sp0"), (t_sp1, "t_sp1")), Cin, conv, bn, b_ids, i_ids, j_ids)
     M = b_ids.shape[0]
     nb = torch.empty(2 * M, 49, ceil32(Cout), dtype=torch.int32, device=t_sp0.device)
     if M:
@@ -589,9 +574,7 @@ def window_head_last(nb, hw_f, Cin, conv, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, 
     M = b_ids.shape[0]
     if not nb.is_cuda or nb.dtype != torch.int32 or not nb.is_contiguous() or tuple(nb.shape) != (2 * M, 49, ceil32(Cin)):
         raise _lib.LoftrHipError(f"nb: expected a contiguous int32 (SP) GPU tensor [{2 * M}, 49, {ceil32(Cin)}]")
-    Cout = conv.weight.shape[0]
-    prepared = _prepared_conv(conv, None)
-    ids = [_ptr(_need(t, n, torch.int64)) for t, n in ((b_ids, "b_ids"), (i_ids, "i_ids"), (j_ids, "j_ids"))]
+    Cout, prepared, ids = _window_conv_inputs((), Cin, conv, None, b_ids, i_ids, j_ids)
     win = torch.empty(2, M, W * W, ceil32(Cout), dtype=torch.int32, device=nb.device)
     if M:
         check(_lib.load().loftr_window_head_last(_ptr(nb), int(hw_f[0]), int(hw_f[1]), Cin, _ptr(prepared), prepared.numel(), Cout, *ids,
@@ -606,29 +589,19 @@ def fine_preprocess_windows2(t_sp0, t_sp1, Cin, conv0, bn0, conv1, feat_c0, feat
     """fine_preprocess with BOTH convolutions of the fine head (conv0 + bn0 + LeakyReLU, conv1) evaluated at the matched windows only:
     t_sp0 / t_sp1 are the head's inputs (SP [N, H, W, ceil32(Cin)]) for the image0 / image1 batch.  Same results, bit for bit, as
     fine_preprocess_windows on conv_bn_act(t, Cin, conv0, bn0, act=2)."""
-    Cmid, prepared0, ids = _window_head_first_common(t_sp0, t_sp1, Cin, conv0, bn0, b_ids, i_ids, j_ids)
+    Cmid, prepared0, _ = _window_conv_inputs(((t_sp0, "t_sp0"), (t_sp1, "t_sp1")), Cin, conv0, bn0, b_ids, i_ids, j_ids)
     Cf = conv1.weight.shape[0]
     if tuple(conv1.weight.shape[1:]) != (Cmid, 3, 3) or conv1.stride[0] != 1 or conv1.padding[0] != 1:
         raise _lib.LoftrHipError("window head: a 3x3 / stride-1 / pad-1 second convolution expected")
     prepared1 = _prepared_conv(conv1, None)
     _need(feat_c0, "feat_c0"); _need(feat_c1, "feat_c1")
-    M = b_ids.shape[0]
     dev = t_sp0.device
-    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)
-    out0, out1 = out[:M], out[M:]
-    if M == 0:
-        return out0, out1
-    lib = _lib.load()
-    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
-    nb = torch.empty(2 * M, 49, ceil32(Cmid), dtype=torch.int32, device=dev)     # the first convolution's neighbourhood rows
+    nb = torch.empty(2 * b_ids.shape[0], 49, ceil32(Cmid), dtype=torch.int32, device=dev)     # the first convolution's neighbourhood rows
     N, H, Wm, _ = t_sp0.shape
-    check(lib.loftr_fine_preprocess_window_head2(_ptr(t_sp0), _ptr(t_sp1), N, H, Wm, Cin, _ptr(prepared0), prepared0.numel(), Cmid,
-                                                 _ptr(prepared1), prepared1.numel(),
-                                                 _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[2],
-                                                 *ids, M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf, _ptr(down_w), _ptr(down_b),
-                                                 _ptr(merge_w), _ptr(merge_b), _ptr(out0), _ptr(out1), _ptr(ws), ws.numel(),
-                                                 _ptr(nb), _stream()), "loftr_fine_preprocess_window_head2")
-    return out0, out1
+    return _fine_preprocess_call("loftr_fine_preprocess_window_head2",
+                                 (_ptr(t_sp0), _ptr(t_sp1), N, H, Wm, Cin, _ptr(prepared0), prepared0.numel(), Cmid, _ptr(prepared1),
+                                  prepared1.numel()), dev, Cf, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride,
+                                 (down_w, down_b, merge_w, merge_b), extra=(_ptr(nb),))
 
 
 def _slot_ids(ids, n_slots, name, device):
@@ -686,23 +659,11 @@ def fine_preprocess_gather(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, b_i
     s1 = _slot_ids(slot1, bank_f1.shape[0], "slot1", bank_f1.device)
     if s0.shape[0] != N or s1.shape[0] != N:
         raise _lib.LoftrHipError(f"slot0 / slot1: expected {N} slot ids (one per pair), got {s0.shape[0]} / {s1.shape[0]}")
-    M = b_ids.shape[0]
-    Cf = bank_f0.shape[1]
-    dev = bank_f0.device
-    out = torch.empty(2 * M, W * W, Cf, device=dev, dtype=torch.float32)     # one buffer, as fine_preprocess
-    out0, out1 = out[:M], out[M:]
-    if M == 0:
-        return out0, out1
-    lib = _lib.load()
-    ws = workspace(lib.loftr_fine_preprocess_workspace_bytes(M, W, Cf), dev)
     f0, f1 = _fmap(bank_f0), _fmap(bank_f1)
-    check(lib.loftr_fine_preprocess_gather(C.byref(f0), bank_f0.shape[0], _ptr(s0), C.byref(f1), bank_f1.shape[0], _ptr(s1),
-                                           _ptr(feat_c0), _ptr(feat_c1), feat_c0.shape[1], feat_c1.shape[1], feat_c0.shape[2],
-                                           _ptr(_need(b_ids, "b_ids", torch.int64)), _ptr(_need(i_ids, "i_ids", torch.int64)),
-                                           _ptr(_need(j_ids, "j_ids", torch.int64)), M, hw0_c[1], hw1_c[1], int(stride), int(W), Cf,
-                                           _ptr(down_w), _ptr(down_b), _ptr(merge_w), _ptr(merge_b), _ptr(out0), _ptr(out1),
-                                           _ptr(ws), ws.numel(), _stream()), "loftr_fine_preprocess_gather")
-    return out0, out1
+    return _fine_preprocess_call("loftr_fine_preprocess_gather",
+                                 (C.byref(f0), bank_f0.shape[0], _ptr(s0), C.byref(f1), bank_f1.shape[0], _ptr(s1)), bank_f0.device,
+                                 bank_f0.shape[1], feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride,
+                                 (down_w, down_b, merge_w, merge_b))
 
 
 @_on_device
