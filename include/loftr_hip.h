@@ -65,7 +65,8 @@ typedef enum {
  *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust; with per-image focal
  *     refinement loftr_bundle_adjust_focal_host, loftr_bundle_adjust_focal_workspace_bytes, loftr_bundle_adjust_focal), the
  *     correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
- *     loftr_register_corr) */
+ *     loftr_register_corr), track completion (loftr_complete_tracks_host, loftr_complete_tracks_workspace_bytes,
+ *     loftr_complete_tracks) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -996,6 +997,65 @@ int loftr_register_corr(const long* offsets, long T, const int* obs_image, const
                         const uint8_t* status, const uint8_t* posed, int n_images, const long* cam_offsets, const int* cam_obs,
                         int min_corr, int* n_corr, int* cand_rank, int* cand_image, long* cand_offsets, float* corr_xyz, float* corr_xy,
                         long* corr_bid, int* corr_obs, long* counts, void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
+/* ---- track completion: points claim the atlas keypoints they project onto (csrc/complete_core.h holds every per-item step) --
+ * The atlas makes a track only where matches of different rows snapped to the same cell, so one physical point tends to end as several
+ * short tracks and loose keypoints.  Completion projects every row that has a 3D point into every posed image the row does not visit
+ * and lets it claim the nearest free keypoint there; its whole result is a relabelled kp_row (the atlas's track_id).
+ * loftr_complete_tracks_host (csrc/complete.hip, host memory) DEFINES the result, loftr_complete_tracks (csrc/complete_gpu.hip, device
+ * memory) reproduces it bit for bit.
+ * Input: the CSR of the rows a triangulation ran on -- offsets [T+1] i64, obs_image [N] i32 --, its xyz [T,3] f32 and status [T] u8
+ *   (0 = ok); the keypoint pool -- kp_offsets [n+1] i64, keypoints [K,2] f32, kp_cell [K] i32 (cy * gw + cx, strictly ascending within
+ *   an image, as loftr_model_cells makes and checks it), kp_row [K] i32 (the row that holds the keypoint, or -1) --; K [n,9] and
+ *   T_cam_from_world [n,16] f64, from which the camera table of the triangulation is built (P = K [R | t]; an invalid camera is all
+ *   NaN); posed [n] u8; the grid (inv, gh, gw) of the atlas; thresh_px (thr2 = thresh_px * thresh_px in fp64); reach in
+ *   [0, LOFTR_COMPLETE_MAX_REACH] cells.  Arithmetic: fp64 without FMA contraction, + - * / only.
+ *   1. Source.  Row j is a source iff status[j] == 0 and the three floats of xyz[j] are finite (exponent bits not all ones).
+ *   2. Target.  Image i is a target of j iff posed[i] != 0, its camera is valid, and no observation of row j lies in image i.
+ *      obs_image must not descend within a row (the routines merge-walk it).
+ *   3. Projection.  X = (double) xyz[j]; x = (P0 . X) + P03, y = (P1 . X) + P13, z = (P2 . X) + P23 with (a0 b0 + a1 b1) + a2 b2 as the
+ *      dot product (the triangulation's residual); z > 0 is required; u = x / z, v = y / z; cx = floorf((float) u * inv) if that lies in
+ *      [0, gw), cy likewise from v and gh; otherwise the pair has no candidates.
+ *   4. Candidates.  The keypoints of image i whose cell (cy', cx') has |cy' - cy| <= reach and |cx' - cx| <= reach, clipped to the grid:
+ *      for each cell row in ascending order one lower-bound search of cy' gw + max(cx - reach, 0) in kp_cell over
+ *      [kp_offsets[i], kp_offsets[i+1]), then a walk while the cell is at most cy' gw + min(cx + reach, gw - 1).  Keypoint k is WITHIN iff
+ *      r2(k) = (x / z - kx)^2 + (y / z - ky)^2 <= thr2 (NaN fails); it is FREE iff kp_row[k] == -1 or status[kp_row[k]] != 0: a row
+ *      without a point yields its keypoints, a row with a point never does.
+ *   5. Proposal.  The proposal of (j, i) is the free keypoint within the threshold with the smallest (bits of (float) r2, k).  A pair
+ *      makes at most one proposal: a row never gains two keypoints in one image, nor one in an image it already visits.
+ *   6. Winner.  A keypoint proposed by several rows goes to the smallest ((uint64) bits of (float) r2 << 32) | j: one unsigned 64-bit
+ *      minimum.  A row that loses gets nothing in that image; there is no second choice.
+ *   7. Output.  kp_row_new [K] i32: the winner's row where there was one, kp_row[k] elsewhere; link_r2 [K] f32: the winner's (float) r2,
+ *      NaN elsewhere; counts [8] i64: [0] accepted links, [1] error bits, [2] sources, [3] (source, target) pairs, [4] pairs in front
+ *      and inside the grid, [5] proposals, [6] proposals that lost, [7] pairs without a proposal that have a keypoint within the
+ *      threshold owned by a row WITH a point (what a future point-merging step would serve).
+ *   8. Errors (counts[1]).  1: an obs_image outside [0, n); 2: offsets (kp_offsets) that do not start at 0, end at N (K) and ascend;
+ *      4: obs_image descending within a row; 8: a kp_row outside [-1, T).
+ * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, thresh_px negative or not finite, reach out of range, observations
+ *   without a row, keypoints without an image; the host routine also for the four error bits, and it then writes the bits to counts[1] and nothing else (the kernels
+ *   raise counts[1] instead, read nothing through the bad value, and write counts[0] = 0, kp_row_new = kp_row, link_r2 = NaN);
+ *   LOFTR_ERR_UNSUPPORTED for T or N >= 2^31, K > 2^31 - 1, a grid beyond the atlas's limits, more than 65535 image chunks;
+ *   LOFTR_ERR_WORKSPACE for a short workspace.
+ * Out of scope: merging two rows that both have a point, descriptor or fine-level verification of a link, second choices, changing the
+ *   two-view matches, per-image extents.  PARITY UNPINNED against COLMAP's CompleteTracks. */
+#define LOFTR_COMPLETE_MAX_REACH 8
+int loftr_complete_tracks_host(const long* offsets, long T, const int* obs_image, long N, const float* xyz, const uint8_t* status,
+                               const long* kp_offsets, const float* keypoints, const int* kp_cell, const int* kp_row, long K,
+                               const double* Kmat, const double* T_cam_from_world, const uint8_t* posed, int n_images, float inv, int gh,
+                               int gw, double thresh_px, int reach, int* kp_row_new, float* link_r2, long* counts);
+/* The kernels: two memsets (the claims, the counts) and four launches on the stream (0 the camera table, 1 the checks, 2 the links -- a
+ * thread per row and LOFTR_COMPLETE_IMAGE_CHUNK images per blockIdx.y; a proposal is one 64-bit atomic minimum --, 3 a thread per
+ * keypoint that writes the output).  No host synchronisation unless stage_ms is given: NULL, or LOFTR_COMPLETE_STAGES host floats that
+ * receive the GPU time of each launch (the call then waits for the stream).
+ * Workspace: loftr_complete_tracks_workspace_bytes(T, N, K, n_images): 192 bytes per image, 8 per keypoint; 0 for sizes out of range. */
+#define LOFTR_COMPLETE_STAGES 4
+#define LOFTR_COMPLETE_IMAGE_CHUNK 64
+size_t loftr_complete_tracks_workspace_bytes(long T, long N, long K, int n_images);
+int loftr_complete_tracks(const long* offsets, long T, const int* obs_image, long N, const float* xyz, const uint8_t* status,
+                          const long* kp_offsets, const float* keypoints, const int* kp_cell, const int* kp_row, long K,
+                          const double* Kmat, const double* T_cam_from_world, const uint8_t* posed, int n_images, float inv, int gh, int gw,
+                          double thresh_px, int reach, int* kp_row_new, float* link_r2, long* counts, void* ws, size_t ws_bytes,
+                          float* stage_ms, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

@@ -1523,6 +1523,65 @@ def register_corr(offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, c
                           (offsets, obs_image, obs_xy, xyz, status, posed, cam_offsets, cam_obs), min_corr, timings)
 
 
+# ---- track completion (csrc/complete.hip, csrc/complete_gpu.hip) -----------------------------------------------------------
+COMPLETE_COUNTS = 8
+COMPLETE_NAMES = ("n_links", "error_bits", "n_sources", "n_pairs", "n_inside", "n_proposals", "n_lost", "n_blocked")      # counts[0..7]
+COMPLETE_MAX_REACH = 8
+COMPLETE_STAGES = ("camera_table", "check", "link", "resolve")
+COMPLETE_ERRORS = BUNDLE_ERRORS[:2] + ((4, "obs_image must not descend within a row"), (8, "kp_row outside [-1, T)"))    # bits of counts[1]
+_CPL_ARGS = (("offsets", "int64", 1), ("obs_image", "int32", 1), ("xyz", "float32", 2), ("status", "uint8", 1), ("kp_offsets", "int64", 1),
+             ("keypoints", "float32", 2), ("kp_cell", "int32", 1), ("kp_row", "int32", 1), ("K", "float64", 3), ("T_cam_from_world", "float64", 3),
+             ("posed", "uint8", 1))
+_CPL_OUT = (("kp_row_new", "K", (), "int32"), ("link_r2", "K", (), "float32"))
+
+
+def _complete_tracks(B, what, hint, arrays, gh, gw, inv, thresh_px, reach, timings):
+    _check_args(B, what, hint, _CPL_ARGS, arrays)
+    offsets, obs_image, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, Tc, posed = arrays
+    N, n, T, Kp = obs_image.shape[0], posed.shape[0], offsets.shape[0] - 1, keypoints.shape[0]
+    if T < 0 or tuple(xyz.shape) != (T, 3) or status.shape[0] != T or kp_offsets.shape[0] != n + 1 or tuple(keypoints.shape) != (Kp, 2) or \
+            kp_cell.shape[0] != Kp or kp_row.shape[0] != Kp or tuple(K.shape) != (n, 3, 3) or tuple(Tc.shape) != (n, 4, 4):
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], xyz [T,3], status [T], kp_offsets [n+1], keypoints [K,2], kp_cell "
+                                 f"/ kp_row [K], K [n,3,3], T_cam_from_world [n,4,4] and posed [n], got {[tuple(a.shape) for a in arrays]}")
+    if not isinstance(reach, int) or isinstance(reach, bool) or not 0 <= reach <= COMPLETE_MAX_REACH:
+        raise ValueError(f"{what}: reach must be an integer in [0, {COMPLETE_MAX_REACH}], got {reach}")
+    if not (float(thresh_px) >= 0 and float(thresh_px) < float("inf")) or min(int(gh), int(gw)) < 0:
+        raise ValueError(f"{what}: thresh_px must be finite and >= 0 and the grid gh x gw >= 0, got {thresh_px}, {gh} x {gw}")
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _CPL_OUT, {"K": Kp}, COMPLETE_COUNTS, offsets)
+    ms = _StageMs(timings, COMPLETE_STAGES)
+    B.call("complete_tracks", (a[0], T, a[1], N, a[2], a[3], a[4], a[5], a[6], a[7], Kp, a[8], a[9], a[10], n, float(inv), int(gh), int(gw),
+                               float(thresh_px), reach, *[B.ptr(out[k]) for k in out]),
+           "offsets / kp_offsets must start at 0, end at N / K and ascend; obs_image must lie in [0, n_images) and not descend within a row; "
+           "kp_row must lie in [-1, T)", offsets, ws=(T, N, Kp, n), tail=(ms.arg,))
+    ms.report()
+    return out
+
+
+def complete_tracks_host(offsets, obs_image, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed, gh, gw, inv,
+                         thresh_px, reach):
+    """loftr_complete_tracks_host: the host routine that DEFINES track completion (include/loftr_hip.h) on numpy arrays: offsets [T+1] i64,
+    obs_image [N] i32, xyz [T,3] f32, status [T] u8, kp_offsets [n+1] i64, keypoints [K,2] f32, kp_cell / kp_row [K] i32, K [n,3,3] f64,
+    T_cam_from_world [n,4,4] f64, posed [n] u8; the atlas grid (gh, gw, inv), thresh_px and reach (0 .. COMPLETE_MAX_REACH cells).
+    -> dict of numpy arrays: kp_row_new [K] i32, link_r2 [K] f32 (NaN where there is no link), counts [8] i64 (COMPLETE_NAMES)."""
+    return _complete_tracks(_Host, "complete_tracks_host", "complete_tracks",
+                            (offsets, obs_image, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed), gh, gw, inv,
+                            thresh_px, reach, None)
+
+
+@_on_device
+def complete_tracks(offsets, obs_image, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed, gh, gw, inv, thresh_px,
+                    reach, timings=None):
+    """loftr_complete_tracks: the completion kernels (csrc/complete_gpu.hip) on GPU tensors of the dtypes and shapes of
+    complete_tracks_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in
+    counts[1], which the caller reads once (kp_row_new is then kp_row).  timings: a list that receives (stage, ms) pairs (the call then
+    waits for the stream)."""
+    return _complete_tracks(_Gpu, "complete_tracks", "the completion kernels have no CPU fallback; the host routine is complete_tracks_host",
+                            (offsets, obs_image, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed), gh, gw, inv,
+                            thresh_px, reach, timings)
+
+
 # ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip; DESIGN §17) ------------------------
 MODEL_COUNTS = 16
 MODEL_REASONS = ("n_kept", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside", "n_no_keypoint", "n_no_point",
