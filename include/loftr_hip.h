@@ -66,7 +66,7 @@ typedef enum {
  *     refinement loftr_bundle_adjust_focal_host, loftr_bundle_adjust_focal_workspace_bytes, loftr_bundle_adjust_focal), the
  *     correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
  *     loftr_register_corr), track completion (loftr_complete_tracks_host, loftr_complete_tracks_workspace_bytes,
- *     loftr_complete_tracks) */
+ *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -1028,7 +1028,7 @@ int loftr_register_corr(const long* offsets, long T, const int* obs_image, const
  *   7. Output.  kp_row_new [K] i32: the winner's row where there was one, kp_row[k] elsewhere; link_r2 [K] f32: the winner's (float) r2,
  *      NaN elsewhere; counts [8] i64: [0] accepted links, [1] error bits, [2] sources, [3] (source, target) pairs, [4] pairs in front
  *      and inside the grid, [5] proposals, [6] proposals that lost, [7] pairs without a proposal that have a keypoint within the
- *      threshold owned by a row WITH a point (what a future point-merging step would serve).
+ *      threshold owned by a row WITH a point (what track merging, below, serves).
  *   8. Errors (counts[1]).  1: an obs_image outside [0, n); 2: offsets (kp_offsets) that do not start at 0, end at N (K) and ascend;
  *      4: obs_image descending within a row; 8: a kp_row outside [-1, T).
  * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, thresh_px negative or not finite, reach out of range, observations
@@ -1056,6 +1056,62 @@ int loftr_complete_tracks(const long* offsets, long T, const int* obs_image, lon
                           const double* Kmat, const double* T_cam_from_world, const uint8_t* posed, int n_images, float inv, int gh, int gw,
                           double thresh_px, int reach, int* kp_row_new, float* link_r2, long* counts, void* ws, size_t ws_bytes,
                           float* stage_ms, void* stream);
+
+/* ---- track merging: rows whose points meet and agree become one track (csrc/merge_core.h holds every per-item step) ---------
+ * Completion stops where two rows both have a point.  Merging serves those meetings: a row with a point that projects onto a keypoint
+ * held by another row with a point, in an image it does not visit, becomes one row with it when the two share no image and every
+ * defining observation of both agrees with their weighted point.  Its whole result is again a relabelled kp_row.
+ * loftr_merge_tracks_host (csrc/merge.hip, host memory) DEFINES the result, loftr_merge_tracks (csrc/merge_gpu.hip, device memory)
+ * reproduces it bit for bit.
+ * Input: everything loftr_complete_tracks_host takes, plus obs_xy [N,2] f32 (the pixel of every observation) and obs_mask [N] u8 (the
+ *   observations that define the row's point: the triangulation's obs_inlier).  Arithmetic: fp64 without FMA contraction, + - * / only;
+ *   thr2 = thresh_px * thresh_px.
+ *   1. Source.  Row j is a source as in completion (status[j] == 0, finite xyz); w[j] = the number of its observations with
+ *      obs_mask != 0.
+ *   2. Meeting.  A source row j is projected into every target image i (posed, valid camera, not visited by j) by completion's rules
+ *      2-4: the same projection, cells and visiting order.  Its candidate in i is the keypoint k with r2(k) <= thr2 and the smallest
+ *      (bits of (float) r2, k) among those whose kp_row[k] = m is ANOTHER source row (m >= 0, m != j, m a source).  Free keypoints and
+ *      keypoints of rows without a point are ignored.  A (row, image) pair makes at most one meeting (j, m).
+ *   3. Disjoint.  The meeting is compatible iff rows j and m share no image: a merge walk over the two ascending obs_image lists, over
+ *      all observations, masked or not.  A merged track therefore never visits an image twice.
+ *   4. Agreement.  a = min(j, m), b = max(j, m); rejected if w[a] == 0 or w[b] == 0;
+ *      X[c] = ((double) w[a] * Xa[c] + (double) w[b] * Xb[c]) / (double)(w[a] + w[b]) in this operation order; every masked observation
+ *      of both rows must lie in an image that is posed with a valid camera and satisfy residual2(camera, X, obs_xy) <= thr2 (in front;
+ *      NaN fails).  The pair's score is the largest of these r2, held as the bits of (float) r2.  It depends on (a, b) alone.
+ *   5. Choice.  best [T] u64 starts as all ones (the empty entry).  An accepted meeting (j, m) does two unsigned 64-bit minima:
+ *      (bits << 32) | m into best[j], (bits << 32) | j into best[m].  For a fixed row the order by (bits, partner) is the order of its
+ *      pairs by (bits, min, max), a total order on pairs, so the globally smallest accepted pair is always mutual.
+ *   6. Merge.  Rows j and m merge iff each is the other's best.  The lower row survives: row_into[j] = row_into[m] = min(j, m);
+ *      row_into[t] = t elsewhere.  merge_r2[t] = the pair's score as a float for both rows of a merged pair, NaN elsewhere.  One pass:
+ *      a row merges with at most one other row, there are no chains; a call after a new triangulation merges further.
+ *   7. Output.  row_into [T] i32, merge_r2 [T] f32, kp_row_new [K] i32 = kp_row[k] < 0 ? kp_row[k] : row_into[kp_row[k]];
+ *      counts [8] i64: [0] merged pairs, [1] error bits, [2] sources, [3] (source, target) pairs, [4] meetings, [5] disjoint meetings,
+ *      [6] accepted meetings, [7] relabelled keypoints.  A pair met in several images or from both sides counts once per meeting;
+ *      every count is defined by the rule, none depends on a schedule.
+ *   8. Errors (counts[1]).  Completion's four bits with the same behaviour.
+ * Status: as loftr_complete_tracks_host; the host routine returns LOFTR_ERR_BAD_ARG for the four error bits after writing them to
+ *   counts[1] and nothing else; the kernels raise counts[1] instead, read nothing through the bad value and write row_into = identity,
+ *   merge_r2 = NaN, kp_row_new = kp_row, counts[0] = 0.
+ * Out of scope: chains and multi-way merges in one pass, merging through shared images, re-estimating the point (the next
+ *   triangulation does), descriptor checks, changing the two-view matches.  PARITY UNPINNED against COLMAP's MergeTracks. */
+int loftr_merge_tracks_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                            const float* xyz, const uint8_t* status, const long* kp_offsets, const float* keypoints, const int* kp_cell,
+                            const int* kp_row, long K, const double* Kmat, const double* T_cam_from_world, const uint8_t* posed,
+                            int n_images, float inv, int gh, int gw, double thresh_px, int reach, int* row_into, float* merge_r2,
+                            int* kp_row_new, long* counts);
+/* The kernels: two memsets (best, the counts) and five launches on the stream (0 the camera table and 1 the checks, completion's; 2 the
+ * meetings -- a thread per row and LOFTR_MERGE_IMAGE_CHUNK images per blockIdx.y; an accepted meeting is two 64-bit atomic minima --,
+ * 3 a thread per row that writes row_into and merge_r2, 4 a thread per keypoint that writes kp_row_new).  No host synchronisation unless
+ * stage_ms is given: NULL, or LOFTR_MERGE_STAGES host floats that receive the GPU time of each launch (the call then waits for the
+ * stream).  Workspace: loftr_merge_tracks_workspace_bytes(T, N, K, n_images): 192 bytes per image, 8 per row; 0 for sizes out of range. */
+#define LOFTR_MERGE_STAGES 5
+#define LOFTR_MERGE_IMAGE_CHUNK 64
+size_t loftr_merge_tracks_workspace_bytes(long T, long N, long K, int n_images);
+int loftr_merge_tracks(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                       const float* xyz, const uint8_t* status, const long* kp_offsets, const float* keypoints, const int* kp_cell,
+                       const int* kp_row, long K, const double* Kmat, const double* T_cam_from_world, const uint8_t* posed, int n_images,
+                       float inv, int gh, int gw, double thresh_px, int reach, int* row_into, float* merge_r2, int* kp_row_new, long* counts,
+                       void* ws, size_t ws_bytes, float* stage_ms, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

@@ -11,4 +11,5 @@ from .triangulation import Points3D, triangulate_tracks           # noqa: F401
 from .bundle import BundleResult, bundle_adjust                   # noqa: F401
 from .registration import Reconstruction, Registration, reconstruct_tracks, register_images    # noqa: F401
 from .completion import Completion, complete_tracks                # noqa: F401
+from .merging import Merge, merge_tracks                            # noqa: F401
 from .localization import LocalizationModel, QueryLocalizer, QueryPoses   # noqa: F401

@@ -144,7 +144,8 @@ class SfmResult:
                 R[r], t[r], ninl[r] = torch.from_numpy(est[0]).float(), torch.from_numpy(est[1]).float(), int(est[2].sum())
         return R, t, ninl
 
-    def reconstruct(self, K, init_row=None, init_candidates=8, thresh_px=4.0, pose_conf=0.99999, consistent_only=True, complete=False, **kwargs):
+    def reconstruct(self, K, init_row=None, init_candidates=8, thresh_px=4.0, pose_conf=0.99999, consistent_only=True, complete=False, merge=False,
+                    **kwargs):
         """Poses of the images and points of the tracks from intrinsics alone (registration.reconstruct_tracks) ->
         Reconstruction on this result's device, its ``points`` carrying the CSR arrays as ``triangulate`` attaches them.
         The initial pair is row ``init_row`` with its five-point pose (``pairwise_poses`` at ``thresh_px``).  With ``init_row=None``:
@@ -153,7 +154,10 @@ class SfmResult:
         triangulation's and the registration's threshold; the other keyword arguments are reconstruct_tracks'.
         ``complete=True``: after the loop, one ``complete`` over the posed images with the final intrinsics, then triangulate -> adjust
         (the same fixed images and ``ba``) -> triangulate on the relabelled atlas; the Reconstruction then carries it as ``.sfm`` and the
-        counts as ``stats['completion']``.  With the default nothing of this runs."""
+        counts as ``stats['completion']``.  ``merge=True``: after the loop (and after the completion and one triangulation
+        of it, when ``complete=True``), one ``merge`` of the tracks whose points meet and agree, then the same triangulate -> adjust ->
+        triangulate; ``.sfm`` is the relabelled atlas and ``stats['merge']`` the counts.  With the defaults nothing of this
+        runs."""
         from .registration import reconstruct_tracks, triangulate_posed
         dev = self.keypoints.device
         n = self.kp_offsets.numel() - 1
@@ -187,8 +191,7 @@ class SfmResult:
         rec = reconstruct_tracks(offsets, obs_image, xy, K, (a, b, R[init_row], t[init_row]), thresh_px=thresh_px, **kwargs)
         rec.points.offsets, rec.points.image, rec.points.keypoint = offsets, image, local
         rec.stats["init_row"], rec.stats["pair_inliers"] = init_row, ninl_host
-        if complete:
-            sfm2, done = self.complete(rec.points, rec.K, rec.T_cam_from_world, posed=rec.posed, thresh_px=thresh_px)
+        if complete or merge:
             ba = dict(kwargs.get("ba") or {})
             fixed = torch.zeros(n, dtype=torch.bool, device=dev)
             fixed[a] = True
@@ -196,13 +199,73 @@ class SfmResult:
             if extra is not None:
                 fixed |= torch.as_tensor(extra).to(dev) != 0
             tri = dict(thresh_px=thresh_px, min_angle_deg=kwargs.get("min_angle_deg", 1.5), consistent_only=consistent_only, posed=rec.posed)
-            pts = sfm2.triangulate(rec.K, rec.T_cam_from_world, **tri)
+            sfm2, pts = self, rec.points
+            if complete:
+                sfm2, done = sfm2.complete(pts, rec.K, rec.T_cam_from_world, posed=rec.posed, thresh_px=thresh_px)
+                pts = sfm2.triangulate(rec.K, rec.T_cam_from_world, **tri)
+                rec.stats.update(completion=done.stats)
+            if merge:
+                sfm2, merged = sfm2.merge(pts, rec.K, rec.T_cam_from_world, posed=rec.posed, thresh_px=thresh_px)
+                pts = sfm2.triangulate(rec.K, rec.T_cam_from_world, **tri)
+                rec.stats.update(merge=merged.stats)
             res = sfm2.adjust(pts, rec.K, rec.T_cam_from_world, fixed=fixed, **ba)
             rec.K = getattr(res, "K", rec.K)                             # (a result without refine_focal carries no K)
             rec.points = sfm2.triangulate(rec.K, res.T_cam_from_world, **tri)
             rec.T_cam_from_world, rec.bundle, rec.sfm = res.T_cam_from_world, res, sfm2
-            rec.stats.update(completion=done.stats, n_points=rec.points.stats["n_ok"], rms_px_after=res.rms_px_after)
+            rec.stats.update(n_points=rec.points.stats["n_ok"], rms_px_after=res.rms_px_after)
         return rec
+
+    def _rows_of(self, who, pts, K, T_cam_from_world):
+        """What ``complete`` and ``merge`` need of the rows of ``pts``: (the track id of every row, K and T on the device in fp64,
+        kp_row [K] i32: the row that holds a keypoint, or -1)."""
+        dev = self.keypoints.device
+        n, n_kp, rows = self.kp_offsets.numel() - 1, self.keypoints.shape[0], pts.offsets.numel() - 1
+        ok = self.track_ok.to(torch.bool)
+        if rows == int(ok.sum()):                                        # tracks(consistent_only=True); the same list when every track is ok
+            ids = torch.nonzero(ok).reshape(-1)
+        elif rows == ok.numel():
+            ids = torch.arange(rows, device=dev)
+        else:
+            raise ValueError(f"SfmResult.{who}: the Points3D has {rows} rows, this result {int(ok.sum())} consistent of {ok.numel()} tracks")
+        K, T = (torch.as_tensor(x).detach().to(dev, torch.float64) for x in (K, T_cam_from_world))
+        if tuple(K.shape) != (n, 3, 3) or tuple(T.shape) != (n, 4, 4):
+            raise ValueError(f"SfmResult.{who}: expected K [{n},3,3] and T_cam_from_world [{n},4,4], got {tuple(K.shape)}, {tuple(T.shape)}")
+        kp_row = torch.full((n_kp,), -1, dtype=torch.int32, device=dev)
+        row = torch.repeat_interleave(torch.arange(rows, device=dev), pts.offsets[1:] - pts.offsets[:-1])
+        kp_row[self.kp_offsets[pts.image] + pts.keypoint] = row.to(torch.int32)          # a keypoint belongs to one track: no two writes meet
+        return ids, K, T, kp_row
+
+    def _relabelled(self, track_id, **stats):
+        """A new SfmResult that shares every tensor with this one except ``track_id`` and the ``track_len`` recomputed from it."""
+        n_tracks = self.track_len.numel()
+        track_len = torch.bincount(track_id[track_id >= 0].to(torch.int64), minlength=n_tracks).to(torch.int32)
+        fields = {k: getattr(self, k) for k in self.FIELDS}
+        fields.update(track_id=track_id, track_len=track_len)
+        sfm2 = SfmResult(dict(self.stats, **stats), **fields)
+        sfm2.image_hw, sfm2.cell_px = self.image_hw, self.cell_px
+        return sfm2
+
+    def merge(self, pts, K, T_cam_from_world, posed=None, thresh_px=4.0, reach=None, timings=None):
+        """Merge the tracks whose points ``pts`` (a Points3D of ``triangulate`` on this result) meet and agree (merging.merge_tracks;
+        DESIGN §21) -> ``(sfm2, merge)``: a new SfmResult that shares every tensor with this one except ``track_id`` (the keypoints of
+        an absorbed track carry the surviving track's id) and ``track_len`` (recomputed: an absorbed track has length 0; ``track_ok`` is
+        unchanged, two merged tracks share no image), and the ``Merge`` whose rows are the tracks of ``pts``.  This result is left
+        untouched.  The points are not re-estimated: triangulate ``sfm2`` next.  Calling again after that merges further."""
+        from .merging import merge_tracks
+        if pts.offsets is None:
+            raise ValueError("SfmResult.merge: this Points3D carries no tracks (use SfmResult.triangulate)")
+        if self.image_hw is None or self.cell_px is None:
+            raise ValueError("SfmResult.merge: this result carries no grid geometry (image_hw / cell_px are set by KeypointAtlas.finalize)")
+        dev = self.keypoints.device
+        ids, K, T, kp_row = self._rows_of("merge", pts, K, T_cam_from_world)
+        xy = self.keypoints[self.kp_offsets[pts.image] + pts.keypoint]
+        done = merge_tracks(pts.offsets, pts.image.to(torch.int32), xy, pts.obs_inlier, self.kp_offsets, self.keypoints, kp_row, pts.xyz,
+                            pts.status, K, T, self.image_hw, self.cell_px, posed=None if posed is None else torch.as_tensor(posed).to(dev),
+                            thresh_px=thresh_px, reach=reach, timings=timings)
+        track_id = self.track_id                                         # (without a row there is nothing to merge)
+        if ids.numel() > 0:
+            track_id = torch.where(done.kp_row_new != kp_row, ids[done.kp_row_new.to(torch.int64).clamp(min=0)].to(torch.int32), self.track_id)
+        return self._relabelled(track_id, n_merges=done.stats["n_merges"]), done
 
     def complete(self, pts, K, T_cam_from_world, posed=None, thresh_px=4.0, reach=None, timings=None):
         """Let the points ``pts`` (a Points3D of ``triangulate`` on this result) claim the keypoints they project onto in the posed
@@ -220,33 +283,15 @@ class SfmResult:
         if self.image_hw is None or self.cell_px is None:
             raise ValueError("SfmResult.complete: this result carries no grid geometry (image_hw / cell_px are set by KeypointAtlas.finalize)")
         dev = self.keypoints.device
-        n, n_kp, rows = self.kp_offsets.numel() - 1, self.keypoints.shape[0], pts.offsets.numel() - 1
-        ok = self.track_ok.to(torch.bool)
-        if rows == int(ok.sum()):                                        # tracks(consistent_only=True); the same list when every track is ok
-            ids = torch.nonzero(ok).reshape(-1)
-        elif rows == ok.numel():
-            ids = torch.arange(rows, device=dev)
-        else:
-            raise ValueError(f"SfmResult.complete: the Points3D has {rows} rows, this result {int(ok.sum())} consistent of {ok.numel()} tracks")
-        K, T = (torch.as_tensor(x).detach().to(dev, torch.float64) for x in (K, T_cam_from_world))
-        if tuple(K.shape) != (n, 3, 3) or tuple(T.shape) != (n, 4, 4):
-            raise ValueError(f"SfmResult.complete: expected K [{n},3,3] and T_cam_from_world [{n},4,4], got {tuple(K.shape)}, {tuple(T.shape)}")
-        kp_row = torch.full((n_kp,), -1, dtype=torch.int32, device=dev)
-        row = torch.repeat_interleave(torch.arange(rows, device=dev), pts.offsets[1:] - pts.offsets[:-1])
-        kp_row[self.kp_offsets[pts.image] + pts.keypoint] = row.to(torch.int32)          # a keypoint belongs to one track: no two writes meet
+        ids, K, T, kp_row = self._rows_of("complete", pts, K, T_cam_from_world)
+        rows = ids.numel()
         done = complete_tracks(pts.offsets, pts.image.to(torch.int32), self.kp_offsets, self.keypoints, kp_row, pts.xyz, pts.status, K, T,
                                self.image_hw, self.cell_px, posed=None if posed is None else torch.as_tensor(posed).to(dev),
                                thresh_px=thresh_px, reach=reach, timings=timings)
         track_id = self.track_id                                         # (without a row there is no link)
         if rows > 0:
             track_id = torch.where(done.linked, ids[done.kp_row_new.to(torch.int64).clamp(min=0)].to(torch.int32), self.track_id)
-        n_tracks = self.track_len.numel()
-        track_len = torch.bincount(track_id[track_id >= 0].to(torch.int64), minlength=n_tracks).to(torch.int32)
-        fields = {k: getattr(self, k) for k in self.FIELDS}
-        fields.update(track_id=track_id, track_len=track_len)
-        sfm2 = SfmResult(dict(self.stats, n_completion_links=done.stats["n_links"]), **fields)
-        sfm2.image_hw, sfm2.cell_px = self.image_hw, self.cell_px
-        return sfm2, done
+        return self._relabelled(track_id, n_completion_links=done.stats["n_links"]), done
 
     def adjust(self, pts, K, T_cam_from_world, fixed=None, **kwargs):
         """Bundle adjustment of the poses and of the points ``pts`` (a Points3D of ``triangulate`` on this result) over the observations

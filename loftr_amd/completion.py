@@ -65,6 +65,22 @@ def _raise(what, bits, cells):
         raise ValueError(f"{what}: {_CELLS_BAD}")
 
 
+def check_host_tables(what, offsets, obs_image, kp_offsets, keypoints, kp_row, n, T):
+    """The errors the kernels report through counts[1], raised on host arrays before the host routine runs (completion and merging)."""
+    if not (all(x.ndim == 1 for x in (offsets, obs_image, kp_offsets, kp_row)) and keypoints.ndim == 2):
+        return
+    _tracks.check_host(what, offsets, obs_image, n)
+    if kp_offsets.size and (kp_offsets[0] != 0 or kp_offsets[-1] != keypoints.shape[0] or (np.diff(kp_offsets) < 0).any()):
+        raise ValueError(f"{what}: kp_offsets must start at 0, end at the number of keypoints and ascend")
+    inner = np.ones(max(obs_image.shape[0] - 1, 0), bool)
+    starts = offsets[1:-1]
+    inner[starts[(starts > 0) & (starts < obs_image.shape[0])] - 1] = False               # a step across a row boundary may descend
+    if (np.diff(obs_image)[inner] < 0).any():
+        raise ValueError(f"{what}: " + ops.COMPLETE_ERRORS[2][1])
+    if kp_row.size and (kp_row.min() < -1 or kp_row.max() >= T):
+        raise ValueError(f"{what}: " + ops.COMPLETE_ERRORS[3][1])
+
+
 def complete_tracks(offsets, obs_image, kp_offsets, keypoints, kp_row, xyz, status, K, T_cam_from_world, image_hw, cell_px, posed=None,
                     thresh_px=4.0, reach=None, timings=None):
     """Let the rows that have a point claim the keypoints they project onto -> ``Completion``.
@@ -113,17 +129,7 @@ def complete_tracks(offsets, obs_image, kp_offsets, keypoints, kp_row, xyz, stat
         n = a[2].shape[0] - 1
         p = np.ones(max(n, 0), np.uint8) if posed is None else np.ascontiguousarray(host(posed) != 0).astype(np.uint8)
         T = a[0].shape[0] - 1
-        if all(x.ndim == 1 for x in (a[0], a[1], a[2], a[4])) and a[3].ndim == 2:       # the errors the kernels report through counts[1]
-            _tracks.check_host(what, a[0], a[1], n)
-            if a[2].size and (a[2][0] != 0 or a[2][-1] != a[3].shape[0] or (np.diff(a[2]) < 0).any()):
-                raise ValueError(f"{what}: kp_offsets must start at 0, end at the number of keypoints and ascend")
-            inner = np.ones(max(a[1].shape[0] - 1, 0), bool)
-            starts = a[0][1:-1]
-            inner[starts[(starts > 0) & (starts < a[1].shape[0])] - 1] = False          # a step across a row boundary may descend
-            if (np.diff(a[1])[inner] < 0).any():
-                raise ValueError(f"{what}: " + ops.COMPLETE_ERRORS[2][1])
-            if a[4].size and (a[4].min() < -1 or a[4].max() >= T):
-                raise ValueError(f"{what}: " + ops.COMPLETE_ERRORS[3][1])
+        check_host_tables(what, a[0], a[1], a[2], a[3], a[4], n, T)
         kp_cell, cells = ops.model_cells_host(a[2], a[3], a[4], max(T, 0), gh, gw, inv)
         out = ops.complete_tracks_host(a[0], a[1], a[5], a[6], a[2], a[3], kp_cell, a[4], a[7], a[8], p, gh, gw, inv, float(thresh_px), reach)
         out = {k: torch.from_numpy(v) for k, v in out.items()}

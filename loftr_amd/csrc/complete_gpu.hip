@@ -16,8 +16,7 @@
 // resolve kernel; counts[1] is raised by the check kernel and read by the link kernel, which returns at once on a bad table and so
 // reads nothing through a bad value; every claim is then empty and the resolve kernel copies kp_row.  No persistent or waiting kernel,
 // no graph, no grid-wide barrier.  Integer atomics only.  Plain C++, ordinary vector stores.
-#include "common.h"
-#include "complete_core.h"
+#include "complete_kernels.h"                                                        // the camera table and the table check, shared with merge_gpu.hip
 #include "stage_timer.h"
 
 #pragma clang fp contract(off)
@@ -26,30 +25,7 @@ namespace {
 
 using namespace complete;
 
-constexpr int kThreads = 256;
 constexpr int kChunk = LOFTR_COMPLETE_IMAGE_CHUNK;                               // images per blockIdx.y (a tuning constant: no result depends on it)
-typedef unsigned long long u64;
-
-// grid ceil(n_images / 64) x 64
-__global__ void complete_camera_kernel(const double* __restrict__ K, const double* __restrict__ T, int n_images, double* __restrict__ tab) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_images) return;
-  double t[tri::kCam];
-  tri::cam_table(K + 9 * (long)i, T + 16 * (long)i, t);
-  for (int k = 0; k < tri::kCam; ++k) tab[(long)tri::kCam * i + k] = t[k];
-}
-
-// grid ceil(max(T, K, n) / 256) x 256
-__global__ void __launch_bounds__(kThreads) complete_check_kernel(In a, u64* counts) {
-  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
-  int err = 0;
-  if (t < a.T) err |= check_row(a, t);
-  if (t < a.K) err |= check_keypoint(a, t);
-  if (t < a.n) err |= check_image(a, (int)t);
-  if (err) atomicOr(counts + kErrors, (u64)err);
-}
-
-__device__ __forceinline__ unsigned votes(bool p) { return (unsigned)__popcll(__ballot(p)); }
 
 // grid ceil(T / 256) x max(1, ceil(n / kChunk)), 256 threads
 __global__ void __launch_bounds__(kThreads) complete_link_kernel(In a, u64* __restrict__ claim, u64* counts) {

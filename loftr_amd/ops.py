@@ -1582,6 +1582,63 @@ def complete_tracks(offsets, obs_image, xyz, status, kp_offsets, keypoints, kp_c
                             thresh_px, reach, timings)
 
 
+# ---- track merging (csrc/merge.hip, csrc/merge_gpu.hip) ------------------------------------------------------------------------
+MERGE_COUNTS = 8
+MERGE_NAMES = ("n_merges", "error_bits", "n_sources", "n_pairs", "n_meetings", "n_disjoint", "n_accepted", "n_relabelled")   # counts[0..7]
+MERGE_STAGES = ("camera_table", "check", "meet", "pair", "relabel")
+_MRG_ARGS = (("offsets", "int64", 1), ("obs_image", "int32", 1), ("obs_xy", "float32", 2), ("obs_mask", "uint8", 1)) + _CPL_ARGS[2:]
+_MRG_OUT = (("row_into", "T", (), "int32"), ("merge_r2", "T", (), "float32"), ("kp_row_new", "K", (), "int32"))
+
+
+def _merge_tracks(B, what, hint, arrays, gh, gw, inv, thresh_px, reach, timings):
+    _check_args(B, what, hint, _MRG_ARGS, arrays)
+    offsets, obs_image, obs_xy, obs_mask, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, Tc, posed = arrays
+    N, n, T, Kp = obs_image.shape[0], posed.shape[0], offsets.shape[0] - 1, keypoints.shape[0]
+    if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or status.shape[0] != T or \
+            kp_offsets.shape[0] != n + 1 or tuple(keypoints.shape) != (Kp, 2) or kp_cell.shape[0] != Kp or kp_row.shape[0] != Kp or \
+            tuple(K.shape) != (n, 3, 3) or tuple(Tc.shape) != (n, 4, 4):
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], status [T], kp_offsets "
+                                 f"[n+1], keypoints [K,2], kp_cell / kp_row [K], K [n,3,3], T_cam_from_world [n,4,4] and posed [n], got "
+                                 f"{[tuple(a.shape) for a in arrays]}")
+    if not isinstance(reach, int) or isinstance(reach, bool) or not 0 <= reach <= COMPLETE_MAX_REACH:
+        raise ValueError(f"{what}: reach must be an integer in [0, {COMPLETE_MAX_REACH}], got {reach}")
+    if not (float(thresh_px) >= 0 and float(thresh_px) < float("inf")) or min(int(gh), int(gw)) < 0:
+        raise ValueError(f"{what}: thresh_px must be finite and >= 0 and the grid gh x gw >= 0, got {thresh_px}, {gh} x {gw}")
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _MRG_OUT, {"T": max(T, 0), "K": Kp}, MERGE_COUNTS, offsets)
+    ms = _StageMs(timings, MERGE_STAGES)
+    B.call("merge_tracks", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], a[8], a[9], Kp, a[10], a[11], a[12], n, float(inv), int(gh),
+                            int(gw), float(thresh_px), reach, *[B.ptr(out[k]) for k in out]),
+           "offsets / kp_offsets must start at 0, end at N / K and ascend; obs_image must lie in [0, n_images) and not descend within a row; "
+           "kp_row must lie in [-1, T)", offsets, ws=(T, N, Kp, n), tail=(ms.arg,))
+    ms.report()
+    return out
+
+
+def merge_tracks_host(offsets, obs_image, obs_xy, obs_mask, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed,
+                      gh, gw, inv, thresh_px, reach):
+    """loftr_merge_tracks_host: the host routine that DEFINES track merging (include/loftr_hip.h) on numpy arrays: those of
+    complete_tracks_host plus obs_xy [N,2] f32 and obs_mask [N] u8 after obs_image.
+    -> dict of numpy arrays: row_into [T] i32, merge_r2 [T] f32 (NaN where the row does not merge), kp_row_new [K] i32, counts [8] i64
+    (MERGE_NAMES)."""
+    return _merge_tracks(_Host, "merge_tracks_host", "merge_tracks",
+                         (offsets, obs_image, obs_xy, obs_mask, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed),
+                         gh, gw, inv, thresh_px, reach, None)
+
+
+@_on_device
+def merge_tracks(offsets, obs_image, obs_xy, obs_mask, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed, gh, gw,
+                 inv, thresh_px, reach, timings=None):
+    """loftr_merge_tracks: the merging kernels (csrc/merge_gpu.hip) on GPU tensors of the dtypes and shapes of merge_tracks_host; the same
+    result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in counts[1], which the caller reads
+    once (row_into is then the identity, kp_row_new is kp_row).  timings: a list that receives (stage, ms) pairs (the call then waits for
+    the stream)."""
+    return _merge_tracks(_Gpu, "merge_tracks", "the merging kernels have no CPU fallback; the host routine is merge_tracks_host",
+                         (offsets, obs_image, obs_xy, obs_mask, xyz, status, kp_offsets, keypoints, kp_cell, kp_row, K, T_cam_from_world, posed),
+                         gh, gw, inv, thresh_px, reach, timings)
+
+
 # ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip; DESIGN §17) ------------------------
 MODEL_COUNTS = 16
 MODEL_REASONS = ("n_kept", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside", "n_no_keypoint", "n_no_point",

@@ -63,7 +63,7 @@ class Reconstruction:
     def __init__(self, T_cam_from_world, posed, round_registered, points, bundle, stats, K=None):
         self.T_cam_from_world, self.posed, self.round_registered = T_cam_from_world, posed, round_registered
         self.points, self.bundle, self.stats, self.K = points, bundle, stats, K
-        self.sfm = None                                                 # the relabelled atlas of SfmResult.reconstruct(complete=True)
+        self.sfm = None                                                 # the relabelled atlas of SfmResult.reconstruct(complete=True / merge=True)
 
 
 def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed, min_corr=15, min_inliers=15, thresh_px=4.0,
