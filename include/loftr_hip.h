@@ -63,8 +63,9 @@ typedef enum {
  *     loftr_triangulate_tracks_workspace_bytes), localisation against the triangulated model (loftr_model_cells_host,
  *     loftr_model_cells, loftr_model_lookup_host, loftr_model_lookup_workspace_bytes, loftr_model_lookup), bundle adjustment of the
  *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust; with per-image focal
- *     refinement loftr_bundle_adjust_focal_host, loftr_bundle_adjust_focal_workspace_bytes, loftr_bundle_adjust_focal), the
- *     correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
+ *     refinement loftr_bundle_adjust_focal_host, loftr_bundle_adjust_focal_workspace_bytes, loftr_bundle_adjust_focal; with one
+ *     focal step per group of images loftr_bundle_adjust_shared_host, loftr_bundle_adjust_shared_workspace_bytes,
+ *     loftr_bundle_adjust_shared), the correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
  *     loftr_register_corr), track completion (loftr_complete_tracks_host, loftr_complete_tracks_workspace_bytes,
  *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks) */
 #define LOFTR_HIP_ABI_VERSION 25
@@ -941,8 +942,8 @@ int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const
  *   counts[13] = the number of refining cameras.
  * Status: as above; LOFTR_ERR_BAD_ARG also for min_focal_obs < 1, bounds that are not finite or do not straddle 1, and null
  *   refine_focal / K_out / cam_focal with n_images > 0.  Workspace: loftr_bundle_adjust_focal_workspace_bytes (about 1100 bytes per image).
- * Out of scope: intrinsics shared between images (they couple camera blocks, so U stops being block diagonal), principal point and
- *   distortion, focal refinement of a fixed-pose camera, focal priors.  PARITY UNPINNED against Ceres / COLMAP. */
+ * Out of scope: principal point and distortion, focal refinement of a fixed-pose camera (the grouped rule below has it), focal priors.
+ *   PARITY UNPINNED against Ceres / COLMAP. */
 int loftr_bundle_adjust_focal_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
                                    const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
                                    const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs, double huber_px,
@@ -957,6 +958,58 @@ int loftr_bundle_adjust_focal(const long* offsets, long T, const int* obs_image,
                               double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out,
                               uint8_t* cam_focal, long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches,
                               void* stream);
+
+/* ---- bundle adjustment with one focal step per GROUP of images (one physical camera) --------------------------------------
+ * The two rules above with ONE relative focal step delta_g per group of images instead of one per image; everything not named here is
+ * unchanged.  loftr_bundle_adjust_shared_host DEFINES the result, loftr_bundle_adjust_shared reproduces it bit for bit.
+ *   Groups.  cam_group [n] i32 (the group of image i, in [0, G)), group_offsets [G+1] i64 (0 first, n last, ascending, no empty group),
+ *      group_cams [n] i32: the members of group 0, then of group 1, ..., strictly ascending within a group, the groups in the order of
+ *      their first members (the stable sort of cam_group after that relabelling).  1 <= G <= n (G = 0 with n = 0).
+ *   Who carries.  Image i CARRIES iff it is valid, refine_focal[i] != 0 and it has at least 1 active observation; its pose may be fixed.
+ *      Group g REFINES iff its carrying members together have at least min_focal_obs active observations.  cam_focal[i] = i carries and
+ *      its group refines.  A member without cam_focal gets its K back bit for bit.  What is shared is the step, not the value: every
+ *      member with cam_focal takes fx' = fx (1 + delta_g), skew' = skew (1 + delta_g), fy' = fy (1 + delta_g) on its own fx, skew, fy.
+ *      The products are formed through the group: s_g starts at 1, a trial has s_g' = s_g (1 + delta_g), and the member's trial values
+ *      are fx_in s_g', skew_in s_g', fy_in s_g' (the input K's), so that after any number of accepted trials the members of a group
+ *      differ from their inputs by ONE factor, each rounded once.
+ *   Live cameras.  A camera takes part in the step when it is free or has cam_focal.  The six pose columns of A are +0 for a camera that is
+ *      not free (`fixed` speaks of the pose only here), the seventh is +0 for one without cam_focal.  U (28 entries) and g_c (7) are summed
+ *      for every live camera by rule 5's osum64.  A camera that is not free gets its 16 pose doubles back bit for bit.
+ *   Operator.  With S7, b7 the 7-wide quantities of §18.1 and E copying delta_g into the seventh slot of the members with cam_focal, the
+ *      system is E^T S7 E x = E^T b7 over 6 unknowns per free camera and 1 per refining group.  E^T: osum64 over the group's list, element
+ *      l being the l-th member; a member without cam_focal adds nothing.  The point half is rule 6's over the active observations of live
+ *      cameras, the vector of a camera being (its 6 pose entries, or +0 when it is not free; its group's entry, or +0 without cam_focal).
+ *      The camera half of a free camera is rows 0..5 of U7d p - sum A^T (B z_j), U7d with its first six diagonals damped.  The seventh
+ *      entry of a member with cam_focal is sum_{k<6} U_k7 p_k - (sum A^T (B z_j))_7; the group's entry is d p_g + E^T of those, where
+ *      d_g = E^T of U77 and d = d_g (1 + lambda), or lambda when d_g is 0: damped once, at the group.  The right-hand side is
+ *      E^T of b7 = -(g_c - sum A^T (B y_j)) likewise.
+ *   Preconditioner.  The 6 x 6 L D L^T of the damped pose block per free camera, and 1 / d per refining group.  A non-positive pivot or a
+ *      non-positive d rejects the step.
+ *   Dot products.  6 terms sequentially per camera (+0 when it is not free), osum over the cameras; 1 term per group (+0 when it does
+ *      not refine), osum over the groups; the result is the camera sum plus the group sum, in that order.
+ *   Trial.  Rule 7 for the free cameras; the focal step and §18.1's bound test for every member with cam_focal.
+ * Input added to §18.1's: cam_group, group_offsets, group_cams, G.  Output added: group_focal [G] u8; counts[13] = the images with
+ *   cam_focal, counts[14] = the refining groups.  Error bit 8 of counts[1]: cam_group / group_offsets / group_cams are not that grouping
+ *   (the host routine returns LOFTR_ERR_BAD_ARG, the kernels raise the bit, read nothing through the bad value and run no trial).
+ * Status: §18.1's; LOFTR_ERR_BAD_ARG also for G outside [1, n] (0 with n = 0) and null group arrays.  Workspace:
+ *   loftr_bundle_adjust_shared_workspace_bytes: §18.1's plus 76 bytes per image (sized by n_images, whatever G is).
+ * Out of scope: groups that share a value rather than a step, principal point, distortion, focal priors.  PARITY UNPINNED. */
+int loftr_bundle_adjust_shared_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                    const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                    const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                    const int* cam_group, const long* group_offsets, const int* group_cams, int G, double huber_px,
+                                    int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs, double focal_lo,
+                                    double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
+                                    uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal, long* counts);
+size_t loftr_bundle_adjust_shared_workspace_bytes(long T, long N, int n_images);
+int loftr_bundle_adjust_shared(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                               const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                               const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs, const int* cam_group,
+                               const long* group_offsets, const int* group_cams, int G, double huber_px, int max_iters, int pcg_iters,
+                               double pcg_tol, double ftol, int min_focal_obs, double focal_lo, double focal_hi, double* T_out,
+                               float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out,
+                               uint8_t* cam_focal, uint8_t* group_focal, long* counts, void* ws, size_t ws_bytes, float* class_ms,
+                               long* class_launches, void* stream);
 
 /* ---- correspondence table of the images without a pose (csrc/register_core.h holds every per-item step) -------------------
  * The 2D-3D correspondences that the tracks give the images that have no pose yet, gathered per image in a defined order: the input of

@@ -55,8 +55,34 @@ def group_by_image(obs_image, n_images):
     return cam_offsets, cam_obs
 
 
-def raise_error_bits(what, bits):
-    """The first set error bit of a counts word that was read back -> ValueError."""
-    for bit, text in ERRORS:
+def group_by_camera(camera_ids):
+    """The images grouped by camera -> (cam_group [n] i32, group_offsets [G+1] i64, group_cams [n] i32), of the kind of ``camera_ids``
+    (an integer tensor or numpy array ``[n]``): the ids are relabelled to dense groups ordered by their smallest member image, then a
+    stable sort as in ``group_by_image``.  DESIGN §18.2."""
+    if isinstance(camera_ids, torch.Tensor):
+        ids = camera_ids.to(torch.int64)
+        n, dev = ids.numel(), ids.device
+        uniq, inv = torch.unique(ids, return_inverse=True)                 # (sorted by id)
+        first = torch.full((uniq.numel(),), n, dtype=torch.int64, device=dev).scatter_reduce(0, inv, torch.arange(n, device=dev), "amin")
+        rank = torch.empty_like(first)
+        rank[torch.argsort(first)] = torch.arange(uniq.numel(), device=dev)
+        group = rank[inv]
+        group_cams = torch.sort(group, stable=True).indices.to(torch.int32)
+        group_offsets = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=dev)
+        group_offsets[1:] = torch.cumsum(torch.bincount(group, minlength=uniq.numel()), 0)
+        return group.to(torch.int32), group_offsets, group_cams
+    ids = np.asarray(camera_ids).astype(np.int64)
+    uniq, first, inv = np.unique(ids, return_index=True, return_inverse=True)
+    rank = np.empty(uniq.size, np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(uniq.size)
+    group = rank[inv.reshape(-1)]
+    group_offsets = np.zeros(uniq.size + 1, np.int64)
+    group_offsets[1:] = np.cumsum(np.bincount(group, minlength=uniq.size))
+    return group.astype(np.int32), group_offsets, np.argsort(group, kind="stable").astype(np.int32)
+
+
+def raise_error_bits(what, bits, errors=None):
+    """The first set error bit of a counts word that was read back -> ValueError (``errors``: the table of the call, ERRORS by default)."""
+    for bit, text in errors or ERRORS:
         if bits & bit:
             raise ValueError(f"{what}: {text} (found on the device)")

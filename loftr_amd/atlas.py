@@ -209,7 +209,10 @@ class SfmResult:
                 pts = sfm2.triangulate(rec.K, rec.T_cam_from_world, **tri)
                 rec.stats.update(merge=merged.stats)
             res = sfm2.adjust(pts, rec.K, rec.T_cam_from_world, fixed=fixed, **ba)
-            rec.K = getattr(res, "K", rec.K)                             # (a result without refine_focal carries no K)
+            K_in, rec.K = rec.K, getattr(res, "K", rec.K)                # (a result without refine_focal carries no K)
+            if hasattr(res, "cam_group"):                                # (§18.2: an image without a pose keeps its camera's scale)
+                from .registration import _follow_group
+                rec.K = _follow_group(K_in, rec.K, res.cam_group.long(), res.cam_focal, res.group_focal.numel())
             rec.points = sfm2.triangulate(rec.K, res.T_cam_from_world, **tri)
             rec.T_cam_from_world, rec.bundle, rec.sfm = res.T_cam_from_world, res, sfm2
             rec.stats.update(n_points=rec.points.stats["n_ok"], rms_px_after=res.rms_px_after)
@@ -297,7 +300,8 @@ class SfmResult:
         """Bundle adjustment of the poses and of the points ``pts`` (a Points3D of ``triangulate`` on this result) over the observations
         the triangulation kept (bundle.bundle_adjust) -> BundleResult on this result's device.  ``fixed`` and the keyword
         arguments are bundle_adjust's; the intended loop is triangulate -> adjust -> triangulate(K, res.T_cam_from_world).  With
-        ``refine_focal`` (True or an [n] mask) the focal lengths are refined as well and the loop goes on with ``res.K``."""
+        ``refine_focal`` (True or an [n] mask; DESIGN §18.1) the focal lengths are refined as well and the loop goes on with ``res.K``;
+        with ``camera_ids`` ([n] integers) the images of one camera share that step."""
         from .bundle import bundle_adjust
         if pts.offsets is None:
             raise ValueError("SfmResult.adjust: this Points3D carries no tracks (use SfmResult.triangulate)")
@@ -308,6 +312,8 @@ class SfmResult:
             fixed = torch.as_tensor(fixed).to(dev)
         if kwargs.get("refine_focal") is not None and kwargs["refine_focal"] is not True:
             kwargs["refine_focal"] = torch.as_tensor(kwargs["refine_focal"]).to(dev)
+        if kwargs.get("camera_ids") is not None:                         # (images with equal ids share one focal step)
+            kwargs["camera_ids"] = torch.as_tensor(kwargs["camera_ids"]).to(dev)
         return bundle_adjust(pts.offsets, pts.image.to(torch.int32), xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **kwargs)
 
     def to_host(self):

@@ -19,6 +19,12 @@ parameters (DESIGN §18.1; ``loftr_bundle_adjust_focal_host`` and its kernels); 
 
     res = sfm.adjust(pts, K, T_cam_from_world, fixed=known, refine_focal=True)
     pts = sfm.triangulate(res.K, res.T_cam_from_world)
+
+Where many images come from ONE camera (a video, a ScanNet sequence, a phone walk, a rig, a few bodies), ``camera_ids`` shares that
+step between the images of a camera (``loftr_bundle_adjust_shared_host`` and its kernels): one parameter per camera,
+estimated from every observation of every one of its images, the fixed-pose ones included::
+
+    res = sfm.adjust(pts, K, T_cam_from_world, fixed=known, refine_focal=True, camera_ids=ids)     # ids [n]: equal ids, one camera
 """
 import numpy as np
 import torch
@@ -27,6 +33,7 @@ from . import _tracks, ops
 
 _OUT = ("T_cam_from_world", "xyz", "obs_active", "cam_free", "point_active")
 _OUT_FOCAL = ("K", "cam_focal")
+_OUT_SHARED = ("cam_group", "group_focal")
 _ARGS = ("offsets", "obs_image", "obs_xy", "obs_mask", "xyz", "K", "T_cam_from_world")
 
 
@@ -40,14 +47,16 @@ class BundleResult:
     converged, max_iters, stalled, nothing_to_adjust); ``stats``: dict of the counts.
 
     A call with ``refine_focal`` also carries ``K [n,3,3] f64`` (the input's bits for a camera that does not refine its focal),
-    ``cam_focal [n] bool`` and ``stats['n_focal_cameras']``; ``FIELDS`` of that result names them too."""
+    ``cam_focal [n] bool`` and ``stats['n_focal_cameras']``; ``FIELDS`` of that result names them too.  A call with ``camera_ids`` adds
+    ``cam_group [n] i32`` (the dense group of each image, groups ordered by their smallest member), ``group_focal [G] bool`` (the group
+    refined) and ``stats['n_focal_groups']``."""
 
     FIELDS = _OUT
 
     def __init__(self, stats, **tensors):
         self.stats = stats
         if "K" in tensors:                                               # a call with refine_focal: K and cam_focal as well
-            self.FIELDS = _OUT + _OUT_FOCAL
+            self.FIELDS = _OUT + _OUT_FOCAL + (_OUT_SHARED if "cam_group" in tensors else ())
         for k in self.FIELDS:
             setattr(self, k, tensors[k])
         for k in ("cost_before", "cost_after", "rms_px_before", "rms_px_after", "n_iters", "n_accepted", "n_pcg", "status"):
@@ -61,7 +70,7 @@ class BundleResult:
 
 
 def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed=None, huber_px=0.0, max_iters=30, pcg_iters=30,
-                  pcg_tol=1e-2, ftol=1e-9, timings=None, refine_focal=None, min_focal_obs=20, focal_bounds=(0.5, 2.0)):
+                  pcg_tol=1e-2, ftol=1e-9, timings=None, refine_focal=None, min_focal_obs=20, focal_bounds=(0.5, 2.0), camera_ids=None):
     """Refine poses and points over the reprojection error -> ``BundleResult``.
 
     ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``; ``obs_mask [N]`` (bool or integers: which
@@ -80,7 +89,14 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     those images refine one relative focal step each -- fx, skew and fy scale together, cx and cy stay -- next to their pose.  An image
     refines only if it is free and has at least ``min_focal_obs`` active observations; a trial that takes a focal outside
     ``focal_bounds = (lo, hi)`` times its input value is rejected.  The result then carries ``K``, ``cam_focal`` and
-    ``stats['n_focal_cameras']``.  Intrinsics shared between images, principal point, distortion and focal priors are not modelled."""
+    ``stats['n_focal_cameras']``.  Principal point, distortion and focal priors are not modelled.
+
+    ``camera_ids`` (needs ``refine_focal``): ``[n]`` non-negative integers on the device of the other arguments; images with
+    equal ids are one physical camera and share ONE relative step -- every member keeps its own fx, skew, fy (so images stored at different
+    resize scales work) and all are multiplied by the same ``1 + delta``.  An image carries its camera's focal when it is valid, flagged in
+    ``refine_focal`` and has an active observation, whether or not its pose is ``fixed``; a camera refines when its carrying images
+    together have at least ``min_focal_obs`` active observations.  ``None`` is the per-image call above, unchanged bit for bit.  The
+    result adds ``cam_group``, ``group_focal`` and ``stats['n_focal_groups']``."""
     what = "bundle_adjust"
     args = [offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world]
     params = ops._ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol)
@@ -91,7 +107,24 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
         focal = ops._ba_focal_params(what, min_focal_obs, *focal_bounds)
         if refine_focal is False:
             raise ValueError(f"{what}: refine_focal must be None, True or an [n] mask")
+    if camera_ids is not None and focal is None:
+        raise ValueError(f"{what}: camera_ids shares the focal step of refine_focal between images; pass refine_focal as well")
     gpu = _tracks.one_device(what, _ARGS + ("fixed",), args + ([] if fixed is None else [fixed]))   # ("fixed" is named only when given)
+    neg_id = None
+    if camera_ids is not None:
+        on_gpu = isinstance(camera_ids, torch.Tensor) and camera_ids.is_cuda
+        if on_gpu != gpu or (gpu and camera_ids.device != args[0].device):
+            raise ValueError(f"{what}: camera_ids is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no "
+                             "silent fallback: move it to their device")
+        if not on_gpu:
+            camera_ids = camera_ids.detach().numpy() if isinstance(camera_ids, torch.Tensor) else np.asarray(camera_ids)
+        _tracks.integers(what, "camera_ids", camera_ids)
+        if tuple(camera_ids.shape) != (len(K),):
+            raise ValueError(f"{what}: camera_ids must have shape ({len(K)},), got {tuple(camera_ids.shape)}")
+        if on_gpu:
+            neg_id = (camera_ids.detach() < 0).any().to(torch.int64).reshape(1)          # read with the counts: the one readback
+        elif camera_ids.size and camera_ids.min() < 0:
+            raise ValueError(f"{what}: camera_ids must not be negative")
     if focal is not None and refine_focal is not True:
         on_gpu = isinstance(refine_focal, torch.Tensor) and refine_focal.is_cuda
         if on_gpu != gpu or (gpu and refine_focal.device != args[0].device):
@@ -117,7 +150,12 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             out = ops.bundle_adjust(*a, fx, *_tracks.group_by_image(a[1], n), *params, timings=timings)
         else:
             rf = torch.ones(n, dtype=torch.uint8, device=dev) if refine_focal is True else (refine_focal.detach() != 0).to(torch.uint8)
-            out = ops.bundle_adjust_focal(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal, timings=timings)
+            if camera_ids is None:
+                out = ops.bundle_adjust_focal(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal, timings=timings)
+            else:
+                groups = _tracks.group_by_camera(camera_ids.detach())
+                out = ops.bundle_adjust_shared(*a, fx, *_tracks.group_by_image(a[1], n), rf, *groups, *params, *focal, timings=timings)
+                out["cam_group"] = groups[0]
     else:
         dts = (np.int64, np.int32, np.float32, None, np.float32, np.float64, np.float64)
         host = lambda x: x.detach().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
@@ -135,12 +173,19 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             out = ops.bundle_adjust_host(*a, fx, *_tracks.group_by_image(a[1], n), *params)
         else:
             rf = np.ones(n, np.uint8) if refine_focal is True else (refine_focal != 0).astype(np.uint8)
-            out = ops.bundle_adjust_focal_host(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal)
+            if camera_ids is None:
+                out = ops.bundle_adjust_focal_host(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal)
+            else:
+                groups = _tracks.group_by_camera(camera_ids)
+                out = ops.bundle_adjust_shared_host(*a, fx, *_tracks.group_by_image(a[1], n), rf, *groups, *params, *focal)
+                out["cam_group"] = groups[0]
         out = {k: torch.from_numpy(v) for k, v in out.items()}
-    counts = out["counts"].cpu()                                        # the one readback
+    counts = (out["counts"] if neg_id is None else torch.cat([out["counts"], neg_id])).cpu()      # the one readback
     reals = counts[8:13].view(torch.float64).tolist()
     counts = counts.tolist()
-    _tracks.raise_error_bits(what, counts[1])
+    if neg_id is not None and counts[16]:
+        raise ValueError(f"{what}: camera_ids must not be negative")
+    _tracks.raise_error_bits(what, counts[1], ops.BUNDLE_SHARED_ERRORS if camera_ids is not None else None)
     stats = {"status": ops.BUNDLE_STATUS[counts[0]], "n_iters": counts[2], "n_accepted": counts[3], "n_pcg": counts[4],
              "n_active_observations": counts[5], "n_active_points": counts[6], "n_free_cameras": counts[7],
              "n_tracks": out["point_active"].numel(), "n_observations": out["obs_active"].numel(), "n_images": out["cam_free"].numel(),
@@ -151,4 +196,8 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
         return BundleResult(stats, **{k: out[k] for k in _OUT})
     stats["n_focal_cameras"] = counts[13]
     out["cam_focal"] = out["cam_focal"].view(torch.bool)
-    return BundleResult(stats, **{k: out[k] for k in _OUT + _OUT_FOCAL})
+    if camera_ids is None:
+        return BundleResult(stats, **{k: out[k] for k in _OUT + _OUT_FOCAL})
+    stats["n_focal_groups"] = counts[14]
+    out["group_focal"] = out["group_focal"].view(torch.bool)
+    return BundleResult(stats, **{k: out[k] for k in _OUT + _OUT_FOCAL + _OUT_SHARED})

@@ -600,4 +600,305 @@ template <int M> BA_HD void ctrl_write(const Ctx& c) {
   if constexpr (M == 7) k[13] = s.n_focal;   // cameras that refine their focal
 }
 
+// ---- §18.2: one relative focal step per GROUP of cameras ----------------------------------------------------------------------------------
+// The unknowns are 6 per free camera and 1 per refining group; the system is E^T S7 E x = E^T b7, E copying a group's value into the seventh
+// slot of its members with cam_focal.  The camera vectors keep §18.1's stride of 7: entries 0..5 are the pose part (read and written for a
+// free camera only; +0 is used for any other), entry 6 of Sp is the camera's seventh entry BEFORE E^T (written for a member with cam_focal
+// only), entry 6 of the others is unused.  The group vectors are [G].  A camera takes part when it is free or has cam_focal ("live"); the
+// pose columns of A are +0 for a camera that is not free, the seventh is +0 for one without cam_focal.
+enum : int { kBadCamGroups = 8 };          // error bit: cam_group / group_offsets / group_cams are not the stable grouping
+enum : int { kActStore = -2 };             // an osum whose result waits in CtrlS::acc for the group sum that follows it
+struct CtrlS { double acc; int n_groups; };
+struct CtxS : Ctx7 {
+  const int* cam_group; const long* group_offsets; const int* group_cams; int G;
+  uint8_t* group_focal;
+  double *dg, *xg, *rg, *zg, *pg, *Spg, *partg;   // [G] each: sum of U77 over the members, the conjugate gradients over the groups, terms of an osum
+  double* sg;                                     // [2][n]: the factor a group has taken so far, in the state and in the trial (ctrl->cur)
+  int* cam_cnt;                                   // [n] active observations of a camera that carries, else 0
+  CtrlS* cs;
+};
+constexpr int idx7(int r, int k) { return r * 7 - r * (r - 1) / 2 + (k - r); }   // entry (r, k), r <= k, of a 7 x 7 upper triangle
+
+// layout<7> and what the groups add, sized by n (G <= n), so that the size does not depend on the grouping
+inline size_t layout_shared(CtxS& c, char* base) {
+  size_t off = layout<7>(c, base);
+  const size_t n = (size_t)c.n;
+  auto take = [&](size_t bytes) { const size_t at = tracks::carve(&off, bytes ? bytes : 1); return base ? base + at : nullptr; };
+  c.cs = (CtrlS*)take(sizeof(CtrlS));
+  c.dg = (double*)take(8 * n); c.xg = (double*)take(8 * n); c.rg = (double*)take(8 * n); c.zg = (double*)take(8 * n);
+  c.pg = (double*)take(8 * n); c.Spg = (double*)take(8 * n); c.partg = (double*)take(8 * n); c.sg = (double*)take(8 * 2 * n);
+  c.cam_cnt = (int*)take(4 * n);
+  return off;
+}
+BA_HD void shared_init(const CtxS& c) { ctrl_init(c); c.cs->acc = 0.0; c.cs->n_groups = 0; }
+BA_HD bool live(const CtxS& c, long i) { return c.cam_free[i] != 0 || c.cam_focal[i] != 0; }
+
+// phase "camera groups", the last step of a camera with cnt active observations: does it carry its group's focal (its pose may be fixed)?
+// -> error bits
+BA_HD int cam_carry(const CtxS& c, long i, long cnt) {
+  c.cam_cnt[i] = (c.cam_valid[i] != 0 && c.refine_focal[i] != 0 && cnt >= 1) ? (int)cnt : 0;
+  c.cam_focal[i] = 0;
+  const int g = c.cam_group[i];
+  return g < 0 || g >= c.G ? kBadCamGroups : 0;
+}
+// phase "focal groups": the span of group g (not empty) and slot k of its list -> error bits, *cnt = what the member carries.  Ascending
+// within a group, and groups in the order of their first members.  Reads nothing through a bad value.
+BA_HD bool cgroup_range(const CtxS& c, long g, long* b, long* e) { return tracks::span(c.group_offsets, c.G, c.n, g, b, e) && *e > *b; }
+BA_HD int cgroup_slot(const CtxS& c, long g, long b, long k, long* cnt) {
+  *cnt = 0;
+  const int i = c.group_cams[k];
+  if (i < 0 || i >= c.n) return kBadCamGroups;
+  if (c.cam_group[i] != g) return kBadCamGroups;
+  if (k > b && !(c.group_cams[k - 1] < i)) return kBadCamGroups;
+  if (k == b && g > 0) {
+    const long pb = c.group_offsets[g - 1];
+    if (pb < 0 || pb >= c.n || !(c.group_cams[pb] < i)) return kBadCamGroups;
+  }
+  *cnt = c.cam_cnt[i];
+  return 0;
+}
+BA_HD double* sg_of(const CtxS& c, int buf, long g) { return c.sg + ((long)buf * c.n + g); }
+// ... and the end of group g's check: does it refine?  Its factor starts at 1 in both states.
+BA_HD bool cgroup_rule(const CtxS& c, long g, long total) {
+  *sg_of(c, 0, g) = 1.0; *sg_of(c, 1, g) = 1.0;
+  return total >= (long)c.min_focal_obs;
+}
+
+// A, B, rs of §18.1 with the columns of a camera that is not free set to +0
+BA_HD void obs_terms_s(const CtxS& c, int buf, long o, long t, double* A, double* B, double* rs) {
+  obs_terms<7>(c, buf, o, t, A, B, rs);
+  if (!c.cam_free[c.image[o]])
+    for (int k = 0; k < 6; ++k) { A[k] = 0.0; A[7 + k] = 0.0; }
+}
+// one element of a live camera's osum64 of the linearisation: a [35]
+BA_HD void cam_lin_term_s(const CtxS& c, int buf, long o, double* a) {
+  double A[14], B[6], rs[2];
+  obs_terms_s(c, buf, o, c.obs_track[o], A, B, rs);
+  int m = 0;
+#pragma unroll
+  for (int i = 0; i < 7; ++i)
+#pragma unroll
+    for (int j = i; j < 7; ++j) { a[m] = a[m] + (A[i] * A[j] + A[7 + i] * A[7 + j]); ++m; }
+#pragma unroll
+  for (int i = 0; i < 7; ++i) a[28 + i] = a[28 + i] + (A[i] * rs[0] + A[7 + i] * rs[1]);
+}
+// phase "factor", per free camera: the 6 x 6 pose block of U (damped) -> Uf [21 of 28]; per refining group: the damped d_g must be positive
+BA_HD bool cam_factor_s(const CtxS& c, long i, double lambda) {
+  if (!c.cam_free[i]) return true;
+  double a[21], f[21];
+  int m = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int k = r; k < 6; ++k) a[m++] = c.U[28 * i + idx7(r, k)];
+  const bool ok = factor<6>(a, lambda, f);
+#pragma unroll
+  for (int k = 0; k < 21; ++k) c.Uf[28 * i + k] = f[k];
+  return ok;
+}
+BA_HD bool group_factor(const CtxS& c, long g, double lambda) { return !c.group_focal[g] || damped(c.dg[g], lambda) > 0.0; }
+// the vector of a live camera as the operator sees it: the pose part of a free camera, its group's value when it has cam_focal, else +0
+BA_HD void cam_vec_s(const CtxS& c, long i, const double* vec, const double* vecg, double* v) {
+  const bool fr = c.cam_free[i] != 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = fr ? vec[7 * i + k] : 0.0;
+  v[6] = c.cam_focal[i] ? vecg[c.cam_group[i]] : 0.0;
+}
+// phase "track half", per track: track_half of the live cameras, with (vec, vecg) the camera and group halves of the vector
+BA_HD bool track_half_s(const CtxS& c, int buf, long t, int mode, const double* vec, const double* vecg) {
+  if (!c.point_active[t]) return true;
+  double s[3] = {0.0, 0.0, 0.0}, z[3];
+  if (mode != 0)
+    for (long o = c.offsets[t]; o < c.offsets[t + 1]; ++o) {
+      const int im = c.image[o];
+      if (!c.obs_active[o] || !live(c, im)) continue;
+      double A[14], B[6], rs[2], v[7];
+      obs_terms_s(c, buf, o, t, A, B, rs);
+      cam_vec_s(c, im, vec, vecg, v);
+      const double eu = dotm<7>(A, v), ev = dotm<7>(A + 7, v);
+      for (int k = 0; k < 3; ++k) s[k] = s[k] + (B[k] * eu + B[3 + k] * ev);
+    }
+  if (mode == 0) for (int k = 0; k < 3; ++k) s[k] = c.gp[3 * t + k];
+  if (mode == 2) for (int k = 0; k < 3; ++k) s[k] = -(c.gp[3 * t + k] + s[k]);
+  solve<3>(c.Vf + 6 * t, s, z);
+  if (mode != 2) {
+    for (int k = 0; k < 3; ++k) c.z[3 * t + k] = z[k];
+    return true;
+  }
+  bool ok = true;
+  for (int k = 0; k < 3; ++k) {
+    const double x = X_of(c, buf, t)[k] + z[k];
+    X_of(c, 1 - buf, t)[k] = x;
+    ok = ok && fin(x);
+  }
+  return ok;
+}
+// phase "camera half", one element of a live camera's osum64: a [7] += A^T (B z_j)
+BA_HD void cam_half_term_s(const CtxS& c, int buf, long o, double* a) {
+  double A[14], B[6], rs[2];
+  const long t = c.obs_track[o];
+  obs_terms_s(c, buf, o, t, A, B, rs);
+  const double* z = c.z + 3 * t;
+  const double eu = (B[0] * z[0] + B[1] * z[1]) + B[2] * z[2], ev = (B[3] * z[0] + B[4] * z[1]) + B[5] * z[2];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) a[k] = a[k] + (A[k] * eu + A[7 + k] * ev);
+}
+// ... and what follows the sum a [7] of camera i.  mode 0: b = -(gc - a); a free camera starts its pose part (x = 0, r = b, zc = M^-1 r,
+// p = zc, part = r . zc over 6 terms), a member with cam_focal leaves b_7 in Sp[6] for its group.  mode 1: rows 0..5 of U7d p - a for a
+// free camera (part = p . Sp over 6 terms); for a member with cam_focal Sp[6] = sum_{k<6} U_k7 p_k - a_7: the group's own diagonal term
+// is added once, at the group.  A camera that is not free has part = +0.
+BA_HD void cam_half_finish_s(const CtxS& c, long i, int mode, double lambda, const double* a) {
+  const bool fr = c.cam_free[i] != 0, fo = c.cam_focal[i] != 0;
+  if (!fr) c.part[i] = 0.0;
+  if (!fr && !fo) return;
+  double *x = c.x + 7 * i, *r = c.r + 7 * i, *zc = c.zc + 7 * i, *p = c.p + 7 * i, *Sp = c.Sp + 7 * i;
+  if (mode == 0) {
+    double b[7], zz[6];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) b[k] = -(c.gc[7 * i + k] - a[k]);
+    if (fr) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { x[k] = 0.0; r[k] = b[k]; }
+      solve<6>(c.Uf + 28 * i, b, zz);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { zc[k] = zz[k]; p[k] = zz[k]; }
+      c.part[i] = dotm<6>(b, zz);
+    }
+    if (fo) Sp[6] = b[6];
+    return;
+  }
+  const double* U = c.U + 28 * i;
+  double pv[7], sp[6];
+  cam_vec_s(c, i, c.p, c.pg, pv);
+  if (fr) {
+#pragma unroll
+    for (int row = 0; row < 6; ++row) {
+      double s = 0.0;
+#pragma unroll
+      for (int col = 0; col < 7; ++col) {
+        const int lo = row < col ? row : col, hi = row < col ? col : row;
+        const double u = U[idx7(lo, hi)];
+        s = s + (row == col ? damped(u, lambda) : u) * pv[col];
+      }
+      sp[row] = s - a[row];
+      Sp[row] = sp[row];
+    }
+    c.part[i] = dotm<6>(pv, sp);
+  }
+  if (fo) {
+    double s = 0.0;
+#pragma unroll
+    for (int col = 0; col < 6; ++col) s = s + U[idx7(col, 6)] * pv[col];
+    Sp[6] = s - a[6];
+  }
+}
+// one element of a group's osum64: member i adds v[i] when it has cam_focal (U77 for d_g, Sp[6] for E^T)
+BA_HD void group_term(const CtxS& c, long i, const double* v, long stride, double* a) {
+  if (c.cam_focal[i]) a[0] = a[0] + v[stride * i];
+}
+// ... and what follows the sum s of group g.  mode 0: b_g = s; x = 0, r = b, z = r / d, p = z, partg = r z.  mode 1: Sp = d p + s,
+// partg = p Sp (d: the damped d_g).  A group that does not refine has partg = +0.
+BA_HD void group_half_finish(const CtxS& c, long g, int mode, double lambda, double s) {
+  if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
+  const double d = damped(c.dg[g], lambda);
+  if (mode == 0) {
+    const double z = s / d;
+    c.xg[g] = 0.0; c.rg[g] = s; c.zg[g] = z; c.pg[g] = z;
+    c.partg[g] = s * z;
+    return;
+  }
+  const double sp = d * c.pg[g] + s;
+  c.Spg[g] = sp;
+  c.partg[g] = c.pg[g] * sp;
+}
+// phase "update 1" / "update 2" of the pose part of a free camera and of a refining group
+BA_HD void cam_update1_s(const CtxS& c, long i, double alpha) {
+  if (!c.cam_free[i]) { c.part[i] = 0.0; return; }
+  double r[6], zz[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    c.x[7 * i + k] = c.x[7 * i + k] + alpha * c.p[7 * i + k];
+    r[k] = c.r[7 * i + k] - alpha * c.Sp[7 * i + k];
+    c.r[7 * i + k] = r[k];
+  }
+  solve<6>(c.Uf + 28 * i, r, zz);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c.zc[7 * i + k] = zz[k];
+  c.part[i] = dotm<6>(r, zz);
+}
+BA_HD void cam_update2_s(const CtxS& c, long i, double beta) {
+  if (!c.cam_free[i]) return;
+  for (int k = 0; k < 6; ++k) c.p[7 * i + k] = c.zc[7 * i + k] + beta * c.p[7 * i + k];
+}
+BA_HD void group_update1(const CtxS& c, long g, double alpha, double lambda) {
+  if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
+  c.xg[g] = c.xg[g] + alpha * c.pg[g];
+  const double r = c.rg[g] - alpha * c.Spg[g], z = r / damped(c.dg[g], lambda);
+  c.rg[g] = r; c.zg[g] = z;
+  c.partg[g] = r * z;
+}
+BA_HD void group_update2(const CtxS& c, long g, double beta) {
+  if (c.group_focal[g]) c.pg[g] = c.zg[g] + beta * c.pg[g];
+}
+// phase "apply", per refining group: the factor of the trial s' = s (1 + delta_g).  Per live camera: cam_apply's pose step for a free
+// camera; for one with cam_focal fx' = fx_in s', skew' = skew_in s', fy' = fy_in s' (the camera forms s' itself, from the same two
+// operands), so that the members of a group leave with ONE factor on their input values however many trials were accepted.
+BA_HD void group_apply(const CtxS& c, int buf, long g) {
+  if (c.group_focal[g]) *sg_of(c, 1 - buf, g) = *sg_of(c, buf, g) * (1.0 + c.xg[g]);
+}
+BA_HD bool cam_apply_s(const CtxS& c, int buf, long i) {
+  bool ok = true;
+  const double* tab = tab_of(c, buf, i);
+  double* tab2 = tab_of(c, 1 - buf, i);
+  if (c.cam_free[i]) {
+    const double *d = c.x + 7 * i, *q = quat_of(c, buf, i);
+    double* q2 = quat_of(c, 1 - buf, i);
+    const double a = 0.5 * d[0], b = 0.5 * d[1], e = 0.5 * d[2];
+    double w = ((q[0] - a * q[1]) - b * q[2]) - e * q[3];
+    double x = ((q[1] + a * q[0]) + b * q[3]) - e * q[2];
+    double y = ((q[2] - a * q[3]) + b * q[0]) + e * q[1];
+    double z = ((q[3] + a * q[2]) - b * q[1]) + e * q[0];
+    const double nq = sqrt(((w * w + x * x) + y * y) + z * z);
+    w = w / nq; x = x / nq; y = y / nq; z = z / nq;
+    q2[0] = w; q2[1] = x; q2[2] = y; q2[3] = z;
+    double R[9];
+    matrix_from_quat(q2, R);
+    ok = fin(w) && fin(x) && fin(y) && fin(z);
+    for (int k = 0; k < 9; ++k) tab2[k] = R[k];
+    for (int k = 0; k < 3; ++k) {
+      tab2[9 + k] = tab[9 + k] + d[3 + k];
+      ok = ok && fin(tab2[9 + k]);
+    }
+  }
+  if (c.cam_focal[i]) {
+    const long g = c.cam_group[i];
+    const double s = *sg_of(c, buf, g) * (1.0 + c.xg[g]);
+    const double fx = c.K[9 * i] * s, sk = c.K[9 * i + 1] * s, fy = c.K[9 * i + 4] * s;
+    tab2[12] = fx; tab2[13] = sk; tab2[15] = fy;
+    const double rx = fx / c.K[9 * i], ry = fy / c.K[9 * i + 4];
+    ok = ok && fin(fx) && fin(fy) && rx > c.focal_lo && rx < c.focal_hi && ry > c.focal_lo && ry < c.focal_hi;
+  }
+  return ok;
+}
+// phase "write": the pose of a free camera, the intrinsics of one with cam_focal; counts[14] = the groups that refine
+BA_HD void cam_write_s(const CtxS& c, int buf, long i) {
+  const double* tab = tab_of(c, buf, i);
+  if (c.cam_free[i]) {
+    double* T = c.T_out + 16 * i;
+    for (int r = 0; r < 3; ++r) {
+      for (int k = 0; k < 3; ++k) T[4 * r + k] = tab[3 * r + k];
+      T[4 * r + 3] = tab[9 + r];
+    }
+    T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
+  }
+  if (c.cam_focal[i]) {
+    double* K = c.K_out + 9 * i;
+    K[0] = tab[12]; K[1] = tab[13]; K[2] = tab[14]; K[4] = tab[15]; K[5] = tab[16];
+  }
+}
+BA_HD void ctrl_write_s(const CtxS& c) {
+  ctrl_write<7>(c);
+  c.counts[14] = c.cs->n_groups;
+}
+
 }  // namespace ba

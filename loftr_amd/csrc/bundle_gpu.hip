@@ -326,7 +326,333 @@ template <int M> int run(CtxT<M>& c, int max_iters, int pcg_iters, void* ws, siz
   return failed ? LOFTR_ERR_LAUNCH : LOFTR_OK;
 }
 
+// ---- §18.2: one focal step per group of cameras.  New kernels for every phase that touches the camera block or the groups; the phases
+// that do not (init of the scalars aside: track setup, evaluate, the track linearisation, the osum of the cost, accept) are the ones above.
+// A wave per group folds its members exactly as a wave per camera folds its observations.
+
+// osum64 of group g's list over the 64 lanes of a wave: member i adds v[stride i] when it has cam_focal; the sum is lane 0's
+__device__ __forceinline__ double wave_gsum64(const CtxS& c, long g, int lane, const double* v, long stride) {
+  double a = 0.0;
+  const long b = c.group_offsets[g], e = c.group_offsets[g + 1];
+  for (long k = b + lane; k < e; k += 64) group_term(c, c.group_cams[k], v, stride, &a);
+  for (int s = 32; s >= 1; s >>= 1) {
+    const double w = __shfl_down(a, s, 64);
+    if (lane < s) a = a + w;
+  }
+  return a;
+}
+
+__global__ void ba_init_shared_kernel(CtxS c) { shared_init(c); }
+
+// a wave per camera, grid ceil(n / 4) x 256: ba_groups_kernel, and what the camera carries for its group
+__global__ void __launch_bounds__(kThreads) ba_groups_shared_kernel(CtxS c) {
+  const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (i >= c.n) return;
+  long b, e;
+  int err = 0, cnt = 0;
+  if (!group_range(c, i, &b, &e)) { err = kBadGroups; b = e = 0; }
+  for (long k = b + lane; k < e; k += 64) {
+    bool active;
+    err |= group_check(c, i, b, k, &active);
+    cnt += active;
+  }
+  for (int m = 32; m >= 1; m >>= 1) { err |= __shfl_xor(err, m, 64); cnt += __shfl_xor(cnt, m, 64); }
+  if (lane == 0) {
+    const bool fr = !c.fixed[i] && c.cam_valid[i] && cnt >= 1;
+    c.cam_free[i] = (uint8_t)fr;
+    if (fr) atomicAdd(&c.ctrl->n_free, 1ull);
+    err |= cam_carry(c, i, cnt);
+    if (err) atomicOr(&c.ctrl->err, err);
+  }
+}
+
+// a wave per group, grid ceil(G / 4) x 256: the check of the group arrays and the count.  Reads them only through checked indices, and
+// writes cam_focal only when the whole list of the group has passed, so it needs no flag.
+__global__ void __launch_bounds__(kThreads) ba_cgroups_kernel(CtxS c) {
+  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (g >= c.G) return;
+  long b, e, total = 0;
+  int err = 0;
+  if (!cgroup_range(c, g, &b, &e)) { err = kBadCamGroups; b = e = 0; }
+  for (long k = b + lane; k < e; k += 64) {
+    long cnt;
+    err |= cgroup_slot(c, g, b, k, &cnt);
+    total += cnt;
+  }
+  for (int m = 32; m >= 1; m >>= 1) { err |= __shfl_xor(err, m, 64); total += __shfl_xor(total, m, 64); }
+  if (err) {
+    if (lane == 0) atomicOr(&c.ctrl->err, err);
+    return;
+  }
+  const bool refines = lane == 0 ? cgroup_rule(c, g, total) : total >= (long)c.min_focal_obs;
+  int nf = 0;
+  for (long k = b + lane; k < e; k += 64) {
+    const int i = c.group_cams[k];
+    const bool fo = refines && c.cam_cnt[i] > 0;
+    c.cam_focal[i] = (uint8_t)fo;
+    nf += fo;
+  }
+  for (int m = 32; m >= 1; m >>= 1) nf += __shfl_xor(nf, m, 64);
+  if (lane == 0) {
+    c.group_focal[g] = (uint8_t)refines;
+    if (refines) atomicAdd(&c.cs->n_groups, 1);
+    if (nf) atomicAdd(&c.ctrl->n_focal, nf);
+  }
+}
+
+// a wave per live camera, grid ceil(n / 4) x 256
+__global__ void __launch_bounds__(kThreads) ba_cam_lin_shared_kernel(CtxS c, int flags) {
+  if (skipped(c, flags)) return;
+  const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64, cur = c.ctrl->cur;
+  if (i >= c.n || !live(c, i)) return;
+  double a[35];
+  wave_osum64<35>(c, i, lane, [&](long o, double* acc) { cam_lin_term_s(c, cur, o, acc); }, a);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 28; ++k) c.U[28 * i + k] = a[k];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) c.gc[7 * i + k] = a[28 + k];
+  }
+}
+
+// a wave per refining group, grid ceil(G / 4) x 256: d_g = the sum of U77 over its members
+__global__ void __launch_bounds__(kThreads) ba_group_lin_kernel(CtxS c, int flags) {
+  if (skipped(c, flags)) return;
+  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (g >= c.G || !c.group_focal[g]) return;
+  const double d = wave_gsum64(c, g, lane, c.U + 27, 28);
+  if (lane == 0) c.dg[g] = d;
+}
+
+// threads [0, T): tracks, [T, T + n): cameras, [T + n, T + n + G): groups
+__global__ void __launch_bounds__(kThreads) ba_factor_shared_kernel(CtxS c, int flags) {
+  if (skipped(c, flags)) return;
+  const long id = (long)blockIdx.x * kThreads + threadIdx.x;
+  const double lambda = c.ctrl->lambda;
+  bool ok = true;
+  if (id < c.T) ok = track_factor(c, id, lambda);
+  else if (id < c.T + c.n) ok = cam_factor_s(c, id - c.T, lambda);
+  else if (id < c.T + c.n + c.G) ok = group_factor(c, id - c.T - c.n, lambda);
+  if (!ok) atomicOr(&c.ctrl->bad_f, 1);
+}
+
+__global__ void __launch_bounds__(kThreads) ba_track_half_shared_kernel(CtxS c, int mode, int flags) {
+  if (skipped(c, flags)) return;
+  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (t < c.T) track_half_s(c, c.ctrl->cur, t, mode, c.p, c.pg);
+}
+
+// a wave per camera, grid ceil(n / 4) x 256
+__global__ void __launch_bounds__(kThreads) ba_cam_half_shared_kernel(CtxS c, int mode, int flags) {
+  if (skipped(c, flags)) return;
+  const long i = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64, cur = c.ctrl->cur;
+  if (i >= c.n) return;
+  double a[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) a[k] = 0.0;
+  if (live(c, i)) wave_osum64<7>(c, i, lane, [&](long o, double* acc) { cam_half_term_s(c, cur, o, acc); }, a);
+  if (lane == 0) cam_half_finish_s(c, i, mode, c.ctrl->lambda, a);
+}
+
+// a wave per group, grid ceil(G / 4) x 256: E^T of the cameras' seventh entries, then the group's own step
+__global__ void __launch_bounds__(kThreads) ba_group_half_kernel(CtxS c, int mode, int flags) {
+  if (skipped(c, flags)) return;
+  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (g >= c.G) return;
+  double s = 0.0;
+  if (c.group_focal[g]) s = wave_gsum64(c, g, lane, c.Sp + 6, 7);
+  if (lane == 0) group_half_finish(c, g, mode, c.ctrl->lambda, s);
+}
+
+// ba_osum_kernel for a dot product of two halves: the cameras' sum waits (action kActStore), the groups' is added to it and fed
+__global__ void __launch_bounds__(64) ba_osum_shared_kernel(CtxS c, const double* in, long count, double* out, int action, int flags) {
+  if (skipped(c, flags)) return;
+  const int lane = threadIdx.x;
+  const long lo = (long)blockIdx.x * kChunk, len = count - lo < kChunk ? count - lo : kChunk;
+  double a = 0.0;
+  for (long e = lane; e < len; e += 64) a = a + in[lo + e];
+  for (int s = 32; s >= 1; s >>= 1) {
+    const double v = __shfl_down(a, s, 64);
+    if (lane < s) a = a + v;
+  }
+  if (lane == 0) {
+    if (action == kActStore) c.cs->acc = a;
+    else if (action >= 0) ctrl_feed(c, action, c.cs->acc + a);
+    else out[blockIdx.x] = a;
+  }
+}
+
+// threads [0, n): cameras, [n, n + G): groups (the scalar update of a group)
+__global__ void __launch_bounds__(kThreads) ba_update_shared_kernel(CtxS c, int which, int flags) {
+  if (skipped(c, flags)) return;
+  const long id = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (id < c.n) {
+    if (which == 1) cam_update1_s(c, id, c.ctrl->alpha);
+    else cam_update2_s(c, id, c.ctrl->beta);
+  } else if (id < c.n + c.G) {
+    if (which == 1) group_update1(c, id - c.n, c.ctrl->alpha, c.ctrl->lambda);
+    else group_update2(c, id - c.n, c.ctrl->beta);
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) ba_apply_shared_kernel(CtxS c, int flags) {
+  if (skipped(c, flags)) return;
+  const long id = (long)blockIdx.x * kThreads + threadIdx.x;
+  const int cur = c.ctrl->cur;
+  bool ok = true;
+  if (id < c.T) ok = track_half_s(c, cur, id, 2, c.x, c.xg);
+  else if (id < c.T + c.n) ok = cam_apply_s(c, cur, id - c.T);
+  else if (id < c.T + c.n + c.G) group_apply(c, cur, id - c.T - c.n);
+  if (!ok) atomicOr(&c.ctrl->bad_a, 1);
+}
+
+__global__ void __launch_bounds__(kThreads) ba_write_shared_kernel(CtxS c) {
+  const long id = (long)blockIdx.x * kThreads + threadIdx.x;
+  const int cur = c.ctrl->cur;
+  if (!c.ctrl->err) {
+    if (id < c.T) track_write(c, cur, id);
+    else if (id < c.T + c.n) cam_write_s(c, cur, id - c.T);
+  }
+  if (id == 0) ctrl_write_s(c);
+}
+
+// the fixed launch schedule of §18.2
+int run_shared(CtxS& c, int max_iters, int pcg_iters, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
+  if (ws_bytes < layout_shared(c, nullptr)) return LOFTR_ERR_WORKSPACE;
+  layout_shared(c, (char*)ws);
+  hipStream_t s = (hipStream_t)stream;
+  const long n = c.n, T = c.T, G = c.G;
+  const bool timed = class_ms != nullptr;
+  std::vector<hipEvent_t> ev;
+  std::vector<int> ev_cls;
+  long launches[kClsCount] = {0};
+  bool failed = false;
+  auto mark = [&]() {
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess || hipEventRecord(e, s) != hipSuccess) failed = true;
+    else ev.push_back(e);
+  };
+  auto after = [&](int cls) {
+    if (hipGetLastError() != hipSuccess) failed = true;
+    launches[cls] += 1;
+    if (timed && !failed) { mark(); ev_cls.push_back(cls); }
+  };
+  auto blocks = [](long items, long per) { return dim3((unsigned)(items > 0 ? (items + per - 1) / per : 1)); };
+  const Ctx& b = c;
+  double* red2 = c.red + ((std::max(T, n) + 1 + kChunk - 1) / kChunk);
+  // osum of v[0 .. count): one launch per level; `pair` = the shared kernel (kActStore, or a feed that adds the stored half)
+  auto osum = [&](const double* v, long count, int action, int flags, bool pair) {
+    const double* in = v;
+    double* out = c.red;
+    for (;;) {
+      const long chunks = count > 0 ? (count + kChunk - 1) / kChunk : 1;
+      const int act = chunks == 1 ? action : -1;
+      if (pair) hipLaunchKernelGGL(ba_osum_shared_kernel, dim3((unsigned)chunks), dim3(64), 0, s, c, in, count, out, act, flags);
+      else hipLaunchKernelGGL(ba_osum_kernel, dim3((unsigned)chunks), dim3(64), 0, s, b, in, count, out, act, flags);
+      after(kClsOsum);
+      if (chunks == 1) return;
+      in = out;
+      out = out == c.red ? red2 : c.red;
+      count = chunks;
+    }
+  };
+  auto dot = [&](int action, int flags) { osum(c.part, n, kActStore, flags, true); osum(c.partg, G, action, flags, true); };
+  auto camera_half = [&](int mode, int flags) {
+    hipLaunchKernelGGL(ba_cam_half_shared_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, mode, flags); after(kClsCamHalf);
+    hipLaunchKernelGGL(ba_group_half_kernel, blocks(G, 4), dim3(kThreads), 0, s, c, mode, flags); after(kClsCamHalf);
+  };
+  if (timed) mark();
+  hipLaunchKernelGGL(ba_init_shared_kernel, dim3(1), dim3(1), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_cam_setup_kernel<7>, blocks(n, kThreads), dim3(kThreads), 0, s, (const Ctx7&)c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_track_setup_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, b); after(kClsSetup);
+  hipLaunchKernelGGL(ba_groups_shared_kernel, blocks(n, 4), dim3(kThreads), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_cgroups_kernel, blocks(G, 4), dim3(kThreads), 0, s, c); after(kClsSetup);
+  hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, b, 0, 0); after(kClsEvaluate);
+  osum(c.part, T, kActCost0, 0, false);
+  osum(c.part2, T, kActSq0, 0, false);
+  for (int it = 0; it < max_iters && !failed; ++it) {
+    hipLaunchKernelGGL(ba_track_lin_kernel<6>, blocks(T, kThreads), dim3(kThreads), 0, s, b, kNeedFresh); after(kClsLinearise);
+    hipLaunchKernelGGL(ba_cam_lin_shared_kernel, blocks(n, 4), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
+    hipLaunchKernelGGL(ba_group_lin_kernel, blocks(G, 4), dim3(kThreads), 0, s, c, kNeedFresh); after(kClsLinearise);
+    hipLaunchKernelGGL(ba_factor_shared_kernel, blocks(T + n + G, kThreads), dim3(kThreads), 0, s, c, 0); after(kClsFactor);
+    hipLaunchKernelGGL(ba_track_half_shared_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 0, kSkipBadF); after(kClsTrackHalf);
+    camera_half(0, kSkipBadF);
+    dot(kActRz0, kSkipBadF);
+    for (int pi = 0; pi < pcg_iters && !failed; ++pi) {
+      const int f = kSkipBadF | kSkipPcg;
+      hipLaunchKernelGGL(ba_track_half_shared_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, c, 1, f); after(kClsTrackHalf);
+      camera_half(1, f);
+      dot(kActPsp, f);
+      hipLaunchKernelGGL(ba_update_shared_kernel, blocks(n + G, kThreads), dim3(kThreads), 0, s, c, 1, f); after(kClsUpdate);
+      dot(kActRz, f);
+      hipLaunchKernelGGL(ba_update_shared_kernel, blocks(n + G, kThreads), dim3(kThreads), 0, s, c, 2, f); after(kClsUpdate);
+    }
+    hipLaunchKernelGGL(ba_apply_shared_kernel, blocks(T + n + G, kThreads), dim3(kThreads), 0, s, c, kSkipBadF); after(kClsApply);
+    hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), dim3(kThreads), 0, s, b, 1, kSkipBadF | kSkipBadA); after(kClsEvaluate);
+    osum(c.part, T, kActCostT, kSkipBadF | kSkipBadA | kSkipBadE, false);
+    osum(c.part2, T, kActSqT, kSkipBadF | kSkipBadA | kSkipBadE, false);
+    hipLaunchKernelGGL(ba_accept_kernel, dim3(1), dim3(1), 0, s, b); after(kClsAccept);
+  }
+  hipLaunchKernelGGL(ba_write_shared_kernel, blocks(T + n, kThreads), dim3(kThreads), 0, s, c); after(kClsWrite);
+  if (class_launches) for (int k = 0; k < kClsCount; ++k) class_launches[k] = launches[k];
+  if (timed) {
+    if (hipStreamSynchronize(s) != hipSuccess) failed = true;
+    std::vector<float> ms[kClsCount];
+    for (size_t k = 0; k + 1 < ev.size() && !failed; ++k) {
+      float v = 0.f;
+      if (hipEventElapsedTime(&v, ev[k], ev[k + 1]) == hipSuccess) ms[ev_cls[k]].push_back(v);
+    }
+    for (int k = 0; k < kClsCount; ++k) {
+      std::sort(ms[k].begin(), ms[k].end());
+      float total = 0.f;
+      for (float v : ms[k]) total += v;
+      class_ms[2 * k] = ms[k].empty() ? 0.f : ms[k][ms[k].size() / 2];
+      class_ms[2 * k + 1] = total;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  return failed ? LOFTR_ERR_LAUNCH : LOFTR_OK;
+}
+
 }  // namespace
+
+extern "C" size_t loftr_bundle_adjust_shared_workspace_bytes(long T, long N, int n_images) {
+  if (!sizes_ok(T, N, n_images)) return 0;
+  CtxS c{};
+  c.T = T; c.N = N; c.n = n_images;
+  return layout_shared(c, nullptr);
+}
+
+extern "C" int loftr_bundle_adjust_shared(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
+                                          long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                          const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                          const int* cam_group, const long* group_offsets, const int* group_cams, int G, double huber_px,
+                                          int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs, double focal_lo,
+                                          double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
+                                          uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal, long* counts,
+                                          void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
+  LOFTR_CHECK_ARG(n_images <= 0 || (refine_focal && K_out && cam_focal && cam_group && group_cams && group_focal));
+  LOFTR_CHECK_ARG(group_offsets && G >= 0 && G <= n_images && (n_images <= 0 || G > 0));
+  LOFTR_CHECK_ARG(min_focal_obs >= 1 && fin(focal_lo) && fin(focal_hi) && focal_lo < 1.0 && 1.0 < focal_hi);
+  const int st = check_args(offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs,
+                            huber_px, max_iters, pcg_iters, pcg_tol, ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts, ws);
+  if (st != LOFTR_OK) return st;
+  CtxS c{};
+  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
+  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
+  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
+  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+  c.refine_focal = refine_focal; c.min_focal_obs = min_focal_obs; c.focal_lo = focal_lo; c.focal_hi = focal_hi;
+  c.K_out = K_out; c.cam_focal = cam_focal;
+  c.cam_group = cam_group; c.group_offsets = group_offsets; c.group_cams = group_cams; c.G = G; c.group_focal = group_focal;
+  return run_shared(c, max_iters, pcg_iters, ws, ws_bytes, class_ms, class_launches, stream);
+}
 
 extern "C" size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images) {
   if (!sizes_ok(T, N, n_images)) return 0;

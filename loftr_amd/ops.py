@@ -1459,6 +1459,66 @@ def bundle_adjust_focal(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from
                                 (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
 
 
+# bits of counts[1] of the grouped pair: BUNDLE_ERRORS and the check of the camera groups
+BUNDLE_SHARED_ERRORS = BUNDLE_ERRORS + ((8, "cam_group / group_offsets / group_cams are not the images grouped by camera in ascending order"),)
+_BA_SHARED_ARGS = _BA_ARGS + (("refine_focal", "uint8", 1), ("cam_group", "int32", 1), ("group_offsets", "int64", 1), ("group_cams", "int32", 1))
+
+
+def _bundle_adjust_shared(B, what, hint, arrays, params, focal, timings):
+    """The body of the grouped pair: _bundle_adjust_focal with cam_group [n] i32, group_offsets [G+1] i64, group_cams [n] i32
+    after cam_obs, and group_focal [G] u8 after the outputs."""
+    _check_args(B, what, hint, _BA_SHARED_ARGS, arrays)
+    offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs, refine, cam_group, group_offsets, group_cams = arrays
+    N, n, T, G = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1, group_offsets.shape[0] - 1
+    if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or tuple(K.shape) != (n, 3, 3) or \
+            tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N or \
+            refine.shape[0] != n or cam_group.shape[0] != n or group_cams.shape[0] != n or G < 0 or G > n or (n > 0 and G == 0):
+        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
+                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1], cam_obs [N], refine_focal [n], cam_group [n], "
+                                 f"group_offsets [G+1] with 1 <= G <= n and group_cams [n], got {[tuple(a.shape) for a in arrays]}")
+    params = _ba_params(what, *params)
+    focal = _ba_focal_params(what, *focal)
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _BA_OUT + (("K", "n", (3, 3), "float64"), ("cam_focal", "n", (), "uint8"), ("group_focal", "G", (), "uint8")),
+                   {"T": T, "N": N, "n": n, "G": G}, BUNDLE_COUNTS, offsets)
+    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
+    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
+    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
+    B.call("bundle_adjust_shared", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], a[10], n, a[8], a[9], a[11], a[12], a[13], G, *params,
+                                    *focal, *[B.ptr(out[k]) for k in out]),
+           _TABLE_RULES + "; cam_group / group_offsets / group_cams must group the images by camera in ascending order", offsets,
+           ws=(T, N, n), tail=(cast(ms), cast(launches)))
+    if timings is not None:
+        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
+    return out
+
+
+def bundle_adjust_shared_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                              cam_group, group_offsets, group_cams, huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo,
+                              focal_hi):
+    """loftr_bundle_adjust_shared_host: the host routine that DEFINES the bundle adjustment with one focal step per group of images
+    (include/loftr_hip.h) on numpy arrays: those of bundle_adjust_focal_host plus cam_group [n] i32, group_offsets [G+1] i64,
+    group_cams [n] i32.  -> its dict plus group_focal [G] u8; counts[14] is the number of groups that refine."""
+    return _bundle_adjust_shared(_Host, "bundle_adjust_shared_host", "bundle_adjust_shared",
+                                 (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                                  cam_group, group_offsets, group_cams),
+                                 (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None)
+
+
+@_on_device
+def bundle_adjust_shared(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
+                         group_offsets, group_cams, huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi,
+                         timings=None):
+    """loftr_bundle_adjust_shared: the kernels of the grouped focal step (csrc/bundle_gpu.hip) on GPU tensors; the same result as
+    bundle_adjust_shared_host bit for bit, the same timing classes and single readback as bundle_adjust."""
+    return _bundle_adjust_shared(_Gpu, "bundle_adjust_shared",
+                                 "the bundle-adjustment kernels have no CPU fallback; the host routine is bundle_adjust_shared_host",
+                                 (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                                  cam_group, group_offsets, group_cams),
+                                 (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
+
+
 @_on_device
 def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, huber_px, max_iters, pcg_iters,
                   pcg_tol, ftol, timings=None):

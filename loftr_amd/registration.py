@@ -186,6 +186,17 @@ def _tensors(what, names, args):
     return [a.detach() for a in out]
 
 
+def _follow_group(K_in, K_out, group, cam_focal, G):
+    """K_out with fx, skew, fy of the images without cam_focal scaled by the factor fx_out / fx_in of a member of their group that has it
+    (1 where the group has none): integer indexing and one multiplication per entry, on the tensors' device."""
+    ratio = torch.where(cam_focal, K_out[:, 0, 0] / K_in[:, 0, 0], torch.zeros_like(K_out[:, 0, 0]))
+    per_group = torch.zeros(G, dtype=K_out.dtype, device=K_out.device).scatter_reduce(0, group, ratio, "amax")
+    scale = torch.where(cam_focal | (per_group[group] == 0), torch.ones_like(ratio), per_group[group])
+    K = K_out.clone()
+    K[:, 0, 0], K[:, 0, 1], K[:, 1, 1] = K_out[:, 0, 0] * scale, K_out[:, 0, 1] * scale, K_out[:, 1, 1] * scale
+    return K
+
+
 def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=None, min_angle_deg=1.5, **register_kw):
     """Incremental reconstruction from tracks and an initial pair -> ``Reconstruction``.
 
@@ -204,7 +215,11 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
 
     With ``ba={'refine_focal': True}`` (or an ``[n]`` mask) every adjustment also refines the focal of the posed images
     named, and every step after an adjustment -- the triangulations, ``register_images``, the next adjustment -- uses the intrinsics it
-    returned; ``Reconstruction.K`` holds the last.  The focal bounds of an adjustment are relative to the intrinsics it was given."""
+    returned; ``Reconstruction.K`` holds the last.  The focal bounds of an adjustment are relative to the intrinsics it was given.
+
+    With ``ba={'refine_focal': True, 'camera_ids': ids}`` the images of one camera share one relative focal step; the
+    members of a camera that did not carry it in an adjustment (not posed yet, say) have their fx, skew, fy scaled by the factor their
+    camera took, so that an image registered later starts from its camera's current focal."""
     from .bundle import bundle_adjust
     what = "reconstruct_tracks"
     offsets, obs_image, obs_xy, K = _tensors(what, ("offsets", "obs_image", "obs_xy", "K"), (offsets, obs_image, obs_xy, K))
@@ -236,6 +251,9 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     if ba.get("refine_focal") is not None and ba["refine_focal"] is not True:
         ba["refine_focal"] = torch.as_tensor(np.asarray(ba["refine_focal"].cpu() if isinstance(ba["refine_focal"], torch.Tensor)
                                                         else ba["refine_focal"])).to(dev)
+    if ba.get("camera_ids") is not None:
+        ba["camera_ids"] = torch.as_tensor(np.asarray(ba["camera_ids"].cpu() if isinstance(ba["camera_ids"], torch.Tensor)
+                                                      else ba["camera_ids"])).to(dev)
     thresh_px = register_kw.get("thresh_px", 4.0)
     T = torch.full((n, 4, 4), float("nan"), dtype=torch.float64, device=dev)
     T[a] = torch.eye(4, dtype=torch.float64)
@@ -255,7 +273,9 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
             raise ValueError(f"{what}: the initial pair ({a}, {b}) triangulates nothing: {pts.stats['n_posed_observations']} observations in "
                              f"{pts.stats['n_tracks']} tracks, statuses {[pts.stats['n_' + s] for s in ops.TRI_STATUS]}")
         res = bundle_adjust(offsets, obs_image, obs_xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **ba)
-        K = getattr(res, "K", K)                                        # (a result without refine_focal carries no K)
+        K_in, K = K, getattr(res, "K", K)                               # (a result without refine_focal carries no K)
+        if hasattr(res, "cam_group"):                                   # an image posed later joins its camera at the camera's scale
+            K = _follow_group(K_in, K, res.cam_group.long(), res.cam_focal, res.group_focal.numel())
         return triangulate_posed(offsets, obs_image, obs_xy, K, res.T_cam_from_world, posed, thresh_px, min_angle_deg), res, K
 
     for r in range(1, int(max_rounds) + 1):

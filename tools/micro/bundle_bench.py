@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Bundle adjustment (loftr_amd/bundle.py, csrc/bundle_gpu.hip) on a MegaDepth-1500-shaped load.  One JSON line.
 
-    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--refine-focal] [--no-host] [--out FILE]
+    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--refine-focal] [--camera-groups G[,G...]] [--no-host] [--out FILE]
 
 Load: the track lengths of tools/micro/atlas_bench.py's synthetic atlas (1500 rows over 806 images), observations as in
 tools/micro/triangulation_bench.py without outliers (one exact camera per image, one 3D point per track, every observation in a random
@@ -14,7 +14,11 @@ bound of the launches that returned at once (from the counts: trials and conjuga
 accepted trials and conjugate-gradient iterations; the host routine (loftr_bundle_adjust_host, one core) on the same input; and the
 assertion that every run's output tensors and counts equal the host routine's.  With --refine-focal the focal of every
 free camera starts 4-10 % off and the line holds two such legs on that load: "fixed_intrinsics" (the 6-wide kernels) and "refine_focal"
-(the 7-wide kernels, refine_focal=True), with the largest relative focal error before and after."""
+(the 7-wide kernels, refine_focal=True), with the largest relative focal error before and after.  With --camera-groups 1,8,806 (DESIGN
+§18.2) the line holds that per-image leg as the reference point ("per_image") and one leg per G ("groups_G"): image i is of camera
+i mod G, every camera's focal -- the fixed-pose images' too -- starts off by one factor of 4-10 %, and the call is
+refine_focal=True, camera_ids=ids; per leg the trials, conjugate-gradient iterations, rms before and after, the largest focal error
+over all images and the wall time."""
 import argparse
 import json
 import os
@@ -93,6 +97,16 @@ def detune(K, fixed, seed=5):
     return K
 
 
+def detune_groups(K, ids, seed=5):
+    """K with fx, skew and fy of every image multiplied by the factor 1 +- U(0.04, 0.10) of its camera ids[i]."""
+    rng = np.random.default_rng(seed)
+    G = int(ids.max()) + 1
+    fac = torch.from_numpy(1 + rng.choice([-1, 1], G) * rng.uniform(0.04, 0.10, G)).to(K.device)[ids]
+    K = K.clone()
+    K[:, 0, 0], K[:, 0, 1], K[:, 1, 1] = K[:, 0, 0] * fac, K[:, 0, 1] * fac, K[:, 1, 1] * fac
+    return K
+
+
 def leg(inputs, fixed, kw, n_tracks, args):
     """One timed leg: a warm-up, 3 timed calls, one call with events, the host routine and the equality assertion -> dict."""
     out = {}
@@ -114,6 +128,8 @@ def leg(inputs, fixed, kw, n_tracks, args):
     issued = sum(v[2] for v in timings.values())
     levels_t = 1 if n_tracks <= 4096 else 2
     per_pcg, per_trial = 6, 3 + 2 + 1 + 2 + 2 * levels_t + 1                # the launches of one iteration / of a trial without them
+    if "camera_ids" in kw:                                              # §18.2: the group kernels, and a dot product is two sums
+        per_pcg, per_trial = 9, 4 + 3 + 2 + 2 + 2 * levels_t + 1
     skipped = (args.max_iters - res.n_iters) * (per_trial + per_pcg * args.pcg_iters) + per_pcg * (res.n_iters * args.pcg_iters - res.n_pcg)
     out["launches_issued"], out["launches_skipped_at_least"] = issued, int(skipped)
     out["stats"] = res.stats
@@ -124,6 +140,8 @@ def leg(inputs, fixed, kw, n_tracks, args):
         out["host_routine_ms"] = round(1e3 * (time.perf_counter() - t), 1)
         out["identical_to_host"] = bool(all(same(r, host) for r in results))
         assert out["identical_to_host"], "a GPU run differs from the host routine"
+    print(f"[bundle_bench] leg {sorted(k for k in kw if k not in ('huber_px', 'max_iters', 'pcg_iters'))}: {res.n_iters} trials, {res.n_pcg} pcg, "
+          f"wall {out['wall_ms']} ms, host {out.get('host_routine_ms')} ms", file=sys.stderr, flush=True)     # (the host routine takes minutes)
     return out, res
 
 
@@ -136,6 +154,8 @@ def main():
     ap.add_argument("--huber", type=float, default=0.0)
     ap.add_argument("--refine-focal", action="store_true",
                     help="the focal of every free camera off by 4-10 %%: a fixed-intrinsics leg and a refine_focal=True leg on that load")
+    ap.add_argument("--camera-groups", default=None,
+                    help="comma-separated group counts G (image i is of camera i mod G): a per-image refine_focal leg and one shared leg per G")
     ap.add_argument("--no-host", action="store_true", help="skip the host routine (and the equality assertion)")
     ap.add_argument("--out", default=None, help="also append the JSON line to this file")
     args = ap.parse_args()
@@ -151,7 +171,18 @@ def main():
     kw = dict(huber_px=args.huber, max_iters=args.max_iters, pcg_iters=args.pcg_iters)
     out = {"workload": "bundle_megadepth1500_shape", "images": n_images, "tracks": int(lens.numel()), "observations": int(inputs[0][-1]),
            "fixed_cameras": 2, **kw}
-    if not args.refine_focal:
+    if args.camera_groups:
+        K_true = inputs[5]
+        err = lambda K: float((K[:, 0, 0] / K_true[:, 0, 0] - 1).abs().max())
+        brief = lambda d, res, K0: dict(d, focal_error_before=round(err(K0), 5), focal_error_after=round(err(res.K), 5))
+        out["workload"] += "_camera_groups"
+        inputs[5] = detune(K_true, fixed)
+        out["per_image"] = brief(*leg(inputs, fixed, dict(kw, refine_focal=True), lens.numel(), args), inputs[5])
+        for G in (int(g) for g in args.camera_groups.split(",")):
+            ids = torch.arange(n_images, device=DEV) % G
+            inputs[5] = detune_groups(K_true, ids)
+            out[f"groups_{G}"] = brief(*leg(inputs, fixed, dict(kw, refine_focal=True, camera_ids=ids), lens.numel(), args), inputs[5])
+    elif not args.refine_focal:
         out.update(leg(inputs, fixed, kw, lens.numel(), args)[0])
     else:
         K_true = inputs[5]
