@@ -67,7 +67,10 @@ typedef enum {
  *     focal step per group of images loftr_bundle_adjust_shared_host, loftr_bundle_adjust_shared_workspace_bytes,
  *     loftr_bundle_adjust_shared), the correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
  *     loftr_register_corr), track completion (loftr_complete_tracks_host, loftr_complete_tracks_workspace_bytes,
- *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks) */
+ *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks),
+ *     3D similarity RANSAC and moving a model (loftr_estimate_similarity, loftr_similarity_minimal,
+ *     loftr_estimate_similarity_batched_workspace_bytes, loftr_estimate_similarity_batched, loftr_transform_model_host,
+ *     loftr_transform_model) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -1165,6 +1168,70 @@ int loftr_merge_tracks(const long* offsets, long T, const int* obs_image, const 
                        const int* kp_row, long K, const double* Kmat, const double* T_cam_from_world, const uint8_t* posed, int n_images,
                        float inv, int gh, int gw, double thresh_px, int reach, int* row_into, float* merge_r2, int* kp_row_new, long* counts,
                        void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
+/* ---- 3D similarity between two point sets; moving a model into another frame ------------------------------------------
+ * dst ~ s R src + t with R a proper rotation and s > 0, or s == 1 when with_scale == 0 (rigid, SE(3)): the closed form of Kabsch /
+ * Umeyama (PAMI 1991) inside RANSAC and as the refit (csrc/similarity.hip; what georegistration against surveyed camera centres and
+ * 3D-3D registration of two depth-lifted point sets need).  HOST function: all pointers are host memory, the call is synchronous.
+ * src [M,3], dst [M,3] fp64; thresh and every residual are in the units of dst.
+ *   Sampling: loftr_estimate_pose's own -- xorshift64* from `seed`, 3 distinct indices, at most 1000 iterations, a hypothesis replaces
+ *   the best only with strictly more inliers, the adaptive stop log(1 - conf) / log(1 - w^3).  The sample stream does not depend on
+ *   the scores.
+ *   Solver (fp64): centroids mu_s, mu_d; H = sum (dst_i - mu_d)(src_i - mu_s)^T = U diag(sigma) V^T by the library's 3 x 3 SVD (factors
+ *   proper or improper); d = +1 if det(U) det(V) > 0, else -1; R = U diag(1, 1, d) V^T; s = tr(R^T H) / sum |src_i - mu_s|^2 -- Umeyama's
+ *   sigma_0 + sigma_1 +- sigma_2 evaluated as nine products, free of the sign and of the square root of the smallest singular value --
+ *   or 1 when rigid; t = mu_d - s R mu_s.  One model per sample.  Degenerate samples give none:
+ *   |(P2 - P1) x (P3 - P1)|^2 <= (1e-6)^2 x (longest squared side)^2 for the source triple or for the destination triple (relative,
+ *   scale-free), and a scale that is not finite or not positive.
+ *   Residual: inlier iff |s R src + t - dst|^2 <= thresh^2.
+ *   Refit: the same closed form over the inliers of the best hypothesis (skipped below 3 inliers), adopted when it has at least as
+ *   many inliers, and repeated on the adopted model's inliers while it strictly gains inliers (at most 4 fits).  Its sums take two
+ *   passes (sum src, sum dst; then the 9 entries of H about the centroids and sum |src - mu_s|^2), each sum in a fixed order (256
+ *   strided partials, partial k over the correspondences i = k mod 256 in ascending i, then a pairwise tree), which the GPU estimator
+ *   reproduces.
+ * Outputs: *s_out, R_out [9] row-major, t_out [3], inliers_out [M] and *n_inliers of the returned model; *n_inliers = -1 with s, R, t and
+ * the mask zero when M < 3, no sample gave a model, or the best model has fewer than 3 inliers.
+ * loftr_similarity_minimal exposes the minimal solver: src3 [3,3], dst3 [3,3] -> *n_solutions <= 1 model in *s, R [9], t [3] (zero
+ * without one). */
+int loftr_estimate_similarity(const double* src, const double* dst, long M, int with_scale, double thresh, float conf, unsigned seed,
+                              double* s_out, double* R_out, double* t_out, uint8_t* inliers_out, long* n_inliers);
+int loftr_similarity_minimal(const double* src3, const double* dst3, int with_scale, double* s, double* R, double* t, int* n_solutions);
+
+/* loftr_estimate_similarity for every problem of a batch, on the GPU (csrc/similarity_gpu.hip).  CONTRACT: for every problem p the
+ * result is the one loftr_estimate_similarity returns for that problem's correspondences with the same seed -- same n_inliers, same
+ * inlier mask, s, R and t equal BIT FOR BIT (the outputs are fp64: there is no float rounding in between).
+ *   src [M,3], dst [M,3] f64, m_bids [M] i64: device memory; the correspondences grouped by ascending problem id (problem p = the
+ *   correspondences with m_bids == p, in order); with_scale, thresh, conf: as the host estimator; seed: one seed shared by every problem.
+ * Outputs (device memory): s_out [P], R_out [P,9], t_out [P,3] f64; inliers_out [M] u8; n_inliers [P] i64, or -1 where the host
+ * estimator returns -1 -- there s, R, t and the problem's mask are 0.
+ * Stream-ordered on `stream`; the points never leave the device.  The call copies the per-hypothesis inlier counts to the host once,
+ * replays the RANSAC loop there (the host estimator's own pow / log), copies one decision per problem back and waits for the stream
+ * before it returns: two host round trips per batch, whatever P.  Workspace:
+ * loftr_estimate_similarity_batched_workspace_bytes(M, P), about 125 kB per problem plus 49 bytes per correspondence.
+ * Status: LOFTR_ERR_BAD_ARG for a null pointer, M < 0 or P < 0, P == 0 with M > 0, and for m_bids outside [0, P) or not grouped by
+ * ascending problem (found on the device, reported at the call's own synchronisation; the outputs are then not written);
+ * LOFTR_ERR_WORKSPACE for a short workspace; LOFTR_ERR_UNSUPPORTED for M >= 2^31 or P >= 2^31 / 1000.
+ * M == 0 is valid (every problem gets -1); P == 0 and M == 0 is a no-op success. */
+size_t loftr_estimate_similarity_batched_workspace_bytes(long M, int P);
+int loftr_estimate_similarity_batched(const double* src, const double* dst, const long* m_bids, long M, int P, int with_scale, double thresh,
+                                      float conf, unsigned seed, double* s_out, double* R_out, double* t_out, uint8_t* inliers_out,
+                                      long* n_inliers, void* ws, size_t ws_bytes, void* stream);
+
+/* Moving a model by one similarity (s, R, t), X' = s R X + t: loftr_transform_model_host (csrc/similarity.hip, host memory, synchronous)
+ * and loftr_transform_model (csrc/similarity_gpu.hip, device memory, stream-ordered; a thread per point and a thread per image) run
+ * one text, fp64 in a stated order without fused multiply-add, so the CPU chain and the GPU chain stay bit-equal.
+ *   xyz [N,3] f32, T_cam_from_world [n_images,4,4] f64 row-major, posed [n_images] u8, s [1], R [9] row-major, t [3] f64 (pointers in
+ *   the memory of the call's side).
+ * Outputs: xyz_out [N,3] = f32(s (R_i0 X_0 + R_i1 X_1 + R_i2 X_2) + t_i), every row (a NaN row stays NaN); T_out [n_images,4,4]: for
+ * a posed image R_c' = R_c R^T (rows left to right), t_c' = s t_c - R_c' t, bottom row 0 0 0 1, so that the camera coordinates of a
+ * world point keep their direction and depths scale by s; an image that is not posed gets its input bits back, NaN included.
+ * In place is allowed: xyz_out == xyz, T_out == T_cam_from_world.
+ * Status: LOFTR_ERR_BAD_ARG for a null pointer (xyz / xyz_out only with N > 0, T / posed / T_out only with n_images > 0) or a negative
+ * count; N == 0 and n_images == 0 is a no-op success. */
+int loftr_transform_model_host(const float* xyz, long N, const double* T_cam_from_world, const uint8_t* posed, int n_images, const double* s,
+                               const double* R, const double* t, float* xyz_out, double* T_out);
+int loftr_transform_model(const float* xyz, long N, const double* T_cam_from_world, const uint8_t* posed, int n_images, const double* s,
+                          const double* R, const double* t, float* xyz_out, double* T_out, void* stream);
 
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the

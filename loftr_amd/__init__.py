@@ -12,4 +12,5 @@ from .bundle import BundleResult, bundle_adjust                   # noqa: F401
 from .registration import Reconstruction, Registration, reconstruct_tracks, register_images    # noqa: F401
 from .completion import Completion, complete_tracks                # noqa: F401
 from .merging import Merge, merge_tracks                            # noqa: F401
+from .alignment import Alignment, align_centres                    # noqa: F401
 from .localization import LocalizationModel, QueryLocalizer, QueryPoses   # noqa: F401

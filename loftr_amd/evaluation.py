@@ -287,6 +287,99 @@ def localize(data, db_side=0, depth=None, K_db=None, K_query=None, T_world_from_
     return data
 
 
+# ---- 3D similarity between two point sets (csrc/similarity.hip, csrc/similarity_gpu.hip) ----------------------
+def estimate_similarity_native(src, dst, with_scale=True, thresh=0.05, conf=0.999, seed=0):
+    """dst ~ s R src + t from 3D-3D correspondences (numpy: src [M,3], dst [M,3]): RANSAC over 3-point Kabsch / Umeyama closed forms
+    + the same closed form as the refit, the library's own host estimator (csrc/similarity.hip).  with_scale=False fits a rigid
+    motion (s == 1.0 exactly).  thresh is the distance |s R src + t - dst| in the units of dst.
+    Returns (s, R [3,3], t [3], inlier mask [M] bool) in float64, or None without a model (fewer than 3 correspondences, only
+    degenerate samples)."""
+    import ctypes as C
+    from . import _lib
+    a = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+    b = np.ascontiguousarray(dst, np.float64).reshape(-1, 3)
+    M = a.shape[0]
+    if b.shape[0] != M:
+        raise ValueError(f"estimate_similarity_native: src and dst differ in length ({M} and {b.shape[0]})")
+    if M < 3:
+        return None
+    s, R, t, inl, n = np.zeros(1), np.zeros(9), np.zeros(3), np.zeros(M, np.uint8), C.c_long(-1)
+    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.load().loftr_estimate_similarity(ptr(a), ptr(b), M, int(bool(with_scale)), float(thresh), float(conf), int(seed), ptr(s),
+                                                     ptr(R), ptr(t), ptr(inl), C.byref(n)), "loftr_estimate_similarity")
+    if n.value < 0:
+        return None
+    return float(s[0]), R.reshape(3, 3), t, inl.astype(bool)
+
+
+def estimate_similarity_native_gpu(src, dst, with_scale=True, thresh=0.05, conf=0.999, seed=0):
+    """estimate_similarity_native on the GPU (ops.estimate_similarities): the same result for the same seed, bit for bit."""
+    a = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+    b = np.ascontiguousarray(dst, np.float64).reshape(-1, 3)
+    if b.shape[0] != a.shape[0]:
+        raise ValueError(f"estimate_similarity_native_gpu: src and dst differ in length ({a.shape[0]} and {b.shape[0]})")
+    if a.shape[0] < 3:
+        return None
+    a, b = torch.as_tensor(a).cuda(), torch.as_tensor(b).cuda()
+    s, R, t, inl, n = ops.estimate_similarities(a, b, torch.zeros(a.shape[0], dtype=torch.int64, device=a.device), 1, with_scale, thresh, conf, seed)
+    if int(n[0]) < 0:
+        return None
+    return float(s[0]), R[0].cpu().numpy(), t[0].cpu().numpy(), inl.cpu().numpy()
+
+
+def register_depth(data, thresh=0.05, conf=0.999, seed=0, depth0=None, depth1=None, K0=None, K1=None):
+    """Rigid motion between the two cameras of every pair of the batch dict that forward / match_pairs leaves, from the matches and a
+    depth map on BOTH sides (RGB-D streams, ScanNet), in GPU calls only: the keypoints of each side are lifted to 3D in their own
+    camera's frame (ops.lift_keypoints), matches without depth on either side are dropped, and a rigid 3D-3D fit
+    (ops.estimate_similarities with with_scale=False) runs for the whole batch in one call.  Unlike the five-point path it is metric
+    and does not degenerate on planar scenes, small baselines or pure rotation.
+    depth0 / depth1 / K0 / K1 default to the batch's own entries.
+    Update: data['R_3d'] float32 [N,3,3], data['t_3d'] float32 [N,3] (x_1 = R x_0 + t, an estimate of T_0to1; zero where no model was
+    found), data['inliers'] bool [M] in match order (False for dropped matches), data['n_inliers'] int64 [N] (-1 without a model) and
+    data['n_lifted'] int64 [N] (matches with a valid depth on both sides).  N is data['bs'].
+    Defaults: thresh = 0.05 in the units of the depth (5 cm for metric depth), conf 0.999, seed 0.  They are this project's choice
+    (a common setting for indoor RGB-D registration); nothing in the reference fixes them."""
+    N = int(data["bs"]) if "bs" in data else int(data["image0"].shape[0])
+    f32 = lambda t: t.to(torch.float32)
+    m_bids = data["m_bids"].to(torch.int64)
+    x0, v0 = ops.lift_keypoints(f32(data["mkpts0_f"]), m_bids, f32(data["depth0"] if depth0 is None else depth0), f32(data["K0"] if K0 is None else K0))
+    x1, v1 = ops.lift_keypoints(f32(data["mkpts1_f"]), m_bids, f32(data["depth1"] if depth1 is None else depth1), f32(data["K1"] if K1 is None else K1))
+    valid = v0 & v1
+    keep = valid.nonzero().squeeze(1)                        # boolean selection keeps the grouping by ascending pair
+    _, R, t, inl, n = ops.estimate_similarities(x0[keep], x1[keep], m_bids[keep], N, False, thresh, conf, seed)
+    inliers = torch.zeros_like(valid)
+    inliers[keep] = inl
+    n_lifted = torch.zeros(N, dtype=torch.int64, device=valid.device).index_add_(0, m_bids, valid.to(torch.int64))
+    data.update({"R_3d": R.to(torch.float32), "t_3d": t.to(torch.float32), "inliers": inliers, "n_inliers": n, "n_lifted": n_lifted})
+    return data
+
+
+def trajectory_errors(T_est, posed, T_gt, thresh=None, with_scale=True, conf=0.999, seed=0):
+    """Errors of estimated camera poses against the truth after aligning the two frames by a similarity of the camera centres (the
+    reconstruction's frame and scale are arbitrary): T_est [n,4,4], T_gt [n,4,4] camera-from-world, posed [n] bool.
+    thresh None: one least-squares fit (Umeyama) over all posed images; otherwise the robust fit of alignment.align_centres with that
+    threshold (units of the truth), which tolerates grossly wrong poses.
+    -> (rot_deg [n], centre_err [n]) float64 numpy, NaN for images without a pose; with fewer than 3 posed images, or without a
+    model, every entry is NaN."""
+    from .alignment import align_centres, fit_centres
+    T = torch.as_tensor(np.asarray(T_est.cpu() if isinstance(T_est, torch.Tensor) else T_est, np.float64))
+    G = np.asarray(T_gt.cpu() if isinstance(T_gt, torch.Tensor) else T_gt, np.float64)
+    p = torch.as_tensor(np.asarray(posed.cpu() if isinstance(posed, torch.Tensor) else posed).astype(bool))
+    n = T.shape[0]
+    rot, cen = np.full(n, np.nan), np.full(n, np.nan)
+    ref = torch.as_tensor(-np.einsum("nji,nj->ni", G[:, :3, :3], G[:, :3, 3]))
+    al = fit_centres(T, p, ref, p, with_scale) if thresh is None else align_centres(T, p, ref, p, thresh, with_scale, conf, seed)
+    if al.n_inliers < 0:
+        return rot, cen
+    _, T2 = ops.transform_model(torch.zeros(0, 3), T, p, al.s, al.R, al.t)
+    T2 = T2.numpy()
+    for i in np.flatnonzero(p.numpy()):
+        R_e, R_g = T2[i, :3, :3], G[i, :3, :3]
+        rot[i] = abs(_angle_deg((np.trace(R_e.T @ R_g) - 1.0) / 2.0))
+        cen[i] = np.linalg.norm(-R_e.T @ T2[i, :3, 3] + R_g.T @ G[i, :3, 3])
+    return rot, cen
+
+
 def absolute_pose_error(T_gt, R, t):
     """(rotation error in degrees, distance between the camera centres in the units of the depth) of an estimate x_cam = R X + t
     against the ground truth T_gt [4,4] or [3,4] (same convention): the geodesic angle of R^T R_gt and |R^T t - R_gt^T t_gt|, the two

@@ -1090,6 +1090,79 @@ def lift_keypoints(kpts, m_bids, depth, K, T=None):
     return out, valid.view(torch.bool)
 
 
+@_on_device
+def estimate_similarities(src, dst, m_bids, P, with_scale=True, thresh=0.05, conf=0.999, seed=0):
+    """3D similarity (dst ~ s R src + t; rigid, s == 1, with with_scale=False) by RANSAC over 3-point closed forms + a closed-form refit
+    for every problem of a batch on the GPU (csrc/similarity_gpu.hip): for each problem, what the host estimator
+    loftr_estimate_similarity (evaluation.estimate_similarity_native) returns for that problem's correspondences with the same seed,
+    bit for bit.
+    src [M,3], dst [M,3] f64 or f32 (widened to f64 here), m_bids [M] i64 grouped by ascending problem id, P problems; thresh in the
+    units of dst.
+    -> (s [P] f64, R [P,3,3] f64, t [P,3] f64, inliers [M] bool, n_inliers [P] i64), device tensors; n_inliers[p] == -1 where the
+    host estimator finds no model (s, R, t and that problem's mask are zero there).  Synchronises the stream."""
+    for name, t, dts in (("src", src, (torch.float64, torch.float32)), ("dst", dst, (torch.float64, torch.float32)), ("m_bids", m_bids, (torch.int64,))):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dts:
+            raise _lib.LoftrHipError(f"{name}: expected a {' or '.join(str(d) for d in dts)} GPU tensor (the similarity kernels have no CPU fallback)")
+    M, P = src.shape[0], int(P)
+    if src.shape != (M, 3) or dst.shape != (M, 3) or m_bids.shape != (M,) or P < 0:
+        raise _lib.LoftrHipError(f"estimate_similarities: expected src [M,3], dst [M,3], m_bids [M] and P >= 0, got "
+                                 f"{tuple(src.shape)}, {tuple(dst.shape)}, {tuple(m_bids.shape)}, {P}")
+    dev = src.device
+    args = [src.double().contiguous(), dst.double().contiguous(), m_bids.contiguous()]
+    s = torch.zeros(P, dtype=torch.float64, device=dev)
+    R = torch.zeros(P, 3, 3, dtype=torch.float64, device=dev)
+    t = torch.zeros(P, 3, dtype=torch.float64, device=dev)
+    inl = torch.zeros(M, dtype=torch.uint8, device=dev)
+    n = torch.full((P,), -1, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(1, lib.loftr_estimate_similarity_batched_workspace_bytes(M, P)), dtype=torch.uint8, device=dev)
+    check(lib.loftr_estimate_similarity_batched(*[_ptr(a) for a in args], M, P, int(bool(with_scale)), float(thresh), float(conf), int(seed),
+                                                _ptr(s), _ptr(R), _ptr(t), _ptr(inl), _ptr(n), _ptr(ws), ws.numel(), _stream()),
+          "loftr_estimate_similarity_batched (m_bids must lie in [0, P) and be grouped by ascending problem)")
+    return s, R, t, inl.view(torch.bool), n
+
+
+@_on_device
+def transform_model(xyz, T_cam_from_world, posed, s, R, t, out_xyz=None, out_T=None):
+    """Move a model by one similarity, X' = s R X + t (loftr_transform_model_host on CPU tensors, loftr_transform_model on GPU tensors:
+    one text, fp64 in a stated order, so the two sides agree bit for bit).
+    xyz [N,3] f32, T_cam_from_world [n,4,4] f64, posed [n] bool or u8, s [] or [1] f64, R [3,3] f64, t [3] f64 -- all on one device.
+    -> (xyz' [N,3] f32, T' [n,4,4] f64): posed images get R_c R^T and s t_c - R_c' t, the others their input bits.  out_xyz / out_T may
+    be the inputs themselves (in place)."""
+    named = (("xyz", xyz, torch.float32, (3,)), ("T_cam_from_world", T_cam_from_world, torch.float64, (4, 4)), ("posed", posed, None, ()),
+             ("s", s, torch.float64, None), ("R", R, torch.float64, None), ("t", t, torch.float64, None))
+    for name, a, dt, tail in named:
+        if not isinstance(a, torch.Tensor):
+            raise _lib.LoftrHipError(f"transform_model: {name} must be a tensor")
+    devs = {a.device for _, a, _, _ in named} | {a.device for a in (out_xyz, out_T) if a is not None}
+    if len(devs) != 1:
+        raise _lib.LoftrHipError(f"transform_model: tensors on different devices ({sorted(str(d) for d in devs)})")
+    if posed.dtype not in (torch.bool, torch.uint8):
+        raise _lib.LoftrHipError(f"transform_model: posed must be bool or uint8, got {posed.dtype}")
+    for name, a, dt, tail in named:
+        if dt is not None and a.dtype != dt:
+            raise _lib.LoftrHipError(f"transform_model: {name} must be {dt}, got {a.dtype}")
+    N, n = xyz.shape[0], T_cam_from_world.shape[0]
+    if xyz.shape != (N, 3) or T_cam_from_world.shape != (n, 4, 4) or posed.shape != (n,) or s.numel() != 1 or R.shape != (3, 3) or t.shape != (3,):
+        raise _lib.LoftrHipError(f"transform_model: expected xyz [N,3], T_cam_from_world [n,4,4], posed [n], s [1], R [3,3], t [3], got "
+                                 f"{tuple(xyz.shape)}, {tuple(T_cam_from_world.shape)}, {tuple(posed.shape)}, {tuple(s.shape)}, "
+                                 f"{tuple(R.shape)}, {tuple(t.shape)}")
+    for name, o, like in (("out_xyz", out_xyz, xyz), ("out_T", out_T, T_cam_from_world)):
+        if o is not None and (o.dtype != like.dtype or o.shape != like.shape or not o.is_contiguous()):
+            raise _lib.LoftrHipError(f"transform_model: {name} must be a contiguous {like.dtype} tensor of shape {tuple(like.shape)}")
+    xyz_c, T_c, R_c, t_c = (a if a is out else a.contiguous() for a, out in ((xyz, out_xyz), (T_cam_from_world, out_T), (R, None), (t, None)))
+    posed_c = posed.contiguous().view(torch.uint8)
+    out_xyz = torch.empty_like(xyz_c) if out_xyz is None else out_xyz
+    out_T = torch.empty_like(T_c) if out_T is None else out_T
+    lib = _lib.load()
+    args = (_ptr(xyz_c), N, _ptr(T_c), _ptr(posed_c), n, _ptr(s), _ptr(R_c), _ptr(t_c), _ptr(out_xyz), _ptr(out_T))
+    if xyz.is_cuda:
+        check(lib.loftr_transform_model(*args, _stream()), "loftr_transform_model")
+    else:
+        check(lib.loftr_transform_model_host(*args), "loftr_transform_model_host")
+    return out_xyz, out_T
+
+
 # ---- the two sides of a routine pair -------------------------------------------------------------------------------------------------
 # The SfM routines below come in pairs: loftr_<name>_host on numpy arrays DEFINES the result, loftr_<name> reproduces it on GPU tensors.
 # A pair shares one body, written against a backend that supplies what differs: how an array that belongs to the other side is refused,

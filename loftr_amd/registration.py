@@ -65,6 +65,21 @@ class Reconstruction:
         self.points, self.bundle, self.stats, self.K = points, bundle, stats, K
         self.sfm = None                                                 # the relabelled atlas of SfmResult.reconstruct(complete=True / merge=True)
 
+    def transformed(self, s, R, t):
+        """A copy moved by the similarity X' = s R X + t (``ops.transform_model``): new ``T_cam_from_world`` and
+        ``points.xyz``; every other tensor is shared with this one, and ``bundle`` is left in the old frame."""
+        from .alignment import transformed
+        return transformed(self, s, R, t)
+
+    def align(self, ref_centres, known=None, thresh=1.0, with_scale=True, apply=True, conf=0.999, seed=0):
+        """Georegister against reference camera positions ``ref_centres [n,3]`` (``known [n]``: which rows hold one; default: the
+        finite rows) -> ``(rec2, alignment)``: ``alignment`` is ``alignment.align_centres`` of the posed and known images at
+        ``thresh`` (units of ``ref_centres``), ``rec2 = self.transformed(s, R, t)``.  ``bundle`` stays in the old frame.  Without a
+        model (``alignment.n_inliers == -1``) nothing is raised and ``rec2`` is this reconstruction itself; likewise with
+        ``apply=False``."""
+        from .alignment import align
+        return align(self, ref_centres, known, thresh, with_scale, apply, conf, seed)
+
 
 def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed, min_corr=15, min_inliers=15, thresh_px=4.0,
                     conf=0.999, seed=0, timings=None):
