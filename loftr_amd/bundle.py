@@ -136,49 +136,40 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             raise ValueError(f"{what}: refine_focal must be None, True or a mask of shape ({len(K)},), got {tuple(refine_focal.shape)}")
     for n, a in zip(_ARGS[:2], args[:2]):
         _tracks.integers(what, n, a)
+    # the arguments in the dtypes of the C call, on their side
     if gpu:
         dev = args[0].device
         dts = (torch.int64, torch.int32, torch.float32, None, torch.float32, torch.float64, torch.float64)
         a = [x.detach() if dt is None else x.detach().to(dt) for x, dt in zip(args, dts)]
-        a[3] = (a[3] != 0).to(torch.uint8)
         n = a[5].shape[0]
-        if fixed is None:
-            fixed = torch.zeros(n, dtype=torch.bool, device=dev)
-            fixed[:1] = True
-        fx = (fixed.detach() != 0).to(torch.uint8)
-        if focal is None:
-            out = ops.bundle_adjust(*a, fx, *_tracks.group_by_image(a[1], n), *params, timings=timings)
-        else:
-            rf = torch.ones(n, dtype=torch.uint8, device=dev) if refine_focal is True else (refine_focal.detach() != 0).to(torch.uint8)
-            if camera_ids is None:
-                out = ops.bundle_adjust_focal(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal, timings=timings)
-            else:
-                groups = _tracks.group_by_camera(camera_ids.detach())
-                out = ops.bundle_adjust_shared(*a, fx, *_tracks.group_by_image(a[1], n), rf, *groups, *params, *focal, timings=timings)
-                out["cam_group"] = groups[0]
+        flags = lambda x: (x.detach() != 0).to(torch.uint8)
+        ones = torch.ones(n, dtype=torch.uint8, device=dev)
     else:
         dts = (np.int64, np.int32, np.float32, None, np.float32, np.float64, np.float64)
         host = lambda x: x.detach().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
         a = [np.ascontiguousarray(host(x)) if dt is None else np.ascontiguousarray(host(x), dt) for x, dt in zip(args, dts)]
-        a[3] = (a[3] != 0).astype(np.uint8)
         n = a[5].shape[0]
-        fx = np.zeros(n, np.uint8)
-        if fixed is None:
-            fx[:1] = 1
-        else:
-            fx = (host(fixed) != 0).astype(np.uint8)
+        flags = lambda x: (host(x) != 0).astype(np.uint8)
+        ones = np.ones(n, np.uint8)
         if a[0].ndim == 1 and a[1].ndim == 1 and a[5].ndim == 3:         # the errors the kernels report through counts[1]
             _tracks.check_host(what, a[0], a[1], n)
-        if focal is None:
-            out = ops.bundle_adjust_host(*a, fx, *_tracks.group_by_image(a[1], n), *params)
-        else:
-            rf = np.ones(n, np.uint8) if refine_focal is True else (refine_focal != 0).astype(np.uint8)
-            if camera_ids is None:
-                out = ops.bundle_adjust_focal_host(*a, fx, *_tracks.group_by_image(a[1], n), rf, *params, *focal)
-            else:
-                groups = _tracks.group_by_camera(camera_ids)
-                out = ops.bundle_adjust_shared_host(*a, fx, *_tracks.group_by_image(a[1], n), rf, *groups, *params, *focal)
-                out["cam_group"] = groups[0]
+    a[3] = flags(a[3])
+    fx = 0 * ones
+    fx[:1] = 1                                                           # fixed = None: image 0 only
+    if fixed is not None:
+        fx = flags(fixed)
+    # the mode, once: which pair of ops, and what it takes after the table of the observations grouped by image
+    extra, mode = [], ""
+    if focal is not None:
+        extra, mode = [ones if refine_focal is True else flags(refine_focal)], "_focal"
+    if camera_ids is not None:
+        groups = _tracks.group_by_camera(camera_ids.detach() if gpu else camera_ids)
+        extra, mode = extra + list(groups), "_shared"
+    call = getattr(ops, "bundle_adjust" + mode + ("" if gpu else "_host"))
+    out = call(*a, fx, *_tracks.group_by_image(a[1], n), *extra, *params, *(focal or ()), **({"timings": timings} if gpu else {}))
+    if camera_ids is not None:
+        out["cam_group"] = groups[0]
+    if not gpu:
         out = {k: torch.from_numpy(v) for k, v in out.items()}
     counts = (out["counts"] if neg_id is None else torch.cat([out["counts"], neg_id])).cpu()      # the one readback
     reals = counts[8:13].view(torch.float64).tolist()

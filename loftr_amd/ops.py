@@ -1438,24 +1438,62 @@ def _ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol):
     return float(huber_px), int(max_iters), int(pcg_iters), float(pcg_tol), float(ftol)
 
 
-def _bundle_adjust(B, what, hint, arrays, params, timings):
-    _check_args(B, what, hint, _BA_ARGS, arrays)
-    offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs = arrays
+def _ba_focal_params(what, min_focal_obs, focal_lo, focal_hi):
+    import math
+    ok = isinstance(min_focal_obs, int) and not isinstance(min_focal_obs, bool) and \
+        all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (focal_lo, focal_hi))
+    if not (ok and min_focal_obs >= 1 and math.isfinite(focal_lo) and math.isfinite(focal_hi) and focal_lo < 1 < focal_hi):
+        raise ValueError(f"{what}: min_focal_obs must be an integer >= 1 and the focal bounds finite with lo < 1 < hi, got {min_focal_obs}, "
+                         f"{focal_lo}, {focal_hi}")
+    return int(min_focal_obs), float(focal_lo), float(focal_hi)
+
+
+# bits of counts[1] of the grouped pair: BUNDLE_ERRORS and the check of the camera groups
+BUNDLE_SHARED_ERRORS = BUNDLE_ERRORS + ((8, "cam_group / group_offsets / group_cams are not the images grouped by camera in ascending order"),)
+# The three modes, each a routine pair loftr_<call>_host / loftr_<call>, differ in a table: the inputs after
+# cam_obs (refine_focal goes after fixed in the C call, the group arrays and G after cam_obs), the outputs after point_active, how the
+# shape error ends, and what the rule text adds.
+_BA_FOCAL_IN, _BA_FOCAL_OUT = (("refine_focal", "uint8", 1),), (("K", "n", (3, 3), "float64"), ("cam_focal", "n", (), "uint8"))
+_BA_MODES = {
+    "bundle_adjust": ((), (), "cam_offsets [n+1] and cam_obs [N]", ""),
+    "bundle_adjust_focal": (_BA_FOCAL_IN, _BA_FOCAL_OUT, "cam_offsets [n+1], cam_obs [N] and refine_focal [n]", ""),
+    "bundle_adjust_shared": (_BA_FOCAL_IN + (("cam_group", "int32", 1), ("group_offsets", "int64", 1), ("group_cams", "int32", 1)),
+                             _BA_FOCAL_OUT + (("group_focal", "G", (), "uint8"),),
+                             "cam_offsets [n+1], cam_obs [N], refine_focal [n], cam_group [n], group_offsets [G+1] with 1 <= G <= n and "
+                             "group_cams [n]",
+                             "; cam_group / group_offsets / group_cams must group the images by camera in ascending order")}
+
+
+def _bundle_adjust(B, call, arrays, params, focal, timings):
+    """The body of all six: the table check, the shapes, the parameters, zeroed outputs, the timing buffers (per kernel class, not per
+    stage: the median launch and the total, and the launches issued), the call."""
+    extra_in, extra_out, shapes, rule = _BA_MODES[call]
+    what, hint = (call + "_host", call) if B is _Host else \
+        (call, f"the bundle-adjustment kernels have no CPU fallback; the host routine is {call}_host")
+    _check_args(B, what, hint, _BA_ARGS + extra_in, arrays)
+    offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs = arrays[:10]
     N, n, T = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
+    refine, groups = arrays[10:11], arrays[11:]          # (refine_focal,) and (cam_group, group_offsets, group_cams), or empty
+    size = {"T": T, "N": N, "n": n}
+    if groups:
+        size["G"] = G = groups[1].shape[0] - 1
     if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or tuple(K.shape) != (n, 3, 3) or \
-            tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N:
+            tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N or \
+            any(x.shape[0] != n for x in (*refine, *groups[::2])) or (groups and (G < 0 or G > n or (n > 0 and G == 0))):
         raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
-                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1] and cam_obs [N], got {[tuple(a.shape) for a in arrays]}")
+                                 f"T_cam_from_world [n,4,4], fixed [n], {shapes}, got {[tuple(a.shape) for a in arrays]}")
     params = _ba_params(what, *params)
+    if focal is not None:
+        params += _ba_focal_params(what, *focal)
     arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
     a = [B.ptr(x) for x in arrays]
-    out = _outputs(B, _BA_OUT, {"T": T, "N": N, "n": n}, BUNDLE_COUNTS, offsets)
-    # per kernel class, not per stage: the median launch and the total, and the launches issued
+    out = _outputs(B, _BA_OUT + extra_out, size, BUNDLE_COUNTS, offsets)
     ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
     launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
     cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
-    B.call("bundle_adjust", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], n, a[8], a[9], *params, *[B.ptr(out[k]) for k in out]),
-           _TABLE_RULES, offsets, ws=(T, N, n), tail=(cast(ms), cast(launches)))
+    B.call(call, (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], *a[10:11], n, a[8], a[9], *a[11:], *([G] if groups else []), *params,
+                  *[B.ptr(out[k]) for k in out]),
+           _TABLE_RULES + rule, offsets, ws=(T, N, n), tail=(cast(ms), cast(launches)))
     if timings is not None:
         timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
     return out
@@ -1467,129 +1505,8 @@ def bundle_adjust_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_
     i64, obs_image [N] i32, obs_xy [N,2] f32, obs_mask [N] u8, xyz [T,3] f32, K [n,3,3] f64, T_cam_from_world [n,4,4] f64, fixed [n] u8,
     cam_offsets [n+1] i64, cam_obs [N] i32.  -> dict of numpy arrays: T_cam_from_world [n,4,4] f64, xyz [T,3] f32, obs_active [N] u8,
     cam_free [n] u8, point_active [T] u8, counts [16] i64."""
-    return _bundle_adjust(_Host, "bundle_adjust_host", "bundle_adjust",
-                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs),
-                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), None)
-
-
-def _ba_focal_params(what, min_focal_obs, focal_lo, focal_hi):
-    import math
-    ok = isinstance(min_focal_obs, int) and not isinstance(min_focal_obs, bool) and \
-        all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (focal_lo, focal_hi))
-    if not (ok and min_focal_obs >= 1 and math.isfinite(focal_lo) and math.isfinite(focal_hi) and focal_lo < 1 < focal_hi):
-        raise ValueError(f"{what}: min_focal_obs must be an integer >= 1 and the focal bounds finite with lo < 1 < hi, got {min_focal_obs}, "
-                         f"{focal_lo}, {focal_hi}")
-    return int(min_focal_obs), float(focal_lo), float(focal_hi)
-
-
-def _bundle_adjust_focal(B, what, hint, arrays, params, focal, timings):
-    """The body of the focal pair: _bundle_adjust with refine_focal [n] u8 after fixed, (min_focal_obs, focal_lo, focal_hi)
-    after the parameters, and K [n,3,3] f64 and cam_focal [n] u8 after the outputs."""
-    _check_args(B, what, hint, _BA_ARGS + (("refine_focal", "uint8", 1),), arrays)
-    offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs, refine = arrays
-    N, n, T = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
-    if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or tuple(K.shape) != (n, 3, 3) or \
-            tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N or \
-            refine.shape[0] != n:
-        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
-                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1], cam_obs [N] and refine_focal [n], got "
-                                 f"{[tuple(a.shape) for a in arrays]}")
-    params = _ba_params(what, *params)
-    focal = _ba_focal_params(what, *focal)
-    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
-    a = [B.ptr(x) for x in arrays]
-    out = _outputs(B, _BA_OUT + (("K", "n", (3, 3), "float64"), ("cam_focal", "n", (), "uint8")), {"T": T, "N": N, "n": n}, BUNDLE_COUNTS,
-                   offsets)
-    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
-    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
-    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
-    B.call("bundle_adjust_focal", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], a[10], n, a[8], a[9], *params, *focal,
-                                   *[B.ptr(out[k]) for k in out]),
-           _TABLE_RULES, offsets, ws=(T, N, n), tail=(cast(ms), cast(launches)))
-    if timings is not None:
-        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
-    return out
-
-
-def bundle_adjust_focal_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
-                             huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi):
-    """loftr_bundle_adjust_focal_host: the host routine that DEFINES the bundle adjustment with focal refinement (include/loftr_hip.h;
-    DESIGN §18.1) on numpy arrays: those of bundle_adjust_host plus refine_focal [n] u8.  -> its dict plus K [n,3,3] f64 and
-    cam_focal [n] u8; counts[13] is the number of cameras that refine their focal."""
-    return _bundle_adjust_focal(_Host, "bundle_adjust_focal_host", "bundle_adjust_focal",
-                                (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal),
-                                (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None)
-
-
-@_on_device
-def bundle_adjust_focal(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, huber_px,
-                        max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi, timings=None):
-    """loftr_bundle_adjust_focal: the kernels of the 7-wide camera block (csrc/bundle_gpu.hip) on GPU tensors; the same result as
-    bundle_adjust_focal_host bit for bit, the same launch schedule, timing classes and single readback as bundle_adjust."""
-    return _bundle_adjust_focal(_Gpu, "bundle_adjust_focal",
-                                "the bundle-adjustment kernels have no CPU fallback; the host routine is bundle_adjust_focal_host",
-                                (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal),
-                                (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
-
-
-# bits of counts[1] of the grouped pair (DESIGN §18.2): BUNDLE_ERRORS and the check of the camera groups
-BUNDLE_SHARED_ERRORS = BUNDLE_ERRORS + ((8, "cam_group / group_offsets / group_cams are not the images grouped by camera in ascending order"),)
-_BA_SHARED_ARGS = _BA_ARGS + (("refine_focal", "uint8", 1), ("cam_group", "int32", 1), ("group_offsets", "int64", 1), ("group_cams", "int32", 1))
-
-
-def _bundle_adjust_shared(B, what, hint, arrays, params, focal, timings):
-    """The body of the grouped pair: _bundle_adjust_focal with cam_group [n] i32, group_offsets [G+1] i64, group_cams [n] i32
-    after cam_obs, and group_focal [G] u8 after the outputs."""
-    _check_args(B, what, hint, _BA_SHARED_ARGS, arrays)
-    offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs, refine, cam_group, group_offsets, group_cams = arrays
-    N, n, T, G = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1, group_offsets.shape[0] - 1
-    if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or tuple(K.shape) != (n, 3, 3) or \
-            tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N or \
-            refine.shape[0] != n or cam_group.shape[0] != n or group_cams.shape[0] != n or G < 0 or G > n or (n > 0 and G == 0):
-        raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
-                                 f"T_cam_from_world [n,4,4], fixed [n], cam_offsets [n+1], cam_obs [N], refine_focal [n], cam_group [n], "
-                                 f"group_offsets [G+1] with 1 <= G <= n and group_cams [n], got {[tuple(a.shape) for a in arrays]}")
-    params = _ba_params(what, *params)
-    focal = _ba_focal_params(what, *focal)
-    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
-    a = [B.ptr(x) for x in arrays]
-    out = _outputs(B, _BA_OUT + (("K", "n", (3, 3), "float64"), ("cam_focal", "n", (), "uint8"), ("group_focal", "G", (), "uint8")),
-                   {"T": T, "N": N, "n": n, "G": G}, BUNDLE_COUNTS, offsets)
-    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
-    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
-    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
-    B.call("bundle_adjust_shared", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], a[10], n, a[8], a[9], a[11], a[12], a[13], G, *params,
-                                    *focal, *[B.ptr(out[k]) for k in out]),
-           _TABLE_RULES + "; cam_group / group_offsets / group_cams must group the images by camera in ascending order", offsets,
-           ws=(T, N, n), tail=(cast(ms), cast(launches)))
-    if timings is not None:
-        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
-    return out
-
-
-def bundle_adjust_shared_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
-                              cam_group, group_offsets, group_cams, huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo,
-                              focal_hi):
-    """loftr_bundle_adjust_shared_host: the host routine that DEFINES the bundle adjustment with one focal step per group of images
-    (include/loftr_hip.h; DESIGN §18.2) on numpy arrays: those of bundle_adjust_focal_host plus cam_group [n] i32, group_offsets [G+1] i64,
-    group_cams [n] i32.  -> its dict plus group_focal [G] u8; counts[14] is the number of groups that refine."""
-    return _bundle_adjust_shared(_Host, "bundle_adjust_shared_host", "bundle_adjust_shared",
-                                 (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
-                                  cam_group, group_offsets, group_cams),
-                                 (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None)
-
-
-@_on_device
-def bundle_adjust_shared(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
-                         group_offsets, group_cams, huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi,
-                         timings=None):
-    """loftr_bundle_adjust_shared: the kernels of the grouped focal step (csrc/bundle_gpu.hip) on GPU tensors; the same result as
-    bundle_adjust_shared_host bit for bit, the same timing classes and single readback as bundle_adjust."""
-    return _bundle_adjust_shared(_Gpu, "bundle_adjust_shared",
-                                 "the bundle-adjustment kernels have no CPU fallback; the host routine is bundle_adjust_shared_host",
-                                 (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
-                                  cam_group, group_offsets, group_cams),
-                                 (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
+    return _bundle_adjust(_Host, "bundle_adjust", (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), None, None)
 
 
 @_on_device
@@ -1599,9 +1516,52 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     bundle_adjust_host; the same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in
     counts[1], which the caller reads once.  timings: a dict that receives per kernel class (BUNDLE_CLASSES) the tuple
     (median ms of a launch, total ms, launches issued); the call then waits for the stream."""
-    return _bundle_adjust(_Gpu, "bundle_adjust", "the bundle-adjustment kernels have no CPU fallback; the host routine is bundle_adjust_host",
-                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs),
-                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), timings)
+    return _bundle_adjust(_Gpu, "bundle_adjust", (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), None, timings)
+
+
+def bundle_adjust_focal_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                             huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi):
+    """loftr_bundle_adjust_focal_host: the host routine that DEFINES the bundle adjustment with focal refinement (include/loftr_hip.h;
+    DESIGN §18.1) on numpy arrays: those of bundle_adjust_host plus refine_focal [n] u8.  -> its dict plus K [n,3,3] f64 and
+    cam_focal [n] u8; counts[13] is the number of cameras that refine their focal."""
+    return _bundle_adjust(_Host, "bundle_adjust_focal",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None)
+
+
+@_on_device
+def bundle_adjust_focal(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, huber_px,
+                        max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi, timings=None):
+    """loftr_bundle_adjust_focal: the kernels of the 7-wide camera block (csrc/bundle_gpu.hip) on GPU tensors; the same result as
+    bundle_adjust_focal_host bit for bit, the same launch schedule, timing classes and single readback as bundle_adjust."""
+    return _bundle_adjust(_Gpu, "bundle_adjust_focal",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
+
+
+def bundle_adjust_shared_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                              cam_group, group_offsets, group_cams, huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo,
+                              focal_hi):
+    """loftr_bundle_adjust_shared_host: the host routine that DEFINES the bundle adjustment with one focal step per group of images
+    (include/loftr_hip.h; DESIGN §18.2) on numpy arrays: those of bundle_adjust_focal_host plus cam_group [n] i32, group_offsets [G+1] i64,
+    group_cams [n] i32.  -> its dict plus group_focal [G] u8; counts[14] is the number of groups that refine."""
+    return _bundle_adjust(_Host, "bundle_adjust_shared",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
+                           group_offsets, group_cams),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None)
+
+
+@_on_device
+def bundle_adjust_shared(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
+                         group_offsets, group_cams, huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs, focal_lo, focal_hi,
+                         timings=None):
+    """loftr_bundle_adjust_shared: the kernels of the grouped focal step (csrc/bundle_gpu.hip) on GPU tensors; the same result as
+    bundle_adjust_shared_host bit for bit, the same timing classes and single readback as bundle_adjust."""
+    return _bundle_adjust(_Gpu, "bundle_adjust_shared",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
+                           group_offsets, group_cams),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
 
 
 # ---- correspondence table of the images without a pose (csrc/register.hip, csrc/register_gpu.hip; DESIGN §19) --------------------------

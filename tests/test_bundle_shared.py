@@ -1,7 +1,7 @@
 """Bundle adjustment with one focal step per group of images on the CPU: the host routine
 loftr_bundle_adjust_shared_host, which DEFINES the result, against the dense oracle with one focal column per group
 (tests/_bundle_shared_oracle.py), against the per-image call on the same inputs, on the cases of the rule, through reconstruct_tracks --
-and both per-image paths against digests taken on the commit before."""
+and both per-image paths, and the grouped one, against digests taken on the commits before."""
 import functools
 import importlib.util
 import json
@@ -343,6 +343,24 @@ def test_per_image_results_equal_the_digests_taken_on_the_parent_commit():
         assert got[case] == want[case], case
         assert sorted(want[case]["wide6"]) == ["T_cam_from_world", "cam_free", "counts", "obs_active", "point_active", "xyz"]
         assert sorted(want[case]["wide7"]) == ["K", "T_cam_from_world", "cam_focal", "cam_free", "counts", "obs_active", "point_active", "xyz"]
+
+
+def test_shared_results_equal_the_digests_taken_on_the_parent_commit():
+    """The grouped host routine returns the bits it returned before the three modes became instantiations of one sequence of phases."""
+    spec = importlib.util.spec_from_file_location("make_bundle_shared_parent_digest", os.path.join(GOLDEN, "make_bundle_shared_parent_digest.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    want = json.load(open(os.path.join(GOLDEN, "bundle_shared_parent_digest.json")))
+    got = mod.digests()
+    assert sorted(got) == sorted(want) == ["bodies", "hand_problem", "huber", "known_poses", "one_a", "one_b", "singletons_a", "thin",
+                                           "thin_above_min", "thin_at_min"]
+    for case in want:
+        assert got[case]["inputs"] == want[case]["inputs"], f"{case}: the scene itself is not the one the digests were taken on"
+        assert got[case] == want[case], case
+        assert sorted(want[case]) == ["K", "T_cam_from_world", "cam_focal", "cam_free", "counts", "group_focal", "inputs", "obs_active",
+                                      "point_active", "xyz"]
+    assert want["thin_at_min"]["group_focal"] != want["thin_above_min"]["group_focal"]        # body 2 refines at 51, not at 52
+    assert want["known_poses"]["cam_free"] != want["one_b"]["cam_free"]
 
 
 def test_without_camera_ids_the_result_has_the_fields_it_had():
