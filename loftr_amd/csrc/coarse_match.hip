@@ -959,7 +959,7 @@ extern "C" int loftr_dual_softmax_bwd(const float* feat_c0, const float* feat_c1
 extern "C" size_t loftr_sinkhorn_bwd_workspace_bytes(int N, int L, int S, int C, int iters) {
   if (N <= 0 || L <= 0 || S <= 0 || C <= 0 || iters < 0) return 0;
   const size_t un = (size_t)N * (L + 1), vn = (size_t)N * (S + 1);
-  return match_ws_bytes(N, L, S, C) + align_up(un * 4 * (iters > 0 ? iters : 1), 256) + align_up(vn * 4 * (iters + 1), 256) +
+  return align_up(match_ws_bytes(N, L, S, C), 256) + align_up(un * 4 * (iters > 0 ? iters : 1), 256) + align_up(vn * 4 * (iters + 1), 256) +
          align_up(un * 4, 256) + align_up(vn * 4, 256) + align_up(vn * 4 * otb::RCH, 256) + 4096;
 }
 
@@ -973,7 +973,10 @@ extern "C" int loftr_sinkhorn_bwd(const float* feat_c0, const float* feat_c1, co
   if (p->N == 0) { (void)hipMemsetAsync(dbin, 0, sizeof(float), st); return LOFTR_OK; }
   LOFTR_CHECK_ARG(ws != nullptr);
   const Geometry g = make_geometry(*p);
-  const size_t base = match_ws_bytes(g.N, g.L, g.S, g.C);
+  // Rounded up: match_ws_bytes counts N (L + S) single bytes (rowkill / colkill) and is a multiple of 4 only when N (L + S) is, and WsAlloc
+  // aligns offsets relative to its base.  On a base that is no multiple of 4 every float buffer below is misaligned, and the backward
+  // returns NaN throughout.
+  const size_t base = align_up(match_ws_bytes(g.N, g.L, g.S, g.C), 256);
   if (ws_bytes < base) return LOFTR_ERR_WORKSPACE;
   MatchWs w = carve(ws, base, g);
   if (!w.ok) return LOFTR_ERR_WORKSPACE;

@@ -155,6 +155,14 @@ class LoFTRLoss(torch.nn.Module):
         return dict(kind=kind, N=N, L=L, S=S, M=M, ids=(b, i, j), masks=(m0, m1), c_pos_w=c_pos_w, c_neg_w=c_neg_w, n_neg=n_neg,
                     alpha=float(self.loss_config.get("focal_alpha", 0.25)), gamma=float(self.loss_config.get("focal_gamma", 2.0)))
 
+    @staticmethod
+    def _placeholder_weighted_out(t):
+        """Dense supervision without ground truth, with masks: the reference plants a positive at (0, 0, 0) and sets ITS weight to 0
+        (:32-36).  The positive mean is multiplied by c_pos_w = 0 anyway; but conf_gt[0, 0, 0] is still 0, so the cell is a negative as
+        well, and its negative term is multiplied by that zero weight.  The kernels weight by mask0 x mask1 only."""
+        m0, m1 = t["masks"]
+        return t["kind"] >= 2 and t["M"] == 0 and m0 is not None and bool(m0[0, 0]) and bool(m1[0, 0])
+
     def _coarse_value(self, conf, t):
         dev = conf.device
         b, i, j = t["ids"]
@@ -166,6 +174,9 @@ class LoFTRLoss(torch.nn.Module):
                                               _ptr(j), t["M"], _ptr(m0), _ptr(m1), t["alpha"], t["gamma"], _ptr(sums), _ptr(ws), ws.numel(),
                                               _stream()), "loftr_coarse_loss_sums")
         s = sums.cpu()
+        if self._placeholder_weighted_out(t):         # :32-36 with loss weights: weight[0, 0, 0] = 0 drops cell (0, 0, 0)'s NEGATIVE term too
+            p = conf[0, 0, 0].clamp(1e-6, 1 - 1e-6).double().cpu()
+            s[2] -= -torch.log(1 - p) if t["kind"] == 3 else -t["alpha"] * p ** t["gamma"] * torch.log(1 - p)
         t["bin_count"] = float(s[3])                  # kind 1: number of supervised dustbin entries (the backward's normaliser)
         pos_mean = s[0] / max(t["M"], 1)
         if t["kind"] == 0:
@@ -263,6 +274,8 @@ class _CoarseLossFn(torch.autograd.Function):
                                                   _ptr(m0), _ptr(m1), t["alpha"], t["gamma"], u * t["c_pos_w"] / max(t["M"], 1),
                                                   u * t["c_neg_w"] / n_neg if n_neg else 0.0, _ptr(g), _ptr(ws), ws.numel(), _stream()),
                        "loftr_coarse_loss_grad")
+        if LoFTRLoss._placeholder_weighted_out(t):
+            g[0, 0, 0] = 0.0
         return g, None, None
 
 

@@ -21,10 +21,11 @@ def _open(c, lo, hi):
 
 
 def coarse_loss_grad(conf, conf_gt, weight=None, coarse_type="focal", sparse_spvs=True, alpha=0.25, gamma=2.0, pos_w=1.0,
-                     neg_w=1.0):
-    """d compute_coarse_loss / d conf for match_type = 'dual_softmax' (loftr_loss.py:22-99)."""
+                     neg_w=1.0, dtype=np.float64):
+    """d compute_coarse_loss / d conf for match_type = 'dual_softmax' (loftr_loss.py:22-99).  dtype: the arithmetic's (float64; float32 is
+    the reference's own precision, for noise estimates)."""
     pos, neg = conf_gt == 1, conf_gt == 0
-    weight = None if weight is None else weight.astype(np.float64).copy()
+    weight = None if weight is None else weight.astype(dtype).copy()
     if not pos.any():                                                     # :31-36
         pos = pos.copy(); pos[0, 0, 0] = True
         if weight is not None:
@@ -35,8 +36,8 @@ def coarse_loss_grad(conf, conf_gt, weight=None, coarse_type="focal", sparse_spv
         if weight is not None:
             weight[0, 0, 0] = 0.
         neg_w = 0.
-    thru = _open(conf, 1e-6, 1 - 1e-6)
-    p = np.clip(conf.astype(F), F(1e-6), F(1 - 1e-6)).astype(np.float64)
+    thru = _open(conf, 1e-6, 1 - 1e-6).astype(dtype)
+    p = np.clip(conf.astype(F), F(1e-6), F(1 - 1e-6)).astype(dtype)
     w = np.ones_like(p) if weight is None else weight
     if coarse_type == "cross_entropy":
         dpos, dneg = -1.0 / p, 1.0 / (1.0 - p)
@@ -75,9 +76,9 @@ def dual_softmax_conf_grad(feat_c0, feat_c1, grad_conf, temperature=0.1, mask_c0
     return np.einsum("nls,nsc->nlc", dsim, f1) * k, np.einsum("nls,nlc->nsc", dsim, f0) * k
 
 
-def fine_loss_grad(expec_f, expec_f_gt, fine_type="l2_with_std", correct_thr=1.0, training=True):
+def fine_loss_grad(expec_f, expec_f_gt, fine_type="l2_with_std", correct_thr=1.0, training=True, dtype=np.float64):
     """d compute_fine_loss / d expec_f [M, 3] (loftr_loss.py:108-157); the std column has no gradient (.detach(), :131)."""
-    e, g = expec_f.astype(np.float64), expec_f_gt.astype(np.float64)
+    e, g = expec_f.astype(dtype), expec_f_gt.astype(dtype)
     correct = np.abs(expec_f_gt).max(1) < correct_thr
     out = np.zeros_like(e)
     if fine_type == "l2":
@@ -87,7 +88,7 @@ def fine_loss_grad(expec_f, expec_f_gt, fine_type="l2_with_std", correct_thr=1.0
             correct = correct.copy(); correct[0] = True
         out[correct, :2] = -2 * (g[correct] - e[correct, :2]) / correct.sum()
         return out
-    inv = 1.0 / np.clip(e[:, 2], 1e-10, None)
+    inv = 1 / np.clip(e[:, 2], dtype(1e-10), None)
     weight = inv / inv.mean()
     if not correct.any():
         if not training:
@@ -98,20 +99,20 @@ def fine_loss_grad(expec_f, expec_f_gt, fine_type="l2_with_std", correct_thr=1.0
     return out
 
 
-def fine_matching_grad(feat_f0, feat_f1, grad_expec):
+def fine_matching_grad(feat_f0, feat_f1, grad_expec, dtype=np.float64):
     """(d L / d feat_f0, d L / d feat_f1) [M, WW, C] from d L / d expec_f [M, 3] (fine_matching.py:43-57)."""
     M, WW, C = feat_f0.shape
     W = int(round(np.sqrt(WW)))
-    f0, f1, g = feat_f0.astype(np.float64), feat_f1.astype(np.float64), grad_expec.astype(np.float64)
+    f0, f1, g = feat_f0.astype(dtype), feat_f1.astype(dtype), grad_expec.astype(dtype)
     pick = f0[:, WW // 2, :]
-    temp = 1.0 / np.sqrt(C)
+    temp = dtype(1.0 / np.sqrt(C))
     heat = _softmax(temp * np.einsum("mc,mrc->mr", pick, f1), 1)
-    lin = np.linspace(-1, 1, W)
+    lin = np.linspace(-1, 1, W).astype(dtype)
     gx, gy = np.tile(lin, W), np.repeat(lin, W)                            # create_meshgrid(W, W, True): x fastest
     grid = np.stack([gx, gy], -1)                                          # [WW, 2]
     c = heat @ grid                                                        # [M, 2]
     var = heat @ grid ** 2 - c ** 2
-    h = np.where(var >= 1e-10, 0.5 / np.sqrt(np.clip(var, 1e-10, None)), 0.0) * g[:, 2:3]     # d L / d var
+    h = np.where(var >= 1e-10, 0.5 / np.sqrt(np.clip(var, dtype(1e-10), None)), 0).astype(dtype) * g[:, 2:3]     # d L / d var
     dc = g[:, :2] - 2 * c * h                                              # d L / d coords (direct + through var)
     dheat = dc @ grid.T + h @ (grid ** 2).T                                # [M, WW]
     dsim = temp * heat * (dheat - (heat * dheat).sum(1, keepdims=True))
@@ -122,22 +123,22 @@ def fine_matching_grad(feat_f0, feat_f1, grad_expec):
 
 
 # ---- Sinkhorn head (coarse_matching.py:121-143 + SuperGlue log_optimal_transport) -------------------------------------------
-def sparse_sinkhorn_loss_grad(assign, conf_gt, weight=None, alpha=0.25, gamma=2.0, pos_w=1.0, neg_w=1.0):
+def sparse_sinkhorn_loss_grad(assign, conf_gt, weight=None, alpha=0.25, gamma=2.0, pos_w=1.0, neg_w=1.0, dtype=np.float64):
     """d compute_coarse_loss / d conf_matrix_with_bin [N, L+1, S+1] for sparse_spvs + match_type 'sinkhorn' (loftr_loss.py:56-81):
     focal positives at the ground-truth cells of the interior, focal 'negatives' at the dustbin entries of the rows / columns
     without a ground-truth match (kept iff the row / column has some loss weight)."""
     pos = conf_gt == 1
-    weight = None if weight is None else weight.astype(np.float64).copy()
+    weight = None if weight is None else weight.astype(dtype).copy()
     if not pos.any():
         pos = pos.copy(); pos[0, 0, 0] = True
         if weight is not None:
             weight[0, 0, 0] = 0.
         pos_w = 0.
-    thru = _open(assign, 1e-6, 1 - 1e-6)
-    p = np.clip(assign.astype(F), F(1e-6), F(1 - 1e-6)).astype(np.float64)
+    thru = _open(assign, 1e-6, 1 - 1e-6).astype(dtype)
+    p = np.clip(assign.astype(F), F(1e-6), F(1 - 1e-6)).astype(dtype)
     dfocal = alpha * (gamma * np.power(1 - p, gamma - 1) * np.log(p) - np.power(1 - p, gamma) / p)
     g = np.zeros_like(p)
-    w = np.ones(conf_gt.shape) if weight is None else weight
+    w = np.ones(conf_gt.shape, dtype) if weight is None else weight
     gi = g[:, :-1, :-1]
     gi[pos] = pos_w * (dfocal[:, :-1, :-1] * w)[pos] / pos.sum()
     neg0, neg1 = conf_gt.sum(-1) == 0, conf_gt.sum(1) == 0          # [N, L], [N, S]
