@@ -1302,6 +1302,7 @@ int loftr_rccl_allgather_counts(void* comm, const int32_t* counts_in, int32_t* c
  *   "pct_grid"          0: the persistent coarse transformer runs 256 workgroups (one per CU); n > 0: n workgroups
  *   "pct_quota"         0: its workgroups stay until the queue is empty; n > 0: a workgroup leaves after n work items (yielding variant)
  *   "pct_skip"          0; bit t: work items of type t (0 X, 1 K, 2 F) are popped and signalled but NOT executed (queue tests: wrong results)
+ *   "fine_waves"        0: fine_pair_kernel runs four or eight waves per workgroup by the match count; 4 / 8: forced (same bits either way)
  * Unknown key: LOFTR_ERR_BAD_ARG.  Results never depend on a switch beyond the last bits of a floating-point sum order. */
 int loftr_hip_debug_set(const char* key, int value);
 int loftr_hip_debug_get(const char* key, int* value, int* default_value);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Where does a match of fine_pair_kernel spend its time?  Needs the probe build (python -m loftr_amd.build --variant fprobe
 -DLOFTR_FINE_PROBE; run with LOFTR_HIP_LIB=loftr_amd/libloftr_hip_fprobe.so): every wave sums the 100 MHz wall clock over its
-phases (four encoder calls).     python tools/micro/fine_probe.py [M=6200]"""
+phases (four encoder calls).     python tools/micro/fine_probe.py [M=6200]
+The launch rule picks the form (four or eight waves per workgroup); tools/micro/fine_waves_crossover.py times both."""
 import ctypes as C
 import os
 import sys
@@ -25,7 +26,7 @@ f0 = torch.randn(M, 25, 128, generator=g).cuda()
 f1 = (0.6 * f0 + 0.8 * torch.randn(M, 25, 128, generator=g).cuda()).contiguous()
 lib = _lib.load()
 lib.loftr_fine_probe_buffer.argtypes = [C.c_void_p]
-buf = torch.zeros(((M + 3) // 4) * 4, 8, dtype=torch.int64, device="cuda")
+buf = torch.zeros(((M + 7) // 8) * 8, 8, dtype=torch.int64, device="cuda")   # every wave of a workgroup writes its row (4 or 8 waves)
 with torch.no_grad():
     for _ in range(3):
         model.loftr_fine(f0.clone(), f1.clone(), inplace=True)
@@ -38,7 +39,7 @@ with torch.no_grad():
     e1.record()
     torch.cuda.synchronize()
 t = buf.cpu().numpy()[:M]
-names = ["call head", "source side: K / V panels + K^T V (216 MFMAs)", "x side: Q, attention, merge (216 MFMAs)", "LayerNorm1 + fragments",
+names = ["call head: source window -> fragments", "source side: K / V panels + K^T V (216 MFMAs)", "x side: Q, attention, merge (216 MFMAs)", "LayerNorm1 + fragments",
          "mlp (576 MFMAs)", "LayerNorm2 + residual + repack"]
 tot = (t[:, 7] - t[:, 6]) / 100.0
 print(f"fine transformer M={M}: {e0.elapsed_time(e1) * 1e3:.1f} us; per wave (= match): {tot.mean():.1f} us (min {tot.min():.1f}, max {tot.max():.1f}); "
