@@ -65,7 +65,8 @@ typedef enum {
  *     triangulated model (loftr_bundle_adjust_host, loftr_bundle_adjust_workspace_bytes, loftr_bundle_adjust; with per-image focal
  *     refinement loftr_bundle_adjust_focal_host, loftr_bundle_adjust_focal_workspace_bytes, loftr_bundle_adjust_focal; with one
  *     focal step per group of images loftr_bundle_adjust_shared_host, loftr_bundle_adjust_shared_workspace_bytes,
- *     loftr_bundle_adjust_shared), the correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
+ *     loftr_bundle_adjust_shared; with position priors on the camera centres loftr_bundle_adjust_prior_host,
+ *     loftr_bundle_adjust_prior_workspace_bytes, loftr_bundle_adjust_prior), the correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
  *     loftr_register_corr), track completion (loftr_complete_tracks_host, loftr_complete_tracks_workspace_bytes,
  *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks),
  *     3D similarity RANSAC and moving a model (loftr_estimate_similarity, loftr_similarity_minimal,
@@ -1013,6 +1014,53 @@ int loftr_bundle_adjust_shared(const long* offsets, long T, const int* obs_image
                                float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out,
                                uint8_t* cam_focal, uint8_t* group_focal, long* counts, void* ws, size_t ws_bytes, float* class_ms,
                                long* class_launches, void* stream);
+
+/* ---- bundle adjustment with position priors on the camera centres (GPS) ----------------------------------------------------
+ * Any of the three rules above (mode 0: §18, 1: §18.1, 2: §18.2) with one more term per camera: its centre is held near a measured
+ * position.  Everything not named here is the rule of its mode unchanged; fp64 without contraction, + - * / sqrt only.
+ * loftr_bundle_adjust_prior_host DEFINES the result, loftr_bundle_adjust_prior reproduces it bit for bit.  A prior couples no point, so
+ * the point elimination, S p, the preconditioner and the conjugate gradients are untouched: only U, g_c and the cost of a camera change.
+ *   Input added.  prior_xyz [n,3] f64 (world units), prior_sigma [n,3] f64 (per axis, world units), prior_mask [n] u8.
+ *   Which cameras.  Camera i HAS A PRIOR iff it is free (rule 2), prior_mask[i] != 0, its three positions are finite and its three
+ *      sigmas are finite and > 0 (a NaN deactivates).  A camera that is not free -- a fixed-pose member of a group included -- never has
+ *      one: its term would be a constant.  cam_prior [n] u8 records the decision.
+ *   Residual.  c_k = -((R_0k t_0 + R_1k t_1) + R_2k t_2) (c = -R^T t, R and t of the state), d_k = c_k - g_k, e_k = d_k / sigma_ik.
+ *   Jacobian.  With §18's perturbation R' = dR R, t' = t + dt: dc/d omega = -R^T [t]x, dc/d dt = -R^T.  Row k, with r = column k of R:
+ *      J_k = (-(r_1 t_2 - r_2 t_1), -(r_2 t_0 - r_0 t_2), -(r_0 t_1 - r_1 t_0), -r_0, -r_1, -r_2), each entry divided by sigma_ik.
+ *      3 x 6; the focal column of the 7-wide modes is not touched.
+ *   Sums.  After the camera's osum64 over its observations: U_ab += (J_0a J_0b + J_1a J_1b) + J_2a J_2b for a <= b < 6 and
+ *      g_c,a += (J_0a e_0 + J_1a e_1) + J_2a e_2 for a < 6, one addition per entry.  A camera without a prior performs no addition.
+ *   Cost.  cost = osum(track shares) + osum(camera shares), one addition, tracks first; a camera's share is (e_0^2 + e_1^2) + e_2^2, +0
+ *      without a prior.  A second camera osum carries (d_0^2 + d_1^2) + d_2^2 for the report.  rms_px and sum |r|^2 stay over the
+ *      observations.  The prior's loss is the square: huber_px acts on the observations only (remove gross errors through prior_mask).
+ *   Trial, acceptance and stopping are rule 7 on the combined cost; "nothing to adjust" is decided by the active observations alone.
+ * Arguments: those of loftr_bundle_adjust_shared(_host), then the prior inputs and mode after G, and cam_prior before counts.  The focal
+ *   arguments are ignored and may be NULL with mode 0, the group arguments with mode < 2.
+ * counts [24] i64: 0..15 as in the mode; 16 = cameras with a prior; 17, 18 = bits of the prior cost (the cameras' osum, in sigma^2)
+ *   before and after; 19, 20 = bits of the root mean squared |c - g| over the cameras with a prior, before and after (world units, 0
+ *   without any); 21..23 = 0.
+ * Status: the mode's; LOFTR_ERR_BAD_ARG also for mode outside 0..2 and for NULL prior_xyz / prior_sigma / prior_mask / cam_prior with
+ *   n_images > 0.  The error bits are unchanged.  Workspace: loftr_bundle_adjust_prior_workspace_bytes(T, N, n_images, mode): the mode's
+ *   plus 16 bytes per image; 0 for sizes out of range or a mode outside 0..2.
+ * Out of scope: rotation priors, priors on points, a robust prior loss, lever arms, covariances with off-diagonal terms.  PARITY UNPINNED. */
+int loftr_bundle_adjust_prior_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                   const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                   const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                   const int* cam_group, const long* group_offsets, const int* group_cams, int G, const double* prior_xyz,
+                                   const double* prior_sigma, const uint8_t* prior_mask, int mode, double huber_px, int max_iters,
+                                   int pcg_iters, double pcg_tol, double ftol, int min_focal_obs, double focal_lo, double focal_hi,
+                                   double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
+                                   double* K_out, uint8_t* cam_focal, uint8_t* group_focal, uint8_t* cam_prior, long* counts);
+size_t loftr_bundle_adjust_prior_workspace_bytes(long T, long N, int n_images, int mode);
+int loftr_bundle_adjust_prior(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                              const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                              const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs, const int* cam_group,
+                              const long* group_offsets, const int* group_cams, int G, const double* prior_xyz, const double* prior_sigma,
+                              const uint8_t* prior_mask, int mode, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
+                              double ftol, int min_focal_obs, double focal_lo, double focal_hi, double* T_out, float* xyz_out,
+                              uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal,
+                              uint8_t* group_focal, uint8_t* cam_prior, long* counts, void* ws, size_t ws_bytes, float* class_ms,
+                              long* class_launches, void* stream);
 
 /* ---- correspondence table of the images without a pose (csrc/register_core.h holds every per-item step) -------------------
  * The 2D-3D correspondences that the tracks give the images that have no pose yet, gathered per image in a defined order: the input of

@@ -169,6 +169,12 @@ SIGNATURES = {
     "loftr_bundle_adjust_shared_workspace_bytes": (_sz, [_l, _l, _i]),
     "loftr_bundle_adjust_shared": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, C.c_double, _i, _i, C.c_double,
                                         C.c_double, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
+    "loftr_bundle_adjust_prior_host": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, C.c_double, _i, _i,
+                                            C.c_double, C.c_double, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "loftr_bundle_adjust_prior_workspace_bytes": (_sz, [_l, _l, _i, _i]),
+    "loftr_bundle_adjust_prior": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, C.c_double, _i, _i,
+                                       C.c_double, C.c_double, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p,
+                                       _p]),
     "loftr_register_corr_host": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "loftr_register_corr_workspace_bytes": (_sz, [_l, _l, _i]),
     "loftr_register_corr": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),

@@ -119,13 +119,40 @@ def transformed(rec, s, R, t):
     return out
 
 
-def align(rec, ref_centres, known=None, thresh=1.0, with_scale=True, apply=True, conf=0.999, seed=0):
+def align(rec, ref_centres, known=None, thresh=1.0, with_scale=True, apply=True, conf=0.999, seed=0, refine=None):
     """``Reconstruction.align``: -> ``(rec2, alignment)``.  known None: every row of ``ref_centres`` that is finite.  Without a model
-    (``alignment.n_inliers == -1``) or with ``apply=False``, ``rec2`` is ``rec`` itself.  Reads ``n_inliers`` back once."""
+    (``alignment.n_inliers == -1``) or with ``apply=False``, ``rec2`` is ``rec`` itself.  Reads ``n_inliers`` back once.  refine: see
+    ``refined``."""
     dev = rec.T_cam_from_world.device
     ref = (ref_centres if isinstance(ref_centres, torch.Tensor) else torch.as_tensor(np.asarray(ref_centres))).to(dev, torch.float64)
     known = torch.isfinite(ref).all(1) if known is None else (known if isinstance(known, torch.Tensor) else torch.as_tensor(np.asarray(known))).to(dev)
     al = align_centres(rec.T_cam_from_world, rec.posed, ref, known, thresh, with_scale, conf, seed)
     if not apply or not al.ok:
         return rec, al
-    return transformed(rec, al.s, al.R, al.t), al
+    rec2 = transformed(rec, al.s, al.R, al.t)
+    return (rec2 if refine is None else refined(rec2, ref, al, **refine)), al
+
+
+def refined(rec, ref_centres, al, sfm=None, sigma=1.0, tri=None, **ba):
+    """The step after georegistration: a bundle adjustment of the aligned ``rec`` over the tracks of ``sfm`` with NO camera
+    fixed and the reference positions of ``al.inliers`` as position priors at ``sigma``, then a triangulation with the adjusted poses
+    (``tri``: keyword arguments of ``SfmResult.triangulate``) -> a copy of ``rec`` with the refined ``T_cam_from_world``, ``K``,
+    ``points`` and ``bundle``.  An image without a pose has a NaN pose: it is an invalid camera of the adjustment (rule 1), keeps its
+    bits, and takes no part in either triangulation."""
+    sfm = sfm if sfm is not None else rec.sfm
+    if sfm is None:
+        raise ValueError("align: refine needs sfm=<the SfmResult of this reconstruction>")
+    if rec.K is None:
+        raise ValueError("align: refine needs a reconstruction that carries K")
+    tri = dict(tri or {})
+    dev = rec.T_cam_from_world.device
+    tri.setdefault("posed", rec.posed)
+    pts = sfm.triangulate(rec.K, rec.T_cam_from_world, **tri)
+    res = sfm.adjust(pts, rec.K, rec.T_cam_from_world, fixed=torch.zeros(rec.posed.shape[0], dtype=torch.bool, device=dev),
+                     position_prior=ref_centres, prior_mask=al.inliers, prior_sigma=sigma, **ba)
+    out = copy.copy(rec)
+    out.T_cam_from_world, out.bundle = res.T_cam_from_world, res
+    if "K" in res.FIELDS:
+        out.K = res.K
+    out.points = sfm.triangulate(out.K, out.T_cam_from_world, **tri)
+    return out

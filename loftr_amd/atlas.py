@@ -301,7 +301,8 @@ class SfmResult:
         the triangulation kept (bundle.bundle_adjust) -> BundleResult on this result's device.  ``fixed`` and the keyword
         arguments are bundle_adjust's; the intended loop is triangulate -> adjust -> triangulate(K, res.T_cam_from_world).  With
         ``refine_focal`` (True or an [n] mask; DESIGN §18.1) the focal lengths are refined as well and the loop goes on with ``res.K``;
-        with ``camera_ids`` ([n] integers) the images of one camera share that step."""
+        with ``camera_ids`` ([n] integers; DESIGN §18.2) the images of one camera share that step; with ``position_prior`` ([n,3];
+        ``prior_sigma``, ``prior_mask``) the camera centres are held near measured positions."""
         from .bundle import bundle_adjust
         if pts.offsets is None:
             raise ValueError("SfmResult.adjust: this Points3D carries no tracks (use SfmResult.triangulate)")
@@ -314,6 +315,9 @@ class SfmResult:
             kwargs["refine_focal"] = torch.as_tensor(kwargs["refine_focal"]).to(dev)
         if kwargs.get("camera_ids") is not None:                         # (images with equal ids share one focal step)
             kwargs["camera_ids"] = torch.as_tensor(kwargs["camera_ids"]).to(dev)
+        for k in ("position_prior", "prior_sigma", "prior_mask"):        # (position priors on the camera centres)
+            if kwargs.get(k) is not None and not isinstance(kwargs[k], (int, float)):
+                kwargs[k] = torch.as_tensor(kwargs[k]).to(dev)
         return bundle_adjust(pts.offsets, pts.image.to(torch.int32), xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **kwargs)
 
     def to_host(self):

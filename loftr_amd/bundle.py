@@ -25,6 +25,16 @@ step between the images of a camera (``loftr_bundle_adjust_shared
 estimated from every observation of every one of its images, the fixed-pose ones included::
 
     res = sfm.adjust(pts, K, T_cam_from_world, fixed=known, refine_focal=True, camera_ids=ids)     # ids [n]: equal ids, one camera
+
+Where the camera positions were measured (GPS), ``position_prior`` holds every camera centre near its measurement in any of the three
+modes (``loftr_bundle_adjust_prior_host`` and its kernels).  The model must already be in the frame of the measurements
+(``Reconstruction.align``); the priors then fix the scale, remove the drift of the positions and hold the gauge without a fixed camera::
+
+    rec2, al = rec.align(gps)                                                         # into the GPS frame
+    none = torch.zeros(n, dtype=torch.bool, device=dev)
+    res = sfm.adjust(pts2, K, rec2.T_cam_from_world, fixed=none, position_prior=gps, prior_mask=al.inliers, prior_sigma=2.0)
+
+(``rec.align(gps, refine=dict(sfm=sfm, sigma=2.0))`` runs exactly that sequence and triangulates again.)
 """
 import numpy as np
 import torch
@@ -34,6 +44,7 @@ from . import _tracks, ops
 _OUT = ("T_cam_from_world", "xyz", "obs_active", "cam_free", "point_active")
 _OUT_FOCAL = ("K", "cam_focal")
 _OUT_SHARED = ("cam_group", "group_focal")
+_OUT_PRIOR = ("cam_prior",)
 _ARGS = ("offsets", "obs_image", "obs_xy", "obs_mask", "xyz", "K", "T_cam_from_world")
 
 
@@ -49,14 +60,17 @@ class BundleResult:
     A call with ``refine_focal`` also carries ``K [n,3,3] f64`` (the input's bits for a camera that does not refine its focal),
     ``cam_focal [n] bool`` and ``stats['n_focal_cameras']``; ``FIELDS`` of that result names them too.  A call with ``camera_ids`` adds
     ``cam_group [n] i32`` (the dense group of each image, groups ordered by their smallest member), ``group_focal [G] bool`` (the group
-    refined) and ``stats['n_focal_groups']``."""
+    refined) and ``stats['n_focal_groups']``.  A call with ``position_prior`` adds ``cam_prior [n] bool`` (the camera had a prior) and
+    ``stats['n_prior_cameras']``, ``prior_cost_before`` / ``prior_cost_after`` (the priors' part of the cost, in sigma^2) and
+    ``prior_rms_before`` / ``prior_rms_after`` (root mean squared distance of the centres from their priors, in world units)."""
 
     FIELDS = _OUT
 
     def __init__(self, stats, **tensors):
         self.stats = stats
-        if "K" in tensors:                                               # a call with refine_focal: K and cam_focal as well
-            self.FIELDS = _OUT + _OUT_FOCAL + (_OUT_SHARED if "cam_group" in tensors else ())
+        if "K" in tensors or "cam_prior" in tensors:                     # a call with refine_focal: K and cam_focal as well; with priors
+            self.FIELDS = _OUT + (_OUT_FOCAL if "K" in tensors else ()) + (_OUT_SHARED if "cam_group" in tensors else ()) + \
+                (_OUT_PRIOR if "cam_prior" in tensors else ())
         for k in self.FIELDS:
             setattr(self, k, tensors[k])
         for k in ("cost_before", "cost_after", "rms_px_before", "rms_px_after", "n_iters", "n_accepted", "n_pcg", "status"):
@@ -70,7 +84,8 @@ class BundleResult:
 
 
 def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed=None, huber_px=0.0, max_iters=30, pcg_iters=30,
-                  pcg_tol=1e-2, ftol=1e-9, timings=None, refine_focal=None, min_focal_obs=20, focal_bounds=(0.5, 2.0), camera_ids=None):
+                  pcg_tol=1e-2, ftol=1e-9, timings=None, refine_focal=None, min_focal_obs=20, focal_bounds=(0.5, 2.0), camera_ids=None,
+                  position_prior=None, prior_sigma=1.0, prior_mask=None):
     """Refine poses and points over the reprojection error -> ``BundleResult``.
 
     ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``; ``obs_mask [N]`` (bool or integers: which
@@ -96,7 +111,18 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     resize scales work) and all are multiplied by the same ``1 + delta``.  An image carries its camera's focal when it is valid, flagged in
     ``refine_focal`` and has an active observation, whether or not its pose is ``fixed``; a camera refines when its carrying images
     together have at least ``min_focal_obs`` active observations.  ``None`` is the per-image call above, unchanged bit for bit.  The
-    result adds ``cam_group``, ``group_focal`` and ``stats['n_focal_groups']``."""
+    result adds ``cam_group``, ``group_focal`` and ``stats['n_focal_groups']``.
+
+    ``position_prior`` (any of the modes above): ``[n,3]`` measured camera centres in world units, on the device of the
+    other arguments; a row with a NaN has no prior.  ``prior_sigma``: a positive scalar, ``[n]`` or ``[n,3]`` (per axis), in world units;
+    an entry that is not finite and positive switches that camera's prior off.  ``prior_mask``: ``[n]``, which priors to use (default:
+    the finite rows).  Each free camera with a prior adds ``|(c - g) / sigma|^2`` to the cost, ``c = -R^T t`` its centre.  The prior's
+    loss is the square -- ``huber_px`` acts on the observations only -- so remove gross GPS errors with
+    ``prior_mask=alignment.inliers``.  A camera that is not free has no prior (its term would be a constant).  ``fixed=None`` still
+    fixes image 0; pass an all-false ``fixed`` to let the priors hold the gauge, which they do when at least three cameras with a
+    prior are not collinear.  ``None`` makes the calls above exactly as before.  The result adds ``cam_prior`` and
+    ``stats['n_prior_cameras']``, ``prior_cost_before`` / ``_after``, ``prior_rms_before`` / ``_after``.  Rotation priors, priors on
+    points, a robust prior loss, lever arms and full covariances are not modelled."""
     what = "bundle_adjust"
     args = [offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world]
     params = ops._ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol)
@@ -134,6 +160,46 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             refine_focal = refine_focal.detach().numpy() if isinstance(refine_focal, torch.Tensor) else np.asarray(refine_focal)
         if tuple(refine_focal.shape) != (len(K),):
             raise ValueError(f"{what}: refine_focal must be None, True or a mask of shape ({len(K)},), got {tuple(refine_focal.shape)}")
+    prior = None
+    if position_prior is not None:
+        given = [("position_prior", position_prior)] + [(k, v) for k, v in (("prior_sigma", prior_sigma), ("prior_mask", prior_mask))
+                                                        if v is not None and not isinstance(v, (int, float))]
+        for k, v in given:
+            on_gpu = isinstance(v, torch.Tensor) and v.is_cuda
+            if on_gpu != gpu or (gpu and v.device != args[0].device):
+                raise ValueError(f"{what}: {k} is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no silent "
+                                 "fallback: move it to their device")
+        nK = len(K)
+        conv = (lambda v: v.detach().to(torch.float64)) if gpu else \
+            (lambda v: np.asarray(v.detach().numpy() if isinstance(v, torch.Tensor) else v, np.float64))
+        xp = torch if gpu else np
+        pxyz = conv(position_prior)
+        if tuple(pxyz.shape) != (nK, 3):
+            raise ValueError(f"{what}: position_prior must have shape ({nK}, 3), got {tuple(pxyz.shape)}")
+        if isinstance(prior_sigma, (int, float)) and not isinstance(prior_sigma, bool):
+            if not (prior_sigma > 0 and prior_sigma < float("inf")):
+                raise ValueError(f"{what}: prior_sigma must be positive and finite, got {prior_sigma}")
+            psig = xp.zeros_like(pxyz) + float(prior_sigma)
+        else:
+            if prior_sigma is None or isinstance(prior_sigma, bool):
+                raise ValueError(f"{what}: prior_sigma must be a positive number or an array of shape ({nK},) or ({nK}, 3)")
+            psig = conv(prior_sigma)
+            if tuple(psig.shape) == (nK,):
+                psig = psig.reshape(nK, 1) + xp.zeros_like(pxyz)
+            if tuple(psig.shape) != (nK, 3):
+                raise ValueError(f"{what}: prior_sigma must be a positive number or have shape ({nK},) or ({nK}, 3), got "
+                                 f"{tuple(psig.shape)}")
+        if prior_mask is None:
+            pm = (xp.isfinite(pxyz).sum(1) == 3)
+            pm = pm.to(torch.uint8) if gpu else pm.astype(np.uint8)
+        else:
+            pm = prior_mask.detach() if isinstance(prior_mask, torch.Tensor) else np.asarray(prior_mask)
+            if not gpu and isinstance(pm, torch.Tensor):
+                pm = pm.numpy()
+            if tuple(pm.shape) != (nK,):
+                raise ValueError(f"{what}: prior_mask must have shape ({nK},), got {tuple(pm.shape)}")
+            pm = (pm != 0).to(torch.uint8) if gpu else (pm != 0).astype(np.uint8)
+        prior = (pxyz.contiguous(), psig.contiguous(), pm) if gpu else (np.ascontiguousarray(pxyz), np.ascontiguousarray(psig), pm)
     for n, a in zip(_ARGS[:2], args[:2]):
         _tracks.integers(what, n, a)
     # the arguments in the dtypes of the C call, on their side
@@ -165,8 +231,13 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     if camera_ids is not None:
         groups = _tracks.group_by_camera(camera_ids.detach() if gpu else camera_ids)
         extra, mode = extra + list(groups), "_shared"
-    call = getattr(ops, "bundle_adjust" + mode + ("" if gpu else "_host"))
-    out = call(*a, fx, *_tracks.group_by_image(a[1], n), *extra, *params, *(focal or ()), **({"timings": timings} if gpu else {}))
+    if prior is None:
+        call = getattr(ops, "bundle_adjust" + mode + ("" if gpu else "_host"))
+        out = call(*a, fx, *_tracks.group_by_image(a[1], n), *extra, *params, *(focal or ()), **({"timings": timings} if gpu else {}))
+    else:                                                                # the one pair with priors: the mode's number, None below it
+        call = ops.bundle_adjust_prior if gpu else ops.bundle_adjust_prior_host
+        out = call(("", "_focal", "_shared").index(mode), *a, fx, *_tracks.group_by_image(a[1], n), *(extra + [None] * (4 - len(extra))), *prior,
+                   *params, *(focal or ()), **({"timings": timings} if gpu else {}))
     if camera_ids is not None:
         out["cam_group"] = groups[0]
     if not gpu:
@@ -174,7 +245,7 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     counts = (out["counts"] if neg_id is None else torch.cat([out["counts"], neg_id])).cpu()      # the one readback
     reals = counts[8:13].view(torch.float64).tolist()
     counts = counts.tolist()
-    if neg_id is not None and counts[16]:
+    if neg_id is not None and counts[-1]:
         raise ValueError(f"{what}: camera_ids must not be negative")
     _tracks.raise_error_bits(what, counts[1], ops.BUNDLE_SHARED_ERRORS if camera_ids is not None else None)
     stats = {"status": ops.BUNDLE_STATUS[counts[0]], "n_iters": counts[2], "n_accepted": counts[3], "n_pcg": counts[4],
@@ -183,12 +254,18 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
              "cost_before": reals[0], "cost_after": reals[1], "rms_px_before": reals[2], "rms_px_after": reals[3], "lambda": reals[4]}
     for k in ("obs_active", "cam_free", "point_active"):
         out[k] = out[k].view(torch.bool)
-    if focal is None:
-        return BundleResult(stats, **{k: out[k] for k in _OUT})
-    stats["n_focal_cameras"] = counts[13]
-    out["cam_focal"] = out["cam_focal"].view(torch.bool)
-    if camera_ids is None:
-        return BundleResult(stats, **{k: out[k] for k in _OUT + _OUT_FOCAL})
-    stats["n_focal_groups"] = counts[14]
-    out["group_focal"] = out["group_focal"].view(torch.bool)
-    return BundleResult(stats, **{k: out[k] for k in _OUT + _OUT_FOCAL + _OUT_SHARED})
+    fields = _OUT
+    if prior is not None:
+        preals = torch.tensor(counts[17:21], dtype=torch.int64).view(torch.float64).tolist()
+        stats.update(n_prior_cameras=counts[16], prior_cost_before=preals[0], prior_cost_after=preals[1], prior_rms_before=preals[2],
+                     prior_rms_after=preals[3])
+        out["cam_prior"] = out["cam_prior"].view(torch.bool)
+    if focal is not None:
+        stats["n_focal_cameras"] = counts[13]
+        out["cam_focal"] = out["cam_focal"].view(torch.bool)
+        fields += _OUT_FOCAL
+        if camera_ids is not None:
+            stats["n_focal_groups"] = counts[14]
+            out["group_focal"] = out["group_focal"].view(torch.bool)
+            fields += _OUT_SHARED
+    return BundleResult(stats, **{k: out[k] for k in fields + (_OUT_PRIOR if prior is not None else ())})

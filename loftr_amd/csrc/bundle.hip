@@ -8,7 +8,8 @@
 // the arithmetic, every per-item step, the context fill and the argument checks live in bundle_core.h and why this file is only the
 // sequence of phases and the order-defined sums.  The sequence is ONE template, run<Mode>, and the three entry points are its three
 // instantiations: Pose (§18), Focal (§18.1: one focal step per camera), Shared (§18.2: one per group of cameras, whose group phases
-// are `if constexpr` in the sequence).
+// are `if constexpr` in the sequence).  Position priors on the camera centres (§18.3) are a trait of the mode as well: PoseP, FocalP and
+// SharedP run the same sequence with the prior's steps, loftr_bundle_adjust_prior_host picks one by `mode`.
 #include <stdint.h>
 #include <vector>
 #include "../../include/loftr_hip.h"
@@ -69,6 +70,7 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   layout<Mode>(c, ws.data());
   Ctrl& s = *c.ctrl;
   ctrl_init(c, groups_ctrl<Mode>(c));
+  if constexpr (Mode::kPrior) ctrl_init_prior(c.pr);
   for (long i = 0; i < n; ++i) {
     cam_setup(c, i);
     if constexpr (S == 7) cam_setup_focal(c, i);
@@ -91,6 +93,10 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
     }
     c.cam_free[i] = (uint8_t)(!c.fixed[i] && c.cam_valid[i] && cnt >= 1);
     s.n_free += c.cam_free[i];
+    if constexpr (Mode::kPrior) {
+      c.pr.cam_prior[i] = (uint8_t)cam_prior_rule(c, c.pr, i);
+      c.pr.cp->n_prior += c.pr.cam_prior[i];
+    }
     if constexpr (kGroups) s.err |= cam_carry(c, i, cnt);
     else if constexpr (S == 7) {
       c.cam_focal[i] = (uint8_t)cam_focal_rule(c, i, c.cam_free[i] != 0, cnt);
@@ -131,11 +137,25 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   auto evaluate = [&](int buf) {
     bool ok = true;
     for (long t = 0; t < T; ++t) ok = track_eval(c, buf, t) && ok;
+    if constexpr (Mode::kPrior)
+      for (long i = 0; i < n; ++i) cam_prior_eval(c, c.pr, buf, i);
     return ok;
   };
+  // the cost and the sum of |r|^2 of what `evaluate` left: the tracks' osum, with priors the cameras' osum added to it (and the
+  // cameras' |c - g|^2 for the report)
+  auto feed_cost = [&](int cost, int sq) {
+    if constexpr (Mode::kPrior) {
+      c.pr.cp->acc = osum(c.part, T);
+      ctrl_feed_prior(c, c.pr, cost, osum(c.pr.part, n));
+      ctrl_feed(c, sq, osum(c.part2, T));
+      ctrl_feed_prior(c, c.pr, sq, osum(c.pr.part2, n));
+    } else {
+      ctrl_feed(c, cost, osum(c.part, T));
+      ctrl_feed(c, sq, osum(c.part2, T));
+    }
+  };
   evaluate(0);
-  ctrl_feed(c, kActCost0, osum(c.part, T));
-  ctrl_feed(c, kActSq0, osum(c.part2, T));
+  feed_cost(kActCost0, kActSq0);
 
   for (int it = 0; it < max_iters && !s.done; ++it) {
     const int cur = s.cur;
@@ -147,6 +167,7 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         cam_sum<kU + S>(c, i, [&](long o, double* acc) { cam_lin_term<Mode>(c, cur, o, acc); }, a);
         for (int k = 0; k < kU; ++k) c.U[kU * i + k] = a[k];
         for (int k = 0; k < S; ++k) c.gc[S * i + k] = a[kU + k];
+        if constexpr (Mode::kPrior) cam_lin_prior<S>(c, c.pr, cur, i);
       }
       if constexpr (kGroups)
         for (long g = 0; g < c.G; ++g) if (c.group_focal[g]) c.dg[g] = group_sum(c, g, c.U + 27, 28);
@@ -191,16 +212,15 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
     }
     if (!s.bad_f && !s.bad_a) {
       if (!evaluate(1 - cur)) s.bad_e = 1;
-      if (!s.bad_e) {
-        ctrl_feed(c, kActCostT, osum(c.part, T));
-        ctrl_feed(c, kActSqT, osum(c.part2, T));
-      }
+      if (!s.bad_e) feed_cost(kActCostT, kActSqT);
     }
-    ctrl_accept(c);
+    if constexpr (Mode::kPrior) ctrl_accept_prior(c, c.pr);
+    else ctrl_accept(c);
   }
   for (long i = 0; i < n; ++i) cam_write<Mode>(c, s.cur, i);
   for (long t = 0; t < T; ++t) track_write(c, s.cur, t);
   ctrl_write<Mode>(c);
+  if constexpr (Mode::kPrior) ctrl_write_prior(c, c.pr);
   return LOFTR_OK;
 }
 
@@ -243,4 +263,33 @@ extern "C" int loftr_bundle_adjust_shared_host(const long* offsets, long T, cons
   fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
   fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
   return run<Shared>(c, max_iters, pcg_iters, pcg_tol);
+}
+
+// with position priors on the camera centres (§18.3): mode 0 pose, 1 focal, 2 shared; the focal and group arguments are ignored below
+// their mode
+extern "C" int loftr_bundle_adjust_prior_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
+                                              long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                              const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                              const int* cam_group, const long* group_offsets, const int* group_cams, int G,
+                                              const double* prior_xyz, const double* prior_sigma, const uint8_t* prior_mask, int mode,
+                                              double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs,
+                                              double focal_lo, double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
+                                              uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal,
+                                              uint8_t* cam_prior, long* counts) {
+  auto go = [&](auto m) {
+    using Mode = decltype(m);
+    typename Mode::Ctx c{};
+    fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol,
+         ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts);
+    if constexpr (Mode::S == 7) fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
+    if constexpr (Mode::kGroups) fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
+    fill_prior(c.pr, prior_xyz, prior_sigma, prior_mask, cam_prior);
+    return run<Mode>(c, max_iters, pcg_iters, pcg_tol);
+  };
+  switch (mode) {
+    case 0: return go(PoseP{});
+    case 1: return go(FocalP{});
+    case 2: return go(SharedP{});
+  }
+  return LOFTR_ERR_BAD_ARG;
 }

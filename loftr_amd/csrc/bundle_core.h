@@ -11,8 +11,10 @@
 // The three modes -- fixed intrinsics, one focal step per camera (§18.1), one per group of cameras (§18.2) -- are instantiations of one
 // text: a step that touches the camera block is a template on the mode (Pose, Focal, Shared below) and decides what differs with
 // `if constexpr`; no mode is reached through another "with a zero column", so each performs exactly its own operations.  Steps that are
-// different rules (cam_focal_rule against cam_carry / cgroup_*, the group_* steps) stay separate functions.  The context fill and the
-// argument checks of all six entry points are at the end.
+// different rules (cam_focal_rule against cam_carry / cgroup_*, the group_* steps) stay separate functions.  Position priors on the
+// camera centres (§18.3) are a second trait of the mode (kPrior: PoseP, FocalP, SharedP): their steps are `if constexpr` inside the same
+// phases, and the three modes without them perform no operation of theirs.  The context fill and the argument checks of all eight entry
+// points are at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -27,6 +29,7 @@
 namespace ba {
 
 constexpr int kCounts = 16;                // counts[]: see include/loftr_hip.h
+constexpr int kCountsPrior = 24;           // ... of the entry points with position priors (§18.3): 16..20 are the prior's
 constexpr int kTab = 17;                   // doubles per camera of the state table: R [9], t [3], fx, skew, cx, fy, cy
 constexpr int kChunk = 4096;               // osum: osum64 per chunk of 4096, then osum of the chunk sums
 constexpr double kLambda0 = 1e-4, kLambdaMin = 1e-10, kLambdaMax = 1e10;
@@ -92,12 +95,33 @@ struct CtxS : Ctx7 {
   CtrlS* cs;
 };
 
+// §18.3, position priors on the camera centres.  A prior couples no point, so it only adds to U, gc and the cost of its camera; what it
+// needs is carried next to any of the three contexts, and only by the instantiations that have it.
+struct CtrlP {
+  double acc;                                // the tracks' sum of the cost, waiting for the cameras' (as CtrlS::acc waits for the groups')
+  double pc0, pc, pc_t, sq0, sq, sq_t;       // sum of the prior shares / of |c - g|^2: at the start, of the state, of the trial
+  unsigned long long n_prior;
+};
+struct Prior {
+  const double *xyz, *sigma; const uint8_t* mask;   // [n,3], [n,3], [n]
+  uint8_t* cam_prior;                               // [n]: the decision
+  double *part, *part2;                             // [n] each: a camera's share of the cost, its |c - g|^2
+  CtrlP* cp;
+};
+template <class Base> struct WithPrior : Base { Prior pr; };
+
 // The three MODES.  The sequence of phases (bundle.hip), the launch schedule (bundle_gpu.hip) and every per-item step that touches the
 // camera block are written once, as templates on one of these: S is the stride of a camera's vectors and the width of its linearised
 // block, W the width of what is factored, solved and updated per camera, kGroups whether the group phases exist.
-struct Pose { static constexpr int S = 6, W = 6; static constexpr bool kGroups = false; using Ctx = ba::Ctx; };       // §18
-struct Focal { static constexpr int S = 7, W = 7; static constexpr bool kGroups = false; using Ctx = ba::Ctx7; };    // §18.1
-struct Shared { static constexpr int S = 7, W = 6; static constexpr bool kGroups = true; using Ctx = ba::CtxS; };    // §18.2
+// kPrior: whether the cameras carry position priors (§18.3); Base is the mode without them, whose kernels and steps serve every phase
+// that the prior does not touch.
+struct Pose { static constexpr int S = 6, W = 6; static constexpr bool kGroups = false, kPrior = false; using Ctx = ba::Ctx; using Base = Pose; };       // §18
+struct Focal { static constexpr int S = 7, W = 7; static constexpr bool kGroups = false, kPrior = false; using Ctx = ba::Ctx7; using Base = Focal; };    // §18.1
+struct Shared { static constexpr int S = 7, W = 6; static constexpr bool kGroups = true, kPrior = false; using Ctx = ba::CtxS; using Base = Shared; };   // §18.2
+template <class M> struct PriorOf : M { static constexpr bool kPrior = true; using Ctx = WithPrior<typename M::Ctx>; using Base = M; };    // §18.3
+using PoseP = PriorOf<Pose>;
+using FocalP = PriorOf<Focal>;
+using SharedP = PriorOf<Shared>;
 template <int S> constexpr int kTri = S * (S + 1) / 2;      // entries of the upper triangle of a camera block: 21 or 28
 template <class Mode> BA_HD CtrlS* groups_ctrl(const typename Mode::Ctx& c) {
   if constexpr (Mode::kGroups) return c.cs;
@@ -124,6 +148,10 @@ template <class Mode> inline size_t layout(typename Mode::Ctx& c, char* base) {
     c.dg = (double*)take(8 * n); c.xg = (double*)take(8 * n); c.rg = (double*)take(8 * n); c.zg = (double*)take(8 * n);
     c.pg = (double*)take(8 * n); c.Spg = (double*)take(8 * n); c.partg = (double*)take(8 * n); c.sg = (double*)take(8 * 2 * n);
     c.cam_cnt = (int*)take(4 * n);
+  }
+  if constexpr (Mode::kPrior) {
+    c.pr.cp = (CtrlP*)take(sizeof(CtrlP));
+    c.pr.part = (double*)take(8 * n); c.pr.part2 = (double*)take(8 * n);
   }
   return off;
 }
@@ -229,6 +257,61 @@ BA_HD double* sg_of(const CtxS& c, int buf, long g) { return c.sg + ((long)buf *
 BA_HD bool cgroup_rule(const CtxS& c, long g, long total) {
   *sg_of(c, 0, g) = 1.0; *sg_of(c, 1, g) = 1.0;
   return total >= (long)c.min_focal_obs;
+}
+
+// ---- §18.3: position priors ------------------------------------------------------------------------------------------------------------
+// phase "camera groups", after cam_free of camera i is known: does it have a prior?  A NaN anywhere deactivates.
+BA_HD bool cam_prior_rule(const Ctx& c, const Prior& p, long i) {
+  bool ok = c.cam_free[i] != 0 && p.mask[i] != 0;
+  for (int k = 0; k < 3; ++k) ok = ok && fin(p.xyz[3 * i + k]) && fin(p.sigma[3 * i + k]) && p.sigma[3 * i + k] > 0.0;
+  return ok;
+}
+// d = c - g with the centre c = -R^T t, each of the three dot products summed left to right
+BA_HD void prior_offset(const double* cam, const double* g, double* d) {
+  for (int k = 0; k < 3; ++k) d[k] = -((cam[k] * cam[9] + cam[3 + k] * cam[10]) + cam[6 + k] * cam[11]) - g[k];
+}
+// the residual e [3] = d / sigma and its Jacobian J [3,6] = (-R^T [t]x, -R^T) with row k divided by sigma_k
+BA_HD void prior_terms(const double* cam, const double* g, const double* sigma, double* e, double* J) {
+  double d[3];
+  prior_offset(cam, g, d);
+  const double t0 = cam[9], t1 = cam[10], t2 = cam[11];
+  for (int k = 0; k < 3; ++k) {
+    const double r0 = cam[k], r1 = cam[3 + k], r2 = cam[6 + k], sg = sigma[k];      // column k of R
+    e[k] = d[k] / sg;
+    J[6 * k] = -(r1 * t2 - r2 * t1) / sg; J[6 * k + 1] = -(r2 * t0 - r0 * t2) / sg; J[6 * k + 2] = -(r0 * t1 - r1 * t0) / sg;
+    J[6 * k + 3] = -r0 / sg; J[6 * k + 4] = -r1 / sg; J[6 * k + 5] = -r2 / sg;
+  }
+}
+// phase "linearise cameras", after the osum64 of camera i has been stored: a camera with a prior adds J^T J to the leading 6 x 6 of U
+// and J^T e to the first six of gc, entry by entry, each the sum of three products left to right.  One without performs no addition.
+template <int S> BA_HD void cam_lin_prior(const Ctx& c, const Prior& p, int buf, long i) {
+  if (!p.cam_prior[i]) return;
+  double e[3], J[18];
+  prior_terms(tab_of(c, buf, i), p.xyz + 3 * i, p.sigma + 3 * i, e, J);
+  double* U = c.U + kTri<S> * i;
+  double* g = c.gc + S * i;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int b = a; b < 6; ++b) {
+      const int m = a * S - a * (a - 1) / 2 + (b - a);
+      U[m] = U[m] + ((J[a] * J[b] + J[6 + a] * J[6 + b]) + J[12 + a] * J[12 + b]);
+    }
+    g[a] = g[a] + ((J[a] * e[0] + J[6 + a] * e[1]) + J[12 + a] * e[2]);
+  }
+}
+// phase "evaluate", per camera at state `buf`: part = e0^2 + e1^2 + e2^2, part2 = |c - g|^2, left to right; +0 without a prior
+BA_HD void cam_prior_eval(const Ctx& c, const Prior& p, int buf, long i) {
+  double cost = 0.0, sq = 0.0;
+  if (p.cam_prior[i]) {
+    double d[3], e[3];
+    prior_offset(tab_of(c, buf, i), p.xyz + 3 * i, d);
+    for (int k = 0; k < 3; ++k) e[k] = d[k] / p.sigma[3 * i + k];
+    cost = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    sq = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+  }
+  p.part[i] = cost;
+  p.part2[i] = sq;
 }
 
 // ---- rule 3: residual and Jacobians ----------------------------------------------------------------------------------------------------
@@ -729,6 +812,22 @@ BA_HD void ctrl_feed(const Ctx& c, int action, double v) {
     case kActSqT: s.sq_t = v; break;
   }
 }
+// ... with priors: the last level of a camera osum.  The cost is the tracks' sum (waiting in acc) plus the cameras', one addition,
+// tracks first; the second sum is the report's |c - g|^2 and feeds nothing else.
+BA_HD void ctrl_init_prior(const Prior& p) {
+  CtrlP& q = *p.cp;
+  q.acc = q.pc0 = q.pc = q.pc_t = q.sq0 = q.sq = q.sq_t = 0.0;
+  q.n_prior = 0;
+}
+BA_HD void ctrl_feed_prior(const Ctx& c, const Prior& p, int action, double v) {
+  CtrlP& q = *p.cp;
+  switch (action) {
+    case kActCost0: q.pc0 = q.pc = v; ctrl_feed(c, kActCost0, q.acc + v); break;
+    case kActCostT: q.pc_t = v; ctrl_feed(c, kActCostT, q.acc + v); break;
+    case kActSq0: q.sq0 = q.sq = v; break;
+    case kActSqT: q.sq_t = v; break;
+  }
+}
 // phase "accept": the end of a trial
 BA_HD void ctrl_accept(const Ctx& c) {
   Ctrl& s = *c.ctrl;
@@ -749,6 +848,12 @@ BA_HD void ctrl_accept(const Ctx& c) {
   }
   s.bad_f = s.bad_a = s.bad_e = 0;
   s.pcg_done = 0;
+}
+// ... with priors: an accepted trial takes its prior sums along
+BA_HD void ctrl_accept_prior(const Ctx& c, const Prior& p) {
+  const int before = c.ctrl->n_accepted;
+  ctrl_accept(c);
+  if (c.ctrl->n_accepted != before) { p.cp->pc = p.cp->pc_t; p.cp->sq = p.cp->sq_t; }
 }
 // phase "write": the pose of a free camera, the intrinsics of one with cam_focal (the other four entries of K_out keep the input's
 // bits: cam_setup_focal), an active point, from the final state
@@ -787,6 +892,16 @@ template <class Mode> BA_HD void ctrl_write(const typename Mode::Ctx& c) {
   if constexpr (Mode::kGroups) k[14] = c.cs->n_groups;     // groups that refine
 }
 
+// counts[16..23] of the entry points with priors
+BA_HD void ctrl_write_prior(const Ctx& c, const Prior& p) {
+  const CtrlP& q = *p.cp;
+  long* k = c.counts;
+  const double np = (double)q.n_prior;
+  k[16] = (long)q.n_prior; k[17] = bits_of(q.pc0); k[18] = bits_of(q.pc);
+  k[19] = bits_of(q.n_prior ? sqrt(q.sq0 / np) : 0.0); k[20] = bits_of(q.n_prior ? sqrt(q.sq / np) : 0.0);
+  k[21] = 0; k[22] = 0; k[23] = 0;
+}
+
 // ---- the entry points' side (host code of both files) ----------------------------------------------------------------------------------
 // the problem, the parameters and the outputs every mode has
 inline void fill(Ctx& c, const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
@@ -803,6 +918,9 @@ inline void fill_focal(Ctx7& c, const uint8_t* refine_focal, int min_focal_obs, 
   c.refine_focal = refine_focal; c.min_focal_obs = min_focal_obs; c.focal_lo = focal_lo; c.focal_hi = focal_hi;
   c.K_out = K_out; c.cam_focal = cam_focal;
 }
+inline void fill_prior(Prior& p, const double* prior_xyz, const double* prior_sigma, const uint8_t* prior_mask, uint8_t* cam_prior) {
+  p.xyz = prior_xyz; p.sigma = prior_sigma; p.mask = prior_mask; p.cam_prior = cam_prior;
+}
 inline void fill_groups(CtxS& c, const int* cam_group, const long* group_offsets, const int* group_cams, int G, uint8_t* group_focal) {
   c.cam_group = cam_group; c.group_offsets = group_offsets; c.group_cams = group_cams; c.G = G; c.group_focal = group_focal;
 }
@@ -815,6 +933,9 @@ template <class Mode> inline int check_args(const typename Mode::Ctx& c, int max
     if (n > 0 && (!c.refine_focal || !c.K_out || !c.cam_focal)) return LOFTR_ERR_BAD_ARG;
     if (!(c.min_focal_obs >= 1 && fin(c.focal_lo) && fin(c.focal_hi) && c.focal_lo < 1.0 && 1.0 < c.focal_hi)) return LOFTR_ERR_BAD_ARG;
   }
+  if constexpr (Mode::kPrior) {
+    if (n > 0 && (!c.pr.xyz || !c.pr.sigma || !c.pr.mask || !c.pr.cam_prior)) return LOFTR_ERR_BAD_ARG;
+  }
   if constexpr (Mode::kGroups) {
     if (n > 0 && (!c.cam_group || !c.group_cams || !c.group_focal)) return LOFTR_ERR_BAD_ARG;
     if (!c.group_offsets || c.G < 0 || c.G > n || (n > 0 && c.G == 0)) return LOFTR_ERR_BAD_ARG;
@@ -826,7 +947,7 @@ template <class Mode> inline int check_args(const typename Mode::Ctx& c, int max
   if (!(c.huber >= 0.0 && fin(c.huber) && c.ftol >= 0.0 && fin(c.ftol) && pcg_tol >= 0.0 && pcg_tol < 1.0)) return LOFTR_ERR_BAD_ARG;
   if (max_iters < 0 || max_iters > LOFTR_BUNDLE_MAX_ITERS || pcg_iters < 1 || pcg_iters > LOFTR_BUNDLE_MAX_PCG) return LOFTR_ERR_BAD_ARG;
   if (!sizes_ok(T, N, n)) return LOFTR_ERR_UNSUPPORTED;
-  if (zero_counts) for (int i = 0; i < kCounts; ++i) c.counts[i] = 0;
+  if (zero_counts) for (int i = 0; i < (Mode::kPrior ? kCountsPrior : kCounts); ++i) c.counts[i] = 0;
   if (N > 0 && (T == 0 || n == 0)) return LOFTR_ERR_BAD_ARG;           // observations outside every track or camera
   return LOFTR_OK;
 }

@@ -16,6 +16,10 @@
 // is up) returns at once on a flag in device memory; a flag is only ever read by kernels launched after the one that wrote it.  No
 // readback, no grid-wide barrier, no persistent kernel, no captured graph: a kernel boundary is the only device-wide ordering.
 // Floating-point values cross lanes only as exact copies (shuffles); atomics are integer only.  Plain C++, ordinary vector stores.
+// Position priors (§18.3) are a trait of the mode: PoseP, FocalP and SharedP run the same schedule; the decision is taken by the lane
+// that ends ba_groups_kernel, the additions to U and gc by the lane that ends ba_cam_lin_kernel, a thread per camera evaluates the
+// prior of a state (ba_prior_eval_kernel), the levels of the cameras' osum follow it (ba_prior_osum_kernel), and every kernel that the
+// prior does not touch is the one of the mode without it.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -71,6 +75,7 @@ __device__ __forceinline__ double wave_group_sum(const CtxS& c, long g, int lane
 template <class Mode> using StepCtx = std::conditional_t<Mode::kGroups, CtxS, Ctx>;
 
 __global__ void ba_init_kernel(Ctx c, CtrlS* cs) { ctrl_init(c, cs); }
+__global__ void ba_prior_init_kernel(Prior p) { ctrl_init_prior(p); }
 
 // grid ceil(n / 256) x 256
 template <int S> __global__ void __launch_bounds__(kThreads) ba_cam_setup_kernel(std::conditional_t<S == 7, Ctx7, Ctx> c) {
@@ -120,6 +125,11 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_groups_kern
     const bool fr = !c.fixed[i] && c.cam_valid[i] && cnt >= 1;
     c.cam_free[i] = (uint8_t)fr;
     if (fr) atomicAdd(&c.ctrl->n_free, 1ull);
+    if constexpr (Mode::kPrior) {
+      const bool pr = cam_prior_rule(c, c.pr, i);
+      c.pr.cam_prior[i] = (uint8_t)pr;
+      if (pr) atomicAdd(&c.pr.cp->n_prior, 1ull);
+    }
     if constexpr (Mode::kGroups) err |= cam_carry(c, i, cnt);
     if (err) atomicOr(&c.ctrl->err, err);
     if constexpr (Mode::S == 7 && !Mode::kGroups) {
@@ -188,6 +198,25 @@ __global__ void __launch_bounds__(64) ba_osum_kernel(Ctx c, const double* in, lo
   }
 }
 
+// §18.3.  A thread per camera, grid ceil(n / 256) x 256: its share of the cost and |c - g|^2 at the state (other = 0) or the trial
+__global__ void __launch_bounds__(kThreads) ba_prior_eval_kernel(Ctx c, Prior p, int other, int flags) {
+  if (skipped(c, flags)) return;
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i < c.n) cam_prior_eval(c, p, c.ctrl->cur ^ other, i);
+}
+// ... and one level of a cameras' osum, as ba_osum_kernel; the last level feeds the owner of the prior's scalars
+__global__ void __launch_bounds__(64) ba_prior_osum_kernel(Ctx c, Prior p, const double* in, long count, double* out, int action, int flags) {
+  if (skipped(c, flags)) return;
+  const int lane = threadIdx.x;
+  const long lo = (long)blockIdx.x * kChunk, len = count - lo < kChunk ? count - lo : kChunk;
+  double a;
+  wave_osum64<1>(0, len, lane, [&](long e, double* s) { s[0] = s[0] + in[lo + e]; }, &a);
+  if (lane == 0) {
+    if (action >= 0) ctrl_feed_prior(c, p, action, a);
+    else out[blockIdx.x] = a;
+  }
+}
+
 __global__ void __launch_bounds__(kThreads) ba_track_lin_kernel(Ctx c, int flags) {
   if (skipped(c, flags)) return;
   const long t = (long)blockIdx.x * kThreads + threadIdx.x;
@@ -208,6 +237,7 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_cam_lin_ker
     for (int k = 0; k < kU; ++k) c.U[kU * i + k] = a[k];
 #pragma unroll
     for (int k = 0; k < S; ++k) c.gc[S * i + k] = a[kU + k];
+    if constexpr (Mode::kPrior) cam_lin_prior<S>(c, c.pr, cur, i);
   }
 }
 
@@ -296,6 +326,7 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_apply_kerne
 }
 
 __global__ void ba_accept_kernel(Ctx c) { ctrl_accept(c); }
+__global__ void ba_prior_accept_kernel(Ctx c, Prior p) { ctrl_accept_prior(c, p); }
 
 // threads [0, T): points, [T, T + n): cameras; thread 0 also writes the counts.  Runs whatever the flags say.
 template <class Mode> __global__ void __launch_bounds__(kThreads) ba_write_kernel(typename Mode::Ctx c) {
@@ -305,14 +336,18 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_write_kerne
     if (id < c.T) track_write(c, cur, id);
     else if (id < c.T + c.n) cam_write<Mode>(c, cur, id - c.T);
   }
-  if (id == 0) ctrl_write<Mode>(c);
+  if (id == 0) {
+    ctrl_write<Mode>(c);
+    if constexpr (Mode::kPrior) ctrl_write_prior(c, c.pr);
+  }
 }
 
 // the fixed launch schedule of every mode; c holds the problem and the result.  The phases that do not touch the camera block or the
 // groups (track setup, evaluate, the track linearisation, accept, the osum) are one kernel for all modes, on the base of the context.
 template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iters, double pcg_tol, void* ws, size_t ws_bytes, float* class_ms,
                               long* class_launches, void* stream) {
-  constexpr bool kGroups = Mode::kGroups;
+  constexpr bool kGroups = Mode::kGroups, kPrior = Mode::kPrior;
+  using BaseMode = typename Mode::Base;                                 // the kernels of the phases that the prior does not touch
   LOFTR_CHECK_ARG(ws);
   const int st = check_args<Mode>(c, max_iters, pcg_iters, pcg_tol, false);
   if (st != LOFTR_OK) return st;
@@ -341,6 +376,9 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   auto blocks = [](long items, long per) { return dim3((unsigned)(items > 0 ? (items + per - 1) / per : 1)); };
   const dim3 threads(kThreads);
   const Ctx& b = c;                                                     // what the kernels of all modes take
+  const typename BaseMode::Ctx& cb = c;                                 // ... and those of the mode, without the prior
+  Prior pr{};
+  if constexpr (kPrior) pr = c.pr;
   double* red2 = c.red + ((std::max(T, n) + 1 + kChunk - 1) / kChunk);
   // osum of v[0 .. count) into `action` (ba_osum_kernel): one launch per level
   auto osum = [&](const double* v, long count, int action, double* wait, int flags) {
@@ -364,40 +402,69 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
     } else osum(c.part, n, action, nullptr, flags);
   };
   auto camera_half = [&](int mode, int flags) {
-    hipLaunchKernelGGL(ba_cam_half_kernel<Mode>, blocks(n, 4), threads, 0, s, c, mode, flags); after(kClsCamHalf);
-    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_half_kernel, blocks(G, 4), threads, 0, s, c, mode, flags); after(kClsCamHalf); }
+    hipLaunchKernelGGL(ba_cam_half_kernel<BaseMode>, blocks(n, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf);
+    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_half_kernel, blocks(G, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf); }
+  };
+  // osum of the cameras' prior terms v[0 .. n) into `action` (ba_prior_osum_kernel): one launch per level
+  auto prior_osum = [&](const double* v, int action, int flags) {
+    const double* in = v;
+    double* out = c.red;
+    long count = n;
+    for (;;) {
+      const long chunks = count > 0 ? (count + kChunk - 1) / kChunk : 1;
+      hipLaunchKernelGGL(ba_prior_osum_kernel, dim3((unsigned)chunks), dim3(64), 0, s, b, pr, in, count, out, chunks == 1 ? action : -1, flags);
+      after(kClsOsum);
+      if (chunks == 1) return;
+      in = out;
+      out = out == c.red ? red2 : c.red;
+      count = chunks;
+    }
+  };
+  // evaluate the state (other = 0) or the trial, then its cost and sum of |r|^2: the tracks' osum, with priors the cameras' added to it
+  auto evaluate = [&](int other, int cost, int sq, int flags) {
+    hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), threads, 0, s, b, other, flags); after(kClsEvaluate);
+    const int f = other ? flags | kSkipBadE : flags;
+    if constexpr (kPrior) {
+      hipLaunchKernelGGL(ba_prior_eval_kernel, blocks(n, kThreads), threads, 0, s, b, pr, other, flags); after(kClsEvaluate);
+      osum(c.part, T, kActStore, &pr.cp->acc, f);
+      prior_osum(pr.part, cost, f);
+      osum(c.part2, T, sq, nullptr, f);
+      prior_osum(pr.part2, sq, f);
+    } else {
+      osum(c.part, T, cost, nullptr, f);
+      osum(c.part2, T, sq, nullptr, f);
+    }
   };
   if (timed) mark();
   hipLaunchKernelGGL(ba_init_kernel, dim3(1), dim3(1), 0, s, b, groups_ctrl<Mode>(c)); after(kClsSetup);
-  hipLaunchKernelGGL(ba_cam_setup_kernel<Mode::S>, blocks(n, kThreads), threads, 0, s, c); after(kClsSetup);
+  if constexpr (kPrior) { hipLaunchKernelGGL(ba_prior_init_kernel, dim3(1), dim3(1), 0, s, pr); after(kClsSetup); }
+  hipLaunchKernelGGL(ba_cam_setup_kernel<Mode::S>, blocks(n, kThreads), threads, 0, s, cb); after(kClsSetup);
   hipLaunchKernelGGL(ba_track_setup_kernel, blocks(T, kThreads), threads, 0, s, b); after(kClsSetup);
   hipLaunchKernelGGL(ba_groups_kernel<Mode>, blocks(n, 4), threads, 0, s, c); after(kClsSetup);
-  if constexpr (kGroups) { hipLaunchKernelGGL(ba_cgroups_kernel, blocks(G, 4), threads, 0, s, c); after(kClsSetup); }
-  hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), threads, 0, s, b, 0, 0); after(kClsEvaluate);
-  osum(c.part, T, kActCost0, nullptr, 0);
-  osum(c.part2, T, kActSq0, nullptr, 0);
+  if constexpr (kGroups) { hipLaunchKernelGGL(ba_cgroups_kernel, blocks(G, 4), threads, 0, s, cb); after(kClsSetup); }
+  evaluate(0, kActCost0, kActSq0, 0);
   for (int it = 0; it < max_iters && !failed; ++it) {
     hipLaunchKernelGGL(ba_track_lin_kernel, blocks(T, kThreads), threads, 0, s, b, kNeedFresh); after(kClsLinearise);
     hipLaunchKernelGGL(ba_cam_lin_kernel<Mode>, blocks(n, 4), threads, 0, s, c, kNeedFresh); after(kClsLinearise);
-    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_lin_kernel, blocks(G, 4), threads, 0, s, c, kNeedFresh); after(kClsLinearise); }
-    hipLaunchKernelGGL(ba_factor_kernel<Mode>, blocks(T + n + G, kThreads), threads, 0, s, c, 0); after(kClsFactor);
-    hipLaunchKernelGGL(ba_track_half_kernel<Mode>, blocks(T, kThreads), threads, 0, s, c, 0, kSkipBadF); after(kClsTrackHalf);
+    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_lin_kernel, blocks(G, 4), threads, 0, s, cb, kNeedFresh); after(kClsLinearise); }
+    hipLaunchKernelGGL(ba_factor_kernel<BaseMode>, blocks(T + n + G, kThreads), threads, 0, s, cb, 0); after(kClsFactor);
+    hipLaunchKernelGGL(ba_track_half_kernel<BaseMode>, blocks(T, kThreads), threads, 0, s, cb, 0, kSkipBadF); after(kClsTrackHalf);
     camera_half(0, kSkipBadF);
     dot(kActRz0, kSkipBadF);
     for (int pi = 0; pi < pcg_iters && !failed; ++pi) {
       const int f = kSkipBadF | kSkipPcg;
-      hipLaunchKernelGGL(ba_track_half_kernel<Mode>, blocks(T, kThreads), threads, 0, s, c, 1, f); after(kClsTrackHalf);
+      hipLaunchKernelGGL(ba_track_half_kernel<BaseMode>, blocks(T, kThreads), threads, 0, s, cb, 1, f); after(kClsTrackHalf);
       camera_half(1, f);
       dot(kActPsp, f);
-      hipLaunchKernelGGL(ba_update_kernel<Mode>, blocks(n + G, kThreads), threads, 0, s, c, 1, f); after(kClsUpdate);
+      hipLaunchKernelGGL(ba_update_kernel<BaseMode>, blocks(n + G, kThreads), threads, 0, s, cb, 1, f); after(kClsUpdate);
       dot(kActRz, f);
-      hipLaunchKernelGGL(ba_update_kernel<Mode>, blocks(n + G, kThreads), threads, 0, s, c, 2, f); after(kClsUpdate);
+      hipLaunchKernelGGL(ba_update_kernel<BaseMode>, blocks(n + G, kThreads), threads, 0, s, cb, 2, f); after(kClsUpdate);
     }
-    hipLaunchKernelGGL(ba_apply_kernel<Mode>, blocks(T + n + G, kThreads), threads, 0, s, c, kSkipBadF); after(kClsApply);
-    hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), threads, 0, s, b, 1, kSkipBadF | kSkipBadA); after(kClsEvaluate);
-    osum(c.part, T, kActCostT, nullptr, kSkipBadF | kSkipBadA | kSkipBadE);
-    osum(c.part2, T, kActSqT, nullptr, kSkipBadF | kSkipBadA | kSkipBadE);
-    hipLaunchKernelGGL(ba_accept_kernel, dim3(1), dim3(1), 0, s, b); after(kClsAccept);
+    hipLaunchKernelGGL(ba_apply_kernel<BaseMode>, blocks(T + n + G, kThreads), threads, 0, s, cb, kSkipBadF); after(kClsApply);
+    evaluate(1, kActCostT, kActSqT, kSkipBadF | kSkipBadA);
+    if constexpr (kPrior) hipLaunchKernelGGL(ba_prior_accept_kernel, dim3(1), dim3(1), 0, s, b, pr);
+    else hipLaunchKernelGGL(ba_accept_kernel, dim3(1), dim3(1), 0, s, b);
+    after(kClsAccept);
   }
   hipLaunchKernelGGL(ba_write_kernel<Mode>, blocks(T + n, kThreads), threads, 0, s, c); after(kClsWrite);
   if (class_launches) for (int k = 0; k < kClsCount; ++k) class_launches[k] = launches[k];
@@ -465,4 +532,43 @@ extern "C" int loftr_bundle_adjust_shared(const long* offsets, long T, const int
   fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
   fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
   return run<Shared>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+}
+
+// with position priors on the camera centres (§18.3): mode 0 pose, 1 focal, 2 shared
+namespace {
+template <class F> auto with_prior_mode(int mode, F go) -> decltype(go(PoseP{})) {
+  switch (mode) {
+    case 0: return go(PoseP{});
+    case 1: return go(FocalP{});
+    case 2: return go(SharedP{});
+  }
+  return decltype(go(PoseP{}))(0);
+}
+}  // namespace
+
+extern "C" size_t loftr_bundle_adjust_prior_workspace_bytes(long T, long N, int n_images, int mode) {
+  return with_prior_mode(mode, [&](auto m) { return workspace_bytes<decltype(m)>(T, N, n_images); });
+}
+
+extern "C" int loftr_bundle_adjust_prior(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
+                                         long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                         const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                         const int* cam_group, const long* group_offsets, const int* group_cams, int G,
+                                         const double* prior_xyz, const double* prior_sigma, const uint8_t* prior_mask, int mode,
+                                         double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs,
+                                         double focal_lo, double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
+                                         uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal,
+                                         uint8_t* cam_prior, long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches,
+                                         void* stream) {
+  if (mode < 0 || mode > 2) return LOFTR_ERR_BAD_ARG;
+  return with_prior_mode(mode, [&](auto m) {
+    using Mode = decltype(m);
+    typename Mode::Ctx c{};
+    fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol,
+         ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts);
+    if constexpr (Mode::S == 7) fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
+    if constexpr (Mode::kGroups) fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
+    fill_prior(c.pr, prior_xyz, prior_sigma, prior_mask, cam_prior);
+    return run<Mode>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+  });
 }

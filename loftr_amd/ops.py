@@ -1464,13 +1464,24 @@ _BA_MODES = {
                              "; cam_group / group_offsets / group_cams must group the images by camera in ascending order")}
 
 
-def _bundle_adjust(B, call, arrays, params, focal, timings):
-    """The body of all six: the table check, the shapes, the parameters, zeroed outputs, the timing buffers (per kernel class, not per
-    stage: the median launch and the total, and the launches issued), the call."""
+# Position priors on the camera centres are one more row of any mode: three inputs, one output, 24 counts, and ONE routine
+# pair, loftr_bundle_adjust_prior(_host), that takes the arguments of the grouped pair (NULL below the mode) and the mode's number.
+BUNDLE_PRIOR_COUNTS = 24
+_BA_PRIOR_IN = (("prior_xyz", "float64", 2), ("prior_sigma", "float64", 2), ("prior_mask", "uint8", 1))
+_BA_PRIOR_OUT = (("cam_prior", "n", (), "uint8"),)
+_BA_PRIOR_MODE = {"bundle_adjust": 0, "bundle_adjust_focal": 1, "bundle_adjust_shared": 2}
+
+
+def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None):
+    """The body of all eight: the table check, the shapes, the parameters, zeroed outputs, the timing buffers (per kernel class, not per
+    stage: the median launch and the total, and the launches issued), the call.  prior: None, or (prior_xyz, prior_sigma, prior_mask)."""
     extra_in, extra_out, shapes, rule = _BA_MODES[call]
-    what, hint = (call + "_host", call) if B is _Host else \
-        (call, f"the bundle-adjustment kernels have no CPU fallback; the host routine is {call}_host")
+    name = call if prior is None else "bundle_adjust_prior"
+    what, hint = (name + "_host", name) if B is _Host else \
+        (name, f"the bundle-adjustment kernels have no CPU fallback; the host routine is {name}_host")
     _check_args(B, what, hint, _BA_ARGS + extra_in, arrays)
+    if prior is not None:
+        _check_args(B, what, hint, _BA_PRIOR_IN, prior)
     offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs = arrays[:10]
     N, n, T = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
     refine, groups = arrays[10:11], arrays[11:]          # (refine_focal,) and (cam_group, group_offsets, group_cams), or empty
@@ -1482,11 +1493,17 @@ def _bundle_adjust(B, call, arrays, params, focal, timings):
             any(x.shape[0] != n for x in (*refine, *groups[::2])) or (groups and (G < 0 or G > n or (n > 0 and G == 0))):
         raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
                                  f"T_cam_from_world [n,4,4], fixed [n], {shapes}, got {[tuple(a.shape) for a in arrays]}")
+    if prior is not None and (tuple(prior[0].shape) != (n, 3) or tuple(prior[1].shape) != (n, 3) or prior[2].shape[0] != n):
+        raise _lib.LoftrHipError(f"{what}: expected prior_xyz [n,3], prior_sigma [n,3] and prior_mask [n] with n = {n}, got "
+                                 f"{[tuple(x.shape) for x in prior]}")
     params = _ba_params(what, *params)
     if focal is not None:
         params += _ba_focal_params(what, *focal)
     arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
     a = [B.ptr(x) for x in arrays]
+    if prior is not None:
+        return _bundle_adjust_prior(B, _BA_PRIOR_MODE[call], a, [B.contiguous(x) for x in prior], params, size, extra_out, rule, offsets,
+                                    timings)
     out = _outputs(B, _BA_OUT + extra_out, size, BUNDLE_COUNTS, offsets)
     ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
     launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
@@ -1497,6 +1514,58 @@ def _bundle_adjust(B, call, arrays, params, focal, timings):
     if timings is not None:
         timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
     return out
+
+
+def _bundle_adjust_prior(B, mode, a, prior, params, size, extra_out, rule, like, timings):
+    """... and the call with priors: the pointers `a` of the mode's arrays laid out as the grouped pair's, NULL for what the mode lacks."""
+    T, N, n = size["T"], size["N"], size["n"]
+    a = a + [None] * (14 - len(a))
+    if len(params) == 5:
+        params += (1, 0.5, 2.0)                                                          # (ignored below mode 1)
+    out = _outputs(B, _BA_OUT + extra_out + _BA_PRIOR_OUT, size, BUNDLE_PRIOR_COUNTS, like)
+    named = dict(out, **{k: None for k in ("K", "cam_focal", "group_focal") if k not in out})
+    order = [k for k, *_ in _BA_OUT] + ["K", "cam_focal", "group_focal", "cam_prior", "counts"]
+    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
+    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
+    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
+    B.call("bundle_adjust_prior", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], a[10], n, a[8], a[9], a[11], a[12], a[13], size.get("G", 0),
+                                   *[B.ptr(x) for x in prior], mode, *params, *[B.ptr(named[k]) for k in order]),
+           _TABLE_RULES + rule, like, ws=(T, N, n, mode), tail=(cast(ms), cast(launches)))
+    if timings is not None:
+        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
+    return out
+
+
+def _ba_prior_call(B, mode, base, refine_focal, groups, prior, params, focal, timings):
+    """The mode's row of _BA_MODES for the prior pair: mode 0 pose, 1 focal, 2 shared."""
+    if mode not in (0, 1, 2):
+        raise ValueError(f"bundle_adjust_prior: mode must be 0 (pose), 1 (focal) or 2 (shared), got {mode!r}")
+    call = ("bundle_adjust", "bundle_adjust_focal", "bundle_adjust_shared")[mode]
+    arrays = tuple(base) + ((refine_focal,) if mode >= 1 else ()) + (tuple(groups) if mode == 2 else ())
+    return _bundle_adjust(B, call, arrays, params, focal if mode >= 1 else None, timings, prior=tuple(prior))
+
+
+def bundle_adjust_prior_host(mode, offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                             cam_group, group_offsets, group_cams, prior_xyz, prior_sigma, prior_mask, huber_px, max_iters, pcg_iters,
+                             pcg_tol, ftol, min_focal_obs=20, focal_lo=0.5, focal_hi=2.0):
+    """loftr_bundle_adjust_prior_host: the host routine that DEFINES the bundle adjustment with position priors on the camera centres
+    (include/loftr_hip.h) on numpy arrays.  mode 0, 1, 2: the rule of bundle_adjust_host, _focal_host, _shared_host with
+    the prior term; refine_focal (mode 0) and the group arrays (mode < 2) are ignored and may be None.  prior_xyz [n,3] f64,
+    prior_sigma [n,3] f64, prior_mask [n] u8.  -> the mode's dict plus cam_prior [n] u8; counts [24] i64."""
+    return _ba_prior_call(_Host, mode, (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs), refine_focal,
+                          (cam_group, group_offsets, group_cams), (prior_xyz, prior_sigma, prior_mask),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None)
+
+
+@_on_device
+def bundle_adjust_prior(mode, offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                        cam_group, group_offsets, group_cams, prior_xyz, prior_sigma, prior_mask, huber_px, max_iters, pcg_iters, pcg_tol,
+                        ftol, min_focal_obs=20, focal_lo=0.5, focal_hi=2.0, timings=None):
+    """loftr_bundle_adjust_prior: the kernels (csrc/bundle_gpu.hip) on GPU tensors; the same result as bundle_adjust_prior_host bit for
+    bit, the same launch schedule, timing classes and single readback as bundle_adjust."""
+    return _ba_prior_call(_Gpu, mode, (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs), refine_focal,
+                          (cam_group, group_offsets, group_cams), (prior_xyz, prior_sigma, prior_mask),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
 
 
 def bundle_adjust_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, huber_px, max_iters,

@@ -71,14 +71,21 @@ class Reconstruction:
         from .alignment import transformed
         return transformed(self, s, R, t)
 
-    def align(self, ref_centres, known=None, thresh=1.0, with_scale=True, apply=True, conf=0.999, seed=0):
+    def align(self, ref_centres, known=None, thresh=1.0, with_scale=True, apply=True, conf=0.999, seed=0, refine=None):
         """Georegister against reference camera positions ``ref_centres [n,3]`` (``known [n]``: which rows hold one; default: the
         finite rows) -> ``(rec2, alignment)``: ``alignment`` is ``alignment.align_centres`` of the posed and known images at
         ``thresh`` (units of ``ref_centres``), ``rec2 = self.transformed(s, R, t)``.  ``bundle`` stays in the old frame.  Without a
         model (``alignment.n_inliers == -1``) nothing is raised and ``rec2`` is this reconstruction itself; likewise with
-        ``apply=False``."""
+        ``apply=False``.
+
+        ``refine=dict(sfm=..., sigma=..., **ba_kwargs)`` goes on from the aligned model: a bundle adjustment over the
+        tracks of ``sfm`` (the ``SfmResult`` this reconstruction came from, or ``self.sfm``) with no camera fixed and the reference
+        positions of ``alignment.inliers`` as position priors at ``sigma`` (a scalar, ``[n]`` or ``[n,3]``, units of ``ref_centres``),
+        then a triangulation with the adjusted poses: align -> adjust -> triangulate.  ``rec2`` then carries the refined poses (an
+        image without a pose keeps its NaN pose), ``K`` (when the focals are refined), ``points`` and ``bundle``.  ``ba_kwargs`` are
+        ``bundle_adjust``'s.  Without ``refine`` the method is as before."""
         from .alignment import align
-        return align(self, ref_centres, known, thresh, with_scale, apply, conf, seed)
+        return align(self, ref_centres, known, thresh, with_scale, apply, conf, seed, refine)
 
 
 def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed, min_corr=15, min_inliers=15, thresh_px=4.0,
@@ -220,7 +227,9 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     ``x_b = R x_a + t``, e.g. a five-point estimate: ``T[a] = I``, ``T[b] = [R | t / |t|]``; every other pose starts as NaN.
 
     A round is: triangulate over the posed images, ``bundle_adjust`` with image ``a`` fixed (``ba``: keyword arguments for
-    ``bundle_adjust``; ``ba['fixed_extra']``: a ``[n]`` mask of further fixed images), triangulate again with the adjusted poses,
+    ``bundle_adjust``; ``ba['fixed_extra']``: a ``[n]`` mask of further fixed images; ``position_prior`` and its keywords pass through
+    as well, which makes sense only for a caller whose initial pair is already in the frame of the priors -- otherwise align first and
+    use ``Reconstruction.align(refine=...)``), triangulate again with the adjusted poses,
     ``register_images`` (``register_kw``: its keyword arguments; ``thresh_px`` is also the triangulation's threshold).  The loop stops
     when a round registers nothing, when every image is posed, or after ``max_rounds``; then one more triangulate -> adjust ->
     triangulate.  An image is registered once: its pose changes afterwards only through the bundle adjustment.

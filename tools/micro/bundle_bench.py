@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Bundle adjustment (loftr_amd/bundle.py, csrc/bundle_gpu.hip) on a MegaDepth-1500-shaped load.  One JSON line.
 
-    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--refine-focal] [--camera-groups G[,G...]] [--no-host] [--out FILE]
+    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--refine-focal] [--camera-groups G[,G...]] [--prior] [--no-host] [--out FILE]
 
 Load: the track lengths of tools/micro/atlas_bench.py's synthetic atlas (1500 rows over 806 images), observations as in
 tools/micro/triangulation_bench.py without outliers (one exact camera per image, one 3D point per track, every observation in a random
@@ -18,7 +18,12 @@ free camera starts 4-10 % off and the line holds two such legs on that load: "fi
 §18.2) the line holds that per-image leg as the reference point ("per_image") and one leg per G ("groups_G"): image i is of camera
 i mod G, every camera's focal -- the fixed-pose images' too -- starts off by one factor of 4-10 %, and the call is
 refine_focal=True, camera_ids=ids; per leg the trials, conjugate-gradient iterations, rms before and after, the largest focal error
-over all images and the wall time."""
+over all images and the wall time.  With --prior the line holds three legs on the default load, run in alternation
+--rounds times (no_prior, prior_masked, prior, no_prior, ...) after one warm-up of each: "no_prior" (the default call: images 0 and 1
+fixed), "prior_masked" (the kernels with priors and an all-zero prior_mask: the same result as no_prior, asserted), "prior" (no camera
+fixed, position_prior = the true centres + N(0, 0.05) per axis at prior_sigma = 0.05); per leg every wall time with its median and
+spread, the trials, accepted trials and conjugate-gradient iterations, the class times of one call with events, and for "prior" the
+rms distance of the centres from their priors before and after."""
 import argparse
 import json
 import os
@@ -132,6 +137,8 @@ def leg(inputs, fixed, kw, n_tracks, args):
         per_pcg, per_trial = 9, 4 + 3 + 2 + 2 + 2 * levels_t + 1
     skipped = (args.max_iters - res.n_iters) * (per_trial + per_pcg * args.pcg_iters) + per_pcg * (res.n_iters * args.pcg_iters - res.n_pcg)
     out["launches_issued"], out["launches_skipped_at_least"] = issued, int(skipped)
+    if "position_prior" in kw:                                          # §18.3: an evaluation has three more launches per level of the cameras' sum
+        del out["launches_skipped_at_least"]
     out["stats"] = res.stats
     if not args.no_host:
         t = time.perf_counter()
@@ -145,6 +152,54 @@ def leg(inputs, fixed, kw, n_tracks, args):
     return out, res
 
 
+def true_centres(n_images, seed=0):
+    """The camera centres make_load(.., seed) draws before it perturbs them."""
+    rng = np.random.default_rng(seed)
+    rotations(rng, n_images, 20.0)
+    return rng.uniform([-2, -1, -0.5], [2, 1, 0.5], (n_images, 3))
+
+
+def prior_legs(inputs, fixed, kw, n_images, args):
+    """--prior: the three legs in alternation -> dict of legs."""
+    sigma = 0.05
+    g = torch.from_numpy(true_centres(n_images) + sigma * np.random.default_rng(7).standard_normal((n_images, 3))).to(DEV)
+    none = torch.zeros_like(fixed)
+    legs = {"no_prior": dict(fixed=fixed, **kw),
+            "prior_masked": dict(fixed=fixed, position_prior=g, prior_sigma=sigma, prior_mask=none, **kw),
+            "prior": dict(fixed=none, position_prior=g, prior_sigma=sigma, **kw)}
+    res, wall = {}, {k: [] for k in legs}
+    for k, a in legs.items():
+        res[k] = bundle_adjust(*inputs, **a)                             # warm-up (kernel load)
+    for _ in range(args.rounds):
+        for k, a in legs.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            r = bundle_adjust(*inputs, **a)
+            wall[k].append(round(1e3 * (time.perf_counter() - t), 3))
+            assert same_fields(r, res[k]), f"{k}: two runs differ"
+    plain, masked = res["no_prior"], res["prior_masked"]
+    assert all(torch.equal(torch.nan_to_num(getattr(plain, f).double()), torch.nan_to_num(getattr(masked, f).double())) for f in plain.FIELDS) and \
+        all(masked.stats[f] == v for f, v in plain.stats.items()), "an all-zero prior_mask differs from the call without priors"
+    out = {}
+    for k, a in legs.items():
+        timings = {}
+        bundle_adjust(*inputs, timings=timings, **a)
+        st = res[k].stats
+        out[k] = {"wall_ms": wall[k], "wall_median_ms": round(float(np.median(wall[k])), 3), "wall_min_ms": min(wall[k]), "wall_max_ms": max(wall[k]),
+                  "n_iters": st["n_iters"], "n_accepted": st["n_accepted"], "n_pcg": st["n_pcg"], "status": st["status"],
+                  "rms_px_before": st["rms_px_before"], "rms_px_after": st["rms_px_after"],
+                  "class_total_ms": {c: round(v[1], 3) for c, v in timings.items()}, "class_launches": {c: v[2] for c, v in timings.items()}}
+        if "prior_rms_after" in st:
+            out[k].update(n_prior_cameras=st["n_prior_cameras"], prior_rms_before=st["prior_rms_before"], prior_rms_after=st["prior_rms_after"])
+    out["prior_masked"]["identical_to_no_prior"] = True
+    return out
+
+
+def same_fields(a, b):
+    return a.FIELDS == b.FIELDS and all(torch.equal(torch.nan_to_num(getattr(a, k).double()), torch.nan_to_num(getattr(b, k).double())) for k in a.FIELDS) \
+        and a.stats == b.stats
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rows", type=int, default=1500)
@@ -156,6 +211,8 @@ def main():
                     help="the focal of every free camera off by 4-10 %%: a fixed-intrinsics leg and a refine_focal=True leg on that load")
     ap.add_argument("--camera-groups", default=None,
                     help="comma-separated group counts G (image i is of camera i mod G): a per-image refine_focal leg and one shared leg per G")
+    ap.add_argument("--prior", action="store_true", help="position priors (DESIGN §18.3): the no_prior, prior_masked and prior legs in alternation")
+    ap.add_argument("--rounds", type=int, default=5, help="(--prior) timed calls per leg")
     ap.add_argument("--no-host", action="store_true", help="skip the host routine (and the equality assertion)")
     ap.add_argument("--out", default=None, help="also append the JSON line to this file")
     args = ap.parse_args()
@@ -171,7 +228,10 @@ def main():
     kw = dict(huber_px=args.huber, max_iters=args.max_iters, pcg_iters=args.pcg_iters)
     out = {"workload": "bundle_megadepth1500_shape", "images": n_images, "tracks": int(lens.numel()), "observations": int(inputs[0][-1]),
            "fixed_cameras": 2, **kw}
-    if args.camera_groups:
+    if args.prior:
+        out["workload"] += "_position_priors"
+        out.update(prior_legs(inputs, fixed, kw, n_images, args))
+    elif args.camera_groups:
         K_true = inputs[5]
         err = lambda K: float((K[:, 0, 0] / K_true[:, 0, 0] - 1).abs().max())
         brief = lambda d, res, K0: dict(d, focal_error_before=round(err(K0), 5), focal_error_after=round(err(res.K), 5))
