@@ -1281,6 +1281,59 @@ int loftr_transform_model_host(const float* xyz, long N, const double* T_cam_fro
 int loftr_transform_model(const float* xyz, long N, const double* T_cam_from_world, const uint8_t* posed, int n_images, const double* s,
                           const double* R, const double* t, float* xyz_out, double* T_out, void* stream);
 
+/* ---- view overlap: image pairs by projected-point overlap (csrc/overlap_core.h holds every per-entry step) ------------------
+ * Two images are worth matching when the points one of them observes project into the other within a viewing-angle and scale change
+ * the matcher can bridge (the idea hloc ships as pairs_from_covisibility / pairs_from_poses).  overlap[i, j] counts the points that
+ * source image i observes and that do so for target view j.  loftr_view_overlap_host (csrc/overlap.hip, host memory) DEFINES the result,
+ * loftr_view_overlap (csrc/overlap_gpu.hip, device memory) reproduces it exactly: every output is an integer, a count is a sum of 0 / 1,
+ * so no summation order needs fixing and identity rests on the per-entry predicate being one text.
+ * Input: the visibility lists of the n source images -- vis_offsets [n+1] i64 over vis_point [V] i32 (point ids) --; the points xyz
+ *   [T,3] f32 and point_ok [T] u8; the sources K_src [n,9], T_src [n,16] f64 (camera from world, row-major) and src_ok [n] u8; the m
+ *   target views K_tgt [m,9], T_tgt [m,16] f64, tgt_ok [m] u8 and tgt_hw [m,2] f64 (H, W); border_px >= 0 (finite); cos_min in [-1, 1]
+ *   (the cosine of the largest viewing-angle change, computed once by the caller and handed to both sides as the same double);
+ *   max_scale2 >= 1 (the square of the largest ratio of apparent sizes; inf disables the test).  Arithmetic: fp64 without FMA
+ *   contraction, + - * / and sqrt only; the camera table and the projection order are the triangulation's (tri::cam_table,
+ *   tri::residual2: P = K [R | t], c = -R^T t, (a0 b0 + a1 b1) + a2 b2 as the dot product).
+ *   1. A source i is valid iff src_ok[i] != 0 and its camera table is valid.  A target j likewise, and its H and W must be finite and
+ *      positive.
+ *   2. Entry p = vis_point[k] of a valid source is USABLE iff point_ok[p] != 0 and the three floats of xyz[p] are finite (exponent bits
+ *      not all ones).  n_vis[i] is the number of usable entries; 0 for an invalid source.
+ *   3. X = (double) xyz[p]; a = c_i - X, b = c_j - X, aa = a . a, bb = b . b, d = a . b.  A usable entry of source i COUNTS FOR the valid
+ *      target j iff all of these hold, in this order (every comparison is written so that a NaN fails):
+ *        z > 0, with x = (P0 . X) + P03, y = (P1 . X) + P13, z = (P2 . X) + P23 of target j;
+ *        border <= u < W_j - border and border <= v < H_j - border, with u = x / z, v = y / z;
+ *        d >= cos_min * sqrt(aa * bb);
+ *        fxj^2 aa <= max_scale2 (fxi^2 bb) and fxi^2 bb <= max_scale2 (fxj^2 aa): the ratio of the apparent sizes f / distance, without a
+ *        division; fx = K[0].
+ *   4. overlap [n, m] i32: the number of entries of i that count for j.  An invalid source gives a zero row, an invalid target a zero
+ *      column; i == j is not special.
+ *   5. counts [8] i64: [0] the sum of n_vis, [1] error bits, [2] valid sources, [3] valid targets, [4] non-zero entries of overlap,
+ *      the rest 0.
+ *   6. Errors (counts[1]).  1: a vis_point outside [0, T); 2: vis_offsets that do not start at 0, end at V and ascend.
+ * Status: LOFTR_ERR_BAD_ARG for null pointers (each only where its size is positive), negative sizes, border_px negative or not finite,
+ *   cos_min outside [-1, 1], max_scale2 < 1, NaN parameters, entries without a list (n == 0 with V > 0); the host routine also for the two
+ *   error bits, and it then writes the bits to counts[1], zero to the other counts and nothing else (the kernels raise counts[1] instead,
+ *   read nothing through the bad value and leave overlap, n_vis and the other counts zero); LOFTR_ERR_UNSUPPORTED for V or T >= 2^31,
+ *   n m > 2^31 entries, more than 65535 target tiles; LOFTR_ERR_WORKSPACE for a short workspace.
+ * Out of scope: occlusion, visibility from the dense cells of the atlas, descriptor retrieval, a sparse output.  PARITY UNPINNED against
+ *   hloc. */
+int loftr_view_overlap_host(const long* vis_offsets, const int* vis_point, long V, const float* xyz, const uint8_t* point_ok, long T,
+                            const double* K_src, const double* T_src, const uint8_t* src_ok, int n, const double* K_tgt,
+                            const double* T_tgt, const uint8_t* tgt_ok, const double* tgt_hw, int m, double border_px, double cos_min,
+                            double max_scale2, int* overlap, int* n_vis, long* counts);
+/* The kernels: three memsets (overlap, n_vis, the counts) and three launches on the stream (0 the checks, 1 the view tables and n_vis
+ * -- a wave per source, a thread per target --, 2 the counts -- a block per source and tile of LOFTR_OVERLAP_TILE targets: a lane owns
+ * one target, the source's points are staged through LDS).  No host synchronisation unless stage_ms is given: NULL, or
+ * LOFTR_OVERLAP_STAGES host floats that receive the GPU time of each launch (the call then waits for the stream).
+ * Workspace: loftr_view_overlap_workspace_bytes(n, m): 224 bytes per source and per target; 0 for sizes out of range. */
+#define LOFTR_OVERLAP_STAGES 3
+#define LOFTR_OVERLAP_TILE 256
+size_t loftr_view_overlap_workspace_bytes(int n, int m);
+int loftr_view_overlap(const long* vis_offsets, const int* vis_point, long V, const float* xyz, const uint8_t* point_ok, long T,
+                       const double* K_src, const double* T_src, const uint8_t* src_ok, int n, const double* K_tgt, const double* T_tgt,
+                       const uint8_t* tgt_ok, const double* tgt_hw, int m, double border_px, double cos_min, double max_scale2, int* overlap,
+                       int* n_vis, long* counts, void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
 /* ---- input wire format (the step before the path; src/utils/dataset.py:78-89,111-118,149, megadepth.py:116-121) ----
  * From resized uint8 grayscale images to the tensors LoFTR.forward consumes: zero padding to [PH,PW] at the
  * bottom / right (pad_bottom_right), `float / 255`, the padding mask and its coarse version

@@ -193,6 +193,10 @@ SIGNATURES = {
     "loftr_estimate_similarity_batched": (_i, [_p, _p, _p, _l, _i, _i, C.c_double, _f, C.c_uint, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "loftr_transform_model_host": (_i, [_p, _l, _p, _p, _i, _p, _p, _p, _p, _p]),
     "loftr_transform_model": (_i, [_p, _l, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "loftr_view_overlap_host": (_i, [_p, _p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _p, _p, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p]),
+    "loftr_view_overlap_workspace_bytes": (_sz, [_i, _i]),
+    "loftr_view_overlap": (_i, [_p, _p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _p, _p, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p,
+                                _p, _sz, _p, _p]),
     "loftr_conv_prepare": (_i, [_p, C.POINTER(_l), _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _sz, _p]),
     "loftr_conv_bn_act_prepared": (_i, [_p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "loftr_conv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

@@ -104,6 +104,12 @@ class LocalizationModel:
         kp_point[(sfm.kp_offsets[pts.image] + pts.keypoint)[sel]] = track[sel].to(torch.int32)   # a keypoint belongs to one track
         return cls(sfm.kp_offsets, sfm.keypoints, kp_point, pts.xyz, sfm.image_hw, sfm.cell_px)
 
+    def propose_for_poses(self, K_db, T_db, K_query, T_query_prior, query_hw, top_k=10, **kw):
+        """The database images to match each query against, chosen from a pose prior of the query by projected-point overlap
+        (``proposals.propose_for_poses``) -> ``(ids [Q,top_k] i64, score [Q,top_k] i64)``, padded with -1."""
+        from .proposals import propose_for_poses
+        return propose_for_poses(self, K_db, T_db, K_query, T_query_prior, query_hw, top_k=top_k, **kw)
+
 
 class QueryPoses:
     """What ``QueryLocalizer.solve`` returns (tensors on the model's device).

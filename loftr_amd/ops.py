@@ -1163,6 +1163,76 @@ def transform_model(xyz, T_cam_from_world, posed, s, R, t, out_xyz=None, out_T=N
     return out_xyz, out_T
 
 
+# ---- view overlap (csrc/overlap.hip, csrc/overlap_gpu.hip) --------------------------------------------------------------
+OVERLAP_COUNTS = 8
+OVERLAP_NAMES = ("n_visible", "error_bits", "n_sources", "n_targets", "n_nonzero")      # counts[0..4]; the rest are 0
+OVERLAP_STAGES = ("check", "tables", "count")
+OVERLAP_ERRORS = ((1, "vis_point must lie in [0, number of points)"),
+                  (2, "vis_offsets must start at 0, end at the number of entries and ascend"))
+_OVL_ARGS = (("vis_offsets", torch.int64, (None,)), ("vis_point", torch.int32, (None,)), ("xyz", torch.float32, (None, 3)),
+             ("point_ok", torch.uint8, (None,)), ("K_src", torch.float64, (None, 9)), ("T_src", torch.float64, (None, 16)),
+             ("src_ok", torch.uint8, (None,)), ("K_tgt", torch.float64, (None, 9)), ("T_tgt", torch.float64, (None, 16)),
+             ("tgt_ok", torch.uint8, (None,)), ("tgt_hw", torch.float64, (None, 2)))
+
+
+def view_overlap(vis_offsets, vis_point, xyz, point_ok, K_src, T_src, src_ok, K_tgt, T_tgt, tgt_ok, tgt_hw, border_px, cos_min, max_scale2,
+                 timings=None):
+    """loftr_view_overlap_host on CPU tensors, loftr_view_overlap (csrc/overlap_gpu.hip) on GPU tensors: the same integers; mixed devices
+    are an error and there is no fallback either way.  vis_offsets [n+1] i64, vis_point [V] i32, xyz [T,3] f32, point_ok [T] u8, K_src
+    [n,9] / T_src [n,16] f64, src_ok [n] u8, K_tgt [m,9] / T_tgt [m,16] f64, tgt_ok [m] u8, tgt_hw [m,2] f64 (H, W); border_px >= 0,
+    cos_min in [-1, 1], max_scale2 >= 1 (inf: no scale test).
+    -> dict of tensors on the inputs' device: overlap [n,m] i32, n_vis [n] i32, counts [8] i64 (OVERLAP_NAMES).  Nothing is read back
+    here: a bad list leaves its bits (OVERLAP_ERRORS) in counts[1] and every other output zero, on both sides.  timings: a list that
+    receives (stage, ms) pairs of the GPU stages (the call then waits for the stream)."""
+    what = "view_overlap"
+    arrays = (vis_offsets, vis_point, xyz, point_ok, K_src, T_src, src_ok, K_tgt, T_tgt, tgt_ok, tgt_hw)
+    for (name, dt, shape), a in zip(_OVL_ARGS, arrays):
+        if not isinstance(a, torch.Tensor):
+            raise _lib.LoftrHipError(f"{what}: {name} must be a tensor")
+    gpu = [a.is_cuda for a in arrays]
+    if any(gpu) and not all(gpu):
+        raise _lib.LoftrHipError(f"{what}: GPU and CPU arguments mixed (" + ", ".join(f"{s[0]}: {'GPU' if g else 'CPU'}" for s, g in zip(_OVL_ARGS, gpu))
+                                 + "); there is no silent fallback: move them to one device")
+    if not all(gpu) and any(a.device.type != "cpu" for a in arrays):
+        raise _lib.LoftrHipError(f"{what}: tensors must live on a GPU (the kernels) or on the CPU (the host routine)")
+    for (name, dt, shape), a in zip(_OVL_ARGS, arrays):
+        if a.dtype != dt or a.dim() != len(shape) or any(s is not None and a.shape[d] != s for d, s in enumerate(shape)):
+            raise _lib.LoftrHipError(f"{what}: {name} must be {dt} of shape {list(shape)}, got {a.dtype} {tuple(a.shape)}")
+    n, m, T, V = vis_offsets.shape[0] - 1, K_tgt.shape[0], xyz.shape[0], vis_point.shape[0]
+    if n < 0 or any(a.shape[0] != n for a in (K_src, T_src, src_ok)) or any(a.shape[0] != m for a in (T_tgt, tgt_ok, tgt_hw)) or \
+            point_ok.shape[0] != T:
+        raise _lib.LoftrHipError(f"{what}: expected vis_offsets [n+1], K_src / T_src / src_ok [n], K_tgt / T_tgt / tgt_ok / tgt_hw [m] and xyz / "
+                                 f"point_ok [T], got {[tuple(a.shape) for a in arrays]}")
+    border_px, cos_min, max_scale2 = float(border_px), float(cos_min), float(max_scale2)
+    if not (0.0 <= border_px < float("inf")) or not (-1.0 <= cos_min <= 1.0) or not (max_scale2 >= 1.0):
+        raise ValueError(f"{what}: border_px must be finite and >= 0, cos_min in [-1, 1] and max_scale2 >= 1, got {border_px}, {cos_min}, {max_scale2}")
+    if n * m > 2 ** 31 or V >= 2 ** 31 or T >= 2 ** 31:
+        raise ValueError(f"{what}: {n} x {m} pairs, {V} entries or {T} points are beyond the supported 2^31 (there is no sparse output)")
+    if n == 0 and V != 0:
+        raise ValueError(f"{what}: {V} entries without a source image")
+    arrays = [a.contiguous() for a in arrays]                                            # (held until the call has returned)
+    dev = arrays[0].device
+    out = {"overlap": torch.zeros((n, m), dtype=torch.int32, device=dev), "n_vis": torch.zeros(n, dtype=torch.int32, device=dev),
+           "counts": torch.zeros(OVERLAP_COUNTS, dtype=torch.int64, device=dev)}
+    p = [_ptr(a) for a in arrays]
+    args = (p[0], p[1], V, p[2], p[3], T, p[4], p[5], p[6], n, p[7], p[8], p[9], p[10], m, border_px, cos_min, max_scale2,
+            _ptr(out["overlap"]), _ptr(out["n_vis"]), _ptr(out["counts"]))
+    lib = _lib.load()
+    if all(gpu):
+        if any(a.device != dev for a in arrays):
+            raise _lib.LoftrHipError(f"{what}: tensors on different devices ({sorted({str(a.device) for a in arrays})})")
+        ms = _StageMs(timings, OVERLAP_STAGES)
+        with torch.cuda.device(dev):                                                     # stream, workspace and pointers belong to the tensors' device
+            buf = torch.empty(max(1, lib.loftr_view_overlap_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
+            check(lib.loftr_view_overlap(*args, _ptr(buf), buf.numel(), ms.arg, _stream()), "loftr_view_overlap")
+        ms.report()
+    else:
+        status = lib.loftr_view_overlap_host(*args)
+        if not (status == -1 and int(out["counts"][1]) != 0):                            # a bad list is reported through counts[1], as on the GPU
+            check(status, "loftr_view_overlap_host")
+    return out
+
+
 # ---- the two sides of a routine pair -------------------------------------------------------------------------------------------------
 # The SfM routines below come in pairs: loftr_<name>_host on numpy arrays DEFINES the result, loftr_<name> reproduces it on GPU tensors.
 # A pair shares one body, written against a backend that supplies what differs: how an array that belongs to the other side is refused,

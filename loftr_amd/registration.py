@@ -87,6 +87,13 @@ class Reconstruction:
         from .alignment import align
         return align(self, ref_centres, known, thresh, with_scale, apply, conf, seed, refine)
 
+    def propose_pairs(self, sfm, top_k=5, min_shared=30, **kw):
+        """The image pairs of ``sfm`` (the ``SfmResult`` this reconstruction came from) that were never matched but overlap, by
+        projected-point overlap of the posed images (``proposals.propose_pairs``) -> ``(pairs [P,2] i64 with a < b, score
+        [P] i64)``: what a second matching pass, and a loop closure of a sequentially matched set, start from."""
+        from .proposals import propose_pairs
+        return propose_pairs(self, sfm, top_k=top_k, min_shared=min_shared, **kw)
+
 
 def register_images(offsets, obs_image, obs_xy, xyz, status, K, T_cam_from_world, posed, min_corr=15, min_inliers=15, thresh_px=4.0,
                     conf=0.999, seed=0, timings=None):
