@@ -66,7 +66,9 @@ typedef enum {
  *     refinement loftr_bundle_adjust_focal_host, loftr_bundle_adjust_focal_workspace_bytes, loftr_bundle_adjust_focal; with one
  *     focal step per group of images loftr_bundle_adjust_shared_host, loftr_bundle_adjust_shared_workspace_bytes,
  *     loftr_bundle_adjust_shared; with position priors on the camera centres loftr_bundle_adjust_prior_host,
- *     loftr_bundle_adjust_prior_workspace_bytes, loftr_bundle_adjust_prior), the correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
+ *     loftr_bundle_adjust_prior_workspace_bytes, loftr_bundle_adjust_prior; with one radial coefficient per group of images
+ *     loftr_bundle_adjust_radial_host, loftr_bundle_adjust_radial_workspace_bytes, loftr_bundle_adjust_radial, and the pixels without
+ *     it loftr_undistort_points_host, loftr_undistort_points, loftr_distort_points_host), the correspondence table of the images without a pose (loftr_register_corr_host, loftr_register_corr_workspace_bytes,
  *     loftr_register_corr), track completion (loftr_complete_tracks_host, loftr_complete_tracks_workspace_bytes,
  *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks),
  *     3D similarity RANSAC and moving a model (loftr_estimate_similarity, loftr_similarity_minimal,
@@ -946,7 +948,7 @@ int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const
  *   counts[13] = the number of refining cameras.
  * Status: as above; LOFTR_ERR_BAD_ARG also for min_focal_obs < 1, bounds that are not finite or do not straddle 1, and null
  *   refine_focal / K_out / cam_focal with n_images > 0.  Workspace: loftr_bundle_adjust_focal_workspace_bytes (about 1100 bytes per image).
- * Out of scope: principal point and distortion, focal refinement of a fixed-pose camera (the grouped rule below has it), focal priors.
+ * Out of scope: principal point, focal refinement of a fixed-pose camera (the grouped rule below has it), focal priors.
  *   PARITY UNPINNED against Ceres / COLMAP. */
 int loftr_bundle_adjust_focal_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
                                    const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
@@ -997,7 +999,8 @@ int loftr_bundle_adjust_focal(const long* offsets, long T, const int* obs_image,
  *   (the host routine returns LOFTR_ERR_BAD_ARG, the kernels raise the bit, read nothing through the bad value and run no trial).
  * Status: §18.1's; LOFTR_ERR_BAD_ARG also for G outside [1, n] (0 with n = 0) and null group arrays.  Workspace:
  *   loftr_bundle_adjust_shared_workspace_bytes: §18.1's plus 76 bytes per image (sized by n_images, whatever G is).
- * Out of scope: groups that share a value rather than a step, principal point, distortion, focal priors.  PARITY UNPINNED. */
+ * Out of scope: groups that share a value rather than a step, principal point, focal priors (one radial coefficient per group: the
+ *   rule after the next).  PARITY UNPINNED. */
 int loftr_bundle_adjust_shared_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
                                     const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
                                     const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
@@ -1061,6 +1064,80 @@ int loftr_bundle_adjust_prior(const long* offsets, long T, const int* obs_image,
                               uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal,
                               uint8_t* group_focal, uint8_t* cam_prior, long* counts, void* ws, size_t ws_bytes, float* class_ms,
                               long* class_launches, void* stream);
+
+/* ---- bundle adjustment with one radial coefficient per GROUP of images ----------------------------------------------------
+ * The grouped rule (§18.2) with the camera model x_d = x (1 + k r^2), y_d = y (1 + k r^2) on normalised coordinates and ONE additive
+ * step dk_g of k per group next to its relative focal step; everything not named here is §18.2's: fp64 without contraction, + - * /
+ * sqrt only, the active set decided once, the Huber loss, the orders of the sums, the flags, the error bits.
+ * loftr_bundle_adjust_radial_host DEFINES the result, loftr_bundle_adjust_radial reproduces it bit for bit.  Only this rule reads a k.
+ *   Input added to §18.2's: radial_in [n] f64 (the start values), refine_radial [n] u8, radial_lo <= radial_hi (finite).
+ *   Projection, in this order: a = Y0 / Y2, b = Y1 / Y2, r2 = a a + b b, m = 1 + k r2, xd = a m, yd = b m,
+ *      r = (((fx xd + skew yd) + cx) - u, (fy yd + cy) - v).  Evaluate, the track linearisation and the track half read it.
+ *   Jacobians.  jaa = m + 2k (a a), jab = 2k (a b), jbb = m + 2k (b b) (d(xd, yd)/d(a, b) = m I + 2k (a, b)(a, b)^T);
+ *      ua = fx jaa + skew jab, ub = fx jab + skew jbb, va = fy jab, vb = fy jbb; du = sw (ua / Y2, ub / Y2, -((ua a + ub b) / Y2)),
+ *      dv likewise from va, vb.  The pose columns of A and B are rule 3's products of du, dv (the v row has no zero entry here).
+ *      Column 7 (focal) = sw (fx xd + skew yd, fy yd) with cam_focal, column 8 (radial) = sw (fx (a r2) + skew (b r2), fy (b r2))
+ *      with cam_radial, +0 otherwise.  U has 36 entries, g_c 8.
+ *   Who carries.  A valid image whose radial_in is not finite is not valid.  cam_focal and group_focal are §18.2's.  Image i is a radial
+ *      candidate iff it carries (§18.2) and refine_radial[i] != 0; group g REFINES ITS RADIAL iff it refines its focal and its candidates
+ *      together have at least min_focal_obs active observations (group_radial [G]); cam_radial[i] = i is a candidate and its group does.
+ *   Group block.  2 unknowns per refining group, focal first.  D_g = (U77, U78; U78, U88) summed over the members with cam_focal by
+ *      osum64 over the member list.  Each diagonal is damped once, at the group: d (1 + lambda), or lambda when d is 0; a group that
+ *      does not refine its radial has U78 = U88 = +0 and right-hand side +0 there.  Preconditioner: the 2 x 2 L D L^T of the damped
+ *      block in rule 6's fixed order; a non-positive pivot rejects the step.  E^T: the seventh entries of the members with cam_focal
+ *      and the eighth of those with cam_radial, osum64 each; the rows U_k7, U_k8 (k < 6) of a member enter its seventh and eighth
+ *      entry as U_k7 does in §18.2.  Group entry: Sp_0 = (d_00 p_0 + d_01 p_1) + E^T_0, Sp_1 = (d_01 p_0 + d_11 p_1) + E^T_1.
+ *   Dot products.  The cameras' osum (6 terms each), then the groups' (2 terms each, focal first), added in that order.
+ *   Trial.  a_g starts at +0; a trial has a_g' = a_g + dk_g and every member with cam_radial k' = radial_in + a_g' (one rounding on the
+ *      input whatever the number of accepted trials).  A k' outside [radial_lo, radial_hi] (a NaN fails) rejects the trial, like a
+ *      focal outside its bounds.
+ *   Output added: radial [n] f64 (the input's bits for an image without cam_radial), cam_radial [n] u8, group_radial [G] u8;
+ *      counts[15] = the images with cam_radial.
+ * Status: §18.2's; LOFTR_ERR_BAD_ARG also for null radial arrays with n_images > 0 and bounds that are not finite or not ordered.
+ * Workspace: loftr_bundle_adjust_radial_workspace_bytes (sized by n_images, whatever G is).
+ * Out of scope: per-image 8 x 8 blocks, priors together with radial, refining k with a trusted focal, k2, tangential and fisheye
+ *   terms, principal point.  PARITY UNPINNED. */
+int loftr_bundle_adjust_radial_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                                    const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                    const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                    const int* cam_group, const long* group_offsets, const int* group_cams, int G, const double* radial_in,
+                                    const uint8_t* refine_radial, double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol,
+                                    int min_focal_obs, double focal_lo, double focal_hi, double radial_lo, double radial_hi, double* T_out,
+                                    float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out,
+                                    uint8_t* cam_focal, uint8_t* group_focal, double* radial_out, uint8_t* cam_radial,
+                                    uint8_t* group_radial, long* counts);
+size_t loftr_bundle_adjust_radial_workspace_bytes(long T, long N, int n_images);
+int loftr_bundle_adjust_radial(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
+                               const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                               const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs, const int* cam_group,
+                               const long* group_offsets, const int* group_cams, int G, const double* radial_in,
+                               const uint8_t* refine_radial, double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol,
+                               int min_focal_obs, double focal_lo, double focal_hi, double radial_lo, double radial_hi, double* T_out,
+                               float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active, double* K_out,
+                               uint8_t* cam_focal, uint8_t* group_focal, double* radial_out, uint8_t* cam_radial, uint8_t* group_radial,
+                               long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream);
+
+/* ---- pixels without the radial coefficient (csrc/radial_core.h holds the arithmetic) ------------------------------------------
+ * Every stage but the adjustment above reads pinhole pixels; this gives them.  xy [M,2] f32, image [M] i32, K [n,9] f64, radial [n] f64
+ * -> xy_out [M,2] f32, ok [M] u8, counts [8] i64.  One fp64 text for both sides, a point depends on its own inputs only.
+ * loftr_undistort_points_host DEFINES the result, loftr_undistort_points (a thread per point) reproduces it bit for bit.
+ *   1. y_d = (v - cy) / fy, x_d = ((u - cx) - skew y_d) / fx, r_d = sqrt(x_d^2 + y_d^2).
+ *   2. r = r_d, then 12 times r = r - (r (1 + k (r r)) - r_d) / (1 + 3k (r r)): a FIXED count, no data-dependent exit.
+ *   3. ok iff fx, skew, cx, fy, cy, k, u, v, r_d and r are finite, fx and fy are not 0, 1 + 3k (r r) > 0 at the result and
+ *      |r (1 + k (r r)) - r_d| <= 1e-9 (1 + r_d).
+ *   4. m = 1 + k (r r); the output is ((fx (x_d / m) + skew (y_d / m)) + cx, fy (y_d / m) + cy) rounded to f32, and must be finite;
+ *      a point that is not ok is (NaN, NaN) with ok = 0 (the triangulation rejects pixels that are not finite).
+ *   k = 0 is ok and the point is recomputed through K: NOT promised to be the input's bits.
+ * counts: 0 = points ok, 1 = error bits, 2 = points not ok, 3..7 = 0.  Error bit 1: an image outside [0, n_images); the host routine
+ *   returns LOFTR_ERR_BAD_ARG, the kernels raise the bit, and neither writes anything beyond the counts.
+ * loftr_distort_points_host is the other direction from the same text (m = 1 + k (x x + y y), (x m, y m) through K), for the tests
+ *   and the tools.  LOFTR_ERR_BAD_ARG: negative sizes, null arrays that would be read or written. */
+int loftr_undistort_points_host(const float* xy, const int* image, long M, const double* K, const double* radial, int n_images,
+                                float* xy_out, uint8_t* ok, long* counts);
+int loftr_undistort_points(const float* xy, const int* image, long M, const double* K, const double* radial, int n_images, float* xy_out,
+                           uint8_t* ok, long* counts, void* stream);
+int loftr_distort_points_host(const float* xy, const int* image, long M, const double* K, const double* radial, int n_images,
+                              float* xy_out, uint8_t* ok, long* counts);
 
 /* ---- correspondence table of the images without a pose (csrc/register_core.h holds every per-item step) -------------------
  * The 2D-3D correspondences that the tracks give the images that have no pose yet, gathered per image in a defined order: the input of

@@ -9,6 +9,7 @@ from .pairs import FeatureBank                                     # noqa: F401
 from .atlas import KeypointAtlas, SfmResult                       # noqa: F401
 from .triangulation import Points3D, triangulate_tracks           # noqa: F401
 from .bundle import BundleResult, bundle_adjust                   # noqa: F401
+from .radial import undistort_points, distort_points              # noqa: F401
 from .registration import Reconstruction, Registration, reconstruct_tracks, register_images    # noqa: F401
 from .completion import Completion, complete_tracks                # noqa: F401
 from .merging import Merge, merge_tracks                            # noqa: F401

@@ -175,6 +175,16 @@ SIGNATURES = {
     "loftr_bundle_adjust_prior": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, C.c_double, _i, _i,
                                        C.c_double, C.c_double, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p,
                                        _p]),
+    "loftr_bundle_adjust_radial_host": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, C.c_double, _i, _i,
+                                             C.c_double, C.c_double, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p,
+                                             _p, _p, _p, _p, _p, _p]),
+    "loftr_bundle_adjust_radial_workspace_bytes": (_sz, [_l, _l, _i]),
+    "loftr_bundle_adjust_radial": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, C.c_double, _i, _i,
+                                        C.c_double, C.c_double, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p,
+                                        _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
+    "loftr_undistort_points_host": (_i, [_p, _p, _l, _p, _p, _i, _p, _p, _p]),
+    "loftr_undistort_points": (_i, [_p, _p, _l, _p, _p, _i, _p, _p, _p, _p]),
+    "loftr_distort_points_host": (_i, [_p, _p, _l, _p, _p, _i, _p, _p, _p]),
     "loftr_register_corr_host": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "loftr_register_corr_workspace_bytes": (_sz, [_l, _l, _i]),
     "loftr_register_corr": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),

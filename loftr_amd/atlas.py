@@ -60,6 +60,27 @@ class SfmResult:
         for k in self.FIELDS:
             setattr(self, k, tensors[k])
         self.image_hw = self.cell_px = None                            # set by KeypointAtlas.finalize
+        self.is_undistorted = False                                     # True for the view that undistorted() returns
+
+    def undistorted(self, K, radial):
+        """The view of this result whose ``keypoints`` are the pinhole pixels of the stored ones under one radial coefficient per image
+        (radial.undistort_points): ``K [n_images,3,3]``, ``radial [n_images]``.  Every other tensor is shared, and
+        ``is_undistorted`` is True.  ``triangulate``, ``register``, ``adjust`` and ``pairwise_poses`` read it as they read any result (a
+        keypoint that could not be undistorted is NaN and is left out by each of them); ``complete`` and ``merge`` raise ValueError on
+        it: their cell lookup is in stored-pixel space.  A ``LocalizationModel`` is built from the ORIGINAL result with the points of
+        this view: its lookups are by keypoint index, which the view does not change."""
+        from .radial import undistort_points
+        dev = self.keypoints.device
+        n = self.kp_offsets.numel() - 1
+        K, radial = (torch.as_tensor(x).detach().to(dev, torch.float64) for x in (K, radial))
+        if tuple(K.shape) != (n, 3, 3) or tuple(radial.shape) != (n,):
+            raise ValueError(f"SfmResult.undistorted: expected K [{n},3,3] and radial [{n}], got {tuple(K.shape)}, {tuple(radial.shape)}")
+        xy, _ = undistort_points(self.keypoints, self.keypoint_image().to(torch.int32), K, radial)
+        fields = {k: getattr(self, k) for k in self.FIELDS}
+        fields.update(keypoints=xy)
+        view = SfmResult(dict(self.stats), **fields)
+        view.image_hw, view.cell_px, view.is_undistorted = self.image_hw, self.cell_px, True
+        return view
 
     def keypoint_image(self):
         """Image of every keypoint [K] i64."""
@@ -130,13 +151,19 @@ class SfmResult:
         m = self.matches.to(torch.int64)
         k0 = self.keypoints[self.kp_offsets[ims[row, 0]] + m[:, 0]].contiguous()
         k1 = self.keypoints[self.kp_offsets[ims[row, 1]] + m[:, 1]].contiguous()
+        row_offsets = self.row_offsets
+        if self.is_undistorted:                                          # a keypoint that could not be undistorted is NaN: its matches are left out
+            keep = torch.isfinite(k0).all(1) & torch.isfinite(k1).all(1)
+            k0, k1, row = k0[keep].contiguous(), k1[keep].contiguous(), row[keep]
+            row_offsets = torch.zeros_like(self.row_offsets)
+            row_offsets[1:] = torch.cumsum(torch.bincount(row, minlength=n_rows), 0)
         K0, K1 = K32[ims[:, 0]].contiguous(), K32[ims[:, 1]].contiguous()
         if dev.type == "cuda":
             R, t, _, ninl = ops.estimate_poses(k0, k1, row, K0, K1, thresh_px, conf, seed)
             return R, t, ninl
         from .evaluation import estimate_pose_native
         R, t, ninl = torch.zeros(n_rows, 3, 3), torch.zeros(n_rows, 3), torch.full((n_rows,), -1, dtype=torch.int64)
-        off = self.row_offsets.tolist()
+        off = row_offsets.tolist()
         for r in range(n_rows):
             sl = slice(off[r], off[r + 1])
             est = estimate_pose_native(k0[sl].numpy(), k1[sl].numpy(), K0[r].numpy(), K1[r].numpy(), thresh_px, conf, seed)
@@ -152,6 +179,9 @@ class SfmResult:
         of the ``init_candidates`` rows with the most five-point inliers (ties to the earliest row), the one whose two images alone
         triangulate the most points (ties to the earliest row); the selection is integer and order-defined.  ``thresh_px`` is also the
         triangulation's and the registration's threshold; the other keyword arguments are reconstruct_tracks'.
+        ``radial`` ([n_images], DESIGN §18.4): the coefficients of the lenses, known or a start for ``ba={'refine_radial': True, ...}``;
+        the five-point poses and the choice of the initial pair then read the undistorted keypoints (``undistorted``), the loop is
+        reconstruct_tracks' with that ``radial``, and ``complete`` / ``merge`` are refused (their cell lookup is in stored-pixel space).
         ``complete=True``: after the loop, one ``complete`` over the posed images with the final intrinsics, then triangulate -> adjust
         (the same fixed images and ``ba``) -> triangulate on the relabelled atlas; the Reconstruction then carries it as ``.sfm`` and the
         counts as ``stats['completion']``.  ``merge=True``: after the loop (and after the completion and one triangulation
@@ -164,10 +194,14 @@ class SfmResult:
         K = torch.as_tensor(K).detach().to(dev, torch.float64)
         if tuple(K.shape) != (n, 3, 3):
             raise ValueError(f"SfmResult.reconstruct: expected K [{n},3,3], got {tuple(K.shape)}")
-        R, t, ninl = self.pairwise_poses(K, thresh_px, pose_conf, kwargs.get("seed", 0))
+        lens = kwargs.get("radial") is not None or (kwargs.get("ba") or {}).get("refine_radial") is not None
+        if lens and (complete or merge):
+            raise ValueError("SfmResult.reconstruct: complete / merge under distortion are not modelled (their cell lookup is in stored-pixel space)")
+        view = self.undistorted(K, kwargs["radial"]) if kwargs.get("radial") is not None else self
+        R, t, ninl = view.pairwise_poses(K, thresh_px, pose_conf, kwargs.get("seed", 0))
         ninl_host, rows = ninl.cpu().tolist(), self.row_images.cpu().tolist()
         offsets, image, local = self.tracks(consistent_only)
-        obs_image, xy = image.to(torch.int32), self.keypoints[self.kp_offsets[image] + local]
+        obs_image, xy = image.to(torch.int32), view.keypoints[self.kp_offsets[image] + local]
         if init_row is None:
             order = sorted((r for r in range(len(rows)) if ninl_host[r] >= 0), key=lambda r: (-ninl_host[r], r))[:max(int(init_candidates), 0)]
             if not order:
@@ -188,6 +222,7 @@ class SfmResult:
             raise ValueError(f"SfmResult.reconstruct: row {init_row} has no five-point model (rows: {len(rows)}, inliers: "
                              f"{ninl_host[init_row] if 0 <= init_row < len(rows) else None})")
         a, b = rows[init_row]
+        xy = self.keypoints[self.kp_offsets[image] + local]              # the loop reads the stored pixels and undistorts them itself
         rec = reconstruct_tracks(offsets, obs_image, xy, K, (a, b, R[init_row], t[init_row]), thresh_px=thresh_px, **kwargs)
         rec.points.offsets, rec.points.image, rec.points.keypoint = offsets, image, local
         rec.stats["init_row"], rec.stats["pair_inliers"] = init_row, ninl_host
@@ -255,6 +290,8 @@ class SfmResult:
         unchanged, two merged tracks share no image), and the ``Merge`` whose rows are the tracks of ``pts``.  This result is left
         untouched.  The points are not re-estimated: triangulate ``sfm2`` next.  Calling again after that merges further."""
         from .merging import merge_tracks
+        if self.is_undistorted:
+            raise ValueError("SfmResult.merge: this is an undistorted view; the cell lookup is in stored-pixel space (merge the original result)")
         if pts.offsets is None:
             raise ValueError("SfmResult.merge: this Points3D carries no tracks (use SfmResult.triangulate)")
         if self.image_hw is None or self.cell_px is None:
@@ -281,6 +318,8 @@ class SfmResult:
         Meant for AFTER the reconstruction loop: only a keypoint that is loose or held by a track WITHOUT a point can be claimed, and
         a track that has no point YET, because its images have no pose yet, would yield its keypoints as well."""
         from .completion import complete_tracks
+        if self.is_undistorted:
+            raise ValueError("SfmResult.complete: this is an undistorted view; the cell lookup is in stored-pixel space (complete the original result)")
         if pts.offsets is None:
             raise ValueError("SfmResult.complete: this Points3D carries no tracks (use SfmResult.triangulate)")
         if self.image_hw is None or self.cell_px is None:
@@ -302,7 +341,9 @@ class SfmResult:
         arguments are bundle_adjust's; the intended loop is triangulate -> adjust -> triangulate(K, res.T_cam_from_world).  With
         ``refine_focal`` (True or an [n] mask; DESIGN §18.1) the focal lengths are refined as well and the loop goes on with ``res.K``;
         with ``camera_ids`` ([n] integers; DESIGN §18.2) the images of one camera share that step; with ``position_prior`` ([n,3];
-        ``prior_sigma``, ``prior_mask``) the camera centres are held near measured positions."""
+        ``prior_sigma``, ``prior_mask``) the camera centres are held near measured positions; with ``refine_radial``
+        (``radial``, ``radial_bounds``; on the ORIGINAL result, whose keypoints are the stored pixels) every camera
+        refines one radial coefficient as well."""
         from .bundle import bundle_adjust
         if pts.offsets is None:
             raise ValueError("SfmResult.adjust: this Points3D carries no tracks (use SfmResult.triangulate)")
@@ -315,6 +356,9 @@ class SfmResult:
             kwargs["refine_focal"] = torch.as_tensor(kwargs["refine_focal"]).to(dev)
         if kwargs.get("camera_ids") is not None:                         # (images with equal ids share one focal step)
             kwargs["camera_ids"] = torch.as_tensor(kwargs["camera_ids"]).to(dev)
+        for k in ("refine_radial", "radial"):                            # (one radial coefficient per camera)
+            if kwargs.get(k) is not None and kwargs[k] is not True:
+                kwargs[k] = torch.as_tensor(kwargs[k]).to(dev)
         for k in ("position_prior", "prior_sigma", "prior_mask"):        # (position priors on the camera centres)
             if kwargs.get(k) is not None and not isinstance(kwargs[k], (int, float)):
                 kwargs[k] = torch.as_tensor(kwargs[k]).to(dev)

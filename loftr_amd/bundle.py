@@ -35,6 +35,13 @@ modes (``loftr_bundle_adjust_prior_host`` and its kernels).  The 
     res = sfm.adjust(pts2, K, rec2.T_cam_from_world, fixed=none, position_prior=gps, prior_mask=al.inliers, prior_sigma=2.0)
 
 (``rec.align(gps, refine=dict(sfm=sfm, sigma=2.0))`` runs exactly that sequence and triangulates again.)
+
+Where the lenses distort (internet photos, phones, action cameras), ``refine_radial`` adds one radial coefficient ``k`` per camera --
+``x_d = x (1 + k r^2)`` on normalised coordinates -- next to its focal step (``loftr_bundle_adjust_radial_host`` and its
+kernels).  The adjustment reads the stored (distorted) pixels; every other stage reads pinhole pixels, which ``undistort_points`` gives::
+
+    res = sfm.adjust(pts, K, T_cam_from_world, fixed=known, refine_focal=True, refine_radial=True, camera_ids=ids)
+    xy, ok = loftr_amd.undistort_points(obs_xy, obs_image, res.K, res.radial)            # what triangulation and registration read
 """
 import numpy as np
 import torch
@@ -45,6 +52,7 @@ _OUT = ("T_cam_from_world", "xyz", "obs_active", "cam_free", "point_active")
 _OUT_FOCAL = ("K", "cam_focal")
 _OUT_SHARED = ("cam_group", "group_focal")
 _OUT_PRIOR = ("cam_prior",)
+_OUT_RADIAL = ("radial", "cam_radial", "group_radial")
 _ARGS = ("offsets", "obs_image", "obs_xy", "obs_mask", "xyz", "K", "T_cam_from_world")
 
 
@@ -62,7 +70,9 @@ class BundleResult:
     ``cam_group [n] i32`` (the dense group of each image, groups ordered by their smallest member), ``group_focal [G] bool`` (the group
     refined) and ``stats['n_focal_groups']``.  A call with ``position_prior`` adds ``cam_prior [n] bool`` (the camera had a prior) and
     ``stats['n_prior_cameras']``, ``prior_cost_before`` / ``prior_cost_after`` (the priors' part of the cost, in sigma^2) and
-    ``prior_rms_before`` / ``prior_rms_after`` (root mean squared distance of the centres from their priors, in world units)."""
+    ``prior_rms_before`` / ``prior_rms_after`` (root mean squared distance of the centres from their priors, in world units).  A call
+    with ``refine_radial`` adds ``radial [n] f64`` (the input's bits for an image that does not refine it), ``cam_radial [n] bool``,
+    ``group_radial [G] bool`` and ``stats['n_radial_cameras']``."""
 
     FIELDS = _OUT
 
@@ -70,7 +80,7 @@ class BundleResult:
         self.stats = stats
         if "K" in tensors or "cam_prior" in tensors:                     # a call with refine_focal: K and cam_focal as well; with priors
             self.FIELDS = _OUT + (_OUT_FOCAL if "K" in tensors else ()) + (_OUT_SHARED if "cam_group" in tensors else ()) + \
-                (_OUT_PRIOR if "cam_prior" in tensors else ())
+                (_OUT_PRIOR if "cam_prior" in tensors else ()) + (_OUT_RADIAL if "radial" in tensors else ())
         for k in self.FIELDS:
             setattr(self, k, tensors[k])
         for k in ("cost_before", "cost_after", "rms_px_before", "rms_px_after", "n_iters", "n_accepted", "n_pcg", "status"):
@@ -85,7 +95,7 @@ class BundleResult:
 
 def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed=None, huber_px=0.0, max_iters=30, pcg_iters=30,
                   pcg_tol=1e-2, ftol=1e-9, timings=None, refine_focal=None, min_focal_obs=20, focal_bounds=(0.5, 2.0), camera_ids=None,
-                  position_prior=None, prior_sigma=1.0, prior_mask=None):
+                  position_prior=None, prior_sigma=1.0, prior_mask=None, refine_radial=None, radial=None, radial_bounds=(-1.0, 1.0)):
     """Refine poses and points over the reprojection error -> ``BundleResult``.
 
     ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``; ``obs_mask [N]`` (bool or integers: which
@@ -104,7 +114,7 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     those images refine one relative focal step each -- fx, skew and fy scale together, cx and cy stay -- next to their pose.  An image
     refines only if it is free and has at least ``min_focal_obs`` active observations; a trial that takes a focal outside
     ``focal_bounds = (lo, hi)`` times its input value is rejected.  The result then carries ``K``, ``cam_focal`` and
-    ``stats['n_focal_cameras']``.  Principal point, distortion and focal priors are not modelled.
+    ``stats['n_focal_cameras']``.  Principal point and focal priors are not modelled.
 
     ``camera_ids`` (needs ``refine_focal``): ``[n]`` non-negative integers on the device of the other arguments; images with
     equal ids are one physical camera and share ONE relative step -- every member keeps its own fx, skew, fy (so images stored at different
@@ -122,7 +132,20 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     fixes image 0; pass an all-false ``fixed`` to let the priors hold the gauge, which they do when at least three cameras with a
     prior are not collinear.  ``None`` makes the calls above exactly as before.  The result adds ``cam_prior`` and
     ``stats['n_prior_cameras']``, ``prior_cost_before`` / ``_after``, ``prior_rms_before`` / ``_after``.  Rotation priors, priors on
-    points, a robust prior loss, lever arms and full covariances are not modelled."""
+    points, a robust prior loss, lever arms and full covariances are not modelled.
+
+    ``refine_radial`` (needs ``refine_focal``): ``None`` is every call above, bit for bit; ``True`` or an ``[n]`` mask lets
+    the cameras of those images refine ONE radial coefficient each, ``x_d = x (1 + k r^2)`` on normalised coordinates, next to their focal
+    step.  ``obs_xy`` are then the stored, distorted pixels.  ``radial``: ``[n]`` start values (default zeros), on the device of the other
+    arguments.  Groups are those of ``camera_ids``; without it every image is a camera of its own (singleton groups: the group
+    preconditioner is then one 2 x 2 block per image beside its 6 x 6 pose block, and §18.2 measured that such splitting of a camera's
+    block costs conjugate-gradient iterations -- many singleton groups may end at ``pcg_iters``; give ``camera_ids`` where images share
+    a camera).  An image refines its coefficient when it carries its camera's focal and is flagged here; a camera does when those images
+    together have ``min_focal_obs`` active observations.  A trial that takes a ``k`` outside ``radial_bounds = (lo, hi)`` is rejected.
+    The steps add: every member leaves with ``radial_in + a`` for ONE ``a`` of its camera.  The result adds ``radial``, ``cam_radial``,
+    ``group_radial`` (and ``cam_group`` / ``group_focal``) and ``stats['n_radial_cameras']``.  Not modelled: priors together with
+    ``refine_radial``, refining ``k`` with a trusted focal, k2, tangential and fisheye terms.  A KNOWN distortion is not an argument of
+    the adjustment: ``undistort_points`` the observations, then make the pinhole call."""
     what = "bundle_adjust"
     args = [offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world]
     params = ops._ba_params(what, huber_px, max_iters, pcg_iters, pcg_tol, ftol)
@@ -135,7 +158,41 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             raise ValueError(f"{what}: refine_focal must be None, True or an [n] mask")
     if camera_ids is not None and focal is None:
         raise ValueError(f"{what}: camera_ids shares the focal step of refine_focal between images; pass refine_focal as well")
+    if refine_radial is None and radial is not None:
+        raise ValueError(f"{what}: radial without refine_radial: a known distortion is not adjusted here; undistort the observations "
+                         "(undistort_points), then make the pinhole call")
+    if refine_radial is not None:
+        if refine_radial is False:
+            raise ValueError(f"{what}: refine_radial must be None, True or an [n] mask")
+        if focal is None:
+            raise ValueError(f"{what}: refine_radial refines a radial coefficient next to the focal step of refine_focal; pass refine_focal as well")
+        if position_prior is not None:
+            raise ValueError(f"{what}: position_prior together with refine_radial is not modelled")
+        if not (isinstance(radial_bounds, (tuple, list)) and len(radial_bounds) == 2):
+            raise ValueError(f"{what}: radial_bounds must be a pair (lo, hi), got {radial_bounds!r}")
+        rbounds = ops._ba_radial_params(what, *radial_bounds)
     gpu = _tracks.one_device(what, _ARGS + ("fixed",), args + ([] if fixed is None else [fixed]))   # ("fixed" is named only when given)
+    if refine_radial is not None:
+        nK = len(K)
+        for k, v in (("refine_radial", refine_radial), ("radial", radial)):
+            if v is None or v is True:
+                continue
+            on_gpu = isinstance(v, torch.Tensor) and v.is_cuda
+            if on_gpu != gpu or (gpu and v.device != args[0].device):
+                raise ValueError(f"{what}: {k} is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no silent "
+                                 "fallback: move it to their device")
+            if not on_gpu:
+                v = v.detach().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            if tuple(v.shape) != (nK,):
+                raise ValueError(f"{what}: {k} must have shape ({nK},), got {tuple(v.shape)}")
+            if k == "radial":
+                radial = v.detach().to(torch.float64).contiguous() if gpu else np.ascontiguousarray(v, np.float64)
+            else:
+                refine_radial = v
+        if radial is None:
+            radial = torch.zeros(nK, dtype=torch.float64, device=args[0].device) if gpu else np.zeros(nK, np.float64)
+        if camera_ids is None:                                           # every image a camera of its own
+            camera_ids = torch.arange(nK, dtype=torch.int64, device=args[0].device) if gpu else np.arange(nK, dtype=np.int64)
     neg_id = None
     if camera_ids is not None:
         on_gpu = isinstance(camera_ids, torch.Tensor) and camera_ids.is_cuda
@@ -231,6 +288,8 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
     if camera_ids is not None:
         groups = _tracks.group_by_camera(camera_ids.detach() if gpu else camera_ids)
         extra, mode = extra + list(groups), "_shared"
+    if refine_radial is not None:
+        extra, mode, focal = extra + [radial, ones if refine_radial is True else flags(refine_radial)], "_radial", focal + rbounds
     if prior is None:
         call = getattr(ops, "bundle_adjust" + mode + ("" if gpu else "_host"))
         out = call(*a, fx, *_tracks.group_by_image(a[1], n), *extra, *params, *(focal or ()), **({"timings": timings} if gpu else {}))
@@ -268,4 +327,8 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             stats["n_focal_groups"] = counts[14]
             out["group_focal"] = out["group_focal"].view(torch.bool)
             fields += _OUT_SHARED
+        if refine_radial is not None:
+            stats["n_radial_cameras"] = counts[15]
+            out["cam_radial"], out["group_radial"] = out["cam_radial"].view(torch.bool), out["group_radial"].view(torch.bool)
+            fields += _OUT_RADIAL
     return BundleResult(stats, **{k: out[k] for k in fields + (_OUT_PRIOR if prior is not None else ())})

@@ -9,7 +9,9 @@
 // sequence of phases and the order-defined sums.  The sequence is ONE template, run<Mode>, and the three entry points are its three
 // instantiations: Pose (§18), Focal (§18.1: one focal step per camera), Shared (§18.2: one per group of cameras, whose group phases
 // are `if constexpr` in the sequence).  Position priors on the camera centres (§18.3) are a trait of the mode as well: PoseP, FocalP and
-// SharedP run the same sequence with the prior's steps, loftr_bundle_adjust_prior_host picks one by `mode`.
+// SharedP run the same sequence with the prior's steps, loftr_bundle_adjust_prior_host picks one by `mode`.  Radial (§18.4) is the
+// grouped mode with an 8-wide camera block and two unknowns per group, the second an additive step of one radial coefficient; its
+// steps stand behind `if constexpr (kRadial)` in the same sequence, and it alone reads the distorted projection.
 #include <stdint.h>
 #include <vector>
 #include "../../include/loftr_hip.h"
@@ -59,10 +61,17 @@ double group_sum(const CtxS& c, long g, const double* v, long stride) {
   return out;
 }
 
-// the sequence of phases of every mode; c holds the problem and the result.  The group phases exist for Shared only.
+// Radial: a group's osum64 of M values per member
+template <int M, class F> void group_sum_radial(const CtxR& c, long g, F term, double* out) {
+  const long b = c.group_offsets[g];
+  osum64<M>(c.group_offsets[g + 1] - b, [&](long e, double* a) { term(c.group_cams[b + e], a); }, out);
+}
+
+// the sequence of phases of every mode; c holds the problem and the result.  The group phases exist for Shared and Radial only.
 template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iters, double pcg_tol) {
   constexpr int S = Mode::S, kU = kTri<S>;
-  constexpr bool kGroups = Mode::kGroups;
+  constexpr bool kGroups = Mode::kGroups, kRadial = Mode::kRadial;
+  using TMode = TrackMode<Mode>;
   const int st = check_args<Mode>(c, max_iters, pcg_iters, pcg_tol, true);
   if (st != LOFTR_OK) return st;
   const long T = c.T, n = c.n;
@@ -71,9 +80,11 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   Ctrl& s = *c.ctrl;
   ctrl_init(c, groups_ctrl<Mode>(c));
   if constexpr (Mode::kPrior) ctrl_init_prior(c.pr);
+  if constexpr (kRadial) c.cr->n_radial = 0;
   for (long i = 0; i < n; ++i) {
     cam_setup(c, i);
-    if constexpr (S == 7) cam_setup_focal(c, i);
+    if constexpr (S >= 7) cam_setup_focal(c, i);
+    if constexpr (kRadial) cam_setup_radial(c, i);
   }
   for (long t = 0; t < T; ++t) {
     long cnt;
@@ -83,7 +94,7 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   }
   if (s.err) return LOFTR_ERR_BAD_ARG;
   for (long i = 0; i < n; ++i) {
-    if constexpr (S == 7) c.cam_focal[i] = 0;
+    if constexpr (S >= 7) c.cam_focal[i] = 0;
     long b, e, cnt = 0;
     if (!group_range(c, i, &b, &e)) { s.err |= kBadGroups; continue; }
     for (long k = b; k < e; ++k) {
@@ -106,13 +117,14 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   if (s.err) return LOFTR_ERR_BAD_ARG;
   if constexpr (kGroups) {
     for (long g = 0; g < c.G; ++g) {
-      long b, e, total = 0;
+      long b, e, total = 0, rtotal = 0;
       int err = 0;
       if (!cgroup_range(c, g, &b, &e)) { s.err |= kBadCamGroups; continue; }
       for (long k = b; k < e; ++k) {
         long cnt;
         err |= cgroup_slot(c, g, b, k, &cnt);
         total += cnt;
+        if constexpr (kRadial) rtotal += cgroup_slot_radial(c, k, cnt);
       }
       s.err |= err;
       if (err) continue;
@@ -123,6 +135,15 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         const int i = c.group_cams[k];
         c.cam_focal[i] = (uint8_t)(refines && c.cam_cnt[i] > 0);
         s.n_focal += c.cam_focal[i];
+      }
+      if constexpr (kRadial) {
+        const bool rr = cgroup_rule_radial(c, g, refines, rtotal);
+        c.group_radial[g] = (uint8_t)rr;
+        for (long k = b; k < e; ++k) {
+          const int i = c.group_cams[k];
+          c.cam_radial[i] = (uint8_t)cam_radial_rule(c, i, rr);
+          c.cr->n_radial += c.cam_radial[i];
+        }
       }
     }
     if (s.err) return LOFTR_ERR_BAD_ARG;
@@ -136,7 +157,7 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   };
   auto evaluate = [&](int buf) {
     bool ok = true;
-    for (long t = 0; t < T; ++t) ok = track_eval(c, buf, t) && ok;
+    for (long t = 0; t < T; ++t) ok = track_eval<TMode>(c, buf, t) && ok;
     if constexpr (Mode::kPrior)
       for (long i = 0; i < n; ++i) cam_prior_eval(c, c.pr, buf, i);
     return ok;
@@ -160,7 +181,7 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   for (int it = 0; it < max_iters && !s.done; ++it) {
     const int cur = s.cur;
     if (s.fresh) {
-      for (long t = 0; t < T; ++t) track_lin(c, cur, t);
+      for (long t = 0; t < T; ++t) track_lin<TMode>(c, cur, t);
       for (long i = 0; i < n; ++i) {
         if (!takes_part<Mode>(c, i)) continue;
         double a[kU + S];
@@ -169,13 +190,18 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         for (int k = 0; k < S; ++k) c.gc[S * i + k] = a[kU + k];
         if constexpr (Mode::kPrior) cam_lin_prior<S>(c, c.pr, cur, i);
       }
-      if constexpr (kGroups)
+      if constexpr (kRadial) {
+        for (long g = 0; g < c.G; ++g)
+          if (c.group_focal[g]) group_sum_radial<3>(c, g, [&](long i, double* a) { group_term_block(c, i, a); }, c.dg + 3 * g);
+      } else if constexpr (kGroups)
         for (long g = 0; g < c.G; ++g) if (c.group_focal[g]) c.dg[g] = group_sum(c, g, c.U + 27, 28);
     }
     const double lambda = s.lambda;
     for (long t = 0; t < T; ++t) if (!track_factor(c, t, lambda)) s.bad_f = 1;
     for (long i = 0; i < n; ++i) if (!cam_factor<Mode>(c, i, lambda)) s.bad_f = 1;
-    if constexpr (kGroups)
+    if constexpr (kRadial) {
+      for (long g = 0; g < c.G; ++g) if (!group_factor_radial(c, g, lambda)) s.bad_f = 1;
+    } else if constexpr (kGroups)
       for (long g = 0; g < c.G; ++g) if (!group_factor(c, g, lambda)) s.bad_f = 1;
     auto camera_half = [&](int mode) {
       for (long i = 0; i < n; ++i) {
@@ -184,7 +210,13 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         if (takes_part<Mode>(c, i)) cam_sum<S>(c, i, [&](long o, double* acc) { cam_half_term<Mode>(c, cur, o, acc); }, a);
         cam_half_finish<Mode>(c, i, mode, lambda, a);
       }
-      if constexpr (kGroups)
+      if constexpr (kRadial) {
+        for (long g = 0; g < c.G; ++g) {
+          double sg[2] = {0.0, 0.0};
+          if (c.group_focal[g]) group_sum_radial<2>(c, g, [&](long i, double* a) { group_term_pair(c, i, a); }, sg);
+          group_half_finish_radial(c, g, mode, lambda, sg);
+        }
+      } else if constexpr (kGroups)
         for (long g = 0; g < c.G; ++g) group_half_finish(c, g, mode, lambda, c.group_focal[g] ? group_sum(c, g, c.Sp + 6, 7) : 0.0);
     };
     if (!s.bad_f) {
@@ -197,16 +229,22 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         ctrl_feed(c, kActPsp, dot());
         if (s.pcg_done) break;
         for (long i = 0; i < n; ++i) cam_update1<Mode>(c, i, s.alpha);
-        if constexpr (kGroups)
+        if constexpr (kRadial) {
+          for (long g = 0; g < c.G; ++g) group_update1_radial(c, g, s.alpha);
+        } else if constexpr (kGroups)
           for (long g = 0; g < c.G; ++g) group_update1(c, g, s.alpha, lambda);
         ctrl_feed(c, kActRz, dot());
         if (s.pcg_done) break;
         for (long i = 0; i < n; ++i) cam_update2<Mode>(c, i, s.beta);
-        if constexpr (kGroups)
+        if constexpr (kRadial) {
+          for (long g = 0; g < c.G; ++g) group_update2_radial(c, g, s.beta);
+        } else if constexpr (kGroups)
           for (long g = 0; g < c.G; ++g) group_update2(c, g, s.beta);
       }
       for (long i = 0; i < n; ++i) if (!cam_apply<Mode>(c, cur, i)) s.bad_a = 1;
-      if constexpr (kGroups)
+      if constexpr (kRadial) {
+        for (long g = 0; g < c.G; ++g) group_apply_radial(c, cur, g);
+      } else if constexpr (kGroups)
         for (long g = 0; g < c.G; ++g) group_apply(c, cur, g);
       for (long t = 0; t < T; ++t) if (!track_half<Mode>(c, cur, t, 2)) s.bad_a = 1;
     }
@@ -263,6 +301,25 @@ extern "C" int loftr_bundle_adjust_shared_host(const long* offsets, long T, cons
   fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
   fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
   return run<Shared>(c, max_iters, pcg_iters, pcg_tol);
+}
+
+// one focal step and one radial coefficient per group of cameras (§18.4)
+extern "C" int loftr_bundle_adjust_radial_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
+                                               long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                               const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                               const int* cam_group, const long* group_offsets, const int* group_cams, int G,
+                                               const double* radial_in, const uint8_t* refine_radial, double huber_px, int max_iters,
+                                               int pcg_iters, double pcg_tol, double ftol, int min_focal_obs, double focal_lo, double focal_hi,
+                                               double radial_lo, double radial_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
+                                               uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal,
+                                               double* radial_out, uint8_t* cam_radial, uint8_t* group_radial, long* counts) {
+  CtxR c{};
+  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
+       T_out, xyz_out, obs_active, cam_free, point_active, counts);
+  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
+  fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
+  fill_radial(c, radial_in, refine_radial, radial_lo, radial_hi, radial_out, cam_radial, group_radial);
+  return run<Radial>(c, max_iters, pcg_iters, pcg_tol);
 }
 
 // with position priors on the camera centres (§18.3): mode 0 pose, 1 focal, 2 shared; the focal and group arguments are ignored below

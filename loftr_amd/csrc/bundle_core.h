@@ -13,12 +13,14 @@
 // `if constexpr`; no mode is reached through another "with a zero column", so each performs exactly its own operations.  Steps that are
 // different rules (cam_focal_rule against cam_carry / cgroup_*, the group_* steps) stay separate functions.  Position priors on the
 // camera centres (§18.3) are a second trait of the mode (kPrior: PoseP, FocalP, SharedP): their steps are `if constexpr` inside the same
-// phases, and the three modes without them perform no operation of theirs.  The context fill and the argument checks of all eight entry
-// points are at the end.
+// phases, and the three modes without them perform no operation of theirs.  One radial coefficient per group (§18.4) is a fourth mode,
+// Radial: the grouped mode 8 wide with two unknowns per group; it alone reads a k (kRadial), the others perform no operation of its.
+// The context fill and the argument checks of all the entry points are at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/loftr_hip.h"
 #include "tracks_core.h"
 
@@ -95,6 +97,19 @@ struct CtxS : Ctx7 {
   CtrlS* cs;
 };
 
+// §18.4, one radial coefficient per group of cameras next to its focal step: x_d = x (1 + k r^2) on normalised coordinates.  The camera
+// block is 8 wide (seventh the relative focal step, eighth the ADDITIVE radial step), the group carries two unknowns, focal first, and
+// every group vector of CtxS holds two doubles per group ([G][2]; dg holds [n][3] the group's 2 x 2 block, then [n][3] its factor).  Only the Radial mode
+// reads a k: no other mode is handed a zero coefficient.
+struct CtrlR { int n_radial; };
+struct CtxR : CtxS {
+  const double* radial_in; const uint8_t* refine_radial; double radial_lo, radial_hi;
+  double* radial_out; uint8_t *cam_radial, *group_radial;
+  double* kr;                                     // [2][n]: a camera's k in the state and in the trial (ctrl->cur)
+  double* ag;                                     // [2][n]: the radial step a group has taken so far, likewise
+  CtrlR* cr;
+};
+
 // §18.3, position priors on the camera centres.  A prior couples no point, so it only adds to U, gc and the cost of its camera; what it
 // needs is carried next to any of the three contexts, and only by the instantiations that have it.
 struct CtrlP {
@@ -115,14 +130,18 @@ template <class Base> struct WithPrior : Base { Prior pr; };
 // block, W the width of what is factored, solved and updated per camera, kGroups whether the group phases exist.
 // kPrior: whether the cameras carry position priors (§18.3); Base is the mode without them, whose kernels and steps serve every phase
 // that the prior does not touch.
-struct Pose { static constexpr int S = 6, W = 6; static constexpr bool kGroups = false, kPrior = false; using Ctx = ba::Ctx; using Base = Pose; };       // §18
-struct Focal { static constexpr int S = 7, W = 7; static constexpr bool kGroups = false, kPrior = false; using Ctx = ba::Ctx7; using Base = Focal; };    // §18.1
-struct Shared { static constexpr int S = 7, W = 6; static constexpr bool kGroups = true, kPrior = false; using Ctx = ba::CtxS; using Base = Shared; };   // §18.2
+// kRadial: whether the projection is the distorted one of §18.4 (then GW = 2 unknowns per group instead of 1).
+struct Pose { static constexpr int S = 6, W = 6, GW = 1; static constexpr bool kGroups = false, kPrior = false, kRadial = false; using Ctx = ba::Ctx; using Base = Pose; };       // §18
+struct Focal { static constexpr int S = 7, W = 7, GW = 1; static constexpr bool kGroups = false, kPrior = false, kRadial = false; using Ctx = ba::Ctx7; using Base = Focal; };    // §18.1
+struct Shared { static constexpr int S = 7, W = 6, GW = 1; static constexpr bool kGroups = true, kPrior = false, kRadial = false; using Ctx = ba::CtxS; using Base = Shared; };   // §18.2
+struct Radial { static constexpr int S = 8, W = 6, GW = 2; static constexpr bool kGroups = true, kPrior = false, kRadial = true; using Ctx = ba::CtxR; using Base = Radial; };    // §18.4
 template <class M> struct PriorOf : M { static constexpr bool kPrior = true; using Ctx = WithPrior<typename M::Ctx>; using Base = M; };    // §18.3
 using PoseP = PriorOf<Pose>;
 using FocalP = PriorOf<Focal>;
 using SharedP = PriorOf<Shared>;
-template <int S> constexpr int kTri = S * (S + 1) / 2;      // entries of the upper triangle of a camera block: 21 or 28
+template <int S> constexpr int kTri = S * (S + 1) / 2;      // entries of the upper triangle of a camera block: 21, 28 or 36
+// the mode whose track steps (linearise, evaluate) a mode runs: they do not depend on the camera block, only on the projection
+template <class Mode> using TrackMode = std::conditional_t<Mode::kRadial, Mode, Pose>;
 template <class Mode> BA_HD CtrlS* groups_ctrl(const typename Mode::Ctx& c) {
   if constexpr (Mode::kGroups) return c.cs;
   else return nullptr;
@@ -144,10 +163,15 @@ template <class Mode> inline size_t layout(typename Mode::Ctx& c, char* base) {
   c.part = (double*)take(8 * m); c.part2 = (double*)take(8 * m); c.red = (double*)take(8 * 2 * ch);
   c.obs_track = (int*)take(4 * N); c.cam_valid = (uint8_t*)take(n);
   if constexpr (Mode::kGroups) {
+    constexpr size_t GW = Mode::GW, DW = Mode::kRadial ? 6 : 1;
     c.cs = (CtrlS*)take(sizeof(CtrlS));
-    c.dg = (double*)take(8 * n); c.xg = (double*)take(8 * n); c.rg = (double*)take(8 * n); c.zg = (double*)take(8 * n);
-    c.pg = (double*)take(8 * n); c.Spg = (double*)take(8 * n); c.partg = (double*)take(8 * n); c.sg = (double*)take(8 * 2 * n);
+    c.dg = (double*)take(8 * n * DW); c.xg = (double*)take(8 * n * GW); c.rg = (double*)take(8 * n * GW); c.zg = (double*)take(8 * n * GW);
+    c.pg = (double*)take(8 * n * GW); c.Spg = (double*)take(8 * n * GW); c.partg = (double*)take(8 * n); c.sg = (double*)take(8 * 2 * n);
     c.cam_cnt = (int*)take(4 * n);
+  }
+  if constexpr (Mode::kRadial) {
+    c.cr = (CtrlR*)take(sizeof(CtrlR));
+    c.kr = (double*)take(8 * 2 * n); c.ag = (double*)take(8 * 2 * n);
   }
   if constexpr (Mode::kPrior) {
     c.pr.cp = (CtrlP*)take(sizeof(CtrlP));
@@ -225,6 +249,16 @@ BA_HD void cam_setup_focal(const Ctx7& c, long i) {
   uint64_t* dst = (uint64_t*)(c.K_out + 9 * i);
   for (int k = 0; k < 9; ++k) dst[k] = src[k];
 }
+// ... and with a radial coefficient: a valid camera whose k is not finite is not valid; both states start at the input's k and the
+// output as its bits
+BA_HD double* kr_of(const CtxR& c, int buf, long i) { return c.kr + ((long)buf * c.n + i); }
+BA_HD void cam_setup_radial(const CtxR& c, long i) {
+  const double k = c.radial_in[i];
+  if (!fin(k)) c.cam_valid[i] = 0;
+  *kr_of(c, 0, i) = k; *kr_of(c, 1, i) = k;
+  *(uint64_t*)(c.radial_out + i) = *(const uint64_t*)(c.radial_in + i);
+  c.cam_radial[i] = 0;
+}
 // phase "camera groups", the last step of a camera with cnt active observations.  Focal: does it refine its focal?
 BA_HD bool cam_focal_rule(const Ctx7& c, long i, bool is_free, long cnt) {
   return is_free && c.refine_focal[i] != 0 && cnt >= (long)c.min_focal_obs;
@@ -258,6 +292,17 @@ BA_HD bool cgroup_rule(const CtxS& c, long g, long total) {
   *sg_of(c, 0, g) = 1.0; *sg_of(c, 1, g) = 1.0;
   return total >= (long)c.min_focal_obs;
 }
+
+// Radial: what slot k (cnt: what cgroup_slot returned for it, 0 for a bad slot) adds to the radial count of its group
+BA_HD long cgroup_slot_radial(const CtxR& c, long k, long cnt) { return cnt > 0 && c.refine_radial[c.group_cams[k]] != 0 ? cnt : 0; }
+BA_HD double* ag_of(const CtxR& c, int buf, long g) { return c.ag + ((long)buf * c.n + g); }
+// ... and does group g, which refines its focal or not, refine its radial coefficient?  Its accumulated step starts at +0 in both states.
+BA_HD bool cgroup_rule_radial(const CtxR& c, long g, bool refines, long rtotal) {
+  *ag_of(c, 0, g) = 0.0; *ag_of(c, 1, g) = 0.0;
+  return refines && rtotal >= (long)c.min_focal_obs;
+}
+// ... and does member i of a group that does (`refines`) carry it?
+BA_HD bool cam_radial_rule(const CtxR& c, long i, bool refines) { return refines && c.cam_cnt[i] > 0 && c.refine_radial[i] != 0; }
 
 // ---- §18.3: position priors ------------------------------------------------------------------------------------------------------------
 // phase "camera groups", after cam_free of camera i is known: does it have a prior?  A NaN anywhere deactivates.
@@ -328,6 +373,48 @@ BA_HD void residual(const double* cam, const double* Y, double u, double v, doub
   r[0] = ((cam[12] * a + cam[13] * b) + cam[14]) - u;
   r[1] = (cam[15] * b + cam[16]) - v;
 }
+// §18.4, the distorted projection, in this order: a = Y0 / Y2, b = Y1 / Y2, r2 = a a + b b, m = 1 + k r2, xd = a m, yd = b m,
+// pixel = ((fx xd + skew yd) + cx, fy yd + cy)
+BA_HD void residual_radial(const double* cam, double k, const double* Y, double u, double v, double* r) {
+  const double a = Y[0] / Y[2], b = Y[1] / Y[2];
+  const double r2 = a * a + b * b, m = 1.0 + k * r2, xd = a * m, yd = b * m;
+  r[0] = ((cam[12] * xd + cam[13] * yd) + cam[14]) - u;
+  r[1] = (cam[15] * yd + cam[16]) - v;
+}
+// ... and its Jacobians.  d(xd, yd)/d(a, b) = m I + 2k (a, b)(a, b)^T: jaa = m + 2k (a a), jab = 2k (a b), jbb = m + 2k (b b);
+// d pixel/d(a, b): ua = fx jaa + skew jab, ub = fx jab + skew jbb, va = fy jab, vb = fy jbb; d pixel/dY = (ua / Y2, ub / Y2,
+// -((ua a + ub b) / Y2)) and likewise for v, each times sw.  A [2,8]: the pose columns as in `jacobians` (the v row has no zero here),
+// column 6 sw (fx xd + skew yd, fy yd) with `focal`, column 7 sw (fx (a r2) + skew (b r2), fy (b r2)) with `radial`, else +0.
+BA_HD void jacobians_radial(const double* cam, double k, const double* P, const double* Y, double sw, bool focal, bool radial, double* A,
+                            double* B) {
+  const double fx = cam[12], sk = cam[13], fy = cam[15];
+  const double a = Y[0] / Y[2], b = Y[1] / Y[2];
+  const double r2 = a * a + b * b, m = 1.0 + k * r2, k2 = 2.0 * k;
+  const double jaa = m + k2 * (a * a), jab = k2 * (a * b), jbb = m + k2 * (b * b);
+  const double ua = fx * jaa + sk * jab, ub = fx * jab + sk * jbb, va = fy * jab, vb = fy * jbb;
+  const double du[3] = {sw * (ua / Y[2]), sw * (ub / Y[2]), sw * -((ua * a + ub * b) / Y[2])};
+  const double dv[3] = {sw * (va / Y[2]), sw * (vb / Y[2]), sw * -((va * a + vb * b) / Y[2])};
+  A[0] = du[2] * P[1] - du[1] * P[2]; A[1] = du[0] * P[2] - du[2] * P[0]; A[2] = du[1] * P[0] - du[0] * P[1];
+  A[3] = du[0]; A[4] = du[1]; A[5] = du[2];
+  A[8] = dv[2] * P[1] - dv[1] * P[2]; A[9] = dv[0] * P[2] - dv[2] * P[0]; A[10] = dv[1] * P[0] - dv[0] * P[1];
+  A[11] = dv[0]; A[12] = dv[1]; A[13] = dv[2];
+  if (focal) {
+    const double xd = a * m, yd = b * m;
+    A[6] = sw * (fx * xd + sk * yd); A[14] = sw * (fy * yd);
+  } else {
+    A[6] = 0.0; A[14] = 0.0;
+  }
+  if (radial) {
+    const double xr = a * r2, yr = b * r2;
+    A[7] = sw * (fx * xr + sk * yr); A[15] = sw * (fy * yr);
+  } else {
+    A[7] = 0.0; A[15] = 0.0;
+  }
+  for (int j = 0; j < 3; ++j) {
+    B[j] = (du[0] * cam[j] + du[1] * cam[3 + j]) + du[2] * cam[6 + j];
+    B[3 + j] = (dv[0] * cam[j] + dv[1] * cam[3 + j]) + dv[2] * cam[6 + j];
+  }
+}
 // rule 4: sw = sqrt(weight), rho, sq = |r|^2
 BA_HD void loss(const double* r, double huber, double* sw, double* rho, double* sq) {
   const double s = r[0] * r[0] + r[1] * r[1];
@@ -367,12 +454,19 @@ template <class Mode> BA_HD void obs_terms(const typename Mode::Ctx& c, int buf,
   constexpr int S = Mode::S;
   const double *cam = tab_of(c, buf, c.image[o]), *X = X_of(c, buf, t);
   bool focal = false;
-  if constexpr (S == 7) focal = c.cam_focal[c.image[o]] != 0;
+  if constexpr (S >= 7) focal = c.cam_focal[c.image[o]] != 0;
   double P[3], Y[3], r[2], sw, rho, sq;
   transform(cam, X, P, Y);
-  residual(cam, Y, (double)c.xy[2 * o], (double)c.xy[2 * o + 1], r);
-  loss(r, c.huber, &sw, &rho, &sq);
-  jacobians<S>(cam, P, Y, sw, focal, A, B);
+  if constexpr (Mode::kRadial) {
+    const double k = *kr_of(c, buf, c.image[o]);
+    residual_radial(cam, k, Y, (double)c.xy[2 * o], (double)c.xy[2 * o + 1], r);
+    loss(r, c.huber, &sw, &rho, &sq);
+    jacobians_radial(cam, k, P, Y, sw, focal, c.cam_radial[c.image[o]] != 0, A, B);
+  } else {
+    residual(cam, Y, (double)c.xy[2 * o], (double)c.xy[2 * o + 1], r);
+    loss(r, c.huber, &sw, &rho, &sq);
+    jacobians<S>(cam, P, Y, sw, focal, A, B);
+  }
   rs[0] = sw * r[0]; rs[1] = sw * r[1];
   if constexpr (Mode::kGroups)
     if (!c.cam_free[c.image[o]])
@@ -490,14 +584,14 @@ template <int M> BA_HD double dotm(const double* a, const double* b) {
 
 // ---- rule 5: the sums ----------------------------------------------------------------------------------------------------------------
 // phase "linearise tracks", per track: V = sum B^T B (upper triangle), gp = sum B^T rs, sequentially over the active observations.
-// B does not depend on the width of the camera block, so one text serves every mode.
-BA_HD void track_lin(const Ctx& c, int buf, long t) {
+// B does not depend on the width of the camera block, so one text (Mode = Pose) serves every mode with the pinhole projection.
+template <class Mode = Pose> BA_HD void track_lin(const typename Mode::Ctx& c, int buf, long t) {
   double V[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
   if (c.point_active[t])
     for (long o = c.offsets[t]; o < c.offsets[t + 1]; ++o) {
       if (!c.obs_active[o]) continue;
-      double A[12], B[6], rs[2];
-      obs_terms<Pose>(c, buf, o, t, A, B, rs);
+      double A[2 * Mode::S], B[6], rs[2];
+      obs_terms<Mode>(c, buf, o, t, A, B, rs);
       V[0] = V[0] + (B[0] * B[0] + B[3] * B[3]); V[1] = V[1] + (B[0] * B[1] + B[3] * B[4]); V[2] = V[2] + (B[0] * B[2] + B[3] * B[5]);
       V[3] = V[3] + (B[1] * B[1] + B[4] * B[4]); V[4] = V[4] + (B[1] * B[2] + B[4] * B[5]); V[5] = V[5] + (B[2] * B[2] + B[5] * B[5]);
       for (int k = 0; k < 3; ++k) g[k] = g[k] + (B[k] * rs[0] + B[3 + k] * rs[1]);
@@ -523,6 +617,18 @@ BA_HD void group_term(const CtxS& c, long i, const double* v, long stride, doubl
   if (c.cam_focal[i]) a[0] = a[0] + v[stride * i];
 }
 
+// Radial: member i adds (U77, U78, U88) to its group's block d [3] when it has cam_focal (U78 and U88 are +0 without cam_radial) ...
+BA_HD void group_term_block(const CtxR& c, long i, double* a) {
+  if (!c.cam_focal[i]) return;
+  const double* U = c.U + kTri<8> * i;
+  a[0] = a[0] + U[33]; a[1] = a[1] + U[34]; a[2] = a[2] + U[35];
+}
+// ... and its seventh and eighth entries of Sp to E^T: the seventh with cam_focal, the eighth with cam_radial
+BA_HD void group_term_pair(const CtxR& c, long i, double* a) {
+  if (c.cam_focal[i]) a[0] = a[0] + c.Sp[8 * i + 6];
+  if (c.cam_radial[i]) a[1] = a[1] + c.Sp[8 * i + 7];
+}
+
 // ---- rule 6: the step ------------------------------------------------------------------------------------------------------------------
 // phase "factor", per track / per free camera (the W x W block of U, damped -> Uf) / per refining group (the damped d_g must be
 // positive) -> false on a non-positive pivot
@@ -543,8 +649,18 @@ template <class Mode> BA_HD bool cam_factor(const Ctx& c, long i, double lambda)
   return ok;
 }
 BA_HD bool group_factor(const CtxS& c, long g, double lambda) { return !c.group_focal[g] || damped(c.dg[g], lambda) > 0.0; }
+// Radial: the 2 x 2 L D L^T of the group's block, both diagonals damped here, once (a group that does not refine its radial has a
+// block (d, 0; 0, 0), whose second pivot is lambda) -> the factor [3], kept behind the n blocks of dg
+BA_HD double* dgf_of(const CtxS& c, long g) { return c.dg + 3 * ((long)c.n + g); }
+BA_HD bool group_factor_radial(const CtxS& c, long g, double lambda) {
+  if (!c.group_focal[g]) return true;
+  double f[3];
+  const bool ok = factor<2>(c.dg + 3 * g, lambda, f);
+  for (int k = 0; k < 3; ++k) dgf_of(c, g)[k] = f[k];
+  return ok;
+}
 // the vector of camera i as the operator sees it, out of x (step) or p: its S entries in place; Shared: the pose part of a free camera,
-// its group's value when it has cam_focal, else +0, formed in tmp [7]
+// its group's value when it has cam_focal (Radial: and its group's second value when it has cam_radial), else +0, formed in tmp [S]
 template <class Mode> BA_HD const double* cam_vec(const typename Mode::Ctx& c, long i, bool step, double* tmp) {
   const double* vec = step ? c.x : c.p;
   if constexpr (!Mode::kGroups) return vec + Mode::S * i;
@@ -552,8 +668,9 @@ template <class Mode> BA_HD const double* cam_vec(const typename Mode::Ctx& c, l
     const double* vecg = step ? c.xg : c.pg;
     const bool fr = c.cam_free[i] != 0;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) tmp[k] = fr ? vec[7 * i + k] : 0.0;
-    tmp[6] = c.cam_focal[i] ? vecg[c.cam_group[i]] : 0.0;
+    for (int k = 0; k < 6; ++k) tmp[k] = fr ? vec[Mode::S * i + k] : 0.0;
+    tmp[6] = c.cam_focal[i] ? vecg[Mode::GW * c.cam_group[i]] : 0.0;
+    if constexpr (Mode::kRadial) tmp[7] = c.cam_radial[i] ? vecg[2 * c.cam_group[i] + 1] : 0.0;
     return tmp;
   }
 }
@@ -568,7 +685,7 @@ template <class Mode> BA_HD bool track_half(const typename Mode::Ctx& c, int buf
     for (long o = c.offsets[t]; o < c.offsets[t + 1]; ++o) {
       const int im = c.image[o];
       if (!c.obs_active[o] || !takes_part<Mode>(c, im)) continue;
-      double A[2 * S], B[6], rs[2], tmp[7];
+      double A[2 * S], B[6], rs[2], tmp[S < 7 ? 7 : S];
       obs_terms<Mode>(c, buf, o, t, A, B, rs);
       const double* v = cam_vec<Mode>(c, im, mode == 2, tmp);
       const double eu = dotm<S>(A, v), ev = dotm<S>(A + S, v);
@@ -607,8 +724,9 @@ template <class Mode> BA_HD void cam_half_term(const typename Mode::Ctx& c, int 
 template <class Mode> BA_HD void cam_half_finish(const typename Mode::Ctx& c, long i, int mode, double lambda, const double* a) {
   constexpr int S = Mode::S, W = Mode::W;
   const bool fr = c.cam_free[i] != 0;
-  bool fo = false;
+  bool fo = false, ra = false;
   if constexpr (Mode::kGroups) fo = c.cam_focal[i] != 0;
+  if constexpr (Mode::kRadial) ra = c.cam_radial[i] != 0;
   if (!fr) c.part[i] = 0.0;
   if (!fr && !fo) return;
   double *x = c.x + S * i, *r = c.r + S * i, *zc = c.zc + S * i, *p = c.p + S * i, *Sp = c.Sp + S * i;
@@ -626,10 +744,12 @@ template <class Mode> BA_HD void cam_half_finish(const typename Mode::Ctx& c, lo
     }
     if constexpr (Mode::kGroups)
       if (fo) Sp[6] = b[6];
+    if constexpr (Mode::kRadial)
+      if (ra) Sp[7] = b[7];
     return;
   }
   const double* U = c.U + kTri<S> * i;
-  double pv[S], sp[W], tmp[7];
+  double pv[S], sp[W], tmp[S < 7 ? 7 : S];
   const double* v = cam_vec<Mode>(c, i, false, tmp);
 #pragma unroll
   for (int k = 0; k < S; ++k) pv[k] = v[k];
@@ -655,6 +775,13 @@ template <class Mode> BA_HD void cam_half_finish(const typename Mode::Ctx& c, lo
       for (int col = 0; col < 6; ++col) s = s + U[col * S - col * (col - 1) / 2 + (6 - col)] * pv[col];
       Sp[6] = s - a[6];
     }
+  if constexpr (Mode::kRadial)
+    if (ra) {
+      double s = 0.0;
+#pragma unroll
+      for (int col = 0; col < 6; ++col) s = s + U[col * S - col * (col - 1) / 2 + (7 - col)] * pv[col];
+      Sp[7] = s - a[7];
+    }
 }
 // ... and what follows the sum s of group g.  mode 0: b_g = s; x = 0, r = b, z = r / d, p = z, partg = r z.  mode 1: Sp = d p + s,
 // partg = p Sp (d: the damped d_g).  A group that does not refine has partg = +0.
@@ -670,6 +797,41 @@ BA_HD void group_half_finish(const CtxS& c, long g, int mode, double lambda, dou
   const double sp = d * c.pg[g] + s;
   c.Spg[g] = sp;
   c.partg[g] = c.pg[g] * sp;
+}
+// Radial: ... of group g with the sums s [2] (focal, radial; the second is taken as +0 when the group does not refine its radial).
+// mode 0: b = s; x = 0, r = b, z = D^-1 r by the factor, p = z, partg = r_0 z_0 + r_1 z_1.  mode 1: Sp_0 = (d_00 p_0 + d_01 p_1) + s_0,
+// Sp_1 = (d_01 p_0 + d_11 p_1) + s_1 with the damped diagonals, partg = p_0 Sp_0 + p_1 Sp_1.
+BA_HD void group_half_finish_radial(const CtxR& c, long g, int mode, double lambda, const double* s) {
+  if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
+  const double b[2] = {s[0], c.group_radial[g] ? s[1] : 0.0};
+  double *x = c.xg + 2 * g, *r = c.rg + 2 * g, *z = c.zg + 2 * g, *p = c.pg + 2 * g, *Sp = c.Spg + 2 * g;
+  if (mode == 0) {
+    double zz[2];
+    solve<2>(dgf_of(c, g), b, zz);
+    for (int k = 0; k < 2; ++k) { x[k] = 0.0; r[k] = b[k]; z[k] = zz[k]; p[k] = zz[k]; }
+    c.partg[g] = dotm<2>(b, zz);
+    return;
+  }
+  const double* d = c.dg + 3 * g;
+  const double sp[2] = {(damped(d[0], lambda) * p[0] + d[1] * p[1]) + b[0], (d[1] * p[0] + damped(d[2], lambda) * p[1]) + b[1]};
+  Sp[0] = sp[0]; Sp[1] = sp[1];
+  c.partg[g] = dotm<2>(p, sp);
+}
+BA_HD void group_update1_radial(const CtxS& c, long g, double alpha) {
+  if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
+  double r[2], zz[2];
+  for (int k = 0; k < 2; ++k) {
+    c.xg[2 * g + k] = c.xg[2 * g + k] + alpha * c.pg[2 * g + k];
+    r[k] = c.rg[2 * g + k] - alpha * c.Spg[2 * g + k];
+    c.rg[2 * g + k] = r[k];
+  }
+  solve<2>(dgf_of(c, g), r, zz);
+  c.zg[2 * g] = zz[0]; c.zg[2 * g + 1] = zz[1];
+  c.partg[g] = dotm<2>(r, zz);
+}
+BA_HD void group_update2_radial(const CtxS& c, long g, double beta) {
+  if (c.group_focal[g])
+    for (int k = 0; k < 2; ++k) c.pg[2 * g + k] = c.zg[2 * g + k] + beta * c.pg[2 * g + k];
 }
 // phase "update 1", per free camera over its W entries: x += alpha p, r -= alpha Sp, zc = M^-1 r, part = r . zc; per refining group
 template <class Mode> BA_HD void cam_update1(const Ctx& c, long i, double alpha) {
@@ -709,11 +871,18 @@ BA_HD void group_update2(const CtxS& c, long g, double beta) {
 BA_HD void group_apply(const CtxS& c, int buf, long g) {
   if (c.group_focal[g]) *sg_of(c, 1 - buf, g) = *sg_of(c, buf, g) * (1.0 + c.xg[g]);
 }
+// Radial: ... and its accumulated radial step a' = a + dk_g
+BA_HD void group_apply_radial(const CtxR& c, int buf, long g) {
+  if (c.group_focal[g]) *sg_of(c, 1 - buf, g) = *sg_of(c, buf, g) * (1.0 + c.xg[2 * g]);
+  if (c.group_radial[g]) *ag_of(c, 1 - buf, g) = *ag_of(c, buf, g) + c.xg[2 * g + 1];
+}
 // phase "apply", per camera.  A free camera: q' = normalise((1, omega / 2) (x) q), t' = t + dt into the other state -> false when not
 // finite.  One with cam_focal: fx' = fx s, skew' = skew s, fy' = fy s with, Focal, s = 1 + delta on the values of the state, and, Shared,
 // s = s_g (1 + delta_g) on the INPUT values (the camera forms s' itself, from the same two operands as group_apply), so that the members
 // of a group leave with ONE factor on their input values however many trials were accepted -> false as well when fx' or fy' is not
-// finite or fx' / fx_in or fy' / fy_in is not strictly inside (focal_lo, focal_hi); a NaN fails every test
+// finite or fx' / fx_in or fy' / fy_in is not strictly inside (focal_lo, focal_hi); a NaN fails every test.  One with cam_radial (Radial):
+// k' = k_in + (a_g + dk_g) on the INPUT value, the sum in brackets formed as group_apply_radial forms it: one rounding on the input
+// whatever the number of accepted trials -> false as well when k' is outside [radial_lo, radial_hi]
 template <class Mode> BA_HD bool cam_apply(const typename Mode::Ctx& c, int buf, long i) {
   constexpr int S = Mode::S;
   bool ok = true;
@@ -740,14 +909,14 @@ template <class Mode> BA_HD bool cam_apply(const typename Mode::Ctx& c, int buf,
       ok = ok && fin(tab2[9 + k]);
     }
   }
-  if constexpr (S == 7) {
+  if constexpr (S >= 7) {
     if (c.cam_focal[i]) {                      // (Focal: only a free camera has cam_focal)
       const double* K = c.K + 9 * i;
       double s;
       const double* from;                      // fx and skew at 0 and 1; fy at 3 of the state table, at 4 of K
       if constexpr (Mode::kGroups) {
         const long g = c.cam_group[i];
-        s = *sg_of(c, buf, g) * (1.0 + c.xg[g]);
+        s = *sg_of(c, buf, g) * (1.0 + c.xg[Mode::GW * g]);
         from = K;
       } else {
         s = 1.0 + d[6];
@@ -759,11 +928,19 @@ template <class Mode> BA_HD bool cam_apply(const typename Mode::Ctx& c, int buf,
       ok = ok && fin(fx) && fin(fy) && rx > c.focal_lo && rx < c.focal_hi && ry > c.focal_lo && ry < c.focal_hi;
     }
   }
+  if constexpr (Mode::kRadial) {
+    if (c.cam_radial[i]) {
+      const long g = c.cam_group[i];
+      const double k = c.radial_in[i] + (*ag_of(c, buf, g) + c.xg[2 * g + 1]);
+      *kr_of(c, 1 - buf, i) = k;
+      ok = ok && k >= c.radial_lo && k <= c.radial_hi;
+    }
+  }
   return ok;
 }
 // phase "evaluate", per track at state `buf`: part = sum rho, part2 = sum |r|^2 sequentially over the active observations
 // -> false when an active observation is not in front of its camera
-BA_HD bool track_eval(const Ctx& c, int buf, long t) {
+template <class Mode = Pose> BA_HD bool track_eval(const typename Mode::Ctx& c, int buf, long t) {
   double cost = 0.0, sq = 0.0;
   bool ok = true;
   if (c.point_active[t])
@@ -772,7 +949,8 @@ BA_HD bool track_eval(const Ctx& c, int buf, long t) {
       const double* cam = tab_of(c, buf, c.image[o]);
       double P[3], Y[3], r[2], sw, rho, s;
       ok = transform(cam, X_of(c, buf, t), P, Y) && ok;
-      residual(cam, Y, (double)c.xy[2 * o], (double)c.xy[2 * o + 1], r);
+      if constexpr (Mode::kRadial) residual_radial(cam, *kr_of(c, buf, c.image[o]), Y, (double)c.xy[2 * o], (double)c.xy[2 * o + 1], r);
+      else residual(cam, Y, (double)c.xy[2 * o], (double)c.xy[2 * o + 1], r);
       loss(r, c.huber, &sw, &rho, &s);
       cost = cost + rho;
       sq = sq + s;
@@ -867,7 +1045,9 @@ template <class Mode> BA_HD void cam_write(const typename Mode::Ctx& c, int buf,
     }
     T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
   }
-  if constexpr (Mode::S == 7) {
+  if constexpr (Mode::kRadial)
+    if (c.cam_radial[i]) c.radial_out[i] = *kr_of(c, buf, i);
+  if constexpr (Mode::S >= 7) {
     if (c.cam_focal[i]) {
       double* K = c.K_out + 9 * i;
       K[0] = tab[12]; K[1] = tab[13]; K[2] = tab[14]; K[4] = tab[15]; K[5] = tab[16];
@@ -888,8 +1068,9 @@ template <class Mode> BA_HD void ctrl_write(const typename Mode::Ctx& c) {
   k[8] = bits_of(s.cost0); k[9] = bits_of(s.cost);
   k[10] = bits_of(s.n_active_obs ? sqrt(s.sq0 / na) : 0.0); k[11] = bits_of(s.n_active_obs ? sqrt(s.sq / na) : 0.0);
   k[12] = bits_of(s.lambda); k[13] = 0; k[14] = 0; k[15] = 0;
-  if constexpr (Mode::S == 7) k[13] = s.n_focal;           // cameras that refine their focal
+  if constexpr (Mode::S >= 7) k[13] = s.n_focal;           // cameras that refine their focal
   if constexpr (Mode::kGroups) k[14] = c.cs->n_groups;     // groups that refine
+  if constexpr (Mode::kRadial) k[15] = c.cr->n_radial;     // cameras that refine their radial coefficient
 }
 
 // counts[16..23] of the entry points with priors
@@ -924,12 +1105,21 @@ inline void fill_prior(Prior& p, const double* prior_xyz, const double* prior_si
 inline void fill_groups(CtxS& c, const int* cam_group, const long* group_offsets, const int* group_cams, int G, uint8_t* group_focal) {
   c.cam_group = cam_group; c.group_offsets = group_offsets; c.group_cams = group_cams; c.G = G; c.group_focal = group_focal;
 }
+inline void fill_radial(CtxR& c, const double* radial_in, const uint8_t* refine_radial, double radial_lo, double radial_hi, double* radial_out,
+                        uint8_t* cam_radial, uint8_t* group_radial) {
+  c.radial_in = radial_in; c.refine_radial = refine_radial; c.radial_lo = radial_lo; c.radial_hi = radial_hi;
+  c.radial_out = radial_out; c.cam_radial = cam_radial; c.group_radial = group_radial;
+}
 // the argument checks of every entry point -> LOFTR_OK when the run may start.  Limits are answered before a pointer is read;
 // zero_counts: the host routines start from counts of zero (the kernels write them on the device).
 template <class Mode> inline int check_args(const typename Mode::Ctx& c, int max_iters, int pcg_iters, double pcg_tol, bool zero_counts) {
   const long T = c.T, N = c.N;
   const int n = c.n;
-  if constexpr (Mode::S == 7) {
+  if constexpr (Mode::kRadial) {
+    if (n > 0 && (!c.radial_in || !c.refine_radial || !c.radial_out || !c.cam_radial || !c.group_radial)) return LOFTR_ERR_BAD_ARG;
+    if (!(fin(c.radial_lo) && fin(c.radial_hi) && c.radial_lo <= c.radial_hi)) return LOFTR_ERR_BAD_ARG;
+  }
+  if constexpr (Mode::S >= 7) {
     if (n > 0 && (!c.refine_focal || !c.K_out || !c.cam_focal)) return LOFTR_ERR_BAD_ARG;
     if (!(c.min_focal_obs >= 1 && fin(c.focal_lo) && fin(c.focal_hi) && c.focal_lo < 1.0 && 1.0 < c.focal_hi)) return LOFTR_ERR_BAD_ARG;
   }

@@ -20,6 +20,8 @@
 // that ends ba_groups_kernel, the additions to U and gc by the lane that ends ba_cam_lin_kernel, a thread per camera evaluates the
 // prior of a state (ba_prior_eval_kernel), the levels of the cameras' osum follow it (ba_prior_osum_kernel), and every kernel that the
 // prior does not touch is the one of the mode without it.
+// Radial (§18.4) runs §18.2's schedule launch for launch: a kernel of its own stands where a kernel without a mode stood (camera
+// setup, the group check, evaluate, the track linearisation, the group sums), the templates get one more instantiation.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -72,10 +74,22 @@ __device__ __forceinline__ double wave_group_sum(const CtxS& c, long g, int lane
 }
 
 // what the factor and update kernels take: the base of the context (their steps need no more), with groups the groups' vectors too
+// (Radial: its group steps of these two phases read nothing beyond CtxS)
 template <class Mode> using StepCtx = std::conditional_t<Mode::kGroups, CtxS, Ctx>;
 
 __global__ void ba_init_kernel(Ctx c, CtrlS* cs) { ctrl_init(c, cs); }
 __global__ void ba_prior_init_kernel(Prior p) { ctrl_init_prior(p); }
+
+// Radial.  grid ceil(n / 256) x 256: the setup of the other modes, then the camera's k; thread 0 owns the radial counter
+__global__ void __launch_bounds__(kThreads) ba_cam_setup_radial_kernel(CtxR c) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i == 0) c.cr->n_radial = 0;
+  if (i < c.n) {
+    cam_setup(c, i);
+    cam_setup_focal(c, i);
+    cam_setup_radial(c, i);
+  }
+}
 
 // grid ceil(n / 256) x 256
 template <int S> __global__ void __launch_bounds__(kThreads) ba_cam_setup_kernel(std::conditional_t<S == 7, Ctx7, Ctx> c) {
@@ -175,12 +189,69 @@ __global__ void __launch_bounds__(kThreads) ba_cgroups_kernel(CtxS c) {
     if (nf) atomicAdd(&c.ctrl->n_focal, nf);
   }
 }
+// Radial.  The same kernel (its text is kept apart so that the device code of ba_cgroups_kernel stays what it was), and then the
+// radial decision of the group and of its members from the same counts.
+__global__ void __launch_bounds__(kThreads) ba_cgroups_radial_kernel(CtxR c) {
+  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (g >= c.G) return;
+  long b, e, total = 0, rtotal = 0;
+  int err = 0;
+  if (!cgroup_range(c, g, &b, &e)) { err = kBadCamGroups; b = e = 0; }
+  for (long k = b + lane; k < e; k += 64) {
+    long cnt;
+    err |= cgroup_slot(c, g, b, k, &cnt);
+    total += cnt;
+    rtotal += cgroup_slot_radial(c, k, cnt);
+  }
+  for (int m = 32; m >= 1; m >>= 1) { err |= __shfl_xor(err, m, 64); total += __shfl_xor(total, m, 64); }
+  for (int m = 32; m >= 1; m >>= 1) rtotal += __shfl_xor(rtotal, m, 64);
+  if (err) {
+    if (lane == 0) atomicOr(&c.ctrl->err, err);
+    return;
+  }
+  const bool refines = lane == 0 ? cgroup_rule(c, g, total) : total >= (long)c.min_focal_obs;
+  int nf = 0;
+  for (long k = b + lane; k < e; k += 64) {
+    const int i = c.group_cams[k];
+    const bool fo = refines && c.cam_cnt[i] > 0;
+    c.cam_focal[i] = (uint8_t)fo;
+    nf += fo;
+  }
+  for (int m = 32; m >= 1; m >>= 1) nf += __shfl_xor(nf, m, 64);
+  if (lane == 0) {
+    c.group_focal[g] = (uint8_t)refines;
+    if (refines) atomicAdd(&c.cs->n_groups, 1);
+    if (nf) atomicAdd(&c.ctrl->n_focal, nf);
+  }
+  {                                                                      // (cam_cnt is read, cam_focal is not: no lane waits for another)
+    const bool rr = lane == 0 ? cgroup_rule_radial(c, g, refines, rtotal) : refines && rtotal >= (long)c.min_focal_obs;
+    int nr = 0;
+    for (long k = b + lane; k < e; k += 64) {
+      const int i = c.group_cams[k];
+      const bool ra = cam_radial_rule(c, i, rr);
+      c.cam_radial[i] = (uint8_t)ra;
+      nr += ra;
+    }
+    for (int m = 32; m >= 1; m >>= 1) nr += __shfl_xor(nr, m, 64);
+    if (lane == 0) {
+      c.group_radial[g] = (uint8_t)rr;
+      if (nr) atomicAdd(&c.cr->n_radial, nr);
+    }
+  }
+}
 
 // grid ceil(T / 256) x 256; other = 0 evaluates the state, 1 the trial
 __global__ void __launch_bounds__(kThreads) ba_evaluate_kernel(Ctx c, int other, int flags) {
   if (skipped(c, flags)) return;
   const long t = (long)blockIdx.x * kThreads + threadIdx.x;
   if (t < c.T && !track_eval(c, c.ctrl->cur ^ other, t)) atomicOr(&c.ctrl->bad_e, 1);
+}
+// Radial: ... through the distorted projection
+__global__ void __launch_bounds__(kThreads) ba_evaluate_radial_kernel(CtxR c, int other, int flags) {
+  if (skipped(c, flags)) return;
+  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (t < c.T && !track_eval<Radial>(c, c.ctrl->cur ^ other, t)) atomicOr(&c.ctrl->bad_e, 1);
 }
 
 // one level of an osum: a wave per chunk of 4096, grid ceil(count / 4096) (at least 1) x 64.  On the last level action >= 0 feeds the
@@ -222,6 +293,11 @@ __global__ void __launch_bounds__(kThreads) ba_track_lin_kernel(Ctx c, int flags
   const long t = (long)blockIdx.x * kThreads + threadIdx.x;
   if (t < c.T) track_lin(c, c.ctrl->cur, t);
 }
+__global__ void __launch_bounds__(kThreads) ba_track_lin_radial_kernel(CtxR c, int flags) {
+  if (skipped(c, flags)) return;
+  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (t < c.T) track_lin<Radial>(c, c.ctrl->cur, t);
+}
 
 // a wave per camera that takes part, grid ceil(n / 4) x 256
 template <class Mode> __global__ void __launch_bounds__(kThreads) ba_cam_lin_kernel(typename Mode::Ctx c, int flags) {
@@ -250,6 +326,17 @@ __global__ void __launch_bounds__(kThreads) ba_group_lin_kernel(CtxS c, int flag
   const double d = wave_group_sum(c, g, lane, c.U + 27, 28);
   if (lane == 0) c.dg[g] = d;
 }
+// Radial.  ... the three sums of its 2 x 2 block
+__global__ void __launch_bounds__(kThreads) ba_group_lin_radial_kernel(CtxR c, int flags) {
+  if (skipped(c, flags)) return;
+  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (g >= c.G || !c.group_focal[g]) return;
+  double d[3];
+  wave_osum64<3>(c.group_offsets[g], c.group_offsets[g + 1], lane, [&](long k, double* acc) { group_term_block(c, c.group_cams[k], acc); }, d);
+  if (lane == 0)
+    for (int k = 0; k < 3; ++k) c.dg[3 * g + k] = d[k];
+}
 
 // threads [0, T): tracks, [T, T + n): cameras, Shared [T + n, T + n + G): groups; grid ceil of that / 256 x 256
 template <class Mode> __global__ void __launch_bounds__(kThreads) ba_factor_kernel(StepCtx<Mode> c, int flags) {
@@ -260,7 +347,10 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_factor_kern
   if (id < c.T) ok = track_factor(c, id, lambda);
   else if (id < c.T + c.n) ok = cam_factor<Mode>(c, id - c.T, lambda);
   else if constexpr (Mode::kGroups) {
-    if (id < c.T + c.n + c.G) ok = group_factor(c, id - c.T - c.n, lambda);
+    if (id < c.T + c.n + c.G) {
+      if constexpr (Mode::kRadial) ok = group_factor_radial(c, id - c.T - c.n, lambda);
+      else ok = group_factor(c, id - c.T - c.n, lambda);
+    }
   }
   if (!ok) atomicOr(&c.ctrl->bad_f, 1);
 }
@@ -296,6 +386,17 @@ __global__ void __launch_bounds__(kThreads) ba_group_half_kernel(CtxS c, int mod
   if (c.group_focal[g]) s = wave_group_sum(c, g, lane, c.Sp + 6, 7);
   if (lane == 0) group_half_finish(c, g, mode, c.ctrl->lambda, s);
 }
+// Radial.  ... of the seventh and eighth entries
+__global__ void __launch_bounds__(kThreads) ba_group_half_radial_kernel(CtxR c, int mode, int flags) {
+  if (skipped(c, flags)) return;
+  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  if (g >= c.G) return;
+  double s[2] = {0.0, 0.0};
+  if (c.group_focal[g])
+    wave_osum64<2>(c.group_offsets[g], c.group_offsets[g + 1], lane, [&](long k, double* acc) { group_term_pair(c, c.group_cams[k], acc); }, s);
+  if (lane == 0) group_half_finish_radial(c, g, mode, c.ctrl->lambda, s);
+}
 
 // threads [0, n): cameras, Shared [n, n + G): groups (the scalar update of a group)
 template <class Mode> __global__ void __launch_bounds__(kThreads) ba_update_kernel(StepCtx<Mode> c, int which, int flags) {
@@ -306,8 +407,13 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_update_kern
     else cam_update2<Mode>(c, id, c.ctrl->beta);
   } else if constexpr (Mode::kGroups) {
     if (id >= c.n + c.G) return;
-    if (which == 1) group_update1(c, id - c.n, c.ctrl->alpha, c.ctrl->lambda);
-    else group_update2(c, id - c.n, c.ctrl->beta);
+    if constexpr (Mode::kRadial) {
+      if (which == 1) group_update1_radial(c, id - c.n, c.ctrl->alpha);
+      else group_update2_radial(c, id - c.n, c.ctrl->beta);
+    } else {
+      if (which == 1) group_update1(c, id - c.n, c.ctrl->alpha, c.ctrl->lambda);
+      else group_update2(c, id - c.n, c.ctrl->beta);
+    }
   }
 }
 
@@ -320,7 +426,10 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_apply_kerne
   if (id < c.T) ok = track_half<Mode>(c, cur, id, 2);
   else if (id < c.T + c.n) ok = cam_apply<Mode>(c, cur, id - c.T);
   else if constexpr (Mode::kGroups) {
-    if (id < c.T + c.n + c.G) group_apply(c, cur, id - c.T - c.n);
+    if (id < c.T + c.n + c.G) {
+      if constexpr (Mode::kRadial) group_apply_radial(c, cur, id - c.T - c.n);
+      else group_apply(c, cur, id - c.T - c.n);
+    }
   }
   if (!ok) atomicOr(&c.ctrl->bad_a, 1);
 }
@@ -346,7 +455,7 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_write_kerne
 // groups (track setup, evaluate, the track linearisation, accept, the osum) are one kernel for all modes, on the base of the context.
 template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iters, double pcg_tol, void* ws, size_t ws_bytes, float* class_ms,
                               long* class_launches, void* stream) {
-  constexpr bool kGroups = Mode::kGroups, kPrior = Mode::kPrior;
+  constexpr bool kGroups = Mode::kGroups, kPrior = Mode::kPrior, kRadial = Mode::kRadial;
   using BaseMode = typename Mode::Base;                                 // the kernels of the phases that the prior does not touch
   LOFTR_CHECK_ARG(ws);
   const int st = check_args<Mode>(c, max_iters, pcg_iters, pcg_tol, false);
@@ -403,7 +512,8 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   };
   auto camera_half = [&](int mode, int flags) {
     hipLaunchKernelGGL(ba_cam_half_kernel<BaseMode>, blocks(n, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf);
-    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_half_kernel, blocks(G, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf); }
+    if constexpr (kRadial) { hipLaunchKernelGGL(ba_group_half_radial_kernel, blocks(G, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf); }
+    else if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_half_kernel, blocks(G, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf); }
   };
   // osum of the cameras' prior terms v[0 .. n) into `action` (ba_prior_osum_kernel): one launch per level
   auto prior_osum = [&](const double* v, int action, int flags) {
@@ -422,7 +532,9 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   };
   // evaluate the state (other = 0) or the trial, then its cost and sum of |r|^2: the tracks' osum, with priors the cameras' added to it
   auto evaluate = [&](int other, int cost, int sq, int flags) {
-    hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), threads, 0, s, b, other, flags); after(kClsEvaluate);
+    if constexpr (kRadial) hipLaunchKernelGGL(ba_evaluate_radial_kernel, blocks(T, kThreads), threads, 0, s, cb, other, flags);
+    else hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), threads, 0, s, b, other, flags);
+    after(kClsEvaluate);
     const int f = other ? flags | kSkipBadE : flags;
     if constexpr (kPrior) {
       hipLaunchKernelGGL(ba_prior_eval_kernel, blocks(n, kThreads), threads, 0, s, b, pr, other, flags); after(kClsEvaluate);
@@ -438,15 +550,21 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   if (timed) mark();
   hipLaunchKernelGGL(ba_init_kernel, dim3(1), dim3(1), 0, s, b, groups_ctrl<Mode>(c)); after(kClsSetup);
   if constexpr (kPrior) { hipLaunchKernelGGL(ba_prior_init_kernel, dim3(1), dim3(1), 0, s, pr); after(kClsSetup); }
-  hipLaunchKernelGGL(ba_cam_setup_kernel<Mode::S>, blocks(n, kThreads), threads, 0, s, cb); after(kClsSetup);
+  if constexpr (kRadial) hipLaunchKernelGGL(ba_cam_setup_radial_kernel, blocks(n, kThreads), threads, 0, s, cb);
+  else hipLaunchKernelGGL(ba_cam_setup_kernel<Mode::S>, blocks(n, kThreads), threads, 0, s, cb);
+  after(kClsSetup);
   hipLaunchKernelGGL(ba_track_setup_kernel, blocks(T, kThreads), threads, 0, s, b); after(kClsSetup);
   hipLaunchKernelGGL(ba_groups_kernel<Mode>, blocks(n, 4), threads, 0, s, c); after(kClsSetup);
-  if constexpr (kGroups) { hipLaunchKernelGGL(ba_cgroups_kernel, blocks(G, 4), threads, 0, s, cb); after(kClsSetup); }
+  if constexpr (kRadial) { hipLaunchKernelGGL(ba_cgroups_radial_kernel, blocks(G, 4), threads, 0, s, cb); after(kClsSetup); }
+  else if constexpr (kGroups) { hipLaunchKernelGGL(ba_cgroups_kernel, blocks(G, 4), threads, 0, s, cb); after(kClsSetup); }
   evaluate(0, kActCost0, kActSq0, 0);
   for (int it = 0; it < max_iters && !failed; ++it) {
-    hipLaunchKernelGGL(ba_track_lin_kernel, blocks(T, kThreads), threads, 0, s, b, kNeedFresh); after(kClsLinearise);
+    if constexpr (kRadial) hipLaunchKernelGGL(ba_track_lin_radial_kernel, blocks(T, kThreads), threads, 0, s, cb, kNeedFresh);
+    else hipLaunchKernelGGL(ba_track_lin_kernel, blocks(T, kThreads), threads, 0, s, b, kNeedFresh);
+    after(kClsLinearise);
     hipLaunchKernelGGL(ba_cam_lin_kernel<Mode>, blocks(n, 4), threads, 0, s, c, kNeedFresh); after(kClsLinearise);
-    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_lin_kernel, blocks(G, 4), threads, 0, s, cb, kNeedFresh); after(kClsLinearise); }
+    if constexpr (kRadial) { hipLaunchKernelGGL(ba_group_lin_radial_kernel, blocks(G, 4), threads, 0, s, cb, kNeedFresh); after(kClsLinearise); }
+    else if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_lin_kernel, blocks(G, 4), threads, 0, s, cb, kNeedFresh); after(kClsLinearise); }
     hipLaunchKernelGGL(ba_factor_kernel<BaseMode>, blocks(T + n + G, kThreads), threads, 0, s, cb, 0); after(kClsFactor);
     hipLaunchKernelGGL(ba_track_half_kernel<BaseMode>, blocks(T, kThreads), threads, 0, s, cb, 0, kSkipBadF); after(kClsTrackHalf);
     camera_half(0, kSkipBadF);
@@ -532,6 +650,27 @@ extern "C" int loftr_bundle_adjust_shared(const long* offsets, long T, const int
   fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
   fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
   return run<Shared>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+}
+
+extern "C" size_t loftr_bundle_adjust_radial_workspace_bytes(long T, long N, int n_images) { return workspace_bytes<Radial>(T, N, n_images); }
+
+extern "C" int loftr_bundle_adjust_radial(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
+                                          long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
+                                          const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
+                                          const int* cam_group, const long* group_offsets, const int* group_cams, int G,
+                                          const double* radial_in, const uint8_t* refine_radial, double huber_px, int max_iters, int pcg_iters,
+                                          double pcg_tol, double ftol, int min_focal_obs, double focal_lo, double focal_hi, double radial_lo,
+                                          double radial_hi, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
+                                          uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal, double* radial_out,
+                                          uint8_t* cam_radial, uint8_t* group_radial, long* counts, void* ws, size_t ws_bytes, float* class_ms,
+                                          long* class_launches, void* stream) {
+  CtxR c{};
+  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
+       T_out, xyz_out, obs_active, cam_free, point_active, counts);
+  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
+  fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
+  fill_radial(c, radial_in, refine_radial, radial_lo, radial_hi, radial_out, cam_radial, group_radial);
+  return run<Radial>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
 }
 
 // with position priors on the camera centres (§18.3): mode 0 pose, 1 focal, 2 shared

@@ -247,11 +247,14 @@ class QueryLocalizer:
             out[k] = out[k][:C]
         return out, stats
 
-    def solve(self, K_query, thresh_px=3.0, conf=0.999, seed=0, timings=None):
+    def solve(self, K_query, thresh_px=3.0, conf=0.999, seed=0, timings=None, radial=None):
         """Localise every query -> ``QueryPoses``.  ``K_query`` [n_queries,3,3]: the queries' intrinsics (an array, or a tensor on the
         model's device).  The lookup, one readback of its counts, then ONE estimator call for all queries (``ops.estimate_absolute_poses``
         on a GPU model, a loop over ``evaluation.estimate_absolute_pose_native`` on a CPU model: the same result for one seed), whose
-        inlier bits are scattered back to match order.  timings: a list that receives (stage, ms) pairs of the GPU lookup stages."""
+        inlier bits are scattered back to match order.  timings: a list that receives (stage, ms) pairs of the GPU lookup stages.
+        ``radial`` [n_queries]: the radial coefficients of the queries' lenses; the query-side pixels are undistorted
+        (``undistort_points``) before the estimator call, and a correspondence whose pixel cannot be is left out (``kpts`` of the result
+        are then the undistorted pixels, and ``stats['n_not_undistorted']`` counts what was left out)."""
         dev, Q = self.model.device, self.n_queries
         if isinstance(K_query, torch.Tensor) and K_query.device != dev:
             raise LoftrHipError(f"QueryLocalizer.solve: K_query on {K_query.device}, the model on {dev}; there is no silent fallback")
@@ -260,6 +263,22 @@ class QueryLocalizer:
             raise ValueError(f"QueryLocalizer.solve: expected K_query [{Q},3,3], got {tuple(Kq.shape)}")
         out, stats = self.correspondences(timings=timings)
         C, M = stats["n_correspondences"], self.n_matches
+        if radial is not None:
+            from .radial import undistort_points
+            if isinstance(radial, torch.Tensor) and radial.device != dev:
+                raise LoftrHipError(f"QueryLocalizer.solve: radial on {radial.device}, the model on {dev}; there is no silent fallback")
+            rad = torch.as_tensor(radial).detach().to(dev, torch.float64)
+            if tuple(rad.shape) != (Q,):
+                raise ValueError(f"QueryLocalizer.solve: expected radial [{Q}], got {tuple(rad.shape)}")
+            K64 = torch.as_tensor(K_query).detach().to(dev, torch.float64)
+            xy, ok = undistort_points(out["kpts"], out["q_ids"].to(torch.int32), K64, rad)
+            for k in ("pts3d", "q_ids", "match", "point", "conf"):
+                out[k] = out[k][ok].contiguous()
+            out["kpts"] = xy[ok].contiguous()
+            out["q_offsets"] = torch.zeros_like(out["q_offsets"])
+            out["q_offsets"][1:] = torch.cumsum(torch.bincount(out["q_ids"].to(torch.int64), minlength=Q), 0)
+            stats["n_not_undistorted"], C = C - int(out["q_ids"].numel()), int(out["q_ids"].numel())
+            stats["n_correspondences"] = C
         if dev.type == "cuda":
             R, t, inl, n = ops.estimate_absolute_poses(out["pts3d"], out["kpts"], out["q_ids"], Kq, thresh_px, conf, seed)
         else:

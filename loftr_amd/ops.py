@@ -1532,6 +1532,22 @@ _BA_MODES = {
                              "cam_offsets [n+1], cam_obs [N], refine_focal [n], cam_group [n], group_offsets [G+1] with 1 <= G <= n and "
                              "group_cams [n]",
                              "; cam_group / group_offsets / group_cams must group the images by camera in ascending order")}
+# ... and the grouped mode with one radial coefficient per group, which takes no priors and so is no row of the table
+# above: two more inputs after G, three more outputs
+_s = _BA_MODES["bundle_adjust_shared"]
+_BA_RADIAL_MODE = {"bundle_adjust_radial": (_s[0] + (("radial", "float64", 1), ("refine_radial", "uint8", 1)),
+                                            _s[1] + (("radial", "n", (), "float64"), ("cam_radial", "n", (), "uint8"),
+                                                     ("group_radial", "G", (), "uint8")),
+                                            _s[2] + ", radial [n] and refine_radial [n]", _s[3])}
+del _s
+
+
+def _ba_radial_params(what, radial_lo, radial_hi):
+    import math
+    ok = all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (radial_lo, radial_hi))
+    if not (ok and math.isfinite(radial_lo) and math.isfinite(radial_hi) and radial_lo <= radial_hi):
+        raise ValueError(f"{what}: the radial bounds must be finite with lo <= hi, got {radial_lo}, {radial_hi}")
+    return float(radial_lo), float(radial_hi)
 
 
 # Position priors on the camera centres are one more row of any mode: three inputs, one output, 24 counts, and ONE routine
@@ -1542,10 +1558,11 @@ _BA_PRIOR_OUT = (("cam_prior", "n", (), "uint8"),)
 _BA_PRIOR_MODE = {"bundle_adjust": 0, "bundle_adjust_focal": 1, "bundle_adjust_shared": 2}
 
 
-def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None):
+def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None, radial=None):
     """The body of all eight: the table check, the shapes, the parameters, zeroed outputs, the timing buffers (per kernel class, not per
-    stage: the median launch and the total, and the launches issued), the call.  prior: None, or (prior_xyz, prior_sigma, prior_mask)."""
-    extra_in, extra_out, shapes, rule = _BA_MODES[call]
+    stage: the median launch and the total, and the launches issued), the call.  prior: None, or (prior_xyz, prior_sigma, prior_mask);
+    radial: None, or (radial_lo, radial_hi) of the mode with a radial coefficient."""
+    extra_in, extra_out, shapes, rule = _BA_MODES[call] if radial is None else _BA_RADIAL_MODE[call]
     name = call if prior is None else "bundle_adjust_prior"
     what, hint = (name + "_host", name) if B is _Host else \
         (name, f"the bundle-adjustment kernels have no CPU fallback; the host routine is {name}_host")
@@ -1554,13 +1571,13 @@ def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None):
         _check_args(B, what, hint, _BA_PRIOR_IN, prior)
     offsets, obs_image, obs_xy, obs_mask, xyz, K, Tc, fixed, cam_offsets, cam_obs = arrays[:10]
     N, n, T = obs_image.shape[0], K.shape[0], offsets.shape[0] - 1
-    refine, groups = arrays[10:11], arrays[11:]          # (refine_focal,) and (cam_group, group_offsets, group_cams), or empty
+    refine, groups, rad = arrays[10:11], arrays[11:14], arrays[14:]     # (refine_focal,), (cam_group, group_offsets, group_cams), (radial, refine_radial), or empty
     size = {"T": T, "N": N, "n": n}
     if groups:
         size["G"] = G = groups[1].shape[0] - 1
     if T < 0 or tuple(obs_xy.shape) != (N, 2) or obs_mask.shape[0] != N or tuple(xyz.shape) != (T, 3) or tuple(K.shape) != (n, 3, 3) or \
             tuple(Tc.shape) != (n, 4, 4) or fixed.shape[0] != n or cam_offsets.shape[0] != n + 1 or cam_obs.shape[0] != N or \
-            any(x.shape[0] != n for x in (*refine, *groups[::2])) or (groups and (G < 0 or G > n or (n > 0 and G == 0))):
+            any(x.shape[0] != n for x in (*refine, *groups[::2], *rad)) or (groups and (G < 0 or G > n or (n > 0 and G == 0))):
         raise _lib.LoftrHipError(f"{what}: expected offsets [T+1], obs_image [N], obs_xy [N,2], obs_mask [N], xyz [T,3], K [n,3,3], "
                                  f"T_cam_from_world [n,4,4], fixed [n], {shapes}, got {[tuple(a.shape) for a in arrays]}")
     if prior is not None and (tuple(prior[0].shape) != (n, 3) or tuple(prior[1].shape) != (n, 3) or prior[2].shape[0] != n):
@@ -1569,6 +1586,8 @@ def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None):
     params = _ba_params(what, *params)
     if focal is not None:
         params += _ba_focal_params(what, *focal)
+    if radial is not None:
+        params += _ba_radial_params(what, *radial)
     arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
     a = [B.ptr(x) for x in arrays]
     if prior is not None:
@@ -1578,7 +1597,7 @@ def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None):
     ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
     launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
     cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
-    B.call(call, (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], *a[10:11], n, a[8], a[9], *a[11:], *([G] if groups else []), *params,
+    B.call(call, (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], *a[10:11], n, a[8], a[9], *a[11:14], *([G] if groups else []), *a[14:], *params,
                   *[B.ptr(out[k]) for k in out]),
            _TABLE_RULES + rule, offsets, ws=(T, N, n), tail=(cast(ms), cast(launches)))
     if timings is not None:
@@ -1701,6 +1720,77 @@ def bundle_adjust_shared(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_fro
                           (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
                            group_offsets, group_cams),
                           (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings)
+
+
+def bundle_adjust_radial_host(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal,
+                              cam_group, group_offsets, group_cams, radial, refine_radial, huber_px, max_iters, pcg_iters, pcg_tol, ftol,
+                              min_focal_obs, focal_lo, focal_hi, radial_lo, radial_hi):
+    """loftr_bundle_adjust_radial_host: the host routine that DEFINES the bundle adjustment with one focal step and one radial coefficient
+    per group of images (include/loftr_hip.h) on numpy arrays: those of bundle_adjust_shared_host plus radial [n] f64 (the
+    start values) and refine_radial [n] u8.  -> its dict plus radial [n] f64, cam_radial [n] u8 and group_radial [G] u8; counts[15] is the
+    number of images that refine their radial coefficient."""
+    return _bundle_adjust(_Host, "bundle_adjust_radial",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
+                           group_offsets, group_cams, radial, refine_radial),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), None, radial=(radial_lo, radial_hi))
+
+
+@_on_device
+def bundle_adjust_radial(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
+                         group_offsets, group_cams, radial, refine_radial, huber_px, max_iters, pcg_iters, pcg_tol, ftol, min_focal_obs,
+                         focal_lo, focal_hi, radial_lo, radial_hi, timings=None):
+    """loftr_bundle_adjust_radial: the kernels of the grouped focal and radial steps (csrc/bundle_gpu.hip) on GPU tensors; the same result
+    as bundle_adjust_radial_host bit for bit, the same timing classes and single readback as bundle_adjust."""
+    return _bundle_adjust(_Gpu, "bundle_adjust_radial",
+                          (offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world, fixed, cam_offsets, cam_obs, refine_focal, cam_group,
+                           group_offsets, group_cams, radial, refine_radial),
+                          (huber_px, max_iters, pcg_iters, pcg_tol, ftol), (min_focal_obs, focal_lo, focal_hi), timings, radial=(radial_lo, radial_hi))
+
+
+# ---- pixels without the radial coefficient of their camera (csrc/radial_core.h, csrc/undistort.hip, csrc/undistort_gpu.hip; DESIGN §18.4) ----
+UNDISTORT_COUNTS = 8
+UNDISTORT_ERRORS = ((1, "image outside [0, n_images)"),)                                  # bits of counts[1]
+_UND_ARGS = (("xy", "float32", 2), ("image", "int32", 1), ("K", "float64", 3), ("radial", "float64", 1))
+
+
+def _undistort(B, name, arrays):
+    what, hint = (name + "_host", name) if B is _Host else (name, f"the kernel has no CPU fallback; the host routine is {name}_host")
+    _check_args(B, what, hint, _UND_ARGS, arrays)
+    xy, image, K, radial = arrays
+    M, n = xy.shape[0], K.shape[0]
+    if tuple(xy.shape) != (M, 2) or image.shape[0] != M or tuple(K.shape) != (n, 3, 3) or radial.shape[0] != n:
+        raise _lib.LoftrHipError(f"{what}: expected xy [M,2], image [M], K [n,3,3] and radial [n], got {[tuple(a.shape) for a in arrays]}")
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = {"xy": B.zeros((M, 2), "float32", xy), "ok": B.zeros((M,), "uint8", xy), "counts": B.zeros(UNDISTORT_COUNTS, "int64", xy)}
+    args = (a[0], a[1], M, a[2], a[3], n, *[B.ptr(out[k]) for k in out])
+    if B is _Host:
+        status = getattr(_lib.load(), f"loftr_{name}_host")(*args)
+        if not (status == -1 and int(out["counts"][1]) != 0):                            # a bad image is reported through counts[1], as on the GPU
+            check(status, f"loftr_{name}_host")
+    else:
+        B.call(name, args, "", xy)
+    return out
+
+
+def undistort_points_host(xy, image, K, radial):
+    """loftr_undistort_points_host: the host routine that DEFINES the pinhole pixels of distorted ones (include/loftr_hip.h)
+    on numpy arrays: xy [M,2] f32, image [M] i32, K [n,3,3] f64, radial [n] f64.  -> dict of numpy arrays: xy [M,2] f32 (NaN where not
+    ok), ok [M] u8, counts [8] i64 (points ok, error bits, points not ok)."""
+    return _undistort(_Host, "undistort_points", (xy, image, K, radial))
+
+
+def distort_points_host(xy, image, K, radial):
+    """loftr_distort_points_host: the other direction from the same text (pinhole pixels -> distorted ones); arguments and result as
+    undistort_points_host."""
+    return _undistort(_Host, "distort_points", (xy, image, K, radial))
+
+
+@_on_device
+def undistort_points(xy, image, K, radial):
+    """loftr_undistort_points: the kernel (csrc/undistort_gpu.hip, a thread per point) on GPU tensors; the same result as
+    undistort_points_host bit for bit.  Nothing is read back here: the error bit is in counts[1], which the caller reads once."""
+    return _undistort(_Gpu, "undistort_points", (xy, image, K, radial))
 
 
 # ---- correspondence table of the images without a pose (csrc/register.hip, csrc/register_gpu.hip; DESIGN §19) --------------------------

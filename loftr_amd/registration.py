@@ -58,11 +58,12 @@ class Reconstruction:
     """What ``reconstruct_tracks`` returns: ``T_cam_from_world [n,4,4] f64`` (NaN for an image that never got a pose), ``posed [n]
     bool``, ``round_registered [n] i32`` (the round in which the image got its pose; 0 for the initial pair; -1 for never), ``points``
     (the final ``Points3D``), ``bundle`` (the final ``BundleResult``), ``stats`` (dict; ``stats['rounds']`` holds the per-round counts),
-    ``K [n,3,3] f64`` (the final intrinsics: the input's for an image that never refined its focal)."""
+    ``K [n,3,3] f64`` (the final intrinsics: the input's for an image that never refined its focal), ``radial [n] f64``
+    (the final radial coefficients of a run with ``radial`` or ``ba['refine_radial']``; else None)."""
 
-    def __init__(self, T_cam_from_world, posed, round_registered, points, bundle, stats, K=None):
+    def __init__(self, T_cam_from_world, posed, round_registered, points, bundle, stats, K=None, radial=None):
         self.T_cam_from_world, self.posed, self.round_registered = T_cam_from_world, posed, round_registered
-        self.points, self.bundle, self.stats, self.K = points, bundle, stats, K
+        self.points, self.bundle, self.stats, self.K, self.radial = points, bundle, stats, K, radial
         self.sfm = None                                                 # the relabelled atlas of SfmResult.reconstruct(complete=True / merge=True)
 
     def transformed(self, s, R, t):
@@ -226,7 +227,15 @@ def _follow_group(K_in, K_out, group, cam_focal, G):
     return K
 
 
-def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=None, min_angle_deg=1.5, **register_kw):
+def _follow_group_radial(k_in, k_out, group, cam_radial, G):
+    """k_out with the k of the images without cam_radial moved by the step k_out - k_in of a member of their group that has it (0 where
+    the group has none): the additive counterpart of _follow_group."""
+    step = torch.where(cam_radial, k_out - k_in, torch.full_like(k_out, float("-inf")))
+    per_group = torch.full((G,), float("-inf"), dtype=k_out.dtype, device=k_out.device).scatter_reduce(0, group, step, "amax")
+    return torch.where(cam_radial | torch.isinf(per_group[group]), k_out, k_out + per_group[group])
+
+
+def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=None, min_angle_deg=1.5, radial=None, **register_kw):
     """Incremental reconstruction from tracks and an initial pair -> ``Reconstruction``.
 
     ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``, ``K [n,3,3]``; tensors on one device (GPU:
@@ -250,8 +259,16 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
 
     With ``ba={'refine_focal': True, 'camera_ids': ids}`` the images of one camera share one relative focal step; the
     members of a camera that did not carry it in an adjustment (not posed yet, say) have their fx, skew, fy scaled by the factor their
-    camera took, so that an image registered later starts from its camera's current focal."""
+    camera took, so that an image registered later starts from its camera's current focal.
+
+    ``radial`` (``[n]``): the radial coefficients of the lenses, ``obs_xy`` being the stored, distorted pixels.  The
+    triangulations and ``register_images`` then read ``undistort_points(obs_xy, obs_image, K, radial)``, recomputed after every
+    adjustment.  With ``ba={'refine_focal': True, 'refine_radial': True[, 'camera_ids': ids]}`` the adjustment reads the stored pixels
+    and refines the coefficients, starting from ``radial`` (default zeros); the members of a camera that did not carry it take their
+    camera's step, as with the focal.  Without ``refine_radial`` the coefficients are taken as known: the adjustment is the pinhole
+    call on the undistorted pixels.  ``Reconstruction.radial`` holds the final values."""
     from .bundle import bundle_adjust
+    from .radial import undistort_points
     what = "reconstruct_tracks"
     offsets, obs_image, obs_xy, K = _tensors(what, ("offsets", "obs_image", "obs_xy", "K"), (offsets, obs_image, obs_xy, K))
     _tracks.integers(what, "offsets", offsets)
@@ -285,6 +302,19 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     if ba.get("camera_ids") is not None:
         ba["camera_ids"] = torch.as_tensor(np.asarray(ba["camera_ids"].cpu() if isinstance(ba["camera_ids"], torch.Tensor)
                                                       else ba["camera_ids"])).to(dev)
+    fits_lens = ba.get("refine_radial") is not None
+    if fits_lens and ba["refine_radial"] is not True:
+        ba["refine_radial"] = torch.as_tensor(np.asarray(ba["refine_radial"].cpu() if isinstance(ba["refine_radial"], torch.Tensor)
+                                                         else ba["refine_radial"])).to(dev)
+    if "radial" in ba:
+        raise ValueError(f"{what}: the radial coefficients are an argument of the loop (radial=...), not of ba")
+    rad = None
+    if radial is not None or fits_lens:
+        rad = torch.zeros(n, dtype=torch.float64, device=dev) if radial is None else \
+            torch.as_tensor(np.asarray(radial.cpu() if isinstance(radial, torch.Tensor) else radial, np.float64)).to(dev)
+        if tuple(rad.shape) != (n,):
+            raise ValueError(f"{what}: expected radial [{n}], got {tuple(rad.shape)}")
+    pinhole = lambda K, rad: obs_xy if rad is None else undistort_points(obs_xy, obs_image, K, rad)[0]
     thresh_px = register_kw.get("thresh_px", 4.0)
     T = torch.full((n, 4, 4), float("nan"), dtype=torch.float64, device=dev)
     T[a] = torch.eye(4, dtype=torch.float64)
@@ -297,21 +327,29 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     round_registered[a] = round_registered[b] = 0
     rounds = []
 
-    def refine(T, posed, K, first=False):
-        """-> (points of the adjusted poses, the adjustment, the intrinsics that hold from here on)"""
-        pts = triangulate_posed(offsets, obs_image, obs_xy, K, T, posed, thresh_px, min_angle_deg)
+    def refine(T, posed, K, rad, first=False):
+        """-> (points of the adjusted poses, the adjustment, the intrinsics and radial coefficients that hold from here on, the pinhole
+        pixels under them)"""
+        xy = pinhole(K, rad)
+        pts = triangulate_posed(offsets, obs_image, xy, K, T, posed, thresh_px, min_angle_deg)
         if first and pts.stats["n_ok"] == 0:
             raise ValueError(f"{what}: the initial pair ({a}, {b}) triangulates nothing: {pts.stats['n_posed_observations']} observations in "
                              f"{pts.stats['n_tracks']} tracks, statuses {[pts.stats['n_' + s] for s in ops.TRI_STATUS]}")
-        res = bundle_adjust(offsets, obs_image, obs_xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **ba)
+        if fits_lens:                                                   # the adjustment fits the lens on the stored pixels
+            res = bundle_adjust(offsets, obs_image, obs_xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, radial=rad, **ba)
+        else:
+            res = bundle_adjust(offsets, obs_image, xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, **ba)
         K_in, K = K, getattr(res, "K", K)                               # (a result without refine_focal carries no K)
         if hasattr(res, "cam_group"):                                   # an image posed later joins its camera at the camera's scale
             K = _follow_group(K_in, K, res.cam_group.long(), res.cam_focal, res.group_focal.numel())
-        return triangulate_posed(offsets, obs_image, obs_xy, K, res.T_cam_from_world, posed, thresh_px, min_angle_deg), res, K
+        if fits_lens:
+            rad = _follow_group_radial(rad, res.radial, res.cam_group.long(), res.cam_radial, res.group_focal.numel())
+        xy = pinhole(K, rad)
+        return triangulate_posed(offsets, obs_image, xy, K, res.T_cam_from_world, posed, thresh_px, min_angle_deg), res, K, rad, xy
 
     for r in range(1, int(max_rounds) + 1):
-        pts, res, K = refine(T, posed, K, first=r == 1)
-        reg = register_images(offsets, obs_image, obs_xy, pts.xyz, pts.status, K, res.T_cam_from_world, posed, **register_kw)
+        pts, res, K, rad, xy = refine(T, posed, K, rad, first=r == 1)
+        reg = register_images(offsets, obs_image, xy, pts.xyz, pts.status, K, res.T_cam_from_world, posed, **register_kw)
         n_new, n_posed = torch.stack([reg.registered.sum(), reg.posed.sum()]).tolist()
         round_registered[reg.registered] = r
         T, posed = reg.T_cam_from_world, reg.posed
@@ -319,7 +357,7 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
                        "n_registered": n_new, "n_posed": n_posed})
         if n_new == 0 or n_posed == n:
             break
-    pts, res, K = refine(T, posed, K, first=not rounds)
+    pts, res, K, rad, _ = refine(T, posed, K, rad, first=not rounds)
     stats = {"rounds": rounds, "n_rounds": len(rounds), "n_images": n, "n_posed": int(posed.sum()), "n_points": pts.stats["n_ok"],
              "rms_px_after": res.rms_px_after, "init": (a, b)}
-    return Reconstruction(res.T_cam_from_world, posed, round_registered, pts, res, stats, K)
+    return Reconstruction(res.T_cam_from_world, posed, round_registered, pts, res, stats, K, rad)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Bundle adjustment (loftr_amd/bundle.py, csrc/bundle_gpu.hip) on a MegaDepth-1500-shaped load.  One JSON line.
 
-    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--refine-focal] [--camera-groups G[,G...]] [--prior] [--no-host] [--out FILE]
+    python tools/micro/bundle_bench.py [--rows 1500] [--matches 1000] [--max-iters 30] [--pcg-iters 30] [--huber 0] [--refine-focal] [--camera-groups G[,G...]] [--radial] [--prior] [--no-host] [--out FILE]
 
 Load: the track lengths of tools/micro/atlas_bench.py's synthetic atlas (1500 rows over 806 images), observations as in
 tools/micro/triangulation_bench.py without outliers (one exact camera per image, one 3D point per track, every observation in a random
@@ -18,7 +18,11 @@ free camera starts 4-10 % off and the line holds two such legs on that load: "fi
 §18.2) the line holds that per-image leg as the reference point ("per_image") and one leg per G ("groups_G"): image i is of camera
 i mod G, every camera's focal -- the fixed-pose images' too -- starts off by one factor of 4-10 %, and the call is
 refine_focal=True, camera_ids=ids; per leg the trials, conjugate-gradient iterations, rms before and after, the largest focal error
-over all images and the wall time.  With --prior the line holds three legs on the default load, run in alternation
+over all images and the wall time.  With --camera-groups 1,8,806 --radial the load of every G is observed through one
+radial coefficient per camera, k drawn from U(-0.08, 0.08), and the line holds per G the shared-focal call of §18.2 on that load as the
+reference point ("groups_G_shared": today's best pinhole model; its equality with the host routine is §18.2's, not repeated here) and
+the radial call ("groups_G_radial": refine_focal=True, refine_radial=True, camera_ids=ids, start k = 0), with the largest focal and
+radial error over all images next to the figures above.  With --prior the line holds three legs on the default load, run in alternation
 --rounds times (no_prior, prior_masked, prior, no_prior, ...) after one warm-up of each: "no_prior" (the default call: images 0 and 1
 fixed), "prior_masked" (the kernels with priors and an all-zero prior_mask: the same result as no_prior, asserted), "prior" (no camera
 fixed, position_prior = the true centres + N(0, 0.05) per axis at prior_sigma = 0.05); per leg every wall time with its median and
@@ -41,8 +45,9 @@ from tools.micro.atlas_bench import DEV, HW, make_chunks                 # noqa:
 from tools.micro.triangulation_bench import rotations                    # noqa: E402
 
 
-def make_load(track_len, n_images, seed=0):
-    """-> (offsets, obs_image, obs_xy, obs_mask, xyz start, K, T start, fixed) on the device."""
+def make_load(track_len, n_images, seed=0, radial=None):
+    """-> (offsets, obs_image, obs_xy, obs_mask, xyz start, K, T start, fixed) on the device.  radial: None, or [n_images] coefficients
+    k of the lens the observations are made through, x_d = x (1 + k r^2) on normalised coordinates."""
     rng = np.random.default_rng(seed)
     R = rotations(rng, n_images, 20.0)
     c = rng.uniform([-2, -1, -0.5], [2, 1, 0.5], (n_images, 3))
@@ -68,7 +73,11 @@ def make_load(track_len, n_images, seed=0):
     lo, hi = torch.tensor([-2, -1.5, 3.0], device=DEV, dtype=torch.float64), torch.tensor([2, 1.5, 8.0], device=DEV, dtype=torch.float64)
     X = lo + (hi - lo) * torch.rand(n_tracks, 3, device=DEV, dtype=torch.float64, generator=g)
     image = torch.randint(0, n_images, (N,), device=DEV, generator=g)
-    p = torch.einsum("nij,nj->ni", K[image], torch.einsum("nij,nj->ni", T[image, :3, :3], X[track]) + T[image, :3, 3])
+    Y = torch.einsum("nij,nj->ni", T[image, :3, :3], X[track]) + T[image, :3, 3]
+    if radial is not None:                                              # the lens acts on the normalised point; its depth stays
+        x = Y[:, :2] / Y[:, 2:]
+        Y = torch.cat([x * (1 + radial.to(DEV)[image][:, None] * (x * x).sum(1, keepdim=True)), torch.ones_like(Y[:, 2:])], 1)
+    p = torch.einsum("nij,nj->ni", K[image], Y)
     xy = p[:, :2] / p[:, 2:] + 0.5 * torch.randn(N, 2, device=DEV, dtype=torch.float64, generator=g)
     xyz = (X + 0.05 * torch.randn(n_tracks, 3, device=DEV, dtype=torch.float64, generator=g)).to(torch.float32)
     fixed = torch.zeros(n_images, dtype=torch.bool, device=DEV)
@@ -112,8 +121,9 @@ def detune_groups(K, ids, seed=5):
     return K
 
 
-def leg(inputs, fixed, kw, n_tracks, args):
-    """One timed leg: a warm-up, 3 timed calls, one call with events, the host routine and the equality assertion -> dict."""
+def leg(inputs, fixed, kw, n_tracks, args, host=True):
+    """One timed leg: a warm-up, 3 timed calls, one call with events, the host routine and the equality assertion (host=False: neither)
+    -> dict."""
     out = {}
     run = lambda timings=None: bundle_adjust(*inputs, fixed=fixed, timings=timings, **kw)
     results = [run()]                                                   # warm-up (kernel load)
@@ -140,7 +150,7 @@ def leg(inputs, fixed, kw, n_tracks, args):
     if "position_prior" in kw:                                          # §18.3: an evaluation has three more launches per level of the cameras' sum
         del out["launches_skipped_at_least"]
     out["stats"] = res.stats
-    if not args.no_host:
+    if host and not args.no_host:
         t = time.perf_counter()
         host_kw = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in kw.items()}
         host = bundle_adjust(*[x.cpu() for x in inputs], fixed=fixed.cpu(), **host_kw)
@@ -211,6 +221,8 @@ def main():
                     help="the focal of every free camera off by 4-10 %%: a fixed-intrinsics leg and a refine_focal=True leg on that load")
     ap.add_argument("--camera-groups", default=None,
                     help="comma-separated group counts G (image i is of camera i mod G): a per-image refine_focal leg and one shared leg per G")
+    ap.add_argument("--radial", action="store_true",
+                    help="(with --camera-groups; DESIGN §18.4) one radial coefficient per camera: a shared-focal leg and a radial leg per G")
     ap.add_argument("--prior", action="store_true", help="position priors (DESIGN §18.3): the no_prior, prior_masked and prior legs in alternation")
     ap.add_argument("--rounds", type=int, default=5, help="(--prior) timed calls per leg")
     ap.add_argument("--no-host", action="store_true", help="skip the host routine (and the equality assertion)")
@@ -231,6 +243,21 @@ def main():
     if args.prior:
         out["workload"] += "_position_priors"
         out.update(prior_legs(inputs, fixed, kw, n_images, args))
+    elif args.camera_groups and args.radial:
+        out["workload"] += "_camera_groups_radial"
+        for G in (int(g) for g in args.camera_groups.split(",")):
+            ids = torch.arange(n_images, device=DEV) % G
+            k_true = torch.from_numpy(np.random.default_rng(9).uniform(-0.08, 0.08, G)).to(DEV)[ids]
+            *inputs, fixed = make_load(lens, n_images, radial=k_true)
+            K_true = inputs[5]
+            err = lambda K: float((K[:, 0, 0] / K_true[:, 0, 0] - 1).abs().max())
+            inputs[5] = detune_groups(K_true, ids)
+            d, res = leg(inputs, fixed, dict(kw, refine_focal=True, camera_ids=ids), lens.numel(), args, host=False)
+            out[f"groups_{G}_shared"] = dict(d, focal_error_before=round(err(inputs[5]), 5), focal_error_after=round(err(res.K), 5))
+            d, res = leg(inputs, fixed, dict(kw, refine_focal=True, refine_radial=True, camera_ids=ids), lens.numel(), args)
+            out[f"groups_{G}_radial"] = dict(d, focal_error_before=round(err(inputs[5]), 5), focal_error_after=round(err(res.K), 5),
+                                             radial_error_before=round(float(k_true.abs().max()), 5),
+                                             radial_error_after=round(float((res.radial - k_true).abs().max()), 5))
     elif args.camera_groups:
         K_true = inputs[5]
         err = lambda K: float((K[:, 0, 0] / K_true[:, 0, 0] - 1).abs().max())
