@@ -56,6 +56,25 @@ _OUT_RADIAL = ("radial", "cam_radial", "group_radial")
 _ARGS = ("offsets", "obs_image", "obs_xy", "obs_mask", "xyz", "K", "T_cam_from_world")
 
 
+def _shaped(what, name, v, shape, must=None):
+    if tuple(v.shape) != shape:
+        raise ValueError(f"{what}: {name} must {must or f'have shape {shape}'}, got {tuple(v.shape)}")
+    return v
+
+
+def _beside(what, name, v, gpu, like, shape=None, must=None):
+    """The optional argument ``v`` must live on the side of the others (``gpu``: on the device of ``like``) -> the tensor on the GPU, a
+    numpy array on the host, of ``shape`` where one is given."""
+    on_gpu = isinstance(v, torch.Tensor) and v.is_cuda
+    if on_gpu != gpu or (gpu and v.device != like.device):
+        raise ValueError(f"{what}: {name} is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no silent "
+                         "fallback: move it to their device")
+    v = v.detach() if isinstance(v, torch.Tensor) else np.asarray(v)
+    if not on_gpu and isinstance(v, torch.Tensor):
+        v = v.numpy()
+    return v if shape is None else _shaped(what, name, v, shape, must)
+
+
 class BundleResult:
     """What ``bundle_adjust`` returns (tensors on the device of the input).
 
@@ -172,67 +191,38 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             raise ValueError(f"{what}: radial_bounds must be a pair (lo, hi), got {radial_bounds!r}")
         rbounds = ops._ba_radial_params(what, *radial_bounds)
     gpu = _tracks.one_device(what, _ARGS + ("fixed",), args + ([] if fixed is None else [fixed]))   # ("fixed" is named only when given)
+    nK, beside = len(K), lambda name, v, *shape: _beside(what, name, v, gpu, args[0], *shape)
     if refine_radial is not None:
-        nK = len(K)
-        for k, v in (("refine_radial", refine_radial), ("radial", radial)):
-            if v is None or v is True:
-                continue
-            on_gpu = isinstance(v, torch.Tensor) and v.is_cuda
-            if on_gpu != gpu or (gpu and v.device != args[0].device):
-                raise ValueError(f"{what}: {k} is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no silent "
-                                 "fallback: move it to their device")
-            if not on_gpu:
-                v = v.detach().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            if tuple(v.shape) != (nK,):
-                raise ValueError(f"{what}: {k} must have shape ({nK},), got {tuple(v.shape)}")
-            if k == "radial":
-                radial = v.detach().to(torch.float64).contiguous() if gpu else np.ascontiguousarray(v, np.float64)
-            else:
-                refine_radial = v
-        if radial is None:
+        if refine_radial is not True:
+            refine_radial = beside("refine_radial", refine_radial, (nK,))
+        if radial is not None:
+            radial = beside("radial", radial, (nK,))
+            radial = radial.to(torch.float64).contiguous() if gpu else np.ascontiguousarray(radial, np.float64)
+        else:
             radial = torch.zeros(nK, dtype=torch.float64, device=args[0].device) if gpu else np.zeros(nK, np.float64)
         if camera_ids is None:                                           # every image a camera of its own
             camera_ids = torch.arange(nK, dtype=torch.int64, device=args[0].device) if gpu else np.arange(nK, dtype=np.int64)
     neg_id = None
     if camera_ids is not None:
-        on_gpu = isinstance(camera_ids, torch.Tensor) and camera_ids.is_cuda
-        if on_gpu != gpu or (gpu and camera_ids.device != args[0].device):
-            raise ValueError(f"{what}: camera_ids is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no "
-                             "silent fallback: move it to their device")
-        if not on_gpu:
-            camera_ids = camera_ids.detach().numpy() if isinstance(camera_ids, torch.Tensor) else np.asarray(camera_ids)
+        camera_ids = beside("camera_ids", camera_ids)
         _tracks.integers(what, "camera_ids", camera_ids)
-        if tuple(camera_ids.shape) != (len(K),):
-            raise ValueError(f"{what}: camera_ids must have shape ({len(K)},), got {tuple(camera_ids.shape)}")
-        if on_gpu:
-            neg_id = (camera_ids.detach() < 0).any().to(torch.int64).reshape(1)          # read with the counts: the one readback
+        _shaped(what, "camera_ids", camera_ids, (nK,))
+        if gpu:
+            neg_id = (camera_ids < 0).any().to(torch.int64).reshape(1)                    # read with the counts: the one readback
         elif camera_ids.size and camera_ids.min() < 0:
             raise ValueError(f"{what}: camera_ids must not be negative")
     if focal is not None and refine_focal is not True:
-        on_gpu = isinstance(refine_focal, torch.Tensor) and refine_focal.is_cuda
-        if on_gpu != gpu or (gpu and refine_focal.device != args[0].device):
-            raise ValueError(f"{what}: refine_focal is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no "
-                             "silent fallback: move it to their device")
-        if not on_gpu:
-            refine_focal = refine_focal.detach().numpy() if isinstance(refine_focal, torch.Tensor) else np.asarray(refine_focal)
-        if tuple(refine_focal.shape) != (len(K),):
-            raise ValueError(f"{what}: refine_focal must be None, True or a mask of shape ({len(K)},), got {tuple(refine_focal.shape)}")
+        refine_focal = beside("refine_focal", refine_focal, (nK,), f"be None, True or a mask of shape ({nK},)")
     prior = None
     if position_prior is not None:
-        given = [("position_prior", position_prior)] + [(k, v) for k, v in (("prior_sigma", prior_sigma), ("prior_mask", prior_mask))
-                                                        if v is not None and not isinstance(v, (int, float))]
-        for k, v in given:
-            on_gpu = isinstance(v, torch.Tensor) and v.is_cuda
-            if on_gpu != gpu or (gpu and v.device != args[0].device):
-                raise ValueError(f"{what}: {k} is on the {'GPU' if on_gpu else 'CPU'}, the other arguments are not; there is no silent "
-                                 "fallback: move it to their device")
-        nK = len(K)
-        conv = (lambda v: v.detach().to(torch.float64)) if gpu else \
-            (lambda v: np.asarray(v.detach().numpy() if isinstance(v, torch.Tensor) else v, np.float64))
+        pxyz = beside("position_prior", position_prior)
+        if prior_sigma is not None and not isinstance(prior_sigma, (int, float)):
+            prior_sigma = beside("prior_sigma", prior_sigma)
+        if prior_mask is not None and not isinstance(prior_mask, (int, float)):
+            prior_mask = beside("prior_mask", prior_mask)
+        conv = (lambda v: v.to(torch.float64)) if gpu else (lambda v: np.asarray(v, np.float64))
         xp = torch if gpu else np
-        pxyz = conv(position_prior)
-        if tuple(pxyz.shape) != (nK, 3):
-            raise ValueError(f"{what}: position_prior must have shape ({nK}, 3), got {tuple(pxyz.shape)}")
+        pxyz = _shaped(what, "position_prior", conv(pxyz), (nK, 3))
         if isinstance(prior_sigma, (int, float)) and not isinstance(prior_sigma, bool):
             if not (prior_sigma > 0 and prior_sigma < float("inf")):
                 raise ValueError(f"{what}: prior_sigma must be positive and finite, got {prior_sigma}")
@@ -250,11 +240,7 @@ def bundle_adjust(offsets, obs_image, obs_xy, obs_mask, xyz, K, T_cam_from_world
             pm = (xp.isfinite(pxyz).sum(1) == 3)
             pm = pm.to(torch.uint8) if gpu else pm.astype(np.uint8)
         else:
-            pm = prior_mask.detach() if isinstance(prior_mask, torch.Tensor) else np.asarray(prior_mask)
-            if not gpu and isinstance(pm, torch.Tensor):
-                pm = pm.numpy()
-            if tuple(pm.shape) != (nK,):
-                raise ValueError(f"{what}: prior_mask must have shape ({nK},), got {tuple(pm.shape)}")
+            pm = _shaped(what, "prior_mask", prior_mask if hasattr(prior_mask, "shape") else np.asarray(prior_mask), (nK,))
             pm = (pm != 0).to(torch.uint8) if gpu else (pm != 0).astype(np.uint8)
         prior = (pxyz.contiguous(), psig.contiguous(), pm) if gpu else (np.ascontiguousarray(pxyz), np.ascontiguousarray(psig), pm)
     for n, a in zip(_ARGS[:2], args[:2]):

@@ -4,14 +4,14 @@
 // include/loftr_hip.h).  What Ceres / COLMAP's bundle adjuster is used for after triangulation; neither is in this image, so this is a
 // statement of the published method (Triggs et al., "Bundle Adjustment -- A Modern Synthesis"; Agarwal et al., "Bundle Adjustment in
 // the Large"), NOT of their source.  PARITY UNPINNED against them.
-// These functions DEFINE the result: loftr_bundle_adjust / _focal / _shared (bundle_gpu.hip) reproduce it bit for bit, which is why all
-// the arithmetic, every per-item step, the context fill and the argument checks live in bundle_core.h and why this file is only the
-// sequence of phases and the order-defined sums.  The sequence is ONE template, run<Mode>, and the three entry points are its three
-// instantiations: Pose (§18), Focal (§18.1: one focal step per camera), Shared (§18.2: one per group of cameras, whose group phases
-// are `if constexpr` in the sequence).  Position priors on the camera centres (§18.3) are a trait of the mode as well: PoseP, FocalP and
-// SharedP run the same sequence with the prior's steps, loftr_bundle_adjust_prior_host picks one by `mode`.  Radial (§18.4) is the
-// grouped mode with an 8-wide camera block and two unknowns per group, the second an additive step of one radial coefficient; its
-// steps stand behind `if constexpr (kRadial)` in the same sequence, and it alone reads the distorted projection.
+// These functions DEFINE the result: the kernels of bundle_gpu.hip reproduce it bit for bit, which is why all the arithmetic, every
+// per-item step, the context fill and the argument checks live in bundle_core.h and why this file is only the sequence of phases and
+// the order-defined sums.  The sequence is ONE template, run<Mode>, and a mode is a row of traits (bundle_core.h): Pose
+// (§18), Focal (§18.1: one focal step per camera), Shared (§18.2: one per group of cameras), Radial (§18.4: the grouped mode with an
+// 8-wide camera block and two unknowns per group, the second an additive step of one radial coefficient), and PoseP, FocalP, SharedP
+// (§18.3: position priors on the camera centres).  The sequence asks the traits only WHETHER a phase has a group part (kGroups) or a
+// prior part (kPrior); what that part is in a mode is the core's `<Mode>` step.  An entry point builds the arguments' superset (Args)
+// and enters its mode; loftr_bundle_adjust_prior_host picks one by `mode` through the one list of modes (with_mode).
 #include <stdint.h>
 #include <vector>
 #include "../../include/loftr_hip.h"
@@ -53,24 +53,17 @@ template <int W, class F> void cam_sum(const Ctx& c, long i, F term, double* out
   const long b = c.cam_offsets[i];
   osum64<W>(c.cam_offsets[i + 1] - b, [&](long e, double* a) { const long o = c.cam_obs[b + e]; if (c.obs_active[o]) term(o, a); }, out);
 }
-// a group's osum64: element l is the l-th member
-double group_sum(const CtxS& c, long g, const double* v, long stride) {
-  const long b = c.group_offsets[g];
-  double out;
-  osum64<1>(c.group_offsets[g + 1] - b, [&](long e, double* a) { group_term(c, c.group_cams[b + e], v, stride, a); }, &out);
-  return out;
-}
-
-// Radial: a group's osum64 of M values per member
-template <int M, class F> void group_sum_radial(const CtxR& c, long g, F term, double* out) {
+// a group's osum64 of M values per member: element l is the l-th member
+template <int M, class F> void group_sum(const CtxS& c, long g, F term, double* out) {
   const long b = c.group_offsets[g];
   osum64<M>(c.group_offsets[g + 1] - b, [&](long e, double* a) { term(c.group_cams[b + e], a); }, out);
 }
 
-// the sequence of phases of every mode; c holds the problem and the result.  The group phases exist for Shared and Radial only.
+// the sequence of phases of every mode; c holds the problem and the result.  The group phases exist for the modes with kGroups only;
+// what a group step is in a mode is the core's business.
 template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iters, double pcg_tol) {
-  constexpr int S = Mode::S, kU = kTri<S>;
-  constexpr bool kGroups = Mode::kGroups, kRadial = Mode::kRadial;
+  constexpr int S = Mode::S, kU = kTri<S>, GW = Mode::GW, kD = kTri<GW>;
+  constexpr bool kGroups = Mode::kGroups;
   using TMode = TrackMode<Mode>;
   const int st = check_args<Mode>(c, max_iters, pcg_iters, pcg_tol, true);
   if (st != LOFTR_OK) return st;
@@ -80,12 +73,8 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   Ctrl& s = *c.ctrl;
   ctrl_init(c, groups_ctrl<Mode>(c));
   if constexpr (Mode::kPrior) ctrl_init_prior(c.pr);
-  if constexpr (kRadial) c.cr->n_radial = 0;
-  for (long i = 0; i < n; ++i) {
-    cam_setup(c, i);
-    if constexpr (S >= 7) cam_setup_focal(c, i);
-    if constexpr (kRadial) cam_setup_radial(c, i);
-  }
+  cam_setup_ctrl<Mode>(c);
+  for (long i = 0; i < n; ++i) cam_setup<Mode>(c, i);
   for (long t = 0; t < T; ++t) {
     long cnt;
     s.err |= track_setup(c, t, &cnt);
@@ -116,36 +105,7 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   }
   if (s.err) return LOFTR_ERR_BAD_ARG;
   if constexpr (kGroups) {
-    for (long g = 0; g < c.G; ++g) {
-      long b, e, total = 0, rtotal = 0;
-      int err = 0;
-      if (!cgroup_range(c, g, &b, &e)) { s.err |= kBadCamGroups; continue; }
-      for (long k = b; k < e; ++k) {
-        long cnt;
-        err |= cgroup_slot(c, g, b, k, &cnt);
-        total += cnt;
-        if constexpr (kRadial) rtotal += cgroup_slot_radial(c, k, cnt);
-      }
-      s.err |= err;
-      if (err) continue;
-      const bool refines = cgroup_rule(c, g, total);
-      c.group_focal[g] = (uint8_t)refines;
-      c.cs->n_groups += refines;
-      for (long k = b; k < e; ++k) {
-        const int i = c.group_cams[k];
-        c.cam_focal[i] = (uint8_t)(refines && c.cam_cnt[i] > 0);
-        s.n_focal += c.cam_focal[i];
-      }
-      if constexpr (kRadial) {
-        const bool rr = cgroup_rule_radial(c, g, refines, rtotal);
-        c.group_radial[g] = (uint8_t)rr;
-        for (long k = b; k < e; ++k) {
-          const int i = c.group_cams[k];
-          c.cam_radial[i] = (uint8_t)cam_radial_rule(c, i, rr);
-          c.cr->n_radial += c.cam_radial[i];
-        }
-      }
-    }
+    for (long g = 0; g < c.G; ++g) cgroup_decide<Mode>(c, g, OneLane{});
     if (s.err) return LOFTR_ERR_BAD_ARG;
   }
 
@@ -190,19 +150,15 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         for (int k = 0; k < S; ++k) c.gc[S * i + k] = a[kU + k];
         if constexpr (Mode::kPrior) cam_lin_prior<S>(c, c.pr, cur, i);
       }
-      if constexpr (kRadial) {
+      if constexpr (kGroups)
         for (long g = 0; g < c.G; ++g)
-          if (c.group_focal[g]) group_sum_radial<3>(c, g, [&](long i, double* a) { group_term_block(c, i, a); }, c.dg + 3 * g);
-      } else if constexpr (kGroups)
-        for (long g = 0; g < c.G; ++g) if (c.group_focal[g]) c.dg[g] = group_sum(c, g, c.U + 27, 28);
+          if (c.group_focal[g]) group_sum<kD>(c, g, [&](long i, double* a) { group_lin_term<Mode>(c, i, a); }, c.dg + kD * g);
     }
     const double lambda = s.lambda;
     for (long t = 0; t < T; ++t) if (!track_factor(c, t, lambda)) s.bad_f = 1;
     for (long i = 0; i < n; ++i) if (!cam_factor<Mode>(c, i, lambda)) s.bad_f = 1;
-    if constexpr (kRadial) {
-      for (long g = 0; g < c.G; ++g) if (!group_factor_radial(c, g, lambda)) s.bad_f = 1;
-    } else if constexpr (kGroups)
-      for (long g = 0; g < c.G; ++g) if (!group_factor(c, g, lambda)) s.bad_f = 1;
+    if constexpr (kGroups)
+      for (long g = 0; g < c.G; ++g) if (!group_factor<Mode>(c, g, lambda)) s.bad_f = 1;
     auto camera_half = [&](int mode) {
       for (long i = 0; i < n; ++i) {
         double a[S];
@@ -210,14 +166,13 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         if (takes_part<Mode>(c, i)) cam_sum<S>(c, i, [&](long o, double* acc) { cam_half_term<Mode>(c, cur, o, acc); }, a);
         cam_half_finish<Mode>(c, i, mode, lambda, a);
       }
-      if constexpr (kRadial) {
+      if constexpr (kGroups)
         for (long g = 0; g < c.G; ++g) {
-          double sg[2] = {0.0, 0.0};
-          if (c.group_focal[g]) group_sum_radial<2>(c, g, [&](long i, double* a) { group_term_pair(c, i, a); }, sg);
-          group_half_finish_radial(c, g, mode, lambda, sg);
+          double sg[GW];
+          for (int k = 0; k < GW; ++k) sg[k] = 0.0;
+          if (c.group_focal[g]) group_sum<GW>(c, g, [&](long i, double* a) { group_half_term<Mode>(c, i, a); }, sg);
+          group_half_finish<Mode>(c, g, mode, lambda, sg);
         }
-      } else if constexpr (kGroups)
-        for (long g = 0; g < c.G; ++g) group_half_finish(c, g, mode, lambda, c.group_focal[g] ? group_sum(c, g, c.Sp + 6, 7) : 0.0);
     };
     if (!s.bad_f) {
       for (long t = 0; t < T; ++t) track_half<Mode>(c, cur, t, 0);
@@ -229,23 +184,17 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
         ctrl_feed(c, kActPsp, dot());
         if (s.pcg_done) break;
         for (long i = 0; i < n; ++i) cam_update1<Mode>(c, i, s.alpha);
-        if constexpr (kRadial) {
-          for (long g = 0; g < c.G; ++g) group_update1_radial(c, g, s.alpha);
-        } else if constexpr (kGroups)
-          for (long g = 0; g < c.G; ++g) group_update1(c, g, s.alpha, lambda);
+        if constexpr (kGroups)
+          for (long g = 0; g < c.G; ++g) group_update1<Mode>(c, g, s.alpha, lambda);
         ctrl_feed(c, kActRz, dot());
         if (s.pcg_done) break;
         for (long i = 0; i < n; ++i) cam_update2<Mode>(c, i, s.beta);
-        if constexpr (kRadial) {
-          for (long g = 0; g < c.G; ++g) group_update2_radial(c, g, s.beta);
-        } else if constexpr (kGroups)
-          for (long g = 0; g < c.G; ++g) group_update2(c, g, s.beta);
+        if constexpr (kGroups)
+          for (long g = 0; g < c.G; ++g) group_update2<Mode>(c, g, s.beta);
       }
       for (long i = 0; i < n; ++i) if (!cam_apply<Mode>(c, cur, i)) s.bad_a = 1;
-      if constexpr (kRadial) {
-        for (long g = 0; g < c.G; ++g) group_apply_radial(c, cur, g);
-      } else if constexpr (kGroups)
-        for (long g = 0; g < c.G; ++g) group_apply(c, cur, g);
+      if constexpr (kGroups)
+        for (long g = 0; g < c.G; ++g) group_apply<Mode>(c, cur, g);
       for (long t = 0; t < T; ++t) if (!track_half<Mode>(c, cur, t, 2)) s.bad_a = 1;
     }
     if (!s.bad_f && !s.bad_a) {
@@ -262,6 +211,12 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   return LOFTR_OK;
 }
 
+template <class Mode> int enter(const Args& a) {
+  typename Mode::Ctx c{};
+  fill<Mode>(c, a);
+  return run<Mode>(c, a.par.max_iters, a.par.pcg_iters, a.par.pcg_tol);
+}
+
 }  // namespace
 
 extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
@@ -269,10 +224,8 @@ extern "C" int loftr_bundle_adjust_host(const long* offsets, long T, const int* 
                                         const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters,
                                         double pcg_tol, double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
                                         uint8_t* point_active, long* counts) {
-  Ctx c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  return run<Pose>(c, max_iters, pcg_iters, pcg_tol);
+  return enter<Pose>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                      {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts}});
 }
 
 extern "C" int loftr_bundle_adjust_focal_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
@@ -281,11 +234,9 @@ extern "C" int loftr_bundle_adjust_focal_host(const long* offsets, long T, const
                                               double huber_px, int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs,
                                               double focal_lo, double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
                                               uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, long* counts) {
-  Ctx7 c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-  return run<Focal>(c, max_iters, pcg_iters, pcg_tol);
+  return enter<Focal>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                       {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+                       {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal}});
 }
 
 extern "C" int loftr_bundle_adjust_shared_host(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
@@ -295,12 +246,10 @@ extern "C" int loftr_bundle_adjust_shared_host(const long* offsets, long T, cons
                                                int max_iters, int pcg_iters, double pcg_tol, double ftol, int min_focal_obs, double focal_lo,
                                                double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
                                                uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal, long* counts) {
-  CtxS c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-  fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
-  return run<Shared>(c, max_iters, pcg_iters, pcg_tol);
+  return enter<Shared>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                        {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+                        {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal},
+                        {cam_group, group_offsets, group_cams, G, group_focal}});
 }
 
 // one focal step and one radial coefficient per group of cameras (§18.4)
@@ -313,13 +262,11 @@ extern "C" int loftr_bundle_adjust_radial_host(const long* offsets, long T, cons
                                                double radial_lo, double radial_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
                                                uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal,
                                                double* radial_out, uint8_t* cam_radial, uint8_t* group_radial, long* counts) {
-  CtxR c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-  fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
-  fill_radial(c, radial_in, refine_radial, radial_lo, radial_hi, radial_out, cam_radial, group_radial);
-  return run<Radial>(c, max_iters, pcg_iters, pcg_tol);
+  return enter<Radial>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                        {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+                        {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal},
+                        {cam_group, group_offsets, group_cams, G, group_focal},
+                        {radial_in, refine_radial, radial_lo, radial_hi, radial_out, cam_radial, group_radial}});
 }
 
 // with position priors on the camera centres (§18.3): mode 0 pose, 1 focal, 2 shared; the focal and group arguments are ignored below
@@ -333,20 +280,9 @@ extern "C" int loftr_bundle_adjust_prior_host(const long* offsets, long T, const
                                               double focal_lo, double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
                                               uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal,
                                               uint8_t* cam_prior, long* counts) {
-  auto go = [&](auto m) {
-    using Mode = decltype(m);
-    typename Mode::Ctx c{};
-    fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol,
-         ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts);
-    if constexpr (Mode::S == 7) fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-    if constexpr (Mode::kGroups) fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
-    fill_prior(c.pr, prior_xyz, prior_sigma, prior_mask, cam_prior);
-    return run<Mode>(c, max_iters, pcg_iters, pcg_tol);
-  };
-  switch (mode) {
-    case 0: return go(PoseP{});
-    case 1: return go(FocalP{});
-    case 2: return go(SharedP{});
-  }
-  return LOFTR_ERR_BAD_ARG;
+  const Args a{{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+               {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+               {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal},
+               {cam_group, group_offsets, group_cams, G, group_focal}, {}, {prior_xyz, prior_sigma, prior_mask, cam_prior}};
+  return with_mode(mode, true, (int)LOFTR_ERR_BAD_ARG, [&](auto m) { return enter<decltype(m)>(a); });
 }

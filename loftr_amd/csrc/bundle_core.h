@@ -8,14 +8,14 @@
 // ordering (a kernel boundary on the device, the end of a loop on the host).  Every per-item step below reads only what earlier phases
 // wrote, so the result does not depend on how a phase is spread over threads.  Every test is written so that a NaN takes the safe side.
 //
-// The three modes -- fixed intrinsics, one focal step per camera (§18.1), one per group of cameras (§18.2) -- are instantiations of one
-// text: a step that touches the camera block is a template on the mode (Pose, Focal, Shared below) and decides what differs with
-// `if constexpr`; no mode is reached through another "with a zero column", so each performs exactly its own operations.  Steps that are
-// different rules (cam_focal_rule against cam_carry / cgroup_*, the group_* steps) stay separate functions.  Position priors on the
-// camera centres (§18.3) are a second trait of the mode (kPrior: PoseP, FocalP, SharedP): their steps are `if constexpr` inside the same
-// phases, and the three modes without them perform no operation of theirs.  One radial coefficient per group (§18.4) is a fourth mode,
-// Radial: the grouped mode 8 wide with two unknowns per group; it alone reads a k (kRadial), the others perform no operation of its.
-// The context fill and the argument checks of all the entry points are at the end.
+// A MODE IS A ROW OF TRAITS (Pose, Focal, Shared, Radial and PriorOf<> below): fixed intrinsics, one focal step per camera
+// (§18.1), one per group of cameras (§18.2), a radial coefficient per group next to it (§18.4), each with or without position priors
+// on the camera centres (§18.3).  Every step that differs between modes is ONE name, a template on the mode, and decides what differs
+// with `if constexpr` on a trait; no mode is reached through another "with a zero column", so each performs exactly its own operations
+// and reads only its own arrays.  Where two modes take genuinely different arithmetic for a step (Shared's scalar group step against
+// Radial's 2 x 2 one; the pinhole against the distorted projection) the two texts stand side by side inside the one template, never
+// merged: the rounding of each is part of the result.  The argument superset of the entry points (Args), the context fill by traits,
+// the one list of modes (with_mode) and the argument checks are at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -125,12 +125,15 @@ struct Prior {
 };
 template <class Base> struct WithPrior : Base { Prior pr; };
 
-// The three MODES.  The sequence of phases (bundle.hip), the launch schedule (bundle_gpu.hip) and every per-item step that touches the
-// camera block are written once, as templates on one of these: S is the stride of a camera's vectors and the width of its linearised
-// block, W the width of what is factored, solved and updated per camera, kGroups whether the group phases exist.
+// The MODES.  The sequence of phases (bundle.hip), the launch schedule (bundle_gpu.hip) and every per-item step that touches the
+// camera block or the groups are written once, as templates on one of these: S is the stride of a camera's vectors and the width of its
+// linearised block, W the width of what is factored, solved and updated per camera, kGroups whether the group phases exist, GW the
+// unknowns per group (kTri<GW> the entries of a group's block).
 // kPrior: whether the cameras carry position priors (§18.3); Base is the mode without them, whose kernels and steps serve every phase
 // that the prior does not touch.
-// kRadial: whether the projection is the distorted one of §18.4 (then GW = 2 unknowns per group instead of 1).
+// kRadial: whether the projection is the distorted one of §18.4 and a group carries its radial step next to its focal step.
+// A new mode supplies: its row here, its context (a struct that extends the one it builds on), its part of Args / fill / check_args /
+// layout, its case in with_mode, its `if constexpr` branch in the steps that it changes, and a row of ops._BA_MODES.
 struct Pose { static constexpr int S = 6, W = 6, GW = 1; static constexpr bool kGroups = false, kPrior = false, kRadial = false; using Ctx = ba::Ctx; using Base = Pose; };       // §18
 struct Focal { static constexpr int S = 7, W = 7, GW = 1; static constexpr bool kGroups = false, kPrior = false, kRadial = false; using Ctx = ba::Ctx7; using Base = Focal; };    // §18.1
 struct Shared { static constexpr int S = 7, W = 6, GW = 1; static constexpr bool kGroups = true, kPrior = false, kRadial = false; using Ctx = ba::CtxS; using Base = Shared; };   // §18.2
@@ -142,6 +145,8 @@ using SharedP = PriorOf<Shared>;
 template <int S> constexpr int kTri = S * (S + 1) / 2;      // entries of the upper triangle of a camera block: 21, 28 or 36
 // the mode whose track steps (linearise, evaluate) a mode runs: they do not depend on the camera block, only on the projection
 template <class Mode> using TrackMode = std::conditional_t<Mode::kRadial, Mode, Pose>;
+// ... and whose camera setup it runs: that depends on what the camera carries (intrinsics to refine, a k), not on groups or priors
+template <class Mode> using SetupMode = std::conditional_t<Mode::kRadial, Mode, std::conditional_t<Mode::S >= 7, Focal, Pose>>;
 template <class Mode> BA_HD CtrlS* groups_ctrl(const typename Mode::Ctx& c) {
   if constexpr (Mode::kGroups) return c.cs;
   else return nullptr;
@@ -218,9 +223,16 @@ BA_HD double* tab_of(const Ctx& c, int buf, long i) { return c.tab + ((long)buf 
 BA_HD double* quat_of(const Ctx& c, int buf, long i) { return c.quat + ((long)buf * c.n + i) * 4; }
 BA_HD double* X_of(const Ctx& c, int buf, long t) { return c.X + ((long)buf * c.T + t) * 3; }
 
-// phase "camera setup", per camera: validity, quaternion, both copies of the table; the output matrix starts as the input's bits.
-// The table holds R(q) for a valid camera that is not fixed and the input's R otherwise.
-BA_HD void cam_setup(const Ctx& c, long i) {
+BA_HD double* kr_of(const CtxR& c, int buf, long i) { return c.kr + ((long)buf * c.n + i); }
+// phase "camera setup", once, before any camera's decision is counted: the counter of the radial decisions starts at 0
+template <class Mode> BA_HD void cam_setup_ctrl(const typename Mode::Ctx& c) {
+  if constexpr (Mode::kRadial) c.cr->n_radial = 0;
+}
+// ... and per camera: validity, quaternion, both copies of the table; the output matrix starts as the input's bits.  The table holds
+// R(q) for a valid camera that is not fixed and the input's R otherwise.  With a focal step (S >= 7) the output intrinsics start as the
+// input's bits.  With a radial coefficient a valid camera whose k is not finite is not valid; both states start at the input's k and
+// the output as its bits.
+template <class Mode> BA_HD void cam_setup(const typename Mode::Ctx& c, long i) {
   const double *K = c.K + 9 * i, *T = c.Tin + 16 * i;
   const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
   bool ok = fin(fx) && fin(sk) && fin(cx) && fin(fy) && fin(cy) && fx != 0.0 && fy != 0.0;
@@ -241,23 +253,18 @@ BA_HD void cam_setup(const Ctx& c, long i) {
   const uint64_t* src = (const uint64_t*)T;
   uint64_t* dst = (uint64_t*)(c.T_out + 16 * i);
   for (int k = 0; k < 16; ++k) dst[k] = src[k];
-}
-
-// ... and with focal refinement: the output intrinsics start as the input's bits
-BA_HD void cam_setup_focal(const Ctx7& c, long i) {
-  const uint64_t* src = (const uint64_t*)(c.K + 9 * i);
-  uint64_t* dst = (uint64_t*)(c.K_out + 9 * i);
-  for (int k = 0; k < 9; ++k) dst[k] = src[k];
-}
-// ... and with a radial coefficient: a valid camera whose k is not finite is not valid; both states start at the input's k and the
-// output as its bits
-BA_HD double* kr_of(const CtxR& c, int buf, long i) { return c.kr + ((long)buf * c.n + i); }
-BA_HD void cam_setup_radial(const CtxR& c, long i) {
-  const double k = c.radial_in[i];
-  if (!fin(k)) c.cam_valid[i] = 0;
-  *kr_of(c, 0, i) = k; *kr_of(c, 1, i) = k;
-  *(uint64_t*)(c.radial_out + i) = *(const uint64_t*)(c.radial_in + i);
-  c.cam_radial[i] = 0;
+  if constexpr (Mode::S >= 7) {
+    const uint64_t* ksrc = (const uint64_t*)(c.K + 9 * i);
+    uint64_t* kdst = (uint64_t*)(c.K_out + 9 * i);
+    for (int k = 0; k < 9; ++k) kdst[k] = ksrc[k];
+  }
+  if constexpr (Mode::kRadial) {
+    const double k = c.radial_in[i];
+    if (!fin(k)) c.cam_valid[i] = 0;
+    *kr_of(c, 0, i) = k; *kr_of(c, 1, i) = k;
+    *(uint64_t*)(c.radial_out + i) = *(const uint64_t*)(c.radial_in + i);
+    c.cam_radial[i] = 0;
+  }
 }
 // phase "camera groups", the last step of a camera with cnt active observations.  Focal: does it refine its focal?
 BA_HD bool cam_focal_rule(const Ctx7& c, long i, bool is_free, long cnt) {
@@ -287,22 +294,72 @@ BA_HD int cgroup_slot(const CtxS& c, long g, long b, long k, long* cnt) {
   return 0;
 }
 BA_HD double* sg_of(const CtxS& c, int buf, long g) { return c.sg + ((long)buf * c.n + g); }
-// ... and the end of group g's check: does it refine?  Its factor starts at 1 in both states.
-BA_HD bool cgroup_rule(const CtxS& c, long g, long total) {
-  *sg_of(c, 0, g) = 1.0; *sg_of(c, 1, g) = 1.0;
-  return total >= (long)c.min_focal_obs;
-}
-
-// Radial: what slot k (cnt: what cgroup_slot returned for it, 0 for a bad slot) adds to the radial count of its group
-BA_HD long cgroup_slot_radial(const CtxR& c, long k, long cnt) { return cnt > 0 && c.refine_radial[c.group_cams[k]] != 0 ? cnt : 0; }
 BA_HD double* ag_of(const CtxR& c, int buf, long g) { return c.ag + ((long)buf * c.n + g); }
-// ... and does group g, which refines its focal or not, refine its radial coefficient?  Its accumulated step starts at +0 in both states.
-BA_HD bool cgroup_rule_radial(const CtxR& c, long g, bool refines, long rtotal) {
-  *ag_of(c, 0, g) = 0.0; *ag_of(c, 1, g) = 0.0;
-  return refines && rtotal >= (long)c.min_focal_obs;
+// How the members of a group are spread over workers: lane `lane` of kLanes takes every kLanes-th member; sum / any fold a value over
+// the lanes (every lane receives the result), add / raise reach a counter / the error bits that other groups reach too.  The host takes
+// the members one after another; the wave of bundle_gpu.hip folds with shuffles and reaches the counters with integer atomics.
+struct OneLane {
+  static constexpr int kLanes = 1;
+  int lane = 0;
+  BA_HD long sum(long v) const { return v; }
+  BA_HD int any(int v) const { return v; }
+  BA_HD void add(int* p, int v) const { *p += v; }
+  BA_HD void raise(int* p, int v) const { *p |= v; }
+};
+// ... and the whole decision of group g (the group check of the schedule).  The slots are checked and counted (Radial: a member with
+// refine_radial adds what it carries to the radial count as well); a group with a bad slot raises the error bits and decides nothing.
+// It refines its focal when the total reaches min_focal_obs, and its factor starts at 1 in both states; a member has cam_focal when its
+// group refines and it carries.  Radial: a group that refines its focal refines its radial coefficient when the radial count reaches
+// min_focal_obs, its accumulated step starts at +0 in both states, and a member has cam_radial when its group does, it carries and it
+// has refine_radial (cam_cnt is read, cam_focal is not: no lane waits for another).
+template <class Mode, class Lanes> BA_HD void cgroup_decide(const typename Mode::Ctx& c, long g, const Lanes& w) {
+  long b, e, total = 0, rtotal = 0;
+  int err = 0;
+  if (!cgroup_range(c, g, &b, &e)) { err = kBadCamGroups; b = e = 0; }
+  for (long k = b + w.lane; k < e; k += Lanes::kLanes) {
+    long cnt;
+    err |= cgroup_slot(c, g, b, k, &cnt);
+    total += cnt;
+    if constexpr (Mode::kRadial) rtotal += cnt > 0 && c.refine_radial[c.group_cams[k]] != 0 ? cnt : 0;
+  }
+  err = w.any(err); total = w.sum(total);
+  if constexpr (Mode::kRadial) rtotal = w.sum(rtotal);
+  if (err) {
+    if (w.lane == 0) w.raise(&c.ctrl->err, err);
+    return;
+  }
+  const bool refines = total >= (long)c.min_focal_obs;
+  long nf = 0;
+  for (long k = b + w.lane; k < e; k += Lanes::kLanes) {
+    const int i = c.group_cams[k];
+    const bool fo = refines && c.cam_cnt[i] > 0;
+    c.cam_focal[i] = (uint8_t)fo;
+    nf += fo;
+  }
+  nf = w.sum(nf);
+  if (w.lane == 0) {
+    *sg_of(c, 0, g) = 1.0; *sg_of(c, 1, g) = 1.0;
+    c.group_focal[g] = (uint8_t)refines;
+    w.add(&c.cs->n_groups, (int)refines);
+    w.add(&c.ctrl->n_focal, (int)nf);
+  }
+  if constexpr (Mode::kRadial) {
+    const bool rr = refines && rtotal >= (long)c.min_focal_obs;
+    long nr = 0;
+    for (long k = b + w.lane; k < e; k += Lanes::kLanes) {
+      const int i = c.group_cams[k];
+      const bool ra = rr && c.cam_cnt[i] > 0 && c.refine_radial[i] != 0;
+      c.cam_radial[i] = (uint8_t)ra;
+      nr += ra;
+    }
+    nr = w.sum(nr);
+    if (w.lane == 0) {
+      *ag_of(c, 0, g) = 0.0; *ag_of(c, 1, g) = 0.0;
+      c.group_radial[g] = (uint8_t)rr;
+      w.add(&c.cr->n_radial, (int)nr);
+    }
+  }
 }
-// ... and does member i of a group that does (`refines`) carry it?
-BA_HD bool cam_radial_rule(const CtxR& c, long i, bool refines) { return refines && c.cam_cnt[i] > 0 && c.refine_radial[i] != 0; }
 
 // ---- §18.3: position priors ------------------------------------------------------------------------------------------------------------
 // phase "camera groups", after cam_free of camera i is known: does it have a prior?  A NaN anywhere deactivates.
@@ -612,21 +669,20 @@ template <class Mode> BA_HD void cam_lin_term(const typename Mode::Ctx& c, int b
 #pragma unroll
   for (int i = 0; i < S; ++i) a[kTri<S> + i] = a[kTri<S> + i] + (A[i] * rs[0] + A[S + i] * rs[1]);
 }
-// one element of a group's osum64: member i adds v[i] when it has cam_focal (U77 for d_g, Sp[6] for E^T)
-BA_HD void group_term(const CtxS& c, long i, const double* v, long stride, double* a) {
-  if (c.cam_focal[i]) a[0] = a[0] + v[stride * i];
-}
-
-// Radial: member i adds (U77, U78, U88) to its group's block d [3] when it has cam_focal (U78 and U88 are +0 without cam_radial) ...
-BA_HD void group_term_block(const CtxR& c, long i, double* a) {
+// phase "linearise groups", one element of a group's osum64 of kTri<GW> values: member i with cam_focal adds U77 to d_g; Radial: (U77,
+// U78, U88) to its group's block d [3] (U78 and U88 are +0 without cam_radial)
+template <class Mode> BA_HD void group_lin_term(const typename Mode::Ctx& c, long i, double* a) {
   if (!c.cam_focal[i]) return;
-  const double* U = c.U + kTri<8> * i;
-  a[0] = a[0] + U[33]; a[1] = a[1] + U[34]; a[2] = a[2] + U[35];
+  const double* U = c.U + kTri<Mode::S> * i;
+  if constexpr (Mode::kRadial) { a[0] = a[0] + U[33]; a[1] = a[1] + U[34]; a[2] = a[2] + U[35]; }
+  else a[0] = a[0] + U[27];
 }
-// ... and its seventh and eighth entries of Sp to E^T: the seventh with cam_focal, the eighth with cam_radial
-BA_HD void group_term_pair(const CtxR& c, long i, double* a) {
-  if (c.cam_focal[i]) a[0] = a[0] + c.Sp[8 * i + 6];
-  if (c.cam_radial[i]) a[1] = a[1] + c.Sp[8 * i + 7];
+// phase "camera half", one element of a group's osum64 of GW values, E^T: member i adds its seventh entry of Sp with cam_focal;
+// Radial: and its eighth with cam_radial
+template <class Mode> BA_HD void group_half_term(const typename Mode::Ctx& c, long i, double* a) {
+  if (c.cam_focal[i]) a[0] = a[0] + c.Sp[Mode::S * i + 6];
+  if constexpr (Mode::kRadial)
+    if (c.cam_radial[i]) a[1] = a[1] + c.Sp[8 * i + 7];
 }
 
 // ---- rule 6: the step ------------------------------------------------------------------------------------------------------------------
@@ -648,16 +704,19 @@ template <class Mode> BA_HD bool cam_factor(const Ctx& c, long i, double lambda)
   for (int k = 0; k < kTri<W>; ++k) c.Uf[kTri<S> * i + k] = f[k];
   return ok;
 }
-BA_HD bool group_factor(const CtxS& c, long g, double lambda) { return !c.group_focal[g] || damped(c.dg[g], lambda) > 0.0; }
-// Radial: the 2 x 2 L D L^T of the group's block, both diagonals damped here, once (a group that does not refine its radial has a
-// block (d, 0; 0, 0), whose second pivot is lambda) -> the factor [3], kept behind the n blocks of dg
+// The group steps below are one name per step; Shared's scalar step (a division by the damped d_g) and Radial's 2 x 2 step (factor<2> /
+// solve<2>) are two texts inside it: a 1 x 1 elimination in place of the division would round differently.
+// Shared: the damped d_g must be positive.  Radial: the 2 x 2 L D L^T of the group's block, both diagonals damped here, once (a group
+// that does not refine its radial has a block (d, 0; 0, 0), whose second pivot is lambda) -> the factor [3], kept behind the n blocks of dg
 BA_HD double* dgf_of(const CtxS& c, long g) { return c.dg + 3 * ((long)c.n + g); }
-BA_HD bool group_factor_radial(const CtxS& c, long g, double lambda) {
-  if (!c.group_focal[g]) return true;
-  double f[3];
-  const bool ok = factor<2>(c.dg + 3 * g, lambda, f);
-  for (int k = 0; k < 3; ++k) dgf_of(c, g)[k] = f[k];
-  return ok;
+template <class Mode> BA_HD bool group_factor(const CtxS& c, long g, double lambda) {
+  if constexpr (Mode::kRadial) {
+    if (!c.group_focal[g]) return true;
+    double f[3];
+    const bool ok = factor<2>(c.dg + 3 * g, lambda, f);
+    for (int k = 0; k < 3; ++k) dgf_of(c, g)[k] = f[k];
+    return ok;
+  } else return !c.group_focal[g] || damped(c.dg[g], lambda) > 0.0;
 }
 // the vector of camera i as the operator sees it, out of x (step) or p: its S entries in place; Shared: the pose part of a free camera,
 // its group's value when it has cam_focal (Radial: and its group's second value when it has cam_radial), else +0, formed in tmp [S]
@@ -783,55 +842,39 @@ template <class Mode> BA_HD void cam_half_finish(const typename Mode::Ctx& c, lo
       Sp[7] = s - a[7];
     }
 }
-// ... and what follows the sum s of group g.  mode 0: b_g = s; x = 0, r = b, z = r / d, p = z, partg = r z.  mode 1: Sp = d p + s,
-// partg = p Sp (d: the damped d_g).  A group that does not refine has partg = +0.
-BA_HD void group_half_finish(const CtxS& c, long g, int mode, double lambda, double s) {
+// ... and what follows the GW sums s of group g; a group that does not refine has partg = +0.  Shared.  mode 0: b_g = s; x = 0, r = b,
+// z = r / d, p = z, partg = r z.  mode 1: Sp = d p + s, partg = p Sp (d: the damped d_g).  Radial: s = (focal, radial), the second
+// taken as +0 when the group does not refine its radial.  mode 0: b = s; x = 0, r = b, z = D^-1 r by the factor, p = z, partg = r_0 z_0
+// + r_1 z_1.  mode 1: Sp_0 = (d_00 p_0 + d_01 p_1) + s_0, Sp_1 = (d_01 p_0 + d_11 p_1) + s_1 with the damped diagonals, partg = p_0 Sp_0
+// + p_1 Sp_1.
+template <class Mode> BA_HD void group_half_finish(const typename Mode::Ctx& c, long g, int mode, double lambda, const double* s) {
   if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
-  const double d = damped(c.dg[g], lambda);
-  if (mode == 0) {
-    const double z = s / d;
-    c.xg[g] = 0.0; c.rg[g] = s; c.zg[g] = z; c.pg[g] = z;
-    c.partg[g] = s * z;
-    return;
+  if constexpr (Mode::kRadial) {
+    const double b[2] = {s[0], c.group_radial[g] ? s[1] : 0.0};
+    double *x = c.xg + 2 * g, *r = c.rg + 2 * g, *z = c.zg + 2 * g, *p = c.pg + 2 * g, *Sp = c.Spg + 2 * g;
+    if (mode == 0) {
+      double zz[2];
+      solve<2>(dgf_of(c, g), b, zz);
+      for (int k = 0; k < 2; ++k) { x[k] = 0.0; r[k] = b[k]; z[k] = zz[k]; p[k] = zz[k]; }
+      c.partg[g] = dotm<2>(b, zz);
+      return;
+    }
+    const double* d = c.dg + 3 * g;
+    const double sp[2] = {(damped(d[0], lambda) * p[0] + d[1] * p[1]) + b[0], (d[1] * p[0] + damped(d[2], lambda) * p[1]) + b[1]};
+    Sp[0] = sp[0]; Sp[1] = sp[1];
+    c.partg[g] = dotm<2>(p, sp);
+  } else {
+    const double d = damped(c.dg[g], lambda);
+    if (mode == 0) {
+      const double z = s[0] / d;
+      c.xg[g] = 0.0; c.rg[g] = s[0]; c.zg[g] = z; c.pg[g] = z;
+      c.partg[g] = s[0] * z;
+      return;
+    }
+    const double sp = d * c.pg[g] + s[0];
+    c.Spg[g] = sp;
+    c.partg[g] = c.pg[g] * sp;
   }
-  const double sp = d * c.pg[g] + s;
-  c.Spg[g] = sp;
-  c.partg[g] = c.pg[g] * sp;
-}
-// Radial: ... of group g with the sums s [2] (focal, radial; the second is taken as +0 when the group does not refine its radial).
-// mode 0: b = s; x = 0, r = b, z = D^-1 r by the factor, p = z, partg = r_0 z_0 + r_1 z_1.  mode 1: Sp_0 = (d_00 p_0 + d_01 p_1) + s_0,
-// Sp_1 = (d_01 p_0 + d_11 p_1) + s_1 with the damped diagonals, partg = p_0 Sp_0 + p_1 Sp_1.
-BA_HD void group_half_finish_radial(const CtxR& c, long g, int mode, double lambda, const double* s) {
-  if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
-  const double b[2] = {s[0], c.group_radial[g] ? s[1] : 0.0};
-  double *x = c.xg + 2 * g, *r = c.rg + 2 * g, *z = c.zg + 2 * g, *p = c.pg + 2 * g, *Sp = c.Spg + 2 * g;
-  if (mode == 0) {
-    double zz[2];
-    solve<2>(dgf_of(c, g), b, zz);
-    for (int k = 0; k < 2; ++k) { x[k] = 0.0; r[k] = b[k]; z[k] = zz[k]; p[k] = zz[k]; }
-    c.partg[g] = dotm<2>(b, zz);
-    return;
-  }
-  const double* d = c.dg + 3 * g;
-  const double sp[2] = {(damped(d[0], lambda) * p[0] + d[1] * p[1]) + b[0], (d[1] * p[0] + damped(d[2], lambda) * p[1]) + b[1]};
-  Sp[0] = sp[0]; Sp[1] = sp[1];
-  c.partg[g] = dotm<2>(p, sp);
-}
-BA_HD void group_update1_radial(const CtxS& c, long g, double alpha) {
-  if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
-  double r[2], zz[2];
-  for (int k = 0; k < 2; ++k) {
-    c.xg[2 * g + k] = c.xg[2 * g + k] + alpha * c.pg[2 * g + k];
-    r[k] = c.rg[2 * g + k] - alpha * c.Spg[2 * g + k];
-    c.rg[2 * g + k] = r[k];
-  }
-  solve<2>(dgf_of(c, g), r, zz);
-  c.zg[2 * g] = zz[0]; c.zg[2 * g + 1] = zz[1];
-  c.partg[g] = dotm<2>(r, zz);
-}
-BA_HD void group_update2_radial(const CtxS& c, long g, double beta) {
-  if (c.group_focal[g])
-    for (int k = 0; k < 2; ++k) c.pg[2 * g + k] = c.zg[2 * g + k] + beta * c.pg[2 * g + k];
 }
 // phase "update 1", per free camera over its W entries: x += alpha p, r -= alpha Sp, zc = M^-1 r, part = r . zc; per refining group
 template <class Mode> BA_HD void cam_update1(const Ctx& c, long i, double alpha) {
@@ -849,12 +892,24 @@ template <class Mode> BA_HD void cam_update1(const Ctx& c, long i, double alpha)
   for (int k = 0; k < W; ++k) c.zc[S * i + k] = zz[k];
   c.part[i] = dotm<W>(r, zz);
 }
-BA_HD void group_update1(const CtxS& c, long g, double alpha, double lambda) {
+template <class Mode> BA_HD void group_update1(const CtxS& c, long g, double alpha, double lambda) {
   if (!c.group_focal[g]) { c.partg[g] = 0.0; return; }
-  c.xg[g] = c.xg[g] + alpha * c.pg[g];
-  const double r = c.rg[g] - alpha * c.Spg[g], z = r / damped(c.dg[g], lambda);
-  c.rg[g] = r; c.zg[g] = z;
-  c.partg[g] = r * z;
+  if constexpr (Mode::kRadial) {                 // (the factor holds the damping)
+    double r[2], zz[2];
+    for (int k = 0; k < 2; ++k) {
+      c.xg[2 * g + k] = c.xg[2 * g + k] + alpha * c.pg[2 * g + k];
+      r[k] = c.rg[2 * g + k] - alpha * c.Spg[2 * g + k];
+      c.rg[2 * g + k] = r[k];
+    }
+    solve<2>(dgf_of(c, g), r, zz);
+    c.zg[2 * g] = zz[0]; c.zg[2 * g + 1] = zz[1];
+    c.partg[g] = dotm<2>(r, zz);
+  } else {
+    c.xg[g] = c.xg[g] + alpha * c.pg[g];
+    const double r = c.rg[g] - alpha * c.Spg[g], z = r / damped(c.dg[g], lambda);
+    c.rg[g] = r; c.zg[g] = z;
+    c.partg[g] = r * z;
+  }
 }
 // phase "update 2", per free camera: p = zc + beta p; per refining group
 template <class Mode> BA_HD void cam_update2(const Ctx& c, long i, double beta) {
@@ -862,26 +917,26 @@ template <class Mode> BA_HD void cam_update2(const Ctx& c, long i, double beta) 
   if (!c.cam_free[i]) return;
   for (int k = 0; k < Mode::W; ++k) c.p[S * i + k] = c.zc[S * i + k] + beta * c.p[S * i + k];
 }
-BA_HD void group_update2(const CtxS& c, long g, double beta) {
-  if (c.group_focal[g]) c.pg[g] = c.zg[g] + beta * c.pg[g];
+template <class Mode> BA_HD void group_update2(const CtxS& c, long g, double beta) {
+  if (!c.group_focal[g]) return;
+  if constexpr (Mode::kRadial) {
+    for (int k = 0; k < 2; ++k) c.pg[2 * g + k] = c.zg[2 * g + k] + beta * c.pg[2 * g + k];
+  } else c.pg[g] = c.zg[g] + beta * c.pg[g];
 }
 
 // ---- rule 7: the trial -----------------------------------------------------------------------------------------------------------------
-// phase "apply", per refining group: the factor of the trial s' = s (1 + delta_g)
-BA_HD void group_apply(const CtxS& c, int buf, long g) {
-  if (c.group_focal[g]) *sg_of(c, 1 - buf, g) = *sg_of(c, buf, g) * (1.0 + c.xg[g]);
-}
-// Radial: ... and its accumulated radial step a' = a + dk_g
-BA_HD void group_apply_radial(const CtxR& c, int buf, long g) {
-  if (c.group_focal[g]) *sg_of(c, 1 - buf, g) = *sg_of(c, buf, g) * (1.0 + c.xg[2 * g]);
-  if (c.group_radial[g]) *ag_of(c, 1 - buf, g) = *ag_of(c, buf, g) + c.xg[2 * g + 1];
+// phase "apply", per refining group: the factor of the trial s' = s (1 + delta_g); Radial: and its accumulated radial step a' = a + dk_g
+template <class Mode> BA_HD void group_apply(const typename Mode::Ctx& c, int buf, long g) {
+  if (c.group_focal[g]) *sg_of(c, 1 - buf, g) = *sg_of(c, buf, g) * (1.0 + c.xg[Mode::GW * g]);
+  if constexpr (Mode::kRadial)
+    if (c.group_radial[g]) *ag_of(c, 1 - buf, g) = *ag_of(c, buf, g) + c.xg[2 * g + 1];
 }
 // phase "apply", per camera.  A free camera: q' = normalise((1, omega / 2) (x) q), t' = t + dt into the other state -> false when not
 // finite.  One with cam_focal: fx' = fx s, skew' = skew s, fy' = fy s with, Focal, s = 1 + delta on the values of the state, and, Shared,
 // s = s_g (1 + delta_g) on the INPUT values (the camera forms s' itself, from the same two operands as group_apply), so that the members
 // of a group leave with ONE factor on their input values however many trials were accepted -> false as well when fx' or fy' is not
 // finite or fx' / fx_in or fy' / fy_in is not strictly inside (focal_lo, focal_hi); a NaN fails every test.  One with cam_radial (Radial):
-// k' = k_in + (a_g + dk_g) on the INPUT value, the sum in brackets formed as group_apply_radial forms it: one rounding on the input
+// k' = k_in + (a_g + dk_g) on the INPUT value, the sum in brackets formed as group_apply forms it: one rounding on the input
 // whatever the number of accepted trials -> false as well when k' is outside [radial_lo, radial_hi]
 template <class Mode> BA_HD bool cam_apply(const typename Mode::Ctx& c, int buf, long i) {
   constexpr int S = Mode::S;
@@ -1084,31 +1139,59 @@ BA_HD void ctrl_write_prior(const Ctx& c, const Prior& p) {
 }
 
 // ---- the entry points' side (host code of both files) ----------------------------------------------------------------------------------
-// the problem, the parameters and the outputs every mode has
-inline void fill(Ctx& c, const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
-                 const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images, const long* cam_offsets,
-                 const int* cam_obs, double huber_px, double pcg_tol, double ftol, double* T_out, float* xyz_out, uint8_t* obs_active,
-                 uint8_t* cam_free, uint8_t* point_active, long* counts) {
-  c.offsets = offsets; c.T = T; c.image = obs_image; c.xy = obs_xy; c.mask = obs_mask; c.N = N;
-  c.xyz_in = xyz; c.K = K; c.Tin = T_cam_from_world; c.fixed = fixed; c.n = n_images; c.cam_offsets = cam_offsets; c.cam_obs = cam_obs;
-  c.huber = huber_px; c.pcg_tol2 = pcg_tol * pcg_tol; c.ftol = ftol;
-  c.T_out = T_out; c.xyz_out = xyz_out; c.obs_active = obs_active; c.cam_free = cam_free; c.point_active = point_active; c.counts = counts;
+// What the ten entry points take, as one superset; what a mode lacks stays NULL or 0.  Each part lists its members in the order of the C
+// signature, so that an entry point is `Args a{{...}, {...}, ...}` with the parts it has.
+struct Args {
+  struct { const long* offsets; long T; const int* obs_image; const float* obs_xy; const uint8_t* obs_mask; long N; const float* xyz;
+           const double *K, *T_cam_from_world; const uint8_t* fixed; int n_images; const long* cam_offsets; const int* cam_obs; } in;
+  struct { double huber_px; int max_iters, pcg_iters; double pcg_tol, ftol; } par;
+  struct { double* T_out; float* xyz_out; uint8_t *obs_active, *cam_free, *point_active; long* counts; } out;
+  struct { const uint8_t* refine_focal; int min_focal_obs; double focal_lo, focal_hi; double* K_out; uint8_t* cam_focal; } focal;              // S >= 7
+  struct { const int* cam_group; const long* group_offsets; const int* group_cams; int G; uint8_t* group_focal; } groups;                     // kGroups
+  struct { const double* radial_in; const uint8_t* refine_radial; double radial_lo, radial_hi; double* radial_out;
+           uint8_t *cam_radial, *group_radial; } radial;                                                                                      // kRadial
+  struct { const double *xyz, *sigma; const uint8_t* mask; uint8_t* cam_prior; } prior;                                                       // kPrior
+};
+// the context of a mode out of the arguments: the problem, the parameters and the outputs every mode has, then what its traits add
+template <class Mode> inline void fill(typename Mode::Ctx& c, const Args& a) {
+  c.offsets = a.in.offsets; c.T = a.in.T; c.image = a.in.obs_image; c.xy = a.in.obs_xy; c.mask = a.in.obs_mask; c.N = a.in.N;
+  c.xyz_in = a.in.xyz; c.K = a.in.K; c.Tin = a.in.T_cam_from_world; c.fixed = a.in.fixed; c.n = a.in.n_images;
+  c.cam_offsets = a.in.cam_offsets; c.cam_obs = a.in.cam_obs;
+  c.huber = a.par.huber_px; c.pcg_tol2 = a.par.pcg_tol * a.par.pcg_tol; c.ftol = a.par.ftol;
+  c.T_out = a.out.T_out; c.xyz_out = a.out.xyz_out; c.obs_active = a.out.obs_active; c.cam_free = a.out.cam_free;
+  c.point_active = a.out.point_active; c.counts = a.out.counts;
+  if constexpr (Mode::S >= 7) {
+    c.refine_focal = a.focal.refine_focal; c.min_focal_obs = a.focal.min_focal_obs; c.focal_lo = a.focal.focal_lo; c.focal_hi = a.focal.focal_hi;
+    c.K_out = a.focal.K_out; c.cam_focal = a.focal.cam_focal;
+  }
+  if constexpr (Mode::kGroups) {
+    c.cam_group = a.groups.cam_group; c.group_offsets = a.groups.group_offsets; c.group_cams = a.groups.group_cams; c.G = a.groups.G;
+    c.group_focal = a.groups.group_focal;
+  }
+  if constexpr (Mode::kRadial) {
+    c.radial_in = a.radial.radial_in; c.refine_radial = a.radial.refine_radial; c.radial_lo = a.radial.radial_lo; c.radial_hi = a.radial.radial_hi;
+    c.radial_out = a.radial.radial_out; c.cam_radial = a.radial.cam_radial; c.group_radial = a.radial.group_radial;
+  }
+  if constexpr (Mode::kPrior) { c.pr.xyz = a.prior.xyz; c.pr.sigma = a.prior.sigma; c.pr.mask = a.prior.mask; c.pr.cam_prior = a.prior.cam_prior; }
 }
-inline void fill_focal(Ctx7& c, const uint8_t* refine_focal, int min_focal_obs, double focal_lo, double focal_hi, double* K_out,
-                       uint8_t* cam_focal) {
-  c.refine_focal = refine_focal; c.min_focal_obs = min_focal_obs; c.focal_lo = focal_lo; c.focal_hi = focal_hi;
-  c.K_out = K_out; c.cam_focal = cam_focal;
+// THE list of modes: f(Mode{}) for the mode of `kind` (the `mode` of the entry points with priors counts the same way) with or without
+// priors, `unknown` for a combination that is no mode
+enum : int { kKindPose = 0, kKindFocal, kKindShared, kKindRadial };
+template <class R, class F> inline R with_mode(int kind, bool prior, R unknown, F f) {
+  if (kind < kKindPose || kind > kKindRadial) return unknown;
+  switch (kind + (prior ? 4 : 0)) {
+    case kKindPose: return f(Pose{});
+    case kKindFocal: return f(Focal{});
+    case kKindShared: return f(Shared{});
+    case kKindRadial: return f(Radial{});
+    case 4 + kKindPose: return f(PoseP{});
+    case 4 + kKindFocal: return f(FocalP{});
+    case 4 + kKindShared: return f(SharedP{});
+  }
+  return unknown;
 }
-inline void fill_prior(Prior& p, const double* prior_xyz, const double* prior_sigma, const uint8_t* prior_mask, uint8_t* cam_prior) {
-  p.xyz = prior_xyz; p.sigma = prior_sigma; p.mask = prior_mask; p.cam_prior = cam_prior;
-}
-inline void fill_groups(CtxS& c, const int* cam_group, const long* group_offsets, const int* group_cams, int G, uint8_t* group_focal) {
-  c.cam_group = cam_group; c.group_offsets = group_offsets; c.group_cams = group_cams; c.G = G; c.group_focal = group_focal;
-}
-inline void fill_radial(CtxR& c, const double* radial_in, const uint8_t* refine_radial, double radial_lo, double radial_hi, double* radial_out,
-                        uint8_t* cam_radial, uint8_t* group_radial) {
-  c.radial_in = radial_in; c.refine_radial = refine_radial; c.radial_lo = radial_lo; c.radial_hi = radial_hi;
-  c.radial_out = radial_out; c.cam_radial = cam_radial; c.group_radial = group_radial;
+inline size_t workspace_bytes(int kind, bool prior, long T, long N, int n) {
+  return with_mode(kind, prior, (size_t)0, [&](auto m) { return workspace_bytes<decltype(m)>(T, N, n); });
 }
 // the argument checks of every entry point -> LOFTR_OK when the run may start.  Limits are answered before a pointer is read;
 // zero_counts: the host routines start from counts of zero (the kernels write them on the device).

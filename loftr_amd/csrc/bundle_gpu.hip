@@ -1,15 +1,17 @@
-// Bundle adjustment on the GPU: the three host routines of bundle.hip with the same result bit for bit.
+// Bundle adjustment on the GPU: the host routines of bundle.hip with the same result bit for bit (DESIGN §18 .. §18.5).
 // Every phase of the host sequence is one kernel here, every per-item step is bundle_core.h's, compiled from the same text, fp64 without
-// FMA contraction.  As on the host there is ONE schedule, run<Mode>, with one event / launch accounting, and the kernels that touch the
-// camera block are templates on the mode (Pose, Focal, Shared); the group kernels and launches of Shared are `if constexpr` in it.  What
-// this file adds is only how a phase is spread over threads:
+// FMA contraction.  As on the host there is ONE schedule, run<Mode>, with one event / launch accounting; every kernel whose phase
+// differs between modes is a template on the mode that names its class: the mode itself where the prior acts, its Base where it does
+// not, TrackMode for the track phases (the projection alone tells them apart), SetupMode for the camera setup.  The group kernels and
+// launches of the grouped modes are `if constexpr (kGroups)` in the schedule.  What this file adds is only how a phase is spread over
+// threads:
 //   a thread per track      setup, linearise, track half of S p, back substitution, evaluate (the sums of a track run sequentially in
 //                           that one thread, as §16's refit);
 //   a wave per camera       groups check, linearise, camera half of S p: lane l accumulates slots l, l + 64, ... of the camera's list
 //                           and the 64 lanes are folded 32, 16, ..., 1 with shuffles -- osum64 exactly as the host's 64-entry array;
-//   a wave per group        (Shared) the group check, the sum of U77, the group half: the members folded as a camera's observations;
+//   a wave per group        (kGroups) the group check, the sums of its block, the group half: the members folded as a camera's observations;
 //   a wave per 4096 terms   osum over tracks, cameras or groups, one launch per level; lane 0 of the last level hands the sum to ctrl_feed;
-//   a thread per camera     factor, the two updates of the conjugate gradients, apply (Shared: the groups in the threads after them);
+//   a thread per camera     factor, the two updates of the conjugate gradients, apply (kGroups: the groups in the threads after them);
 //   one thread              init, accept: the owner of lambda, the counters and the flags.
 // The whole run is a FIXED launch schedule on the caller's stream: max_iters trials of pcg_iters iterations each.  A kernel whose phase
 // the host routine would not run (the run has stopped, the conjugate gradients have stopped, the step is already rejected, an error bit
@@ -19,9 +21,8 @@
 // Position priors (§18.3) are a trait of the mode: PoseP, FocalP and SharedP run the same schedule; the decision is taken by the lane
 // that ends ba_groups_kernel, the additions to U and gc by the lane that ends ba_cam_lin_kernel, a thread per camera evaluates the
 // prior of a state (ba_prior_eval_kernel), the levels of the cameras' osum follow it (ba_prior_osum_kernel), and every kernel that the
-// prior does not touch is the one of the mode without it.
-// Radial (§18.4) runs §18.2's schedule launch for launch: a kernel of its own stands where a kernel without a mode stood (camera
-// setup, the group check, evaluate, the track linearisation, the group sums), the templates get one more instantiation.
+// prior does not touch is the one of the mode without it (it takes the Base context by value: a wider kernel argument alone cost time,
+// profiles/bundle_refactor_bench.txt).  Radial (§18.4) runs §18.2's schedule launch for launch, as one more instantiation.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -66,38 +67,32 @@ template <int M, class F> __device__ __forceinline__ void wave_cam_sum(const Ctx
     if (c.obs_active[o]) term(o, acc);
   }, a);
 }
-// ... of group g's list: member i adds v[stride i] when it has cam_focal
-__device__ __forceinline__ double wave_group_sum(const CtxS& c, long g, int lane, const double* v, long stride) {
-  double a;
-  wave_osum64<1>(c.group_offsets[g], c.group_offsets[g + 1], lane, [&](long k, double* acc) { group_term(c, c.group_cams[k], v, stride, acc); }, &a);
-  return a;
+// ... of group g's list: term(i, a) adds member i
+template <int M, class F> __device__ __forceinline__ void wave_group_sum(const CtxS& c, long g, int lane, F term, double* a) {
+  wave_osum64<M>(c.group_offsets[g], c.group_offsets[g + 1], lane, [&](long k, double* acc) { term(c.group_cams[k], acc); }, a);
 }
+// the wave as the workers of a group's decision (OneLane of the core is the host's): folds with shuffles, integer atomics
+struct WaveLanes {
+  static constexpr int kLanes = 64;
+  int lane;
+  __device__ long sum(long v) const { for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64); return v; }
+  __device__ int any(int v) const { for (int m = 32; m >= 1; m >>= 1) v |= __shfl_xor(v, m, 64); return v; }
+  __device__ void add(int* p, int v) const { if (v) atomicAdd(p, v); }
+  __device__ void raise(int* p, int v) const { atomicOr(p, v); }
+};
 
 // what the factor and update kernels take: the base of the context (their steps need no more), with groups the groups' vectors too
-// (Radial: its group steps of these two phases read nothing beyond CtxS)
+// (the group steps of these two phases read nothing beyond CtxS in any mode)
 template <class Mode> using StepCtx = std::conditional_t<Mode::kGroups, CtxS, Ctx>;
 
 __global__ void ba_init_kernel(Ctx c, CtrlS* cs) { ctrl_init(c, cs); }
 __global__ void ba_prior_init_kernel(Prior p) { ctrl_init_prior(p); }
 
-// Radial.  grid ceil(n / 256) x 256: the setup of the other modes, then the camera's k; thread 0 owns the radial counter
-__global__ void __launch_bounds__(kThreads) ba_cam_setup_radial_kernel(CtxR c) {
+// grid ceil(n / 256) x 256; Mode: Pose, Focal or Radial (SetupMode).  Thread 0 owns what the phase resets.
+template <class Mode> __global__ void __launch_bounds__(kThreads) ba_cam_setup_kernel(typename Mode::Ctx c) {
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i == 0) c.cr->n_radial = 0;
-  if (i < c.n) {
-    cam_setup(c, i);
-    cam_setup_focal(c, i);
-    cam_setup_radial(c, i);
-  }
-}
-
-// grid ceil(n / 256) x 256
-template <int S> __global__ void __launch_bounds__(kThreads) ba_cam_setup_kernel(std::conditional_t<S == 7, Ctx7, Ctx> c) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i < c.n) {
-    cam_setup(c, i);
-    if constexpr (S == 7) cam_setup_focal(c, i);
-  }
+  if (i == 0) cam_setup_ctrl<Mode>(c);
+  if (i < c.n) cam_setup<Mode>(c, i);
 }
 
 // grid ceil(T / 256) x 256
@@ -154,104 +149,19 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_groups_kern
   }
 }
 
-// Shared.  A wave per group, grid ceil(G / 4) x 256: the check of the group arrays and the count; a wave per group folds its members
-// exactly as a wave per camera folds its observations.  Reads the arrays only through checked indices, and writes cam_focal only when
-// the whole list of the group has passed, so it needs no flag.
-__global__ void __launch_bounds__(kThreads) ba_cgroups_kernel(CtxS c) {
+// A wave per group, grid ceil(G / 4) x 256: the check of the group arrays, the counts and the decisions (cgroup_decide); a wave per
+// group folds its members exactly as a wave per camera folds its observations.  Reads the arrays only through checked indices, and
+// writes cam_focal only when the whole list of the group has passed, so it needs no flag.
+template <class Mode> __global__ void __launch_bounds__(kThreads) ba_cgroups_kernel(typename Mode::Ctx c) {
   const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  if (g >= c.G) return;
-  long b, e, total = 0;
-  int err = 0;
-  if (!cgroup_range(c, g, &b, &e)) { err = kBadCamGroups; b = e = 0; }
-  for (long k = b + lane; k < e; k += 64) {
-    long cnt;
-    err |= cgroup_slot(c, g, b, k, &cnt);
-    total += cnt;
-  }
-  for (int m = 32; m >= 1; m >>= 1) { err |= __shfl_xor(err, m, 64); total += __shfl_xor(total, m, 64); }
-  if (err) {
-    if (lane == 0) atomicOr(&c.ctrl->err, err);
-    return;
-  }
-  const bool refines = lane == 0 ? cgroup_rule(c, g, total) : total >= (long)c.min_focal_obs;
-  int nf = 0;
-  for (long k = b + lane; k < e; k += 64) {
-    const int i = c.group_cams[k];
-    const bool fo = refines && c.cam_cnt[i] > 0;
-    c.cam_focal[i] = (uint8_t)fo;
-    nf += fo;
-  }
-  for (int m = 32; m >= 1; m >>= 1) nf += __shfl_xor(nf, m, 64);
-  if (lane == 0) {
-    c.group_focal[g] = (uint8_t)refines;
-    if (refines) atomicAdd(&c.cs->n_groups, 1);
-    if (nf) atomicAdd(&c.ctrl->n_focal, nf);
-  }
-}
-// Radial.  The same kernel (its text is kept apart so that the device code of ba_cgroups_kernel stays what it was), and then the
-// radial decision of the group and of its members from the same counts.
-__global__ void __launch_bounds__(kThreads) ba_cgroups_radial_kernel(CtxR c) {
-  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  if (g >= c.G) return;
-  long b, e, total = 0, rtotal = 0;
-  int err = 0;
-  if (!cgroup_range(c, g, &b, &e)) { err = kBadCamGroups; b = e = 0; }
-  for (long k = b + lane; k < e; k += 64) {
-    long cnt;
-    err |= cgroup_slot(c, g, b, k, &cnt);
-    total += cnt;
-    rtotal += cgroup_slot_radial(c, k, cnt);
-  }
-  for (int m = 32; m >= 1; m >>= 1) { err |= __shfl_xor(err, m, 64); total += __shfl_xor(total, m, 64); }
-  for (int m = 32; m >= 1; m >>= 1) rtotal += __shfl_xor(rtotal, m, 64);
-  if (err) {
-    if (lane == 0) atomicOr(&c.ctrl->err, err);
-    return;
-  }
-  const bool refines = lane == 0 ? cgroup_rule(c, g, total) : total >= (long)c.min_focal_obs;
-  int nf = 0;
-  for (long k = b + lane; k < e; k += 64) {
-    const int i = c.group_cams[k];
-    const bool fo = refines && c.cam_cnt[i] > 0;
-    c.cam_focal[i] = (uint8_t)fo;
-    nf += fo;
-  }
-  for (int m = 32; m >= 1; m >>= 1) nf += __shfl_xor(nf, m, 64);
-  if (lane == 0) {
-    c.group_focal[g] = (uint8_t)refines;
-    if (refines) atomicAdd(&c.cs->n_groups, 1);
-    if (nf) atomicAdd(&c.ctrl->n_focal, nf);
-  }
-  {                                                                      // (cam_cnt is read, cam_focal is not: no lane waits for another)
-    const bool rr = lane == 0 ? cgroup_rule_radial(c, g, refines, rtotal) : refines && rtotal >= (long)c.min_focal_obs;
-    int nr = 0;
-    for (long k = b + lane; k < e; k += 64) {
-      const int i = c.group_cams[k];
-      const bool ra = cam_radial_rule(c, i, rr);
-      c.cam_radial[i] = (uint8_t)ra;
-      nr += ra;
-    }
-    for (int m = 32; m >= 1; m >>= 1) nr += __shfl_xor(nr, m, 64);
-    if (lane == 0) {
-      c.group_radial[g] = (uint8_t)rr;
-      if (nr) atomicAdd(&c.cr->n_radial, nr);
-    }
-  }
+  if (g < c.G) cgroup_decide<Mode>(c, g, WaveLanes{(int)(threadIdx.x % 64)});
 }
 
-// grid ceil(T / 256) x 256; other = 0 evaluates the state, 1 the trial
-__global__ void __launch_bounds__(kThreads) ba_evaluate_kernel(Ctx c, int other, int flags) {
+// grid ceil(T / 256) x 256; other = 0 evaluates the state, 1 the trial.  TMode: Pose or Radial (TrackMode), the projection
+template <class TMode> __global__ void __launch_bounds__(kThreads) ba_evaluate_kernel(typename TMode::Ctx c, int other, int flags) {
   if (skipped(c, flags)) return;
   const long t = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (t < c.T && !track_eval(c, c.ctrl->cur ^ other, t)) atomicOr(&c.ctrl->bad_e, 1);
-}
-// Radial: ... through the distorted projection
-__global__ void __launch_bounds__(kThreads) ba_evaluate_radial_kernel(CtxR c, int other, int flags) {
-  if (skipped(c, flags)) return;
-  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (t < c.T && !track_eval<Radial>(c, c.ctrl->cur ^ other, t)) atomicOr(&c.ctrl->bad_e, 1);
+  if (t < c.T && !track_eval<TMode>(c, c.ctrl->cur ^ other, t)) atomicOr(&c.ctrl->bad_e, 1);
 }
 
 // one level of an osum: a wave per chunk of 4096, grid ceil(count / 4096) (at least 1) x 64.  On the last level action >= 0 feeds the
@@ -288,15 +198,10 @@ __global__ void __launch_bounds__(64) ba_prior_osum_kernel(Ctx c, Prior p, const
   }
 }
 
-__global__ void __launch_bounds__(kThreads) ba_track_lin_kernel(Ctx c, int flags) {
+template <class TMode> __global__ void __launch_bounds__(kThreads) ba_track_lin_kernel(typename TMode::Ctx c, int flags) {
   if (skipped(c, flags)) return;
   const long t = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (t < c.T) track_lin(c, c.ctrl->cur, t);
-}
-__global__ void __launch_bounds__(kThreads) ba_track_lin_radial_kernel(CtxR c, int flags) {
-  if (skipped(c, flags)) return;
-  const long t = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (t < c.T) track_lin<Radial>(c, c.ctrl->cur, t);
+  if (t < c.T) track_lin<TMode>(c, c.ctrl->cur, t);
 }
 
 // a wave per camera that takes part, grid ceil(n / 4) x 256
@@ -317,25 +222,17 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_cam_lin_ker
   }
 }
 
-// Shared.  A wave per refining group, grid ceil(G / 4) x 256: d_g = the sum of U77 over its members
-__global__ void __launch_bounds__(kThreads) ba_group_lin_kernel(CtxS c, int flags) {
+// A wave per refining group, grid ceil(G / 4) x 256: d_g = the sum of U77 over its members (Radial: the three sums of its 2 x 2 block)
+template <class Mode> __global__ void __launch_bounds__(kThreads) ba_group_lin_kernel(typename Mode::Ctx c, int flags) {
   if (skipped(c, flags)) return;
   const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
   const int lane = threadIdx.x % 64;
   if (g >= c.G || !c.group_focal[g]) return;
-  const double d = wave_group_sum(c, g, lane, c.U + 27, 28);
-  if (lane == 0) c.dg[g] = d;
-}
-// Radial.  ... the three sums of its 2 x 2 block
-__global__ void __launch_bounds__(kThreads) ba_group_lin_radial_kernel(CtxR c, int flags) {
-  if (skipped(c, flags)) return;
-  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  if (g >= c.G || !c.group_focal[g]) return;
-  double d[3];
-  wave_osum64<3>(c.group_offsets[g], c.group_offsets[g + 1], lane, [&](long k, double* acc) { group_term_block(c, c.group_cams[k], acc); }, d);
+  constexpr int kD = kTri<Mode::GW>;
+  double d[kD];
+  wave_group_sum<kD>(c, g, lane, [&](long i, double* acc) { group_lin_term<Mode>(c, i, acc); }, d);
   if (lane == 0)
-    for (int k = 0; k < 3; ++k) c.dg[3 * g + k] = d[k];
+    for (int k = 0; k < kD; ++k) c.dg[kD * g + k] = d[k];
 }
 
 // threads [0, T): tracks, [T, T + n): cameras, Shared [T + n, T + n + G): groups; grid ceil of that / 256 x 256
@@ -347,10 +244,7 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_factor_kern
   if (id < c.T) ok = track_factor(c, id, lambda);
   else if (id < c.T + c.n) ok = cam_factor<Mode>(c, id - c.T, lambda);
   else if constexpr (Mode::kGroups) {
-    if (id < c.T + c.n + c.G) {
-      if constexpr (Mode::kRadial) ok = group_factor_radial(c, id - c.T - c.n, lambda);
-      else ok = group_factor(c, id - c.T - c.n, lambda);
-    }
+    if (id < c.T + c.n + c.G) ok = group_factor<Mode>(c, id - c.T - c.n, lambda);
   }
   if (!ok) atomicOr(&c.ctrl->bad_f, 1);
 }
@@ -376,26 +270,17 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_cam_half_ke
   if (lane == 0) cam_half_finish<Mode>(c, i, mode, c.ctrl->lambda, a);
 }
 
-// Shared.  A wave per group, grid ceil(G / 4) x 256: E^T of the cameras' seventh entries, then the group's own step
-__global__ void __launch_bounds__(kThreads) ba_group_half_kernel(CtxS c, int mode, int flags) {
+// A wave per group, grid ceil(G / 4) x 256: E^T of the cameras' seventh (Radial: and eighth) entries, then the group's own step
+template <class Mode> __global__ void __launch_bounds__(kThreads) ba_group_half_kernel(typename Mode::Ctx c, int mode, int flags) {
   if (skipped(c, flags)) return;
   const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
   const int lane = threadIdx.x % 64;
   if (g >= c.G) return;
-  double s = 0.0;
-  if (c.group_focal[g]) s = wave_group_sum(c, g, lane, c.Sp + 6, 7);
-  if (lane == 0) group_half_finish(c, g, mode, c.ctrl->lambda, s);
-}
-// Radial.  ... of the seventh and eighth entries
-__global__ void __launch_bounds__(kThreads) ba_group_half_radial_kernel(CtxR c, int mode, int flags) {
-  if (skipped(c, flags)) return;
-  const long g = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  if (g >= c.G) return;
-  double s[2] = {0.0, 0.0};
-  if (c.group_focal[g])
-    wave_osum64<2>(c.group_offsets[g], c.group_offsets[g + 1], lane, [&](long k, double* acc) { group_term_pair(c, c.group_cams[k], acc); }, s);
-  if (lane == 0) group_half_finish_radial(c, g, mode, c.ctrl->lambda, s);
+  double s[Mode::GW];
+#pragma unroll
+  for (int k = 0; k < Mode::GW; ++k) s[k] = 0.0;
+  if (c.group_focal[g]) wave_group_sum<Mode::GW>(c, g, lane, [&](long i, double* acc) { group_half_term<Mode>(c, i, acc); }, s);
+  if (lane == 0) group_half_finish<Mode>(c, g, mode, c.ctrl->lambda, s);
 }
 
 // threads [0, n): cameras, Shared [n, n + G): groups (the scalar update of a group)
@@ -407,13 +292,8 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_update_kern
     else cam_update2<Mode>(c, id, c.ctrl->beta);
   } else if constexpr (Mode::kGroups) {
     if (id >= c.n + c.G) return;
-    if constexpr (Mode::kRadial) {
-      if (which == 1) group_update1_radial(c, id - c.n, c.ctrl->alpha);
-      else group_update2_radial(c, id - c.n, c.ctrl->beta);
-    } else {
-      if (which == 1) group_update1(c, id - c.n, c.ctrl->alpha, c.ctrl->lambda);
-      else group_update2(c, id - c.n, c.ctrl->beta);
-    }
+    if (which == 1) group_update1<Mode>(c, id - c.n, c.ctrl->alpha, c.ctrl->lambda);
+    else group_update2<Mode>(c, id - c.n, c.ctrl->beta);
   }
 }
 
@@ -426,10 +306,7 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_apply_kerne
   if (id < c.T) ok = track_half<Mode>(c, cur, id, 2);
   else if (id < c.T + c.n) ok = cam_apply<Mode>(c, cur, id - c.T);
   else if constexpr (Mode::kGroups) {
-    if (id < c.T + c.n + c.G) {
-      if constexpr (Mode::kRadial) group_apply_radial(c, cur, id - c.T - c.n);
-      else group_apply(c, cur, id - c.T - c.n);
-    }
+    if (id < c.T + c.n + c.G) group_apply<Mode>(c, cur, id - c.T - c.n);
   }
   if (!ok) atomicOr(&c.ctrl->bad_a, 1);
 }
@@ -452,11 +329,13 @@ template <class Mode> __global__ void __launch_bounds__(kThreads) ba_write_kerne
 }
 
 // the fixed launch schedule of every mode; c holds the problem and the result.  The phases that do not touch the camera block or the
-// groups (track setup, evaluate, the track linearisation, accept, the osum) are one kernel for all modes, on the base of the context.
+// groups (track setup, accept, the osum; evaluate and the track linearisation per projection) are one kernel for all modes, on the
+// base of the context.
 template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iters, double pcg_tol, void* ws, size_t ws_bytes, float* class_ms,
                               long* class_launches, void* stream) {
-  constexpr bool kGroups = Mode::kGroups, kPrior = Mode::kPrior, kRadial = Mode::kRadial;
+  constexpr bool kGroups = Mode::kGroups, kPrior = Mode::kPrior;
   using BaseMode = typename Mode::Base;                                 // the kernels of the phases that the prior does not touch
+  using TMode = TrackMode<Mode>;                                        // ... of the track phases: the projection alone tells them apart
   LOFTR_CHECK_ARG(ws);
   const int st = check_args<Mode>(c, max_iters, pcg_iters, pcg_tol, false);
   if (st != LOFTR_OK) return st;
@@ -486,22 +365,36 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   const dim3 threads(kThreads);
   const Ctx& b = c;                                                     // what the kernels of all modes take
   const typename BaseMode::Ctx& cb = c;                                 // ... and those of the mode, without the prior
+  const typename TMode::Ctx& tb = c;                                    // ... those of the track phases
+  const typename SetupMode<Mode>::Ctx& sb = c;                          // ... and the camera setup
   Prior pr{};
   if constexpr (kPrior) pr = c.pr;
   double* red2 = c.red + ((std::max(T, n) + 1 + kChunk - 1) / kChunk);
-  // osum of v[0 .. count) into `action` (ba_osum_kernel): one launch per level
-  auto osum = [&](const double* v, long count, int action, double* wait, int flags) {
+  // the levels of an osum of v[0 .. count): launch(chunks, in, count, out, last) once per level
+  auto levels = [&](const double* v, long count, auto launch) {
     const double* in = v;
     double* out = c.red;
     for (;;) {
       const long chunks = count > 0 ? (count + kChunk - 1) / kChunk : 1;
-      hipLaunchKernelGGL(ba_osum_kernel, dim3((unsigned)chunks), dim3(64), 0, s, b, in, count, out, chunks == 1 ? action : -1, wait, flags);
+      launch(dim3((unsigned)chunks), in, count, out, chunks == 1);
       after(kClsOsum);
       if (chunks == 1) return;
       in = out;
       out = out == c.red ? red2 : c.red;
       count = chunks;
     }
+  };
+  // osum of v[0 .. count) into `action` (ba_osum_kernel)
+  auto osum = [&](const double* v, long count, int action, double* wait, int flags) {
+    levels(v, count, [&](dim3 grid, const double* in, long cnt, double* out, bool last) {
+      hipLaunchKernelGGL(ba_osum_kernel, grid, dim3(64), 0, s, b, in, cnt, out, last ? action : -1, wait, flags);
+    });
+  };
+  // ... of the cameras' prior terms v[0 .. n) into `action` (ba_prior_osum_kernel)
+  auto prior_osum = [&](const double* v, int action, int flags) {
+    levels(v, n, [&](dim3 grid, const double* in, long cnt, double* out, bool last) {
+      hipLaunchKernelGGL(ba_prior_osum_kernel, grid, dim3(64), 0, s, b, pr, in, cnt, out, last ? action : -1, flags);
+    });
   };
   // a dot product over the unknowns: the cameras' terms, and with groups the groups' terms added to their sum
   auto dot = [&](int action, int flags) {
@@ -512,29 +405,11 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   };
   auto camera_half = [&](int mode, int flags) {
     hipLaunchKernelGGL(ba_cam_half_kernel<BaseMode>, blocks(n, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf);
-    if constexpr (kRadial) { hipLaunchKernelGGL(ba_group_half_radial_kernel, blocks(G, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf); }
-    else if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_half_kernel, blocks(G, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf); }
-  };
-  // osum of the cameras' prior terms v[0 .. n) into `action` (ba_prior_osum_kernel): one launch per level
-  auto prior_osum = [&](const double* v, int action, int flags) {
-    const double* in = v;
-    double* out = c.red;
-    long count = n;
-    for (;;) {
-      const long chunks = count > 0 ? (count + kChunk - 1) / kChunk : 1;
-      hipLaunchKernelGGL(ba_prior_osum_kernel, dim3((unsigned)chunks), dim3(64), 0, s, b, pr, in, count, out, chunks == 1 ? action : -1, flags);
-      after(kClsOsum);
-      if (chunks == 1) return;
-      in = out;
-      out = out == c.red ? red2 : c.red;
-      count = chunks;
-    }
+    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_half_kernel<BaseMode>, blocks(G, 4), threads, 0, s, cb, mode, flags); after(kClsCamHalf); }
   };
   // evaluate the state (other = 0) or the trial, then its cost and sum of |r|^2: the tracks' osum, with priors the cameras' added to it
   auto evaluate = [&](int other, int cost, int sq, int flags) {
-    if constexpr (kRadial) hipLaunchKernelGGL(ba_evaluate_radial_kernel, blocks(T, kThreads), threads, 0, s, cb, other, flags);
-    else hipLaunchKernelGGL(ba_evaluate_kernel, blocks(T, kThreads), threads, 0, s, b, other, flags);
-    after(kClsEvaluate);
+    hipLaunchKernelGGL(ba_evaluate_kernel<TMode>, blocks(T, kThreads), threads, 0, s, tb, other, flags); after(kClsEvaluate);
     const int f = other ? flags | kSkipBadE : flags;
     if constexpr (kPrior) {
       hipLaunchKernelGGL(ba_prior_eval_kernel, blocks(n, kThreads), threads, 0, s, b, pr, other, flags); after(kClsEvaluate);
@@ -550,21 +425,15 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   if (timed) mark();
   hipLaunchKernelGGL(ba_init_kernel, dim3(1), dim3(1), 0, s, b, groups_ctrl<Mode>(c)); after(kClsSetup);
   if constexpr (kPrior) { hipLaunchKernelGGL(ba_prior_init_kernel, dim3(1), dim3(1), 0, s, pr); after(kClsSetup); }
-  if constexpr (kRadial) hipLaunchKernelGGL(ba_cam_setup_radial_kernel, blocks(n, kThreads), threads, 0, s, cb);
-  else hipLaunchKernelGGL(ba_cam_setup_kernel<Mode::S>, blocks(n, kThreads), threads, 0, s, cb);
-  after(kClsSetup);
+  hipLaunchKernelGGL(ba_cam_setup_kernel<SetupMode<Mode>>, blocks(n, kThreads), threads, 0, s, sb); after(kClsSetup);
   hipLaunchKernelGGL(ba_track_setup_kernel, blocks(T, kThreads), threads, 0, s, b); after(kClsSetup);
   hipLaunchKernelGGL(ba_groups_kernel<Mode>, blocks(n, 4), threads, 0, s, c); after(kClsSetup);
-  if constexpr (kRadial) { hipLaunchKernelGGL(ba_cgroups_radial_kernel, blocks(G, 4), threads, 0, s, cb); after(kClsSetup); }
-  else if constexpr (kGroups) { hipLaunchKernelGGL(ba_cgroups_kernel, blocks(G, 4), threads, 0, s, cb); after(kClsSetup); }
+  if constexpr (kGroups) { hipLaunchKernelGGL(ba_cgroups_kernel<BaseMode>, blocks(G, 4), threads, 0, s, cb); after(kClsSetup); }
   evaluate(0, kActCost0, kActSq0, 0);
   for (int it = 0; it < max_iters && !failed; ++it) {
-    if constexpr (kRadial) hipLaunchKernelGGL(ba_track_lin_radial_kernel, blocks(T, kThreads), threads, 0, s, cb, kNeedFresh);
-    else hipLaunchKernelGGL(ba_track_lin_kernel, blocks(T, kThreads), threads, 0, s, b, kNeedFresh);
-    after(kClsLinearise);
+    hipLaunchKernelGGL(ba_track_lin_kernel<TMode>, blocks(T, kThreads), threads, 0, s, tb, kNeedFresh); after(kClsLinearise);
     hipLaunchKernelGGL(ba_cam_lin_kernel<Mode>, blocks(n, 4), threads, 0, s, c, kNeedFresh); after(kClsLinearise);
-    if constexpr (kRadial) { hipLaunchKernelGGL(ba_group_lin_radial_kernel, blocks(G, 4), threads, 0, s, cb, kNeedFresh); after(kClsLinearise); }
-    else if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_lin_kernel, blocks(G, 4), threads, 0, s, cb, kNeedFresh); after(kClsLinearise); }
+    if constexpr (kGroups) { hipLaunchKernelGGL(ba_group_lin_kernel<BaseMode>, blocks(G, 4), threads, 0, s, cb, kNeedFresh); after(kClsLinearise); }
     hipLaunchKernelGGL(ba_factor_kernel<BaseMode>, blocks(T + n + G, kThreads), threads, 0, s, cb, 0); after(kClsFactor);
     hipLaunchKernelGGL(ba_track_half_kernel<BaseMode>, blocks(T, kThreads), threads, 0, s, cb, 0, kSkipBadF); after(kClsTrackHalf);
     camera_half(0, kSkipBadF);
@@ -605,21 +474,28 @@ template <class Mode> int run(typename Mode::Ctx& c, int max_iters, int pcg_iter
   return failed ? LOFTR_ERR_LAUNCH : LOFTR_OK;
 }
 
+template <class Mode> int enter(const Args& a, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
+  typename Mode::Ctx c{};
+  fill<Mode>(c, a);
+  return run<Mode>(c, a.par.max_iters, a.par.pcg_iters, a.par.pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+}
+
 }  // namespace
 
-extern "C" size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images) { return workspace_bytes<Pose>(T, N, n_images); }
-extern "C" size_t loftr_bundle_adjust_focal_workspace_bytes(long T, long N, int n_images) { return workspace_bytes<Focal>(T, N, n_images); }
-extern "C" size_t loftr_bundle_adjust_shared_workspace_bytes(long T, long N, int n_images) { return workspace_bytes<Shared>(T, N, n_images); }
+extern "C" size_t loftr_bundle_adjust_workspace_bytes(long T, long N, int n_images) { return workspace_bytes(kKindPose, false, T, N, n_images); }
+extern "C" size_t loftr_bundle_adjust_focal_workspace_bytes(long T, long N, int n_images) { return workspace_bytes(kKindFocal, false, T, N, n_images); }
+extern "C" size_t loftr_bundle_adjust_shared_workspace_bytes(long T, long N, int n_images) { return workspace_bytes(kKindShared, false, T, N, n_images); }
+extern "C" size_t loftr_bundle_adjust_radial_workspace_bytes(long T, long N, int n_images) { return workspace_bytes(kKindRadial, false, T, N, n_images); }
+extern "C" size_t loftr_bundle_adjust_prior_workspace_bytes(long T, long N, int n_images, int mode) { return workspace_bytes(mode, true, T, N, n_images); }
 
 extern "C" int loftr_bundle_adjust(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask, long N,
                                    const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed, int n_images,
                                    const long* cam_offsets, const int* cam_obs, double huber_px, int max_iters, int pcg_iters, double pcg_tol,
                                    double ftol, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free, uint8_t* point_active,
                                    long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
-  Ctx c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  return run<Pose>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+  return enter<Pose>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                      {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts}},
+                     ws, ws_bytes, class_ms, class_launches, stream);
 }
 
 extern "C" int loftr_bundle_adjust_focal(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
@@ -629,11 +505,10 @@ extern "C" int loftr_bundle_adjust_focal(const long* offsets, long T, const int*
                                          double focal_lo, double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active,
                                          uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, long* counts, void* ws,
                                          size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
-  Ctx7 c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-  return run<Focal>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+  return enter<Focal>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                       {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+                       {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal}},
+                      ws, ws_bytes, class_ms, class_launches, stream);
 }
 
 extern "C" int loftr_bundle_adjust_shared(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
@@ -644,15 +519,11 @@ extern "C" int loftr_bundle_adjust_shared(const long* offsets, long T, const int
                                           double focal_hi, double* T_out, float* xyz_out, uint8_t* obs_active, uint8_t* cam_free,
                                           uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal, long* counts,
                                           void* ws, size_t ws_bytes, float* class_ms, long* class_launches, void* stream) {
-  CtxS c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-  fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
-  return run<Shared>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+  return enter<Shared>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                        {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+                        {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal}, {cam_group, group_offsets, group_cams, G, group_focal}},
+                       ws, ws_bytes, class_ms, class_launches, stream);
 }
-
-extern "C" size_t loftr_bundle_adjust_radial_workspace_bytes(long T, long N, int n_images) { return workspace_bytes<Radial>(T, N, n_images); }
 
 extern "C" int loftr_bundle_adjust_radial(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
                                           long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
@@ -664,31 +535,15 @@ extern "C" int loftr_bundle_adjust_radial(const long* offsets, long T, const int
                                           uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal, double* radial_out,
                                           uint8_t* cam_radial, uint8_t* group_radial, long* counts, void* ws, size_t ws_bytes, float* class_ms,
                                           long* class_launches, void* stream) {
-  CtxR c{};
-  fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol, ftol,
-       T_out, xyz_out, obs_active, cam_free, point_active, counts);
-  fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-  fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
-  fill_radial(c, radial_in, refine_radial, radial_lo, radial_hi, radial_out, cam_radial, group_radial);
-  return run<Radial>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
+  return enter<Radial>({{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+                        {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+                        {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal}, {cam_group, group_offsets, group_cams, G, group_focal},
+                        {radial_in, refine_radial, radial_lo, radial_hi, radial_out, cam_radial, group_radial}},
+                       ws, ws_bytes, class_ms, class_launches, stream);
 }
 
-// with position priors on the camera centres (§18.3): mode 0 pose, 1 focal, 2 shared
-namespace {
-template <class F> auto with_prior_mode(int mode, F go) -> decltype(go(PoseP{})) {
-  switch (mode) {
-    case 0: return go(PoseP{});
-    case 1: return go(FocalP{});
-    case 2: return go(SharedP{});
-  }
-  return decltype(go(PoseP{}))(0);
-}
-}  // namespace
-
-extern "C" size_t loftr_bundle_adjust_prior_workspace_bytes(long T, long N, int n_images, int mode) {
-  return with_prior_mode(mode, [&](auto m) { return workspace_bytes<decltype(m)>(T, N, n_images); });
-}
-
+// with position priors on the camera centres (§18.3): mode 0 pose, 1 focal, 2 shared; the focal and group arguments are ignored below
+// their mode
 extern "C" int loftr_bundle_adjust_prior(const long* offsets, long T, const int* obs_image, const float* obs_xy, const uint8_t* obs_mask,
                                          long N, const float* xyz, const double* K, const double* T_cam_from_world, const uint8_t* fixed,
                                          const uint8_t* refine_focal, int n_images, const long* cam_offsets, const int* cam_obs,
@@ -699,15 +554,9 @@ extern "C" int loftr_bundle_adjust_prior(const long* offsets, long T, const int*
                                          uint8_t* cam_free, uint8_t* point_active, double* K_out, uint8_t* cam_focal, uint8_t* group_focal,
                                          uint8_t* cam_prior, long* counts, void* ws, size_t ws_bytes, float* class_ms, long* class_launches,
                                          void* stream) {
-  if (mode < 0 || mode > 2) return LOFTR_ERR_BAD_ARG;
-  return with_prior_mode(mode, [&](auto m) {
-    using Mode = decltype(m);
-    typename Mode::Ctx c{};
-    fill(c, offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs, huber_px, pcg_tol,
-         ftol, T_out, xyz_out, obs_active, cam_free, point_active, counts);
-    if constexpr (Mode::S == 7) fill_focal(c, refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal);
-    if constexpr (Mode::kGroups) fill_groups(c, cam_group, group_offsets, group_cams, G, group_focal);
-    fill_prior(c.pr, prior_xyz, prior_sigma, prior_mask, cam_prior);
-    return run<Mode>(c, max_iters, pcg_iters, pcg_tol, ws, ws_bytes, class_ms, class_launches, stream);
-  });
+  const Args a{{offsets, T, obs_image, obs_xy, obs_mask, N, xyz, K, T_cam_from_world, fixed, n_images, cam_offsets, cam_obs},
+               {huber_px, max_iters, pcg_iters, pcg_tol, ftol}, {T_out, xyz_out, obs_active, cam_free, point_active, counts},
+               {refine_focal, min_focal_obs, focal_lo, focal_hi, K_out, cam_focal}, {cam_group, group_offsets, group_cams, G, group_focal}, {},
+               {prior_xyz, prior_sigma, prior_mask, cam_prior}};
+  return with_mode(mode, true, (int)LOFTR_ERR_BAD_ARG, [&](auto m) { return enter<decltype(m)>(a, ws, ws_bytes, class_ms, class_launches, stream); });
 }

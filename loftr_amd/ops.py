@@ -1520,26 +1520,22 @@ def _ba_focal_params(what, min_focal_obs, focal_lo, focal_hi):
 
 # bits of counts[1] of the grouped pair: BUNDLE_ERRORS and the check of the camera groups
 BUNDLE_SHARED_ERRORS = BUNDLE_ERRORS + ((8, "cam_group / group_offsets / group_cams are not the images grouped by camera in ascending order"),)
-# The three modes, each a routine pair loftr_<call>_host / loftr_<call>, differ in a table: the inputs after
-# cam_obs (refine_focal goes after fixed in the C call, the group arrays and G after cam_obs), the outputs after point_active, how the
-# shape error ends, and what the rule text adds.
+# A mode (DESIGN §18 .. §18.4) is a routine pair loftr_<call>_host / loftr_<call> and ONE row of this table: the inputs after cam_obs
+# (refine_focal goes after fixed in the C call, the group arrays and G after cam_obs, radial and refine_radial after G), the outputs
+# after point_active, how the shape error ends, what the rule text adds, the mode's number in the pair with position priors (§18.3;
+# None: the mode takes no priors), and whether its parameters end with the radial bounds.
 _BA_FOCAL_IN, _BA_FOCAL_OUT = (("refine_focal", "uint8", 1),), (("K", "n", (3, 3), "float64"), ("cam_focal", "n", (), "uint8"))
+_BA_GROUP_IN = _BA_FOCAL_IN + (("cam_group", "int32", 1), ("group_offsets", "int64", 1), ("group_cams", "int32", 1))
+_BA_GROUP_OUT = _BA_FOCAL_OUT + (("group_focal", "G", (), "uint8"),)
+_BA_GROUP_SHAPES = "cam_offsets [n+1], cam_obs [N], refine_focal [n], cam_group [n], group_offsets [G+1] with 1 <= G <= n and group_cams [n]"
+_BA_GROUP_RULE = "; cam_group / group_offsets / group_cams must group the images by camera in ascending order"
 _BA_MODES = {
-    "bundle_adjust": ((), (), "cam_offsets [n+1] and cam_obs [N]", ""),
-    "bundle_adjust_focal": (_BA_FOCAL_IN, _BA_FOCAL_OUT, "cam_offsets [n+1], cam_obs [N] and refine_focal [n]", ""),
-    "bundle_adjust_shared": (_BA_FOCAL_IN + (("cam_group", "int32", 1), ("group_offsets", "int64", 1), ("group_cams", "int32", 1)),
-                             _BA_FOCAL_OUT + (("group_focal", "G", (), "uint8"),),
-                             "cam_offsets [n+1], cam_obs [N], refine_focal [n], cam_group [n], group_offsets [G+1] with 1 <= G <= n and "
-                             "group_cams [n]",
-                             "; cam_group / group_offsets / group_cams must group the images by camera in ascending order")}
-# ... and the grouped mode with one radial coefficient per group, which takes no priors and so is no row of the table
-# above: two more inputs after G, three more outputs
-_s = _BA_MODES["bundle_adjust_shared"]
-_BA_RADIAL_MODE = {"bundle_adjust_radial": (_s[0] + (("radial", "float64", 1), ("refine_radial", "uint8", 1)),
-                                            _s[1] + (("radial", "n", (), "float64"), ("cam_radial", "n", (), "uint8"),
-                                                     ("group_radial", "G", (), "uint8")),
-                                            _s[2] + ", radial [n] and refine_radial [n]", _s[3])}
-del _s
+    "bundle_adjust": ((), (), "cam_offsets [n+1] and cam_obs [N]", "", 0, False),
+    "bundle_adjust_focal": (_BA_FOCAL_IN, _BA_FOCAL_OUT, "cam_offsets [n+1], cam_obs [N] and refine_focal [n]", "", 1, False),
+    "bundle_adjust_shared": (_BA_GROUP_IN, _BA_GROUP_OUT, _BA_GROUP_SHAPES, _BA_GROUP_RULE, 2, False),
+    "bundle_adjust_radial": (_BA_GROUP_IN + (("radial", "float64", 1), ("refine_radial", "uint8", 1)),
+                             _BA_GROUP_OUT + (("radial", "n", (), "float64"), ("cam_radial", "n", (), "uint8"), ("group_radial", "G", (), "uint8")),
+                             _BA_GROUP_SHAPES + ", radial [n] and refine_radial [n]", _BA_GROUP_RULE, None, True)}
 
 
 def _ba_radial_params(what, radial_lo, radial_hi):
@@ -1550,19 +1546,18 @@ def _ba_radial_params(what, radial_lo, radial_hi):
     return float(radial_lo), float(radial_hi)
 
 
-# Position priors on the camera centres are one more row of any mode: three inputs, one output, 24 counts, and ONE routine
+# Position priors on the camera centres are one more trait of a mode: three inputs, one output, 24 counts, and ONE routine
 # pair, loftr_bundle_adjust_prior(_host), that takes the arguments of the grouped pair (NULL below the mode) and the mode's number.
 BUNDLE_PRIOR_COUNTS = 24
 _BA_PRIOR_IN = (("prior_xyz", "float64", 2), ("prior_sigma", "float64", 2), ("prior_mask", "uint8", 1))
 _BA_PRIOR_OUT = (("cam_prior", "n", (), "uint8"),)
-_BA_PRIOR_MODE = {"bundle_adjust": 0, "bundle_adjust_focal": 1, "bundle_adjust_shared": 2}
 
 
 def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None, radial=None):
-    """The body of all eight: the table check, the shapes, the parameters, zeroed outputs, the timing buffers (per kernel class, not per
+    """The body of all ten: the table check, the shapes, the parameters, zeroed outputs, the timing buffers (per kernel class, not per
     stage: the median launch and the total, and the launches issued), the call.  prior: None, or (prior_xyz, prior_sigma, prior_mask);
-    radial: None, or (radial_lo, radial_hi) of the mode with a radial coefficient."""
-    extra_in, extra_out, shapes, rule = _BA_MODES[call] if radial is None else _BA_RADIAL_MODE[call]
+    radial: (radial_lo, radial_hi) of the mode with a radial coefficient."""
+    extra_in, extra_out, shapes, rule, prior_mode, radial_bounds = _BA_MODES[call]
     name = call if prior is None else "bundle_adjust_prior"
     what, hint = (name + "_host", name) if B is _Host else \
         (name, f"the bundle-adjustment kernels have no CPU fallback; the host routine is {name}_host")
@@ -1586,50 +1581,38 @@ def _bundle_adjust(B, call, arrays, params, focal, timings, prior=None, radial=N
     params = _ba_params(what, *params)
     if focal is not None:
         params += _ba_focal_params(what, *focal)
-    if radial is not None:
+    if radial_bounds:
         params += _ba_radial_params(what, *radial)
     arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
     a = [B.ptr(x) for x in arrays]
-    if prior is not None:
-        return _bundle_adjust_prior(B, _BA_PRIOR_MODE[call], a, [B.contiguous(x) for x in prior], params, size, extra_out, rule, offsets,
-                                    timings)
-    out = _outputs(B, _BA_OUT + extra_out, size, BUNDLE_COUNTS, offsets)
+    head = (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7])
+    if prior is None:
+        out = _outputs(B, _BA_OUT + extra_out, size, BUNDLE_COUNTS, offsets)
+        args = (*head, *a[10:11], n, a[8], a[9], *a[11:14], *([G] if groups else []), *a[14:], *params, *[B.ptr(out[k]) for k in out])
+        ws = (T, N, n)
+    else:               # the pointers laid out as the grouped pair's, NULL for what the mode lacks (its parameters are ignored below mode 1)
+        prior = [B.contiguous(x) for x in prior]
+        a += [None] * (14 - len(a))
+        out = _outputs(B, _BA_OUT + extra_out + _BA_PRIOR_OUT, size, BUNDLE_PRIOR_COUNTS, offsets)
+        named = dict(out, **{k: None for k in ("K", "cam_focal", "group_focal") if k not in out})
+        order = [k for k, *_ in _BA_OUT] + ["K", "cam_focal", "group_focal", "cam_prior", "counts"]
+        args = (*head, a[10], n, a[8], a[9], a[11], a[12], a[13], size.get("G", 0), *[B.ptr(x) for x in prior], prior_mode,
+                *(params if len(params) > 5 else params + (1, 0.5, 2.0)), *[B.ptr(named[k]) for k in order])
+        ws = (T, N, n, prior_mode)
     ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
     launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
     cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
-    B.call(call, (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], *a[10:11], n, a[8], a[9], *a[11:14], *([G] if groups else []), *a[14:], *params,
-                  *[B.ptr(out[k]) for k in out]),
-           _TABLE_RULES + rule, offsets, ws=(T, N, n), tail=(cast(ms), cast(launches)))
-    if timings is not None:
-        timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
-    return out
-
-
-def _bundle_adjust_prior(B, mode, a, prior, params, size, extra_out, rule, like, timings):
-    """... and the call with priors: the pointers `a` of the mode's arrays laid out as the grouped pair's, NULL for what the mode lacks."""
-    T, N, n = size["T"], size["N"], size["n"]
-    a = a + [None] * (14 - len(a))
-    if len(params) == 5:
-        params += (1, 0.5, 2.0)                                                          # (ignored below mode 1)
-    out = _outputs(B, _BA_OUT + extra_out + _BA_PRIOR_OUT, size, BUNDLE_PRIOR_COUNTS, like)
-    named = dict(out, **{k: None for k in ("K", "cam_focal", "group_focal") if k not in out})
-    order = [k for k, *_ in _BA_OUT] + ["K", "cam_focal", "group_focal", "cam_prior", "counts"]
-    ms = (C.c_float * (2 * len(BUNDLE_CLASSES)))() if timings is not None else None
-    launches = (C.c_long * len(BUNDLE_CLASSES))() if timings is not None else None
-    cast = lambda x: C.cast(x, C.c_void_p) if x is not None else None
-    B.call("bundle_adjust_prior", (a[0], T, a[1], a[2], a[3], N, a[4], a[5], a[6], a[7], a[10], n, a[8], a[9], a[11], a[12], a[13], size.get("G", 0),
-                                   *[B.ptr(x) for x in prior], mode, *params, *[B.ptr(named[k]) for k in order]),
-           _TABLE_RULES + rule, like, ws=(T, N, n, mode), tail=(cast(ms), cast(launches)))
+    B.call(name, args, _TABLE_RULES + rule, offsets, ws=ws, tail=(cast(ms), cast(launches)))
     if timings is not None:
         timings.update({name: (float(ms[2 * k]), float(ms[2 * k + 1]), int(launches[k])) for k, name in enumerate(BUNDLE_CLASSES)})
     return out
 
 
 def _ba_prior_call(B, mode, base, refine_focal, groups, prior, params, focal, timings):
-    """The mode's row of _BA_MODES for the prior pair: mode 0 pose, 1 focal, 2 shared."""
+    """The row of _BA_MODES whose number in the prior pair is `mode`: 0 pose, 1 focal, 2 shared."""
     if mode not in (0, 1, 2):
         raise ValueError(f"bundle_adjust_prior: mode must be 0 (pose), 1 (focal) or 2 (shared), got {mode!r}")
-    call = ("bundle_adjust", "bundle_adjust_focal", "bundle_adjust_shared")[mode]
+    call = {row[4]: call for call, row in _BA_MODES.items()}[mode]
     arrays = tuple(base) + ((refine_focal,) if mode >= 1 else ()) + (tuple(groups) if mode == 2 else ())
     return _bundle_adjust(B, call, arrays, params, focal if mode >= 1 else None, timings, prior=tuple(prior))
 

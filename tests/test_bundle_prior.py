@@ -164,6 +164,25 @@ def test_counts_of_an_all_zero_mask_through_the_ops_layer(lib):
             assert got[k].tobytes() == want[k].tobytes(), (mode, k)
 
 
+def _digest_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_bundle_prior_parent_digest", os.path.join(ROOT, "tests", "golden", "make_bundle_prior_parent_digest.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("case", sorted(_digest_module().CASES))
+def test_the_prior_host_routine_equals_the_digest_taken_on_the_commit_before_the_modes_became_traits(lib, case):
+    """loftr_bundle_adjust_prior_host in modes 0, 1 and 2 through this build: every output tensor and the 24 counts, bit for bit what
+    the commit before the mode refactor returned (tests/golden/make_bundle_prior_parent_digest.py)."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "bundle_prior_parent_digest.json")))
+    got = _digest_module().digests(only=[case])
+    assert len(want) == 18 and sorted(got) == [case] and len(want[case]) == 8 + (2 if "K" in want[case] else 0) + ("group_focal" in want[case])
+    assert got[case] == want[case]
+
+
 def test_one_prior_moves_a_camera_along_the_free_scale(lib):
     """Two cameras with exact observations of 24 grid points: camera 0 fixed at the origin, camera 1 free at (1, 0, 0).  The start is an
     optimum of the reprojection error with a cost of exactly 0, and the only direction the observations leave free is the scale about

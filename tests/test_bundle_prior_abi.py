@@ -30,7 +30,9 @@ def test_entry_points_are_exported_and_declared(lib):
     assert len(host) == len(shared) + 5 and dev == host + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     assert host[18:22] == [ctypes.c_void_p] * 3 + [ctypes.c_int] and _lib.SIGNATURES[NAMES[1]][1] == [ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int]
     assert ops.BUNDLE_COUNTS == 16 and ops.BUNDLE_PRIOR_COUNTS == 24
-    assert ops._BA_PRIOR_MODE == {"bundle_adjust": 0, "bundle_adjust_focal": 1, "bundle_adjust_shared": 2} and set(ops._BA_PRIOR_MODE) == set(ops._BA_MODES)
+    # the one mode table: the number of each mode in the prior pair; the radial mode takes no priors
+    assert {call: row[4] for call, row in ops._BA_MODES.items()} == {"bundle_adjust": 0, "bundle_adjust_focal": 1, "bundle_adjust_shared": 2,
+                                                                      "bundle_adjust_radial": None}
     assert [k for k, *_ in ops._BA_PRIOR_IN] == ["prior_xyz", "prior_sigma", "prior_mask"] and [k for k, *_ in ops._BA_PRIOR_OUT] == ["cam_prior"]
     assert ops.bundle_adjust_prior_host is not None and ops.bundle_adjust_prior is not None
 

@@ -297,6 +297,23 @@ def test_calls_without_refine_radial_equal_the_digests_taken_on_the_commits_befo
         assert got[case] == want[case], case
 
 
+def _digest_module(which):
+    spec = importlib.util.spec_from_file_location(f"make_{which}_parent_digest", os.path.join(GOLDEN, f"make_{which}_parent_digest.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("case", sorted(_digest_module("bundle_radial").CASES))
+def test_the_radial_host_routine_equals_the_digest_taken_on_the_commit_before_the_modes_became_traits(case):
+    """loftr_bundle_adjust_radial_host through this build: every output tensor and the 16 counts, bit for bit what the commit before
+    the mode refactor returned (tests/golden/make_bundle_radial_parent_digest.py)."""
+    want = json.load(open(os.path.join(GOLDEN, "bundle_radial_parent_digest.json")))
+    got = _digest_module("bundle_radial").digests(only=[case])
+    assert len(want) == 8 and sorted(got) == [case] and len(want[case]) == 13
+    assert got[case] == want[case]
+
+
 def test_without_refine_radial_the_result_has_the_fields_it_had():
     s = RC.radial_case("one_a")
     res = shared(s)
