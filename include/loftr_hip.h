@@ -73,7 +73,7 @@ typedef enum {
  *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks),
  *     3D similarity RANSAC and moving a model (loftr_estimate_similarity, loftr_similarity_minimal,
  *     loftr_estimate_similarity_batched_workspace_bytes, loftr_estimate_similarity_batched, loftr_transform_model_host,
- *     loftr_transform_model) */
+ *     loftr_transform_model), track splitting (loftr_split_tracks_host, loftr_split_tracks_workspace_bytes, loftr_split_tracks) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -1293,6 +1293,63 @@ int loftr_merge_tracks(const long* offsets, long T, const int* obs_image, const 
                        const int* kp_row, long K, const double* Kmat, const double* T_cam_from_world, const uint8_t* posed, int n_images,
                        float inv, int gh, int gw, double thresh_px, int reach, int* row_into, float* merge_r2, int* kp_row_new, long* counts,
                        void* ws, size_t ws_bytes, float* stage_ms, void* stream);
+
+/* ---- track splitting: consistent tracks from the components that visit an image twice (csrc/split_core.h holds every
+ * per-item step) -----------------------------------------------------------------------------------------------------------------------
+ * Rule 4 of the atlas makes a track of every connected component of the kept matches and marks it track_ok = 0 when two of its keypoints
+ * lie in one image; every consumer then drops it whole.  Splitting grows the keypoints of such a track again along its matches,
+ * strongest first, never joining two components that share an image.  Integer and order-defined, one unsigned 64-bit maximum per
+ * decision.  loftr_split_tracks_host (csrc/split.hip, host memory) DEFINES the result, loftr_split_tracks (csrc/split_gpu.hip, device
+ * memory) reproduces it bit for bit.
+ * Input: edge_kp [E,2] i32 (the kept matches as GLOBAL keypoint indices; edge e is match e), edge_conf [E] f32, kp_image [K] i32 (must
+ *   not descend: keypoints are ordered by image), track_id [K] i32 (-1: none), track_ok [T] u8, n_images, min_track_len >= 1,
+ *   max_rounds >= 0.
+ *   1. Open edges.  Edge e = (u, v) is OPEN iff track_id[u] == track_id[v] = t >= 0 and track_ok[t] == 0; every other edge is IGNORED.
+ *   2. Frozen and free keypoints.  A keypoint of a track with track_ok != 0 is frozen: its label is the smallest keypoint index of its
+ *      track.  A keypoint with track_id = -1 has no label.  A keypoint of a track with track_ok == 0 is free and starts as a component
+ *      of its own: label = its index, member list = itself.  A member list ascends by keypoint index, so by image.
+ *   3. Round r = 0 .. max_rounds - 1, three phases over the open edges; no phase reads what it writes.
+ *      propose: label[u] == label[v] makes the edge INTERNAL.  Otherwise the two member lists are walked in step; an image that occurs
+ *        in both (two endpoints in one image included) makes the edge CONFLICT, for good, because components only grow.  Otherwise the
+ *        edge is a candidate with the word (bits of edge_conf[e], -0.0 as +0.0) << 32 | (0xFFFFFFFF - e), and best[label[u]] and
+ *        best[label[v]] take the maximum of the word (best starts every round as 0).
+ *      accept: a candidate whose word equals both best entries is accepted.  Words are unique, so a component is in at most one accepted
+ *        edge of a round; the greatest candidate is always accepted.
+ *      merge: for every accepted edge the two lists are spliced into one ascending list, every member takes the smaller label (the head
+ *        of a list is its label), and the edge becomes INTERNAL.  round_accepted[r] = the accepted edges.  A round that accepts nothing
+ *        ends the procedure.
+ *   4. An edge that is still a candidate after the last round stays OPEN: counts[5] > 0 means max_rounds was too small to finish (a
+ *      chain whose confidences descend merges one edge per round).
+ *   5. Numbering, as rule 4 of the atlas over frozen and grown components together: the labels with at least min_track_len members, in
+ *      ascending label, are the tracks 0 .. T' - 1; track_id_new [K] i32 (-1 elsewhere), track_len_new [K] i32 (the first T' entries;
+ *      0 behind them).  Every numbered track visits an image at most once.
+ *   6. edge_state [E] u8: 0 ignored, 1 internal, 2 conflict, 3 open.  round_accepted [max_rounds] i32.  counts [16] i64: [0] T',
+ *      [1] error bits, [2..5] ignored / internal / conflict / open edges, [6] tracks with track_ok == 0, [7] their keypoints, [8] those
+ *      of them that end in a numbered track, [9] rounds that accepted something, [10] the members of the largest grown component,
+ *      the rest 0.
+ *   7. Errors (counts[1]).  1: an edge_kp entry outside [0, K); 2: a track_id outside [-1, T) or a kp_image outside [0, n_images);
+ *      4: kp_image descends; 8: an edge_conf that is not finite or is negative; 16: a member list longer than n_images, which no valid
+ *      input produces and which bounds every walk: n_images + 1 steps on either list.
+ * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, min_track_len < 1; the host routine also for the error bits, and it then
+ *   writes the bits to counts[1] and nothing else (the kernels raise counts[1] instead, read nothing through the bad value and write
+ *   no other output); LOFTR_ERR_UNSUPPORTED for E > 2^31 - 2, K or T >= 2^31, max_rounds >= 2^20; LOFTR_ERR_WORKSPACE.
+ * Out of scope: geometric verification (the triangulation's inlier test follows), a second home for the keypoints that end -1
+ *   (completion may claim them), any criterion but the match confidence, a sequential greedy (Kruskal) order, the atlas's rule 4. */
+int loftr_split_tracks_host(const int* edge_kp, const float* edge_conf, long E, const int* kp_image, const int* track_id, long K,
+                            const uint8_t* track_ok, long T, int n_images, int min_track_len, int max_rounds, int* track_id_new,
+                            int* track_len_new, uint8_t* edge_state, int* round_accepted, long* counts);
+/* The kernels: memsets, a check and an init launch, per round a memset of best and three launches (propose and accept a thread per edge,
+ * merge a thread per accepted edge), then lengths, flags, the u32 scan, numbering and one launch that writes the outputs.  A round's
+ * launches return at once when counts[1] is set or the round before accepted nothing.  No host synchronisation unless stage_ms is
+ * given: NULL, or LOFTR_SPLIT_STAGES(max_rounds) host floats (check + init; per round: clear, propose, accept, merge; number; write; the
+ * call then waits for the stream).  Workspace: loftr_split_tracks_workspace_bytes(E, K, T, max_rounds): 24 bytes per keypoint, 5 per
+ * edge, 4 per track and per round; 0 for sizes out of range. */
+#define LOFTR_SPLIT_STAGES(max_rounds) (3 + 4 * (max_rounds))
+size_t loftr_split_tracks_workspace_bytes(long E, long K, long T, int max_rounds);
+int loftr_split_tracks(const int* edge_kp, const float* edge_conf, long E, const int* kp_image, const int* track_id, long K,
+                       const uint8_t* track_ok, long T, int n_images, int min_track_len, int max_rounds, int* track_id_new,
+                       int* track_len_new, uint8_t* edge_state, int* round_accepted, long* counts, void* ws, size_t ws_bytes,
+                       float* stage_ms, void* stream);
 
 /* ---- 3D similarity between two point sets; moving a model into another frame ------------------------------------------
  * dst ~ s R src + t with R a proper rotation and s > 0, or s == 1 when with_scale == 0 (rigid, SE(3)): the closed form of Kabsch /

@@ -172,7 +172,7 @@ class SfmResult:
         return R, t, ninl
 
     def reconstruct(self, K, init_row=None, init_candidates=8, thresh_px=4.0, pose_conf=0.99999, consistent_only=True, complete=False, merge=False,
-                    **kwargs):
+                    split=False, **kwargs):
         """Poses of the images and points of the tracks from intrinsics alone (registration.reconstruct_tracks) ->
         Reconstruction on this result's device, its ``points`` carrying the CSR arrays as ``triangulate`` attaches them.
         The initial pair is row ``init_row`` with its five-point pose (``pairwise_poses`` at ``thresh_px``).  With ``init_row=None``:
@@ -186,9 +186,19 @@ class SfmResult:
         (the same fixed images and ``ba``) -> triangulate on the relabelled atlas; the Reconstruction then carries it as ``.sfm`` and the
         counts as ``stats['completion']``.  ``merge=True``: after the loop (and after the completion and one triangulation
         of it, when ``complete=True``), one ``merge`` of the tracks whose points meet and agree, then the same triangulate -> adjust ->
-        triangulate; ``.sfm`` is the relabelled atlas and ``stats['merge']`` the counts.  With the defaults nothing of this
-        runs."""
+        triangulate; ``.sfm`` is the relabelled atlas and ``stats['merge']`` the counts.  ``split=True``: ``split`` runs first
+        and everything after it, the five-point poses included, reads the split atlas, whose tracks are all consistent; ``.sfm`` is that
+        atlas (or what ``complete`` / ``merge`` made of it) and ``stats['split']`` the counts.  With the defaults nothing
+        of this runs."""
         from .registration import reconstruct_tracks, triangulate_posed
+        if split:
+            sfm2, done = self.split()
+            rec = sfm2.reconstruct(K, init_row=init_row, init_candidates=init_candidates, thresh_px=thresh_px, pose_conf=pose_conf,
+                                   consistent_only=consistent_only, complete=complete, merge=merge, **kwargs)
+            if rec.sfm is None:
+                rec.sfm = sfm2
+            rec.stats.update(split=done.stats)
+            return rec
         dev = self.keypoints.device
         n = self.kp_offsets.numel() - 1
         K = torch.as_tensor(K).detach().to(dev, torch.float64)
@@ -282,6 +292,28 @@ class SfmResult:
         sfm2 = SfmResult(dict(self.stats, **stats), **fields)
         sfm2.image_hw, sfm2.cell_px = self.image_hw, self.cell_px
         return sfm2
+
+    def edge_keypoints(self):
+        """The kept matches as GLOBAL keypoint indices [Mk,2] i32 (integer indexing: the row of a match, its two images, their offsets)."""
+        n_rows = self.row_offsets.numel() - 1
+        row = torch.repeat_interleave(torch.arange(n_rows, device=self.row_offsets.device), self.row_offsets[1:] - self.row_offsets[:-1])
+        base = self.kp_offsets[self.row_images.to(torch.int64)[row]]                         # [Mk,2]
+        return (base + self.matches.to(torch.int64)).to(torch.int32).reshape(-1, 2)
+
+    def split(self, min_track_len=2, max_rounds=32, timings=None):
+        """Grow the keypoints of the tracks with ``track_ok`` false again into consistent tracks (splitting.split_tracks)
+        -> ``(sfm2, split)``: a new SfmResult that shares every tensor with this one except ``track_id``, ``track_len`` and
+        ``track_ok`` (all true), and the ``Split``.  A consistent track keeps its members; the tracks are numbered anew.  No pixel
+        is read, so an undistorted view splits like the original.  This result is left untouched."""
+        from .splitting import split_tracks
+        n = self.kp_offsets.numel() - 1
+        done = split_tracks(self.edge_keypoints(), self.match_conf, self.keypoint_image().to(torch.int32), self.track_id,
+                            self.track_ok, n, min_track_len=min_track_len, max_rounds=max_rounds, timings=timings)
+        fields = {k: getattr(self, k) for k in self.FIELDS}
+        fields.update(track_id=done.track_id_new, track_len=done.track_len_new, track_ok=torch.ones_like(done.track_len_new, dtype=torch.bool))
+        sfm2 = SfmResult(dict(self.stats, n_tracks=done.stats["n_tracks"], n_split_rounds=done.stats["n_rounds"]), **fields)
+        sfm2.image_hw, sfm2.cell_px, sfm2.is_undistorted = self.image_hw, self.cell_px, self.is_undistorted
+        return sfm2, done
 
     def merge(self, pts, K, T_cam_from_world, posed=None, thresh_px=4.0, reach=None, timings=None):
         """Merge the tracks whose points ``pts`` (a Points3D of ``triangulate`` on this result) meet and agree (merging.merge_tracks;

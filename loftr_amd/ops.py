@@ -1944,6 +1944,68 @@ def merge_tracks(offsets, obs_image, obs_xy, obs_mask, xyz, status, kp_offsets, 
                          gh, gw, inv, thresh_px, reach, timings)
 
 
+# ---- track splitting (csrc/split.hip, csrc/split_gpu.hip) ------------------------------------------------------------------
+SPLIT_COUNTS = 16
+SPLIT_NAMES = ("n_tracks", "error_bits", "n_ignored", "n_internal", "n_conflict", "n_open", "n_inconsistent_tracks", "n_inconsistent_keypoints",
+               "n_rescued", "n_rounds", "largest_component")                                # counts[0..10]
+SPLIT_STATES = ("ignored", "internal", "conflict", "open")                               # edge_state codes 0..3
+SPLIT_STAGES = ("check", "clear", "propose", "accept", "merge", "number", "write")       # the launch classes; a round's four are summed
+SPLIT_ERRORS = ((1, "edge_kp outside [0, K)"), (2, "track_id outside [-1, T) or kp_image outside [0, n_images)"),
+                (4, "kp_image must not descend (keypoints are ordered by image)"), (8, "edge_conf must be finite and >= 0"),
+                (16, "a member list longer than n_images"))                              # bits of counts[1]
+_SPL_ARGS = (("edge_kp", "int32", 2), ("edge_conf", "float32", 1), ("kp_image", "int32", 1), ("track_id", "int32", 1), ("track_ok", "uint8", 1))
+_SPL_OUT = (("track_id_new", "K", (), "int32"), ("track_len_new", "K", (), "int32"), ("edge_state", "E", (), "uint8"),
+            ("round_accepted", "R", (), "int32"))
+
+
+def _split_tracks(B, what, hint, arrays, n_images, min_track_len, max_rounds, timings):
+    _check_args(B, what, hint, _SPL_ARGS, arrays)
+    edge_kp, edge_conf, kp_image, track_id, track_ok = arrays
+    E, K, T = edge_kp.shape[0], kp_image.shape[0], track_ok.shape[0]
+    if tuple(edge_kp.shape) != (E, 2) or edge_conf.shape[0] != E or track_id.shape[0] != K:
+        raise _lib.LoftrHipError(f"{what}: expected edge_kp [E,2], edge_conf [E], kp_image [K], track_id [K] and track_ok [T], got "
+                                 f"{[tuple(a.shape) for a in arrays]}")
+    for name, v, lo in (("n_images", n_images, 0), ("min_track_len", min_track_len, 1), ("max_rounds", max_rounds, 0)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < lo:
+            raise ValueError(f"{what}: {name} must be an integer >= {lo}, got {v}")
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _SPL_OUT, {"K": K, "E": E, "R": max_rounds}, SPLIT_COUNTS, edge_kp)
+    args = (a[0], a[1], E, a[2], a[3], K, a[4], T, n_images, min_track_len, max_rounds, *[B.ptr(out[k]) for k in out])
+    if B is _Host:
+        status = _lib.load().loftr_split_tracks_host(*args)
+        if not (status == -1 and int(out["counts"][1]) != 0):                            # a bad table is reported through counts[1], as on the GPU
+            check(status, "loftr_split_tracks_host")
+        return out
+    stages = ("check",) + ("clear", "propose", "accept", "merge") * max_rounds + ("number", "write")
+    ms = _StageMs(None if timings is None else [], stages)
+    B.call("split_tracks", args, "", edge_kp, ws=(E, K, T, max_rounds), tail=(ms.arg,))
+    if timings is not None:
+        ms.report()
+        timings.extend((name, sum(v for n, v in ms.timings if n == name)) for name in SPLIT_STAGES)
+    return out
+
+
+def split_tracks_host(edge_kp, edge_conf, kp_image, track_id, track_ok, n_images, min_track_len=2, max_rounds=32):
+    """loftr_split_tracks_host: the host routine that DEFINES track splitting (include/loftr_hip.h) on numpy arrays: edge_kp
+    [E,2] i32 (global keypoint indices), edge_conf [E] f32, kp_image [K] i32 (not descending), track_id [K] i32, track_ok [T] u8.
+    -> dict of numpy arrays: track_id_new [K] i32, track_len_new [K] i32 (the first counts[0] entries), edge_state [E] u8 (SPLIT_STATES),
+    round_accepted [max_rounds] i32, counts [16] i64 (SPLIT_NAMES).  A bad table leaves its bits in counts[1] and every other output
+    zero."""
+    return _split_tracks(_Host, "split_tracks_host", "split_tracks", (edge_kp, edge_conf, kp_image, track_id, track_ok), n_images,
+                         min_track_len, max_rounds, None)
+
+
+@_on_device
+def split_tracks(edge_kp, edge_conf, kp_image, track_id, track_ok, n_images, min_track_len=2, max_rounds=32, timings=None):
+    """loftr_split_tracks: the splitting kernels (csrc/split_gpu.hip) on GPU tensors of the dtypes and shapes of split_tracks_host; the
+    same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in counts[1], which the caller
+    reads once (every other output is then zero).  timings: a list that receives (launch class, ms) pairs, the rounds summed (the call
+    then waits for the stream)."""
+    return _split_tracks(_Gpu, "split_tracks", "the splitting kernels have no CPU fallback; the host routine is split_tracks_host",
+                         (edge_kp, edge_conf, kp_image, track_id, track_ok), n_images, min_track_len, max_rounds, timings)
+
+
 # ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip; DESIGN §17) ------------------------
 MODEL_COUNTS = 16
 MODEL_REASONS = ("n_kept", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside", "n_no_keypoint", "n_no_point",
