@@ -73,7 +73,8 @@ typedef enum {
  *     loftr_complete_tracks), track merging (loftr_merge_tracks_host, loftr_merge_tracks_workspace_bytes, loftr_merge_tracks),
  *     3D similarity RANSAC and moving a model (loftr_estimate_similarity, loftr_similarity_minimal,
  *     loftr_estimate_similarity_batched_workspace_bytes, loftr_estimate_similarity_batched, loftr_transform_model_host,
- *     loftr_transform_model), track splitting (loftr_split_tracks_host, loftr_split_tracks_workspace_bytes, loftr_split_tracks) */
+ *     loftr_transform_model), track splitting (loftr_split_tracks_host, loftr_split_tracks_workspace_bytes, loftr_split_tracks), track
+ *     refinement (loftr_refine_centres_host, loftr_refine_centres, loftr_fine_preprocess_gather_at) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -1350,6 +1351,53 @@ int loftr_split_tracks(const int* edge_kp, const float* edge_conf, long E, const
                        const uint8_t* track_ok, long T, int n_images, int min_track_len, int max_rounds, int* track_id_new,
                        int* track_len_new, uint8_t* edge_state, int* round_accepted, long* counts, void* ws, size_t ws_bytes,
                        float* stage_ms, void* stream);
+
+/* ---- track refinement: the fine stage at points the caller names (csrc/refine_core.h holds the per-row step) ------------
+ * The atlas snaps matched points to cells, so the observations of a track are up to one cell apart.  Refinement re-localises every
+ * observation of a track against one reference view with the matcher's fine level.  What that needs of the library is narrow: every
+ * other entry point places the fine windows at coarse cells chosen by coarse matching; these two place them at given points.
+ * Side 0 is the reference (its point is snapped to the fine grid and fixed), side 1 the query (refined, as loftr_fine_match refines it).
+ *
+ * loftr_refine_centres_host (csrc/refine.hip, host memory) DEFINES the result, loftr_refine_centres (csrc/refine_gpu.hip, device
+ * memory, a thread per row, one launch, no synchronisation) reproduces it bit for bit.
+ *   pts0, pts1 [M,2] f32 (x, y) in the coordinates the forward returns; b_ids [M] i64 the pair of every row; scale0 / scale1 NULL or
+ *   [n_pairs,2] f32 (w, h) as in the batch dict; (hf, wf) the fine-map extents and (hc, wc) the coarse-map extents per side; stride =
+ *   fine pixels per coarse cell; s = image pixels per fine pixel.  All arithmetic in fp32 without contraction.
+ *   1. Per side and axis the centre is c = clamp((int)floorf(p / scale[b] / s + 0.5f), 0, extent - 1); without a scale the division by
+ *      it is left out.  The clamp is taken on the float, so no value outside int is converted.
+ *   2. The coarse cell per axis is min((c + stride / 2) / stride, extent_c - 1); i_ids / j_ids [M] i64 = cell_y * wc + cell_x.  A centre
+ *      stride * cell gives back that cell.
+ *   3. The snapped point per axis is (float)c * s, then * scale[b] where a scale is given: at c = stride * cell the bits of the
+ *      forward's mkpts0_c / mkpts1_c.
+ *   4. ok [M] u8 = 0 where a coordinate is not finite or b is outside [0, n_pairs) (no scale is read for such a row); the row then has
+ *      centre 0, cell 0 and the snapped point (0, 0), so nothing downstream reads out of range.
+ *   Outputs: c0, c1 [M,2] i32 (x, y) in fine pixels, i_ids, j_ids [M] i64, pts0_s, pts1_s [M,2] f32, ok [M] u8.
+ * Status: LOFTR_ERR_BAD_ARG for M < 0, n_pairs < 0, an extent or stride that is not positive, s not finite or not positive, and null
+ *   arrays with M > 0 (scale0 / scale1 may be NULL); M == 0 is a no-op success; LOFTR_ERR_UNSUPPORTED for M >= 2^39 on the GPU. */
+int loftr_refine_centres_host(const float* pts0, const float* pts1, const int64_t* b_ids, long M, const float* scale0,
+                              const float* scale1, int n_pairs, int hf0, int wf0, int hf1, int wf1, int h0c, int w0c, int h1c, int w1c,
+                              int stride, float s, int* c0, int* c1, int64_t* i_ids, int64_t* j_ids, float* pts0_s, float* pts1_s,
+                              uint8_t* ok);
+int loftr_refine_centres(const float* pts0, const float* pts1, const int64_t* b_ids, long M, const float* scale0, const float* scale1,
+                         int n_pairs, int hf0, int wf0, int hf1, int wf1, int h0c, int w0c, int h1c, int w1c, int stride, float s,
+                         int* c0, int* c1, int64_t* i_ids, int64_t* j_ids, float* pts0_s, float* pts1_s, uint8_t* ok, void* stream);
+
+/* loftr_fine_preprocess_gather with the windows at given centres: the window of match m on side 0 covers
+ * [c0y - W/2, c0y + W/2] x [c0x - W/2, c0x + W/2] of bank_f0[slot0[b_ids[m]]], zero outside the map, side 1 likewise; c0, c1 [M,2] i32
+ * (x, y) in fine pixels (device memory; any value is safe, a centre far outside the map gives a window of zeros).  i_ids / j_ids are
+ * still what the coarse gather reads (loftr_refine_centres gives the cells that hold the centres), w0c / w1c and stride are accepted
+ * and checked as in the twin and not read by the window gather.  Per-element arithmetic and store as in loftr_fine_preprocess_gather:
+ * at c = stride * cell the outputs are that entry point's, bit for bit.  Everything after the window gather, the workspace
+ * (loftr_fine_preprocess_workspace_bytes) and the status codes as for loftr_fine_preprocess_gather; c0 / c1 NULL with M > 0 is
+ * LOFTR_ERR_BAD_ARG. */
+int loftr_fine_preprocess_gather_at(const loftr_fmap* bank_f0, int n_slots0, const int32_t* slot0,
+                                    const loftr_fmap* bank_f1, int n_slots1, const int32_t* slot1,
+                                    const float* feat_c0, const float* feat_c1, int L, int S, int Cc,
+                                    const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, int M,
+                                    int w0c, int w1c, int stride, int W, int Cf,
+                                    const float* down_w, const float* down_b, const float* merge_w,
+                                    const float* merge_b, float* out0, float* out1, void* ws,
+                                    size_t ws_bytes, const int* c0, const int* c1, void* stream);
 
 /* ---- 3D similarity between two point sets; moving a model into another frame ------------------------------------------
  * dst ~ s R src + t with R a proper rotation and s > 0, or s == 1 when with_scale == 0 (rigid, SE(3)): the closed form of Kabsch /

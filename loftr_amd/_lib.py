@@ -200,6 +200,10 @@ SIGNATURES = {
     "loftr_split_tracks_host": (_i, [_p, _p, _l, _p, _p, _l, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p]),
     "loftr_split_tracks_workspace_bytes": (_sz, [_l, _l, _l, _i]),
     "loftr_split_tracks": (_i, [_p, _p, _l, _p, _p, _l, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "loftr_refine_centres_host": (_i, [_p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p]),
+    "loftr_refine_centres": (_i, [_p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "loftr_fine_preprocess_gather_at": (_i, [C.POINTER(FMap), _i, _p, C.POINTER(FMap), _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i,
+                                             _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
     "loftr_estimate_similarity": (_i, [_p, _p, _l, _i, C.c_double, _f, C.c_uint, _p, _p, _p, _p, C.POINTER(_l)]),
     "loftr_similarity_minimal": (_i, [_p, _p, _i, _p, _p, _p, C.POINTER(_i)]),
     "loftr_estimate_similarity_batched_workspace_bytes": (_sz, [_l, _i]),

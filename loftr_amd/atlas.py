@@ -61,6 +61,7 @@ class SfmResult:
             setattr(self, k, tensors[k])
         self.image_hw = self.cell_px = None                            # set by KeypointAtlas.finalize
         self.is_undistorted = False                                     # True for the view that undistorted() returns
+        self.is_refined = False                                         # True for the view that refine_tracks() returns
 
     def undistorted(self, K, radial):
         """The view of this result whose ``keypoints`` are the pinhole pixels of the stored ones under one radial coefficient per image
@@ -79,8 +80,24 @@ class SfmResult:
         fields = {k: getattr(self, k) for k in self.FIELDS}
         fields.update(keypoints=xy)
         view = SfmResult(dict(self.stats), **fields)
-        view.image_hw, view.cell_px, view.is_undistorted = self.image_hw, self.cell_px, True
+        view.image_hw, view.cell_px, view.is_undistorted, view.is_refined = self.image_hw, self.cell_px, True, self.is_refined
         return view
+
+    def refine_tracks(self, model, load, image_hw=None, obs_mask=None, max_std=None, max_shift_px=None, min_jobs_per_pair=1, **pair_list_kw):
+        """Re-localise every observation of a consistent track against the track's reference view with the matcher's fine level
+        (refinement.py) -> ``(view, refinement)``: the view shares every tensor with this result except ``keypoints`` and has
+        ``is_refined`` True, the ``Refinement`` says what happened to every keypoint.  ``model``: a LoFTR in .eval() on a GPU; ``load``
+        and the keyword arguments ``budget_bytes``, ``batch_size``, ``extract_batch`` as for ``pairs.match_pair_list``; ``image_hw``:
+        the size of the loaded images (default: this result's); ``obs_mask`` [N] in the order of ``tracks(consistent_only=True)``,
+        e.g. ``pts.obs_inlier``; a refined query is accepted when it is finite, inside the image, ``expec_f[:, 2] <= max_std`` and
+        within ``max_shift_px`` of its old position (None: no limit).  ``triangulate``, ``register``, ``adjust`` and ``pairwise_poses``
+        read the view as they read any result; ``complete``, ``merge`` and ``split`` raise ValueError on it (their cell lookups are
+        in stored-pixel space), so refinement comes after the topology stages.  ``undistorted()`` of the view keeps ``is_refined``; an
+        undistorted view is refused here, because the network saw the stored pixels.  A ``LocalizationModel`` is built from the
+        ORIGINAL result with the points of the view."""
+        from .refinement import refine_tracks
+        return refine_tracks(self, model, load, image_hw=image_hw, obs_mask=obs_mask, max_std=max_std, max_shift_px=max_shift_px,
+                             min_jobs_per_pair=min_jobs_per_pair, **pair_list_kw)
 
     def keypoint_image(self):
         """Image of every keypoint [K] i64."""
@@ -306,6 +323,8 @@ class SfmResult:
         ``track_ok`` (all true), and the ``Split``.  A consistent track keeps its members; the tracks are numbered anew.  No pixel
         is read, so an undistorted view splits like the original.  This result is left untouched."""
         from .splitting import split_tracks
+        if self.is_refined:
+            raise ValueError("SfmResult.split: this is a refined view; the atlas's cells are in stored-pixel space (split the original result, then refine)")
         n = self.kp_offsets.numel() - 1
         done = split_tracks(self.edge_keypoints(), self.match_conf, self.keypoint_image().to(torch.int32), self.track_id,
                             self.track_ok, n, min_track_len=min_track_len, max_rounds=max_rounds, timings=timings)
@@ -322,6 +341,8 @@ class SfmResult:
         unchanged, two merged tracks share no image), and the ``Merge`` whose rows are the tracks of ``pts``.  This result is left
         untouched.  The points are not re-estimated: triangulate ``sfm2`` next.  Calling again after that merges further."""
         from .merging import merge_tracks
+        if self.is_refined:
+            raise ValueError("SfmResult.merge: this is a refined view; the cell lookup is in stored-pixel space (merge the original result, then refine)")
         if self.is_undistorted:
             raise ValueError("SfmResult.merge: this is an undistorted view; the cell lookup is in stored-pixel space (merge the original result)")
         if pts.offsets is None:
@@ -350,6 +371,8 @@ class SfmResult:
         Meant for AFTER the reconstruction loop: only a keypoint that is loose or held by a track WITHOUT a point can be claimed, and
         a track that has no point YET, because its images have no pose yet, would yield its keypoints as well."""
         from .completion import complete_tracks
+        if self.is_refined:
+            raise ValueError("SfmResult.complete: this is a refined view; the cell lookup is in stored-pixel space (complete the original result, then refine)")
         if self.is_undistorted:
             raise ValueError("SfmResult.complete: this is an undistorted view; the cell lookup is in stored-pixel space (complete the original result)")
         if pts.offsets is None:

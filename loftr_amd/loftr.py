@@ -391,6 +391,15 @@ class FinePreprocess(nn.Module):
         return ops.fine_preprocess_gather(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
                                           *geo, **kw)
 
+    def forward_gather_at(self, bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data, c0, c1):
+        """forward_gather with the window of match m centred at c0[m] / c1[m] ([M,2] i32 (x, y) in fine pixels) instead of at its
+        coarse cell (LoFTR.refine_points); data["i_ids"] / data["j_ids"] are the cells the coarse features are read from."""
+        geo, kw, empty = self._begin(data, bank_f0.device)
+        if empty is not None:
+            return empty
+        return ops.fine_preprocess_gather_at(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, data["b_ids"], data["i_ids"], data["j_ids"],
+                                             c0, c1, *geo, **kw)
+
 
 class FineMatching(nn.Module):
     """fine_matching.py:9-74."""
@@ -587,20 +596,7 @@ class LoFTR(nn.Module):
     def _match_encoded(self, feat_c0, feat_c1, data, fine_preprocess):
         """Steps 3-5 of forward from the position-encoded coarse features [N, L, C] (shared by match_from_features and match_pairs):
         coarse transformer, coarse matching, fine stage.  fine_preprocess(feat_c0, feat_c1) -> the two window tensors."""
-        mask_c0 = mask_c1 = None
-        if "mask0" in data:
-            mask_c0, mask_c1 = data["mask0"].flatten(-2), data["mask1"].flatten(-2)
-        # The coarse transformer has two forms with the same results to float32 noise (csrc/encoder_fused.hip): ONE persistent launch whose
-        # 256 resident workgroups pull the layers' work items from a dependency-ordered queue, or per-call launches.  Alone on the GPU the
-        # persistent form takes 3.13 ms against 3.29 (8 pairs, back to back); inside the bench step the variants of the schedule
-        # (persistent / launches, fine branch on a side stream, half batches on two streams) all end within 2 % of each other -- the
-        # MFMA-dense kernels run at the part's power limit (profiles/r06_coarse_mode_ab.txt, r06_power.txt).  ops.COARSE_MODE "auto" (the
-        # default) takes the persistent form from 8 pairs on (profiles/r06_mode_sweep.txt).
-        # Padding tokens (MegaDepth batches): nothing below reads their features -- coarse matching fills their scores, the fine stage gathers
-        # at matched tokens only -- so the 128-token tiles without a valid token are not computed (self.skip_padded_tiles = False: the
-        # reference's per-token mlp result for them; every other token is bit-identical either way).
-        feat_c0, feat_c1 = self.loftr_coarse(feat_c0, feat_c1, mask_c0, mask_c1, inplace=True, mode=self.coarse_mode,
-                                             skip_padded=self.skip_padded_tiles and mask_c0 is not None)   # fresh pos-encoded copies
+        feat_c0, feat_c1, mask_c0, mask_c1 = self._coarse_transformer(feat_c0, feat_c1, data)
         # Join the side stream (FPN fine branch) HERE, not after coarse matching (self.fine_join_late restores that): the encoder
         # launches leave partly filled rounds that the convolution workgroups use, the score-volume kernels do not -- sharing the
         # GPU only doubled their duration (660 vs 340 us for pass B, profiles/r03_overlap_ab.txt) without shortening the step.
@@ -624,6 +620,25 @@ class LoFTR(nn.Module):
             data["_head_inputs"].update({"feat_f0_unfold": feat_f0_unfold, "feat_f1_unfold": feat_f1_unfold})
         with torch.enable_grad() if grads else contextlib.nullcontext():
             self.fine_matching(feat_f0_unfold, feat_f1_unfold, data)
+
+    def _coarse_transformer(self, feat_c0, feat_c1, data):
+        """The coarse transformer on the position-encoded coarse features [N, L, C], in place, with the padding masks of `data` (shared by
+        _match_encoded and LoFTR.refine_points) -> (feat_c0, feat_c1, mask_c0, mask_c1), the masks flattened or None."""
+        mask_c0 = mask_c1 = None
+        if "mask0" in data:
+            mask_c0, mask_c1 = data["mask0"].flatten(-2), data["mask1"].flatten(-2)
+        # The coarse transformer has two forms with the same results to float32 noise (csrc/encoder_fused.hip): ONE persistent launch whose
+        # 256 resident workgroups pull the layers' work items from a dependency-ordered queue, or per-call launches.  Alone on the GPU the
+        # persistent form takes 3.13 ms against 3.29 (8 pairs, back to back); inside the bench step the variants of the schedule
+        # (persistent / launches, fine branch on a side stream, half batches on two streams) all end within 2 % of each other -- the
+        # MFMA-dense kernels run at the part's power limit (profiles/r06_coarse_mode_ab.txt, r06_power.txt).  ops.COARSE_MODE "auto" (the
+        # default) takes the persistent form from 8 pairs on (profiles/r06_mode_sweep.txt).
+        # Padding tokens (MegaDepth batches): nothing below reads their features -- coarse matching fills their scores, the fine stage gathers
+        # at matched tokens only -- so the 128-token tiles without a valid token are not computed (self.skip_padded_tiles = False: the
+        # reference's per-token mlp result for them; every other token is bit-identical either way).
+        feat_c0, feat_c1 = self.loftr_coarse(feat_c0, feat_c1, mask_c0, mask_c1, inplace=True, mode=self.coarse_mode,
+                                             skip_padded=self.skip_padded_tiles and mask_c0 is not None)   # fresh pos-encoded copies
+        return feat_c0, feat_c1, mask_c0, mask_c1
 
     def forward(self, data):
         """Updates `data` in place exactly like the reference (loftr.py:29-75).
@@ -659,6 +674,20 @@ class LoFTR(nn.Module):
         only; runs without a graph."""
         from .pairs import match_pairs
         return match_pairs(self, bank0, ids0, bank1, ids1)
+
+    def refine_points(self, bank0, ids0, bank1, ids1, b_ids, pts0, pts1):
+        """Run the fine stage at points the caller names (loftr_amd/pairs.py): n image pairs from feature banks as in
+        match_pairs, M point pairs ``pts0`` / ``pts1`` [M,2] in the coordinates forward returns, ``b_ids`` [M] the pair of each, ascending.
+        Side 0 is the reference: its point is snapped to the fine grid (at most s/2 per axis, s = image pixels per fine pixel) and
+        fixed.  Side 1 is the query: its window is centred at the fine pixel nearest to ``pts1`` and FineMatching refines it from there.
+        The coarse transformer runs exactly as in match_pairs (masks from the banks, coarse_mode, skip_padded_tiles, the status check);
+        coarse matching does not run.  -> dict: ``pts0`` [M,2] the snapped reference points, ``pts1_start`` [M,2] the snapped query
+        points, ``pts1`` [M,2] the refined query points, ``expec_f`` [M,3], ``ok`` [M] u8 (0: a coordinate was not finite; ``pts1`` and
+        ``expec_f`` are NaN there).  Called with the rows of a match_pairs result (b_ids, mkpts0_c, mkpts1_c) it returns that result's
+        mkpts0_c, mkpts1_c, mkpts1_f and expec_f bit for bit.  Inference only; runs without a graph; ``b_ids`` given on the host is
+        checked there, a device tensor costs the readback of one flag before anything is launched."""
+        from .pairs import refine_points
+        return refine_points(self, bank0, ids0, bank1, ids1, b_ids, pts0, pts1)
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         for k in list(state_dict.keys()):

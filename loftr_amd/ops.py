@@ -666,6 +666,59 @@ def fine_preprocess_gather(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, b_i
                                  (down_w, down_b, merge_w, merge_b))
 
 
+# ---- track refinement: the fine stage at points the caller names (csrc/refine_core.h, refine.hip, refine_gpu.hip) ----------
+@_on_device
+def refine_centres(pts0, pts1, b_ids, n_pairs, hw0_f, hw1_f, hw0_c, hw1_c, stride, s, scale0=None, scale1=None):
+    """loftr_refine_centres: fine-window centres, coarse cells and snapped points of M point pairs (include/loftr_hip.h).  pts0, pts1
+    [M,2] f32, b_ids [M] i64, scale0 / scale1 None or [n_pairs,2] f32, all on one device.  GPU tensors run the kernel (one launch, no
+    synchronisation), CPU tensors the host routine that defines the result; both give the same bits.
+    -> dict: c0, c1 [M,2] i32 (x, y), i_ids, j_ids [M] i64, pts0_s, pts1_s [M,2] f32, ok [M] u8."""
+    dev = pts0.device if isinstance(pts0, torch.Tensor) else None
+    for t, name, dtype, tail in ((pts0, "pts0", torch.float32, (2,)), (pts1, "pts1", torch.float32, (2,)), (b_ids, "b_ids", torch.int64, ()),
+                                 (scale0, "scale0", torch.float32, (2,)), (scale1, "scale1", torch.float32, (2,))):
+        if t is None and name.startswith("scale"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape[1:]) != tail:
+            raise _lib.LoftrHipError(f"refine_centres: {name} must be a contiguous {dtype} tensor [*{', 2' if tail else ''}] on {dev}")
+    M, n_pairs = pts0.shape[0], int(n_pairs)
+    if pts1.shape[0] != M or b_ids.shape[0] != M or any(t is not None and t.shape[0] != n_pairs for t in (scale0, scale1)):
+        raise _lib.LoftrHipError(f"refine_centres: expected pts0, pts1 [M,2], b_ids [M] and scales [{n_pairs},2], got "
+                                 f"{[None if t is None else tuple(t.shape) for t in (pts0, pts1, b_ids, scale0, scale1)]}")
+    out = {"c0": torch.zeros(M, 2, dtype=torch.int32, device=dev), "c1": torch.zeros(M, 2, dtype=torch.int32, device=dev),
+           "i_ids": torch.zeros(M, dtype=torch.int64, device=dev), "j_ids": torch.zeros(M, dtype=torch.int64, device=dev),
+           "pts0_s": torch.zeros(M, 2, dtype=torch.float32, device=dev), "pts1_s": torch.zeros(M, 2, dtype=torch.float32, device=dev),
+           "ok": torch.zeros(M, dtype=torch.uint8, device=dev)}
+    args = (_ptr(pts0), _ptr(pts1), _ptr(b_ids), M, _ptr(scale0), _ptr(scale1), n_pairs, int(hw0_f[0]), int(hw0_f[1]), int(hw1_f[0]),
+            int(hw1_f[1]), int(hw0_c[0]), int(hw0_c[1]), int(hw1_c[0]), int(hw1_c[1]), int(stride), float(s), *[_ptr(t) for t in out.values()])
+    if dev.type == "cuda":
+        check(_lib.load().loftr_refine_centres(*args, _stream()), "loftr_refine_centres")
+    else:
+        check(_lib.load().loftr_refine_centres_host(*args), "loftr_refine_centres_host")
+    return out
+
+
+@_on_device
+def fine_preprocess_gather_at(bank_f0, slot0, bank_f1, slot1, feat_c0, feat_c1, b_ids, i_ids, j_ids, c0, c1, hw0_c, hw1_c, W, stride,
+                              down_w=None, down_b=None, merge_w=None, merge_b=None):
+    """fine_preprocess_gather with the window of match m centred at c0[m] / c1[m] ([M,2] i32 (x, y) in fine pixels) instead of at
+    stride * cell; i_ids / j_ids are still what the coarse gather reads.  Returns (feat_f0_unfold, feat_f1_unfold) [M, W*W, Cf]."""
+    _bank_map(bank_f0, "bank_f0"); _bank_map(bank_f1, "bank_f1")
+    _need(feat_c0, "feat_c0"); _need(feat_c1, "feat_c1")
+    N, M = feat_c0.shape[0], b_ids.shape[0]
+    s0 = _slot_ids(slot0, bank_f0.shape[0], "slot0", bank_f0.device)
+    s1 = _slot_ids(slot1, bank_f1.shape[0], "slot1", bank_f1.device)
+    if s0.shape[0] != N or s1.shape[0] != N:
+        raise _lib.LoftrHipError(f"slot0 / slot1: expected {N} slot ids (one per pair), got {s0.shape[0]} / {s1.shape[0]}")
+    for t, name in ((c0, "c0"), (c1, "c1")):
+        if tuple(_need(t, name, torch.int32).shape) != (M, 2):
+            raise _lib.LoftrHipError(f"{name}: expected [{M}, 2], got {tuple(t.shape)}")
+    f0, f1 = _fmap(bank_f0), _fmap(bank_f1)
+    return _fine_preprocess_call("loftr_fine_preprocess_gather_at",
+                                 (C.byref(f0), bank_f0.shape[0], _ptr(s0), C.byref(f1), bank_f1.shape[0], _ptr(s1)), bank_f0.device,
+                                 bank_f0.shape[1], feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride,
+                                 (down_w, down_b, merge_w, merge_b), extra=(_ptr(c0), _ptr(c1)))
+
+
 @_on_device
 def fine_preprocess_bwd(feat_f0, feat_f1, feat_c0, feat_c1, b_ids, i_ids, j_ids, hw0_c, hw1_c, W, stride, down_w, down_b, merge_w,
                         grad_out0, grad_out1):

@@ -198,68 +198,138 @@ def _host_ids(ids, name):
     return [int(v) for v in ids]
 
 
-def _side_flag(bank, ids, flags, what, name):
+def _side_flag(bank, ids, flags, what, name, who):
     have = [flags[s] for s in ids]
     if any(have) and not all(have):
-        raise ValueError(f"match_pairs: some slots of {name} carry a {what} and some do not")
+        raise ValueError(f"{who}: some slots of {name} carry a {what} and some do not")
     return all(have)
+
+
+def _encode_pairs(model, bank0, ids0, bank1, ids1, flags):
+    """The front half that ``match_pairs`` and ``refine_points`` share, after ``_pair_guards``: the batch dict of the n pairs (masks and
+    scales gathered from the banks, the map extents) and the position-encoded coarse features.  -> (data, feat_c0, feat_c1, t0, t1):
+    t0 / t1 are the slot ids as host int32 tensors.  The caller holds ``torch.no_grad()`` and the model's device."""
+    n = len(ids0)
+    dev = _model_device(model)
+    m0, s0, s1 = flags
+    # the slot ids go to the kernels as host tensors: the wrappers check them before any launch
+    t0, t1 = torch.tensor(ids0, dtype=torch.int32), torch.tensor(ids1, dtype=torch.int32)
+    data = {}
+    if m0:
+        g0, g1 = t0.to(dev, torch.long), t1.to(dev, torch.long)
+        data.update(mask0=bank0.mask[g0], mask1=bank1.mask[g1])
+    if s0:
+        data["scale0"] = bank0.scale[t0.to(dev, torch.long)]
+    if s1:
+        data["scale1"] = bank1.scale[t1.to(dev, torch.long)]
+    data.update({"bs": n, "hw0_i": torch.Size(bank0.image_hw), "hw1_i": torch.Size(bank1.image_hw)})
+    data.update({"hw0_c": torch.Size((bank0.h_c, bank0.w_c)), "hw1_c": torch.Size((bank1.h_c, bank1.w_c)),
+                 "hw0_f": torch.Size((bank0.h_f, bank0.w_f)), "hw1_f": torch.Size((bank1.h_f, bank1.w_f))})
+    model._fine_join = None                               # the fine maps are in the banks: no side stream to join
+    pe = model.pos_encoding.pe[0]
+    L0, L1, Cc = bank0.h_c * bank0.w_c, bank1.h_c * bank1.w_c, bank0.coarse.shape[3]
+    if (bank0.h_c, bank0.w_c) == (bank1.h_c, bank1.w_c):
+        # both halves of the ONE [2n, L, C] buffer the coarse transformer runs on in place (as stacked_halves arranges it in forward)
+        both = torch.empty(2 * n, L0, Cc, device=dev)
+        feat_c0, feat_c1 = both[:n], both[n:]
+    else:
+        feat_c0 = torch.empty(n, L0, Cc, device=dev)
+        feat_c1 = torch.empty(n, L1, Cc, device=dev)
+    ops.pos_encode_flatten_gather(bank0.coarse_map(), t0, pe, out=feat_c0)
+    ops.pos_encode_flatten_gather(bank1.coarse_map(), t1, pe, out=feat_c1)
+    return data, feat_c0, feat_c1, t0, t1
+
+
+def _pair_guards(model, bank0, ids0, bank1, ids1, who):
+    """The checks of a call on n pairs of bank slots -> (bank1, ids0, ids1, flags): the ids as host lists, flags = (the slots carry
+    masks, the side-0 slots carry scales, the side-1 slots carry scales)."""
+    if model.training:
+        raise LoftrHipError(f"{who}: inference only; call .eval()")
+    bank1 = bank0 if bank1 is None else bank1
+    if ids1 is None:
+        raise ValueError(f"{who}: ids1 is required")
+    ids0, ids1 = _host_ids(ids0, "ids0"), _host_ids(ids1, "ids1")
+    n = len(ids0)
+    if n == 0 or len(ids1) != n:
+        raise ValueError(f"{who}: ids0 / ids1 must hold the same positive number of slot ids, got {len(ids0)} / {len(ids1)}")
+    dev = _model_device(model)
+    for tag, bank in (("bank0", bank0), ("bank1", bank1)):
+        if not isinstance(bank, FeatureBank):
+            raise TypeError(f"{who}: {tag} must be a FeatureBank")
+        if bank.coarse.device != dev or bank.fine.device != dev:
+            raise LoftrHipError(f"{who}: {tag} is on {bank.coarse.device}, the model on {dev}")
+    bank0._check(ids0, model, "ids0")
+    bank1._check(ids1, model, "ids1")
+    m0 = _side_flag(bank0, ids0, bank0._has_mask, "mask", "ids0", who)
+    m1 = _side_flag(bank1, ids1, bank1._has_mask, "mask", "ids1", who)
+    if m0 != m1:
+        raise ValueError(f"{who}: the slots of one side carry masks and those of the other do not (forward needs both or neither)")
+    s0 = _side_flag(bank0, ids0, bank0._has_scale, "scale", "ids0", who)
+    s1 = _side_flag(bank1, ids1, bank1._has_scale, "scale", "ids1", who)
+    return bank1, ids0, ids1, (m0, s0, s1)
 
 
 def match_pairs(model, bank0, ids0, bank1=None, ids1=None):
     """LoFTR.match_pairs (see there)."""
-    if model.training:
-        raise LoftrHipError("match_pairs: inference only; call .eval()")
-    bank1 = bank0 if bank1 is None else bank1
-    if ids1 is None:
-        raise ValueError("match_pairs: ids1 is required")
-    ids0, ids1 = _host_ids(ids0, "ids0"), _host_ids(ids1, "ids1")
-    n = len(ids0)
-    if n == 0 or len(ids1) != n:
-        raise ValueError(f"match_pairs: ids0 / ids1 must hold the same positive number of slot ids, got {len(ids0)} / {len(ids1)}")
-    dev = _model_device(model)
-    for tag, bank in (("bank0", bank0), ("bank1", bank1)):
-        if not isinstance(bank, FeatureBank):
-            raise TypeError(f"match_pairs: {tag} must be a FeatureBank")
-        if bank.coarse.device != dev or bank.fine.device != dev:
-            raise LoftrHipError(f"match_pairs: {tag} is on {bank.coarse.device}, the model on {dev}")
-    bank0._check(ids0, model, "ids0")
-    bank1._check(ids1, model, "ids1")
-    m0 = _side_flag(bank0, ids0, bank0._has_mask, "mask", "ids0")
-    m1 = _side_flag(bank1, ids1, bank1._has_mask, "mask", "ids1")
-    if m0 != m1:
-        raise ValueError("match_pairs: the slots of one side carry masks and those of the other do not (forward needs both or neither)")
-    s0 = _side_flag(bank0, ids0, bank0._has_scale, "scale", "ids0")
-    s1 = _side_flag(bank1, ids1, bank1._has_scale, "scale", "ids1")
-    # the slot ids go to the kernels as host tensors: the wrappers check them before any launch
-    t0, t1 = torch.tensor(ids0, dtype=torch.int32), torch.tensor(ids1, dtype=torch.int32)
-    with torch.no_grad(), torch.cuda.device(dev):
-        data = {}
-        if m0:
-            g0, g1 = t0.to(dev, torch.long), t1.to(dev, torch.long)
-            data.update(mask0=bank0.mask[g0], mask1=bank1.mask[g1])
-        if s0:
-            data["scale0"] = bank0.scale[t0.to(dev, torch.long)]
-        if s1:
-            data["scale1"] = bank1.scale[t1.to(dev, torch.long)]
-        data.update({"bs": n, "hw0_i": torch.Size(bank0.image_hw), "hw1_i": torch.Size(bank1.image_hw)})
-        data.update({"hw0_c": torch.Size((bank0.h_c, bank0.w_c)), "hw1_c": torch.Size((bank1.h_c, bank1.w_c)),
-                     "hw0_f": torch.Size((bank0.h_f, bank0.w_f)), "hw1_f": torch.Size((bank1.h_f, bank1.w_f))})
-        model._fine_join = None                               # the fine maps are in the banks: no side stream to join
-        pe = model.pos_encoding.pe[0]
-        L0, L1, Cc = bank0.h_c * bank0.w_c, bank1.h_c * bank1.w_c, bank0.coarse.shape[3]
-        if (bank0.h_c, bank0.w_c) == (bank1.h_c, bank1.w_c):
-            # both halves of the ONE [2n, L, C] buffer the coarse transformer runs on in place (as stacked_halves arranges it in forward)
-            both = torch.empty(2 * n, L0, Cc, device=dev)
-            feat_c0, feat_c1 = both[:n], both[n:]
-        else:
-            feat_c0 = torch.empty(n, L0, Cc, device=dev)
-            feat_c1 = torch.empty(n, L1, Cc, device=dev)
-        ops.pos_encode_flatten_gather(bank0.coarse_map(), t0, pe, out=feat_c0)
-        ops.pos_encode_flatten_gather(bank1.coarse_map(), t1, pe, out=feat_c1)
+    bank1, ids0, ids1, flags = _pair_guards(model, bank0, ids0, bank1, ids1, "match_pairs")
+    with torch.no_grad(), torch.cuda.device(_model_device(model)):
+        data, feat_c0, feat_c1, t0, t1 = _encode_pairs(model, bank0, ids0, bank1, ids1, flags)
         f0, f1 = bank0.fine_map(), bank1.fine_map()
         model._match_encoded(feat_c0, feat_c1, data,
                              lambda c0, c1: model.fine_preprocess.forward_gather(f0, t0, f1, t1, c0, c1, data))
     return data
+
+
+def _point_pairs(b_ids, pts0, pts1, n, dev):
+    """The checks of the point pairs of ``refine_points`` -> (b_ids i64, pts0 f32, pts1 f32) contiguous on ``dev``.  ``b_ids`` must
+    ascend and lie in [0, n): a host sequence is checked for free, a device tensor costs the readback of one flag, here, before
+    anything is launched (a pair outside the batch would index the slot tables out of range)."""
+    b = b_ids if isinstance(b_ids, torch.Tensor) else torch.as_tensor(np.asarray(b_ids))
+    if b.dim() != 1 or b.dtype.is_floating_point or b.dtype == torch.bool:
+        raise ValueError(f"refine_points: b_ids must be a 1-D integer sequence, got {tuple(b.shape)} {b.dtype}")
+    M = b.shape[0]
+    pts = []
+    for p, name in ((pts0, "pts0"), (pts1, "pts1")):
+        p = p if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p))
+        if tuple(p.shape) != (M, 2) or not p.dtype.is_floating_point:
+            raise ValueError(f"refine_points: {name} must be a floating-point [{M}, 2] (one point per b_ids entry), got {tuple(p.shape)} {p.dtype}")
+        pts.append(p)
+    b = b.detach().to(torch.int64)
+    if M:
+        bad = (b[1:] < b[:-1]).any() | (b[0] < 0) | (b[-1] >= n)
+        if bool(bad):
+            raise ValueError(f"refine_points: b_ids must ascend and lie in [0, {n})")
+    return (b.to(dev).contiguous(), *[p.detach().to(dev, torch.float32).contiguous() for p in pts])
+
+
+def refine_points(model, bank0, ids0, bank1, ids1, b_ids, pts0, pts1):
+    """LoFTR.refine_points (see there)."""
+    n = len(ids0) if hasattr(ids0, "__len__") else 0
+    dev = _model_device(model)
+    b_ids, pts0, pts1 = _point_pairs(b_ids, pts0, pts1, n, dev)
+    bank1, ids0, ids1, flags = _pair_guards(model, bank0, ids0, bank1, ids1, "refine_points")
+    with torch.no_grad(), torch.cuda.device(dev):
+        data, feat_c0, feat_c1, t0, t1 = _encode_pairs(model, bank0, ids0, bank1, ids1, flags)
+        feat_c0, feat_c1 = model._coarse_transformer(feat_c0, feat_c1, data)[:2]
+        ops.check_transformer_status(dev)
+        s = data["hw0_i"][0] / data["hw0_f"][0]                 # FineMatching's scale: image pixels per fine pixel
+        stride = data["hw0_f"][0] // data["hw0_c"][0]           # FinePreprocess's stride: fine pixels per coarse cell
+        at = ops.refine_centres(pts0, pts1, b_ids, n, data["hw0_f"], data["hw1_f"], data["hw0_c"], data["hw1_c"], stride, s,
+                                data.get("scale0"), data.get("scale1"))
+        ok = at["ok"]
+        if b_ids.shape[0] == 0:
+            return {"pts0": at["pts0_s"], "pts1_start": at["pts1_s"], "pts1": at["pts1_s"].clone(),
+                    "expec_f": torch.empty(0, 3, device=dev), "ok": ok}
+        data.update(b_ids=b_ids, i_ids=at["i_ids"], j_ids=at["j_ids"])
+        w0, w1 = model.fine_preprocess.forward_gather_at(bank0.fine_map(), t0, bank1.fine_map(), t1, feat_c0, feat_c1, data,
+                                                         at["c0"], at["c1"])
+        w0, w1 = model.loftr_fine(w0, w1, inplace=True)
+        # reference quirk kept: scale1 is applied iff the side-0 slots carry a scale (fine_matching.py:68)
+        expec, pts1_f = ops.fine_match(w0, w1, at["pts1_s"], b_ids, s, data["scale1"] if "scale0" in data else None)
+        bad = (ok == 0).unsqueeze(1)
+        nan = torch.full((), float("nan"), device=dev)
+        return {"pts0": at["pts0_s"], "pts1_start": at["pts1_s"], "pts1": torch.where(bad, nan, pts1_f),
+                "expec_f": torch.where(bad, nan, expec), "ok": ok}
 
 
 # ---- pair lists -----------------------------------------------------------------------------------------------------------
@@ -369,9 +439,16 @@ def match_pair_list(model, pairs, load, image_hw, budget_bytes=None, batch_size=
     device memory; never more than the distinct images need).  Yields ``(rows, data)`` per chunk of ``batch_size`` consecutive
     rows, in input order, ``data`` as from ``LoFTR.match_pairs``.  Runs serially on the current stream.  ``stats`` (a dict):
     filled with n_slots, bank_bytes, images_extracted, backbone_calls."""
+    for bank, st in _scheduled_chunks("match_pair_list", model, pairs, load, image_hw, budget_bytes, batch_size, extract_batch, stats):
+        yield st.rows, match_pairs(model, bank, st.slots0, bank, st.slots1)
+
+
+def _scheduled_chunks(who, model, pairs, load, image_hw, budget_bytes, batch_size, extract_batch, stats):
+    """The schedule of ``plan_pair_list`` carried out on one bank: runs the Extract steps and yields ``(bank, step)`` at every Match
+    step (what ``match_pair_list`` and ``refine_pair_list`` share)."""
     p = np.asarray(pairs)
     if p.ndim != 2 or p.shape[1] != 2:
-        raise ValueError(f"match_pair_list: pairs must be [P, 2], got {p.shape}")
+        raise ValueError(f"{who}: pairs must be [P, 2], got {p.shape}")
     distinct = len(np.unique(p)) if p.size else 0
     per_image = FeatureBank.image_bytes(model, image_hw)
     if budget_bytes is None:
@@ -387,6 +464,25 @@ def match_pair_list(model, pairs, load, image_hw, budget_bytes=None, batch_size=
             batch = load(list(st.images))
             bank.add(batch["image"], mask=batch.get("mask"), scale=batch.get("scale"), slots=st.slots)
         else:
-            yield st.rows, match_pairs(model, bank, st.slots0, bank, st.slots1)
+            yield bank, st
     if stats is not None:
         stats.update(images_extracted=bank.images_extracted, backbone_calls=bank.backbone_calls)
+
+
+def refine_pair_list(model, pairs, pair_offsets, pts0, pts1, load, image_hw, budget_bytes=None, batch_size=8, extract_batch=16, stats=None):
+    """``LoFTR.refine_points`` over a whole job list, scheduled like ``match_pair_list`` (the same chunks, the same eviction, one bank).
+
+    ``pairs`` [P, 2] (reference image, query image); ``pair_offsets`` [P+1], a host array that delimits the jobs of each pair in
+    ``pts0`` / ``pts1`` [J, 2] (reference point, query point; any device).  Yields ``(job_slice, result)`` per chunk of ``batch_size``
+    consecutive pairs, in input order: ``job_slice`` the jobs of the chunk, ``result`` the dict of ``refine_points`` for them with
+    ``b_ids`` = the pair's index within the chunk.  ``load``, ``image_hw``, ``budget_bytes``, ``stats`` as for ``match_pair_list``."""
+    p = np.asarray(pairs)
+    off = np.asarray(pair_offsets).astype(np.int64).reshape(-1)
+    if p.ndim != 2 or off.shape[0] != p.shape[0] + 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != pts0.shape[0] or \
+            tuple(pts1.shape) != tuple(pts0.shape):
+        raise ValueError(f"refine_pair_list: pair_offsets must be [P+1], ascending from 0 to the number of jobs ({tuple(pts0.shape)}, "
+                         f"{tuple(pts1.shape)}), got {off.shape} for pairs {p.shape}")
+    for bank, st in _scheduled_chunks("refine_pair_list", model, pairs, load, image_hw, budget_bytes, batch_size, extract_batch, stats):
+        jobs = slice(int(off[st.rows.start]), int(off[st.rows.stop]))
+        b_ids = torch.from_numpy(np.repeat(np.arange(len(st.rows), dtype=np.int64), np.diff(off[st.rows.start:st.rows.stop + 1])))
+        yield jobs, refine_points(model, bank, st.slots0, bank, st.slots1, b_ids, pts0[jobs], pts1[jobs])
