@@ -74,7 +74,8 @@ typedef enum {
  *     3D similarity RANSAC and moving a model (loftr_estimate_similarity, loftr_similarity_minimal,
  *     loftr_estimate_similarity_batched_workspace_bytes, loftr_estimate_similarity_batched, loftr_transform_model_host,
  *     loftr_transform_model), track splitting (loftr_split_tracks_host, loftr_split_tracks_workspace_bytes, loftr_split_tracks), track
- *     refinement (loftr_refine_centres_host, loftr_refine_centres, loftr_fine_preprocess_gather_at) */
+ *     refinement (loftr_refine_centres_host, loftr_refine_centres, loftr_fine_preprocess_gather_at), rotation averaging over the
+ *     view graph (loftr_rotation_averaging_host, loftr_rotation_averaging_workspace_bytes, loftr_rotation_averaging) */
 #define LOFTR_HIP_ABI_VERSION 25
 
 int loftr_hip_abi_version(void);
@@ -1398,6 +1399,72 @@ int loftr_fine_preprocess_gather_at(const loftr_fmap* bank_f0, int n_slots0, con
                                     const float* down_w, const float* down_b, const float* merge_w,
                                     const float* merge_b, float* out0, float* out1, void* ws,
                                     size_t ws_bytes, const int* c0, const int* c1, void* stream);
+
+/* ---- rotation averaging over the view graph; the pairs that disagree (csrc/rotation_core.h holds every per-item step) ---
+ * The image pairs with their relative rotations are the edges of a graph over the images.  Relative rotations around a cycle must
+ * compose to the identity, so a pair that no cycle supports is suspect; robust averaging gives one rotation per image, and every pair
+ * a residual against them.  fp64, `+ - * /` and sqrt only, no contraction, every sum in a stated order.
+ * loftr_rotation_averaging_host (csrc/rotation.hip, host memory) DEFINES the result, loftr_rotation_averaging (csrc/rotation_gpu.hip,
+ * device memory) reproduces it bit for bit.  Rotations are unit quaternions (w, x, y, z) inside, by §18's Shepperd conversion.
+ * Input: edge_image [E,2] i32 (a, b); edge_R [E,3,3] f64 with x_b = R x_a, so R_b = R_ab R_a for camera-from-world rotations;
+ *   edge_weight [E] i32 (for example inlier counts); n_images; root (-1: rule 4); the adjacency the caller builds with integer
+ *   sorts: adj_offsets [n_images + 1] i64 and adj_edge [2E] i32, the edges of every node ordered by (neighbour, edge); edge_use_in
+ *   [E] u8 (rule 2).  Angles arrive converted: cycle_cos_half = cos(cycle / 2), loss_chord = 2 sin(loss / 2), max_chord =
+ *   2 sin(max_err / 2), step_tol in radians.
+ *   1. Checks (counts[1]).  1: an edge_image entry outside [0, n_images); 2: a == b; 4: adj_offsets that do not start at 0, end at 2E
+ *      and ascend, a slot that does not hold an edge of its node, neighbours that descend, edges that do not ascend strictly within a
+ *      neighbour, or two used edges that join one pair; 8: root outside [-1, n_images).
+ *   2. Edge e is VALID iff its weight is positive, its matrix is finite, det > 0 and max |R^T R - I| <= 1e-3 (the zeros of a refused
+ *      model are invalid, not an error).  Among the valid edges of one unordered pair the caller marks the heaviest (ties: the lowest
+ *      index) in edge_use_in; edge_use = edge_use_in on valid edges, 0 on the others; valid edges that are not used are duplicates.
+ *   3. support[e] of a used edge (a, b): the nodes c that both ends reach by a used edge and whose cycle quaternion
+ *      q_ca (x) q_bc (x) q_ab (a factor conjugated when its edge is stored the other way round) has |w| >= cycle_cos_half;
+ *      saturates at 65535; 0 for the other edges.
+ *   4. With root = -1 the root is the image with the greatest i64 sum of used weights, the lowest on ties.  Only the root's
+ *      component is solved, which need not be the largest.
+ *   5. The tree is the maximum spanning forest of the used edges under the strict order of the words
+ *      min(support, 0xFFFF) << 48 | min(weight, 0xFFFF) << 32 | (0xFFFFFFFF - e).  Words are unique, so the forest is: the host runs
+ *      Kruskal, the kernels Boruvka rounds in which every component accepts its best outgoing edge.
+ *   6. Start values: q_root = (1, 0, 0, 0); along the tree away from the root q_child = normalise(q (x) q_parent), q the edge's
+ *      quaternion from the parent's side.  Images the root does not reach have in_graph = 0.
+ *   7. At most max_iters Gauss-Newton steps over the used edges of the graph.  Residual of edge (a, b): e = conj(q_b) (x) q_ab (x) q_a
+ *      with the sign that makes e.w >= 0, r = 2 e.xyz (the chord).  Weight w = weight (d^2 / (d^2 + |r|^2))^2, d = loss_chord
+ *      (Geman-McClure); the robust cost is the osum over the edges of weight d^2 |r|^2 / (d^2 + |r|^2).  The step omega minimises
+ *      sum_e w_e |r_e - (omega_b - omega_a)|^2 with omega_root = 0: Jacobi-preconditioned conjugate gradients from 0, at most pcg_iters
+ *      iterations, ended by r.z <= pcg_tol^2 (r.z)_0; a node's sums run over its list in order, dot products over the 3 n_images
+ *      scalars by §18's osum.  q_i <- normalise(q_i (x) (1, omega_i / 2)).  The refinement ends when the largest |omega_i| is below
+ *      step_tol (status 0), after max_iters (1), or on a step that is not finite, which is not applied (2); 3: the root has no used edge.
+ *   8. Every valid edge with both ends in the graph, duplicates included, gets edge_chord [E] f64 = |r| at the final state and
+ *      edge_state [E] u8 = 2 (ok: chord <= max_chord) or 3 (outlier); the others have chord NaN and state 0 (invalid) or 1 (an end
+ *      outside the graph).  R [n_images,3,3] f64: exactly the identity at the root, NaN outside the graph.  in_graph [n_images] u8,
+ *      support [E] i32, tree [E] u8, edge_use [E] u8.  counts [16] i64: [0] images in the graph, [1] error bits, [2..4] invalid /
+ *      duplicate / used edges, [5] the sum of support, [6] tree edges, [7] tree edges with support 0 (the warning sign: the tree had to
+ *      cross an edge no cycle vouches for), [8] the depth of the tree below the root, [9] components of the used edges, [10] outer
+ *      iterations, [11] conjugate-gradient iterations, [12] ok, [13] outlier edges, [14] status, [15] the root (-1 without images).
+ *      info [4] f64: the robust cost at the start values and at the end, the last step (radians), the largest chord of an ok edge.
+ * Status: LOFTR_ERR_BAD_ARG for null pointers, negative sizes, edges without images, loss_chord <= 0, a negative max_chord or step_tol,
+ *   pcg_tol outside [0, 1), anything not finite; the host routine also for the error bits, and it then writes the bits to counts[1] and
+ *   nothing else (the kernels raise counts[1] instead, read nothing through the bad value and write no other output);
+ *   LOFTR_ERR_UNSUPPORTED for E > 2^31 - 2, n_images > 2^30, max_iters or pcg_iters > 65536; LOFTR_ERR_WORKSPACE.
+ * Out of scope: translations and global positions, rotation priors for the bundle adjustment, the components the root does not reach,
+ *   any weighting but the caller's integers.  The defaults of the Python layer come from synthetic graphs only. */
+int loftr_rotation_averaging_host(const int* edge_image, const double* edge_R, const int* edge_weight, long E, int n_images, int root,
+                                  const long* adj_offsets, const int* adj_edge, const uint8_t* edge_use_in, double cycle_cos_half,
+                                  double loss_chord, double max_chord, double step_tol, int max_iters, int pcg_iters, double pcg_tol,
+                                  double* R, uint8_t* in_graph, uint8_t* edge_state, double* edge_chord, int* support, uint8_t* tree,
+                                  uint8_t* edge_use, long* counts, double* info);
+/* The kernels: a fixed schedule of launches that depends on the sizes, max_iters and pcg_iters only; a launch whose phase the host
+ * routine would not run returns at once on flags an earlier launch wrote.  No host synchronisation unless stage_ms is given: NULL, or
+ * LOFTR_ROTATION_STAGES host floats (check, support, tree, start, refine, write; the call then waits for the stream).  Workspace:
+ * loftr_rotation_averaging_workspace_bytes(E, n_images): about 90 bytes per edge and 190 per image; 0 without images (none is needed
+ * then) and for sizes out of range. */
+#define LOFTR_ROTATION_STAGES 6
+size_t loftr_rotation_averaging_workspace_bytes(long E, int n_images);
+int loftr_rotation_averaging(const int* edge_image, const double* edge_R, const int* edge_weight, long E, int n_images, int root,
+                             const long* adj_offsets, const int* adj_edge, const uint8_t* edge_use_in, double cycle_cos_half,
+                             double loss_chord, double max_chord, double step_tol, int max_iters, int pcg_iters, double pcg_tol,
+                             double* R, uint8_t* in_graph, uint8_t* edge_state, double* edge_chord, int* support, uint8_t* tree,
+                             uint8_t* edge_use, long* counts, double* info, void* ws, size_t ws_bytes, float* stage_ms, void* stream);
 
 /* ---- 3D similarity between two point sets; moving a model into another frame ------------------------------------------
  * dst ~ s R src + t with R a proper rotation and s > 0, or s == 1 when with_scale == 0 (rigid, SE(3)): the closed form of Kabsch /

@@ -204,6 +204,11 @@ SIGNATURES = {
     "loftr_refine_centres": (_i, [_p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
     "loftr_fine_preprocess_gather_at": (_i, [C.POINTER(FMap), _i, _p, C.POINTER(FMap), _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i,
                                              _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
+    "loftr_rotation_averaging_host": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double,
+                                           _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "loftr_rotation_averaging_workspace_bytes": (_sz, [_l, _i]),
+    "loftr_rotation_averaging": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double,
+                                      _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "loftr_estimate_similarity": (_i, [_p, _p, _l, _i, C.c_double, _f, C.c_uint, _p, _p, _p, _p, C.POINTER(_l)]),
     "loftr_similarity_minimal": (_i, [_p, _p, _i, _p, _p, _p, C.POINTER(_i)]),
     "loftr_estimate_similarity_batched_workspace_bytes": (_sz, [_l, _i]),

@@ -189,7 +189,7 @@ class SfmResult:
         return R, t, ninl
 
     def reconstruct(self, K, init_row=None, init_candidates=8, thresh_px=4.0, pose_conf=0.99999, consistent_only=True, complete=False, merge=False,
-                    split=False, **kwargs):
+                    split=False, rotations=False, _candidate_rows=None, **kwargs):
         """Poses of the images and points of the tracks from intrinsics alone (registration.reconstruct_tracks) ->
         Reconstruction on this result's device, its ``points`` carrying the CSR arrays as ``triangulate`` attaches them.
         The initial pair is row ``init_row`` with its five-point pose (``pairwise_poses`` at ``thresh_px``).  With ``init_row=None``:
@@ -205,13 +205,29 @@ class SfmResult:
         of it, when ``complete=True``), one ``merge`` of the tracks whose points meet and agree, then the same triangulate -> adjust ->
         triangulate; ``.sfm`` is the relabelled atlas and ``stats['merge']`` the counts.  ``split=True``: ``split`` runs first
         and everything after it, the five-point poses included, reads the split atlas, whose tracks are all consistent; ``.sfm`` is that
-        atlas (or what ``complete`` / ``merge`` made of it) and ``stats['split']`` the counts.  With the defaults nothing
-        of this runs."""
+        atlas (or what ``complete`` / ``merge`` made of it) and ``stats['split']`` the counts.  ``rotations=True`` (or a dict
+        of ``average_rotations`` keywords): ``rotation_averaging`` runs first, everything after it reads
+        ``without_rows(ok rows | rows the graph could not judge)``, the initial pair is chosen among the ok rows only, and the
+        Reconstruction carries the ``GlobalRotations`` as ``.rotations``, its counts as ``stats['rotations']`` and the atlas it was built
+        on as ``.sfm``.  With the defaults nothing of this runs."""
         from .registration import reconstruct_tracks, triangulate_posed
+        if rotations:
+            view = self.undistorted(K, kwargs["radial"]) if kwargs.get("radial") is not None else self
+            rot = view.rotation_averaging(K, thresh_px=thresh_px, pose_conf=pose_conf, seed=kwargs.get("seed", 0),
+                                          **(rotations if isinstance(rotations, dict) else {}))
+            sfm2, done = self.without_rows(rot.edge_ok | (rot.edge_state < 2))
+            rec = sfm2.reconstruct(K, init_row=init_row, init_candidates=init_candidates, thresh_px=thresh_px, pose_conf=pose_conf,
+                                   consistent_only=consistent_only, complete=complete, merge=merge, split=split,
+                                   _candidate_rows=rot.edge_ok.cpu().tolist(), **kwargs)
+            if rec.sfm is None:
+                rec.sfm = sfm2
+            rec.rotations = rot
+            rec.stats.update(rotations=rot.stats, rows_removed=done.stats)
+            return rec
         if split:
             sfm2, done = self.split()
             rec = sfm2.reconstruct(K, init_row=init_row, init_candidates=init_candidates, thresh_px=thresh_px, pose_conf=pose_conf,
-                                   consistent_only=consistent_only, complete=complete, merge=merge, **kwargs)
+                                   consistent_only=consistent_only, complete=complete, merge=merge, _candidate_rows=_candidate_rows, **kwargs)
             if rec.sfm is None:
                 rec.sfm = sfm2
             rec.stats.update(split=done.stats)
@@ -230,7 +246,8 @@ class SfmResult:
         offsets, image, local = self.tracks(consistent_only)
         obs_image, xy = image.to(torch.int32), view.keypoints[self.kp_offsets[image] + local]
         if init_row is None:
-            order = sorted((r for r in range(len(rows)) if ninl_host[r] >= 0), key=lambda r: (-ninl_host[r], r))[:max(int(init_candidates), 0)]
+            order = sorted((r for r in range(len(rows)) if ninl_host[r] >= 0 and (_candidate_rows is None or _candidate_rows[r])),
+                           key=lambda r: (-ninl_host[r], r))[:max(int(init_candidates), 0)]
             if not order:
                 raise ValueError(f"SfmResult.reconstruct: no row has a five-point model (inlier counts of the {len(rows)} rows: {ninl_host})")
             n_ok = []
@@ -331,6 +348,48 @@ class SfmResult:
         fields = {k: getattr(self, k) for k in self.FIELDS}
         fields.update(track_id=done.track_id_new, track_len=done.track_len_new, track_ok=torch.ones_like(done.track_len_new, dtype=torch.bool))
         sfm2 = SfmResult(dict(self.stats, n_tracks=done.stats["n_tracks"], n_split_rounds=done.stats["n_rounds"]), **fields)
+        sfm2.image_hw, sfm2.cell_px, sfm2.is_undistorted = self.image_hw, self.cell_px, self.is_undistorted
+        return sfm2, done
+
+    def rotation_averaging(self, K, thresh_px=4.0, pose_conf=0.99999, seed=0, **kwargs):
+        """The rows of the pair list as a view graph: the five-point rotations of ``pairwise_poses`` averaged into one rotation per image,
+        the inlier counts as weights (rotations.average_rotations) -> ``GlobalRotations`` on this result's device.  Edge
+        ``e`` is row ``e``: ``edge_ok[e]`` is the verdict of the row, a row without a model is invalid (state 0).  The keyword
+        arguments are average_rotations'."""
+        from .rotations import average_rotations
+        R, _, ninl = self.pairwise_poses(K, thresh_px, pose_conf, seed)
+        n = self.kp_offsets.numel() - 1
+        return average_rotations(self.row_images, R.to(torch.float64), ninl.clamp(min=0).to(torch.int32), n, **kwargs)
+
+    def without_rows(self, rows_ok, min_track_len=2, max_rounds=32, timings=None):
+        """This result without the matches of the rows where ``rows_ok [R]`` is false -> ``(sfm2, split)``.  Every track that holds a
+        match of a rejected row loses its ``track_ok``; ``split_tracks`` then grows the keypoints of those tracks (and of the tracks
+        that were inconsistent before) again over the matches of the kept rows only, so a consistent track that no rejected row touched
+        keeps its members.  ``sfm2`` shares the keypoints with this result; its rejected rows are empty, its tracks are
+        numbered anew and all consistent.  No kernel of its own.  This result is left untouched."""
+        from .splitting import split_tracks
+        if self.is_refined:
+            raise ValueError("SfmResult.without_rows: this is a refined view; the atlas's cells are in stored-pixel space (drop the rows of the "
+                             "original result, then refine)")
+        dev = self.keypoints.device
+        n, n_rows = self.kp_offsets.numel() - 1, self.row_offsets.numel() - 1
+        rows_ok = torch.as_tensor(rows_ok).to(dev) != 0
+        if tuple(rows_ok.shape) != (n_rows,):
+            raise ValueError(f"SfmResult.without_rows: expected rows_ok [{n_rows}], got {tuple(rows_ok.shape)}")
+        per_row = self.row_offsets[1:] - self.row_offsets[:-1]
+        keep = rows_ok[torch.repeat_interleave(torch.arange(n_rows, device=dev), per_row)]
+        edges = self.edge_keypoints()
+        hit = self.track_id[edges[~keep].reshape(-1).to(torch.int64)].to(torch.int64)
+        track_ok = self.track_ok.clone()
+        track_ok[hit[hit >= 0]] = False
+        done = split_tracks(edges[keep], self.match_conf[keep], self.keypoint_image().to(torch.int32), self.track_id, track_ok, n,
+                            min_track_len=min_track_len, max_rounds=max_rounds, timings=timings)
+        row_offsets = torch.zeros_like(self.row_offsets)
+        row_offsets[1:] = torch.cumsum(torch.where(rows_ok, per_row, torch.zeros_like(per_row)), 0)
+        fields = {k: getattr(self, k) for k in self.FIELDS}
+        fields.update(matches=self.matches[keep], match_conf=self.match_conf[keep], row_offsets=row_offsets, track_id=done.track_id_new,
+                      track_len=done.track_len_new, track_ok=torch.ones_like(done.track_len_new, dtype=torch.bool))
+        sfm2 = SfmResult(dict(self.stats, n_tracks=done.stats["n_tracks"], n_kept=int(keep.sum()), n_rows_removed=int((~rows_ok).sum())), **fields)
         sfm2.image_hw, sfm2.cell_px, sfm2.is_undistorted = self.image_hw, self.cell_px, self.is_undistorted
         return sfm2, done
 

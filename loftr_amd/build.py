@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(HERE, "libloftr_hip.so")
 SOURCES = ["linear.hip", "coarse_plan.hip", "attention.hip", "transformer.hip", "coarse_match.hip", "fine.hip", "misc.hip",
-           "sp_convert.hip", "conv.hip", "eval.hip", "input.hip", "comm.hip", "pose.hip", "train.hip", "train_bwd.hip", "encoder_fused.hip", "fine_fused.hip", "head_grads.hip", "encoder_bwd.hip", "fine_bwd.hip", "train_glue.hip", "bank.hip", "pose_gpu.hip", "window_head.hip", "window_head_first.hip", "geometry.hip", "geometry_gpu.hip", "absolute_pose.hip", "absolute_pose_gpu.hip", "scan.hip", "atlas.hip", "atlas_gpu.hip", "triangulate.hip", "triangulate_gpu.hip", "model_lookup.hip", "model_lookup_gpu.hip", "bundle.hip", "bundle_gpu.hip", "register.hip", "register_gpu.hip", "complete.hip", "complete_gpu.hip", "merge.hip", "merge_gpu.hip", "split.hip", "split_gpu.hip", "similarity.hip", "similarity_gpu.hip", "overlap.hip", "overlap_gpu.hip", "undistort.hip", "undistort_gpu.hip", "refine.hip", "refine_gpu.hip"]
+           "sp_convert.hip", "conv.hip", "eval.hip", "input.hip", "comm.hip", "pose.hip", "train.hip", "train_bwd.hip", "encoder_fused.hip", "fine_fused.hip", "head_grads.hip", "encoder_bwd.hip", "fine_bwd.hip", "train_glue.hip", "bank.hip", "pose_gpu.hip", "window_head.hip", "window_head_first.hip", "geometry.hip", "geometry_gpu.hip", "absolute_pose.hip", "absolute_pose_gpu.hip", "scan.hip", "atlas.hip", "atlas_gpu.hip", "triangulate.hip", "triangulate_gpu.hip", "model_lookup.hip", "model_lookup_gpu.hip", "bundle.hip", "bundle_gpu.hip", "register.hip", "register_gpu.hip", "complete.hip", "complete_gpu.hip", "merge.hip", "merge_gpu.hip", "split.hip", "split_gpu.hip", "similarity.hip", "similarity_gpu.hip", "overlap.hip", "overlap_gpu.hip", "undistort.hip", "undistort_gpu.hip", "refine.hip", "refine_gpu.hip", "rotation.hip", "rotation_gpu.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-parameter"]
 
 

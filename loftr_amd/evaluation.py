@@ -380,6 +380,27 @@ def trajectory_errors(T_est, posed, T_gt, thresh=None, with_scale=True, conf=0.9
     return rot, cen
 
 
+def global_rotation_errors(R, R_gt, mask=None):
+    """Angle between estimated and true camera-from-world rotations, degrees per image, after the one free rotation is removed:
+    ``R [n,3,3]`` is defined up to ``R_i G`` (rotation averaging fixes ``R[root] = I``), so ``G`` is taken as the chordal mean of
+    ``R_i^T R_gt_i`` over the images of ``mask`` (default: those with a finite ``R``), the 3 x 3 polar factor with ``det = +1``, computed
+    with torch on the host.  Images outside the mask get NaN."""
+    R = torch.as_tensor(R, dtype=torch.float64).cpu()
+    R_gt = torch.as_tensor(R_gt, dtype=torch.float64).cpu()
+    m = torch.isfinite(R).reshape(R.shape[0], -1).all(1) if mask is None else torch.as_tensor(mask).cpu().bool()
+    out = torch.full((R.shape[0],), float("nan"), dtype=torch.float64)
+    if not bool(m.any()):
+        return out
+    U, _, Vh = torch.linalg.svd((R[m].transpose(1, 2) @ R_gt[m]).sum(0))
+    D = torch.diag(torch.tensor([1.0, 1.0, float(torch.sign(torch.linalg.det(U @ Vh)))], dtype=torch.float64))
+    G = U @ D @ Vh
+    rel = (R[m] @ G) @ R_gt[m].transpose(1, 2)
+    # the chord |R - I|_F = 2 sqrt(2) sin(angle / 2) keeps its precision near zero, where acos of the trace loses it
+    chord = (rel - torch.eye(3, dtype=torch.float64)).reshape(-1, 9).norm(dim=1)
+    out[m] = torch.rad2deg(2.0 * torch.asin((chord / (2.0 * 2.0 ** 0.5)).clamp(max=1.0)))
+    return out
+
+
 def absolute_pose_error(T_gt, R, t):
     """(rotation error in degrees, distance between the camera centres in the units of the depth) of an estimate x_cam = R X + t
     against the ground truth T_gt [4,4] or [3,4] (same convention): the geodesic angle of R^T R_gt and |R^T t - R_gt^T t_gt|, the two

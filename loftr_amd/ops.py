@@ -2059,7 +2059,79 @@ def split_tracks(edge_kp, edge_conf, kp_image, track_id, track_ok, n_images, min
                          (edge_kp, edge_conf, kp_image, track_id, track_ok), n_images, min_track_len, max_rounds, timings)
 
 
-# ---- localisation against a triangulated model (csrc/model_lookup.hip, csrc/model_lookup_gpu.hip) ------------------------
+# ---- rotation averaging over the view graph (csrc/rotation.hip, csrc/rotation_gpu.hip) ------------------------------------
+ROTATION_COUNTS = 16
+ROTATION_NAMES = ("n_in_graph", "error_bits", "n_invalid", "n_duplicate", "n_used", "support_sum", "n_tree", "n_tree_unsupported", "tree_depth",
+                  "n_components", "n_iters", "n_pcg_iters", "n_ok", "n_outlier", "status", "root")          # counts[0..15]
+ROTATION_INFO = ("cost_start", "cost_end", "last_step", "max_ok_chord")                  # info[0..3]
+ROTATION_STATES = ("invalid", "outside", "ok", "outlier")                                # edge_state codes 0..3
+ROTATION_STATUS = ("converged", "max_iters", "stalled", "nothing")                       # counts[14]
+ROTATION_STAGES = ("check", "support", "tree", "start", "refine", "write")
+ROTATION_ERRORS = ((1, "edge_image outside [0, n_images)"), (2, "an edge that joins an image to itself"),
+                   (4, "adj_offsets / adj_edge must group the edges by image with neighbours ascending, one used edge per pair"),
+                   (8, "root outside [-1, n_images)"))                                   # bits of counts[1]
+_ROT_ARGS = (("edge_image", "int32", 2), ("edge_R", "float64", 3), ("edge_weight", "int32", 1), ("adj_offsets", "int64", 1),
+             ("adj_edge", "int32", 1), ("edge_use", "uint8", 1))
+_ROT_OUT = (("R", "n", (3, 3), "float64"), ("in_graph", "n", (), "uint8"), ("edge_state", "E", (), "uint8"), ("edge_chord", "E", (), "float64"),
+            ("support", "E", (), "int32"), ("tree", "E", (), "uint8"), ("edge_use", "E", (), "uint8"))
+
+
+def _rotation_averaging(B, what, hint, arrays, n_images, root, cycle_cos_half, loss_chord, max_chord, step_tol, max_iters, pcg_iters, pcg_tol,
+                        timings):
+    _check_args(B, what, hint, _ROT_ARGS, arrays)
+    edge_image, edge_R, edge_weight, adj_offsets, adj_edge, edge_use = arrays
+    E = edge_image.shape[0]
+    for name, v, lo in (("n_images", n_images, 0), ("root", root, -(1 << 31)), ("max_iters", max_iters, 0), ("pcg_iters", pcg_iters, 0)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < lo:
+            raise ValueError(f"{what}: {name} must be an integer >= {lo}, got {v}")
+    if (tuple(edge_image.shape) != (E, 2) or tuple(edge_R.shape) != (E, 3, 3) or edge_weight.shape[0] != E or adj_edge.shape[0] != 2 * E
+            or adj_offsets.shape[0] != n_images + 1 or edge_use.shape[0] != E):
+        raise _lib.LoftrHipError(f"{what}: expected edge_image [E,2], edge_R [E,3,3], edge_weight [E], adj_offsets [n_images + 1], adj_edge "
+                                 f"[2E] and edge_use [E], got {[tuple(a.shape) for a in arrays]}")
+    arrays = [B.contiguous(x) for x in arrays]                                           # (held until the call has returned)
+    a = [B.ptr(x) for x in arrays]
+    out = _outputs(B, _ROT_OUT, {"n": n_images, "E": E}, ROTATION_COUNTS, edge_image)
+    out["info"] = B.zeros(len(ROTATION_INFO), "float64", edge_image)
+    args = (a[0], a[1], a[2], E, n_images, root, a[3], a[4], a[5], float(cycle_cos_half), float(loss_chord), float(max_chord), float(step_tol),
+            max_iters, pcg_iters, float(pcg_tol), *[B.ptr(out[k]) for k in out])
+    if B is _Host:
+        status = _lib.load().loftr_rotation_averaging_host(*args)
+        if not (status == -1 and int(out["counts"][1]) != 0):                            # a bad graph is reported through counts[1], as on the GPU
+            check(status, "loftr_rotation_averaging_host")
+        return out
+    ms = _StageMs(timings, ROTATION_STAGES)
+    B.call("rotation_averaging", args, "", edge_image, ws=(E, n_images), tail=(ms.arg,))
+    ms.report()
+    return out
+
+
+def rotation_averaging_host(edge_image, edge_R, edge_weight, adj_offsets, adj_edge, edge_use, n_images, root, cycle_cos_half, loss_chord,
+                            max_chord, step_tol, max_iters=20, pcg_iters=30, pcg_tol=1e-4):
+    """loftr_rotation_averaging_host: the host routine that DEFINES rotation averaging (include/loftr_hip.h) on numpy arrays:
+    edge_image [E,2] i32, edge_R [E,3,3] f64, edge_weight [E] i32, adj_offsets [n_images + 1] i64, adj_edge [2E] i32, edge_use [E] u8; the
+    angles already converted (rotations.average_rotations does that, and builds the adjacency).
+    -> dict of numpy arrays: R [n,3,3] f64, in_graph [n] u8, edge_state [E] u8 (ROTATION_STATES), edge_chord [E] f64, support [E] i32,
+    tree [E] u8, edge_use [E] u8, counts [16] i64 (ROTATION_NAMES), info [4] f64 (ROTATION_INFO).  A bad graph leaves its bits in
+    counts[1] and every other output zero."""
+    return _rotation_averaging(_Host, "rotation_averaging_host", "rotation_averaging",
+                               (edge_image, edge_R, edge_weight, adj_offsets, adj_edge, edge_use), n_images, root, cycle_cos_half,
+                               loss_chord, max_chord, step_tol, max_iters, pcg_iters, pcg_tol, None)
+
+
+@_on_device
+def rotation_averaging(edge_image, edge_R, edge_weight, adj_offsets, adj_edge, edge_use, n_images, root, cycle_cos_half, loss_chord,
+                       max_chord, step_tol, max_iters=20, pcg_iters=30, pcg_tol=1e-4, timings=None):
+    """loftr_rotation_averaging: the kernels (csrc/rotation_gpu.hip) on GPU tensors of the dtypes and shapes of rotation_averaging_host;
+    the same result bit for bit.  -> dict of device tensors; nothing is read back here: the error bits are in counts[1], which the caller
+    reads once (every other output is then zero).  timings: a list that receives (stage, ms) pairs (the call then waits for the
+    stream)."""
+    return _rotation_averaging(_Gpu, "rotation_averaging",
+                               "the rotation-averaging kernels have no CPU fallback; the host routine is rotation_averaging_host",
+                               (edge_image, edge_R, edge_weight, adj_offsets, adj_edge, edge_use), n_images, root, cycle_cos_half,
+                               loss_chord, max_chord, step_tol, max_iters, pcg_iters, pcg_tol, timings)
+
+
+# ---- localisation against a triangulated model (csrc/model_lookup.hip,csrc/model_lookup_gpu.hip; DESIGN §17) ------------------------
 MODEL_COUNTS = 16
 MODEL_REASONS = ("n_kept", "n_bad_row", "n_masked", "n_nonfinite", "n_negative_conf", "n_outside", "n_no_keypoint", "n_no_point",
                  "n_fused")                                                                  # match_reason codes 0..8 = counts[4 + reason]

@@ -65,6 +65,7 @@ class Reconstruction:
         self.T_cam_from_world, self.posed, self.round_registered = T_cam_from_world, posed, round_registered
         self.points, self.bundle, self.stats, self.K, self.radial = points, bundle, stats, K, radial
         self.sfm = None                                                 # the relabelled atlas of SfmResult.reconstruct(complete=True / merge=True)
+        self.rotations = None                                           # the GlobalRotations of SfmResult.reconstruct(rotations=True)
 
     def transformed(self, s, R, t):
         """A copy moved by the similarity X' = s R X + t (``ops.transform_model``): new ``T_cam_from_world`` and
