@@ -361,6 +361,59 @@ class SfmResult:
         n = self.kp_offsets.numel() - 1
         return average_rotations(self.row_images, R.to(torch.float64), ninl.clamp(min=0).to(torch.int32), n, **kwargs)
 
+    def global_positions(self, K, rot, thresh_px=4.0, pose_conf=0.99999, seed=0, **kwargs):
+        """A centre for every camera of the view graph and a point for every consistent track, all at once, from the averaged rotations
+        ``rot`` (a ``GlobalRotations`` of ``rotation_averaging`` on this pair list or on the one it was cut from; positions.global_positions;
+        DESIGN §27) -> ``GlobalPositions`` on this result's device.  The start values walk the rows of ``rot.tree`` inside the root's
+        component with the translation directions of ``pairwise_poses`` (the same seed gives the poses the averaging saw; a tree row
+        that was removed since has no direction and is counted).  The keyword arguments are global_positions'."""
+        from .positions import global_positions
+        if self.is_refined:
+            raise ValueError("SfmResult.global_positions: this is a refined view; position the original result, then refine")
+        dev = self.keypoints.device
+        n = self.kp_offsets.numel() - 1
+        K = torch.as_tensor(K).detach().to(dev, torch.float64)
+        if tuple(K.shape) != (n, 3, 3) or tuple(rot.R.shape) != (n, 3, 3) or rot.tree.numel() != self.row_images.shape[0]:
+            raise ValueError(f"SfmResult.global_positions: expected K [{n},3,3] and the rotations of these {self.row_images.shape[0]} rows over "
+                             f"{n} images, got {tuple(K.shape)}, {tuple(rot.R.shape)}, {rot.tree.numel()} rows")
+        _, t, _ = self.pairwise_poses(K, thresh_px, pose_conf, seed)
+        ims = self.row_images.to(torch.int64)
+        in_graph = rot.in_graph.to(dev)
+        rows = rot.tree.to(dev) & in_graph[ims[:, 0]] & in_graph[ims[:, 1]]
+        offsets, image, local = self.tracks(consistent_only=True)
+        xy = self.keypoints[self.kp_offsets[image] + local]
+        return global_positions(offsets, image.to(torch.int32), xy, K, rot.R.to(dev), in_graph, int(rot.root), self.row_images[rows].to(torch.int32),
+                                t[rows].to(torch.float64), **kwargs)
+
+    def reconstruct_global(self, K, thresh_px=4.0, ba=None, rotations_kw=None, positions_kw=None, **register_kw):
+        """Global reconstruction from intrinsics alone (DESIGN §27) -> Reconstruction on this result's device: ``rotation_averaging``;
+        everything after it reads ``without_rows(ok rows | rows the graph could not judge)``; ``global_positions`` gives every camera of
+        the root's component with enough observations a pose at once; then registration.reconstruct_tracks continues from those poses
+        (``start``): triangulate over the posed images, adjust with only the root fixed, triangulate again, and the images that still
+        have no pose (chained only, or outside the graph) go through the existing rounds of register -> triangulate -> adjust ->
+        triangulate.  ``ba``: bundle_adjust's keywords; ``rotations_kw`` / ``positions_kw``: average_rotations' / global_positions';
+        ``register_kw``: reconstruct_tracks' other keywords.  The Reconstruction carries ``.rotations``, ``.positions``, the atlas it was
+        built on as ``.sfm`` and the counts as ``stats['rotations']``, ``stats['positions']``."""
+        from .registration import reconstruct_tracks
+        dev = self.keypoints.device
+        n = self.kp_offsets.numel() - 1
+        K = torch.as_tensor(K).detach().to(dev, torch.float64)
+        if tuple(K.shape) != (n, 3, 3):
+            raise ValueError(f"SfmResult.reconstruct_global: expected K [{n},3,3], got {tuple(K.shape)}")
+        rot = self.rotation_averaging(K, thresh_px=thresh_px, **(rotations_kw or {}))
+        sfm2, done = self.without_rows(rot.edge_ok | (rot.edge_state < 2))
+        pos = sfm2.global_positions(K, rot, thresh_px=thresh_px, **(positions_kw or {}))
+        if not bool(pos.posed.any()):
+            raise ValueError(f"SfmResult.reconstruct_global: global positioning posed no image ({pos.stats})")
+        offsets, image, local = sfm2.tracks(consistent_only=True)
+        xy = sfm2.keypoints[sfm2.kp_offsets[image] + local]
+        rec = reconstruct_tracks(offsets, image.to(torch.int32), xy, K, None, start=(pos.T_cam_from_world, pos.posed, int(rot.root)), ba=ba,
+                                 thresh_px=thresh_px, **register_kw)
+        rec.points.offsets, rec.points.image, rec.points.keypoint = offsets, image, local
+        rec.sfm, rec.rotations, rec.positions = sfm2, rot, pos
+        rec.stats.update(rotations=rot.stats, rows_removed=done.stats, positions=pos.stats)
+        return rec
+
     def without_rows(self, rows_ok, min_track_len=2, max_rounds=32, timings=None):
         """This result without the matches of the rows where ``rows_ok [R]`` is false -> ``(sfm2, split)``.  Every track that holds a
         match of a rejected row loses its ``track_ok``; ``split_tracks`` then grows the keypoints of those tracks (and of the tracks

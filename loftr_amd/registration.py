@@ -66,6 +66,7 @@ class Reconstruction:
         self.points, self.bundle, self.stats, self.K, self.radial = points, bundle, stats, K, radial
         self.sfm = None                                                 # the relabelled atlas of SfmResult.reconstruct(complete=True / merge=True)
         self.rotations = None                                           # the GlobalRotations of SfmResult.reconstruct(rotations=True)
+        self.positions = None                                           # the GlobalPositions of SfmResult.reconstruct_global
 
     def transformed(self, s, R, t):
         """A copy moved by the similarity X' = s R X + t (``ops.transform_model``): new ``T_cam_from_world`` and
@@ -236,7 +237,7 @@ def _follow_group_radial(k_in, k_out, group, cam_radial, G):
     return torch.where(cam_radial | torch.isinf(per_group[group]), k_out, k_out + per_group[group])
 
 
-def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=None, min_angle_deg=1.5, radial=None, **register_kw):
+def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=None, min_angle_deg=1.5, radial=None, start=None, **register_kw):
     """Incremental reconstruction from tracks and an initial pair -> ``Reconstruction``.
 
     ``offsets [T+1]``, ``obs_image [N]``, ``obs_xy [N,2]`` as for ``triangulate_tracks``, ``K [n,3,3]``; tensors on one device (GPU:
@@ -267,7 +268,14 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     adjustment.  With ``ba={'refine_focal': True, 'refine_radial': True[, 'camera_ids': ids]}`` the adjustment reads the stored pixels
     and refines the coefficients, starting from ``radial`` (default zeros); the members of a camera that did not carry it take their
     camera's step, as with the focal.  Without ``refine_radial`` the coefficients are taken as known: the adjustment is the pinhole
-    call on the undistorted pixels.  ``Reconstruction.radial`` holds the final values."""
+    call on the undistorted pixels.  ``Reconstruction.radial`` holds the final values.
+
+    ``start = (T_cam_from_world [n,4,4], posed [n])`` or ``(T_cam_from_world, posed, fixed_image)`` instead of ``init`` (which must then
+    be ``None``): the loop continues from poses somebody else found, for example ``global_positions`` (positions.py).
+    ``fixed_image`` is the posed image the adjustments hold fixed (``SfmResult.reconstruct_global`` names the root of the rotation
+    averaging); without it, it is the first posed image whose pose is exactly the identity, else the first posed one.  The images of
+    ``start`` count as registered in round 0, and ``stats['init']`` is ``(fixed_image, None)``: there is no second image of a pair.  A
+    start that holds exactly what ``init`` would have set gives the same result bit for bit."""
     from .bundle import bundle_adjust
     from .radial import undistort_points
     what = "reconstruct_tracks"
@@ -279,16 +287,36 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3):
         raise LoftrHipError(f"{what}: expected K [n,3,3], got {tuple(K.shape)}")
     n = K.shape[0]
-    a, b, R, t = init
-    a, b = int(a), int(b)
-    R = torch.as_tensor(np.asarray(R.cpu() if isinstance(R, torch.Tensor) else R, np.float64)).reshape(3, 3)
-    t = torch.as_tensor(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, np.float64)).reshape(3)
-    if a == b or not (0 <= a < n and 0 <= b < n):
-        raise ValueError(f"{what}: the initial pair must be two different images in [0, {n}), got a = {a}, b = {b}")
-    norm = float(torch.linalg.norm(t))
-    if not (bool(torch.isfinite(R).all()) and math.isfinite(norm) and norm > 0 and float(torch.linalg.det(R)) > 0):
-        raise ValueError(f"{what}: init holds no relative pose (a refused five-point or P3P model returns zeros): det R = "
-                         f"{float(torch.linalg.det(R))}, |t| = {norm}")
+    if start is not None:
+        if init is not None:
+            raise ValueError(f"{what}: with start, init must be None")
+        if len(start) not in (2, 3):
+            raise ValueError(f"{what}: expected start = (T_cam_from_world, posed[, fixed_image]), got {len(start)} items")
+        T0, posed0 = _tensors(what, ("start[0]", "start[1]"), tuple(start[:2]))
+        T0, posed0 = T0.to(dev).to(torch.float64), posed0.to(dev) != 0
+        if tuple(T0.shape) != (n, 4, 4) or tuple(posed0.shape) != (n,) or not bool(posed0.any()):
+            raise ValueError(f"{what}: expected start = (T_cam_from_world [{n},4,4], posed [{n}]) with a posed image, got {tuple(T0.shape)}, "
+                             f"{tuple(posed0.shape)}")
+        if not bool(torch.isfinite(T0[posed0]).all()):
+            raise ValueError(f"{what}: a posed image of start has a pose that is not finite")
+        if len(start) == 3:
+            a, b = int(start[2]), None
+            if not 0 <= a < n or not bool(posed0[a]):
+                raise ValueError(f"{what}: the fixed image of start must be a posed image in [0, {n}), got {start[2]!r}")
+        else:
+            gauge = posed0 & (T0 == torch.eye(4, dtype=torch.float64, device=dev)).reshape(n, 16).all(1)
+            a, b = int(torch.nonzero(gauge if bool(gauge.any()) else posed0)[0]), None
+    else:
+        a, b, R, t = init
+        a, b = int(a), int(b)
+        R = torch.as_tensor(np.asarray(R.cpu() if isinstance(R, torch.Tensor) else R, np.float64)).reshape(3, 3)
+        t = torch.as_tensor(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, np.float64)).reshape(3)
+        if a == b or not (0 <= a < n and 0 <= b < n):
+            raise ValueError(f"{what}: the initial pair must be two different images in [0, {n}), got a = {a}, b = {b}")
+        norm = float(torch.linalg.norm(t))
+        if not (bool(torch.isfinite(R).all()) and math.isfinite(norm) and norm > 0 and float(torch.linalg.det(R)) > 0):
+            raise ValueError(f"{what}: init holds no relative pose (a refused five-point or P3P model returns zeros): det R = "
+                             f"{float(torch.linalg.det(R))}, |t| = {norm}")
     ba = dict(ba or {})
     fixed = torch.zeros(n, dtype=torch.bool, device=dev)
     fixed[a] = True
@@ -318,14 +346,18 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
     pinhole = lambda K, rad: obs_xy if rad is None else undistort_points(obs_xy, obs_image, K, rad)[0]
     thresh_px = register_kw.get("thresh_px", 4.0)
     T = torch.full((n, 4, 4), float("nan"), dtype=torch.float64, device=dev)
-    T[a] = torch.eye(4, dtype=torch.float64)
-    Tb = torch.eye(4, dtype=torch.float64)
-    Tb[:3, :3], Tb[:3, 3] = R, t / norm
-    T[b] = Tb
     posed = torch.zeros(n, dtype=torch.bool, device=dev)
-    posed[a] = posed[b] = True
+    if start is not None:
+        T[posed0] = T0[posed0]
+        posed |= posed0
+    else:
+        T[a] = torch.eye(4, dtype=torch.float64)
+        Tb = torch.eye(4, dtype=torch.float64)
+        Tb[:3, :3], Tb[:3, 3] = R, t / norm
+        T[b] = Tb
+        posed[a] = posed[b] = True
     round_registered = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    round_registered[a] = round_registered[b] = 0
+    round_registered[posed] = 0
     rounds = []
 
     def refine(T, posed, K, rad, first=False):
@@ -334,7 +366,9 @@ def reconstruct_tracks(offsets, obs_image, obs_xy, K, init, max_rounds=50, ba=No
         xy = pinhole(K, rad)
         pts = triangulate_posed(offsets, obs_image, xy, K, T, posed, thresh_px, min_angle_deg)
         if first and pts.stats["n_ok"] == 0:
-            raise ValueError(f"{what}: the initial pair ({a}, {b}) triangulates nothing: {pts.stats['n_posed_observations']} observations in "
+            begun = f"the initial pair ({a}, {b}) triangulates" if start is None else \
+                f"the {int(posed.sum())} posed images of start (fixed: {a}) triangulate"
+            raise ValueError(f"{what}: {begun} nothing: {pts.stats['n_posed_observations']} observations in "
                              f"{pts.stats['n_tracks']} tracks, statuses {[pts.stats['n_' + s] for s in ops.TRI_STATUS]}")
         if fits_lens:                                                   # the adjustment fits the lens on the stored pixels
             res = bundle_adjust(offsets, obs_image, obs_xy, pts.obs_inlier, pts.xyz, K, T, fixed=fixed, radial=rad, **ba)
