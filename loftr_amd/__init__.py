@@ -16,6 +16,7 @@ from .merging import Merge, merge_tracks                            # noqa: F401
 from .splitting import Split, split_tracks                          # noqa: F401
 from .rotations import GlobalRotations, average_rotations     # noqa: F401
 from .positions import GlobalPositions, global_positions      # noqa: F401
+from .calibration import ViewGraphCalibration, calibrate_view_graph   # noqa: F401
 from .refinement import Refinement, RefinePlan, plan_track_refinement, apply_refinement    # noqa: F401
 from .alignment import Alignment, align_centres                    # noqa: F401
 from .proposals import Overlap, view_overlap, select_pairs, select_database      # noqa: F401

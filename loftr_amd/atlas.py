@@ -414,6 +414,76 @@ class SfmResult:
         rec.stats.update(rotations=rot.stats, rows_removed=done.stats, positions=pos.stats)
         return rec
 
+    def pairwise_fundamentals(self, thresh_px=1.0, conf=0.999, seed=0):
+        """Fundamental matrices of ALL rows from the kept matches, no intrinsics needed: one ``ops.estimate_geometry`` call on a GPU
+        result, a loop over ``evaluation.estimate_fundamental_native`` on a CPU one (the same result for one seed).
+        -> (F [R,3,3] f32 with x_b^T F x_a = 0 in pixels and unit norm, zero without a model; n_inliers [R] i64, -1 without a model), on
+        this result's device."""
+        dev = self.keypoints.device
+        n_rows = self.row_offsets.numel() - 1
+        row = torch.repeat_interleave(torch.arange(n_rows, device=dev), self.row_offsets[1:] - self.row_offsets[:-1])
+        ims = self.row_images.to(torch.int64)
+        m = self.matches.to(torch.int64)
+        k0 = self.keypoints[self.kp_offsets[ims[row, 0]] + m[:, 0]].contiguous()
+        k1 = self.keypoints[self.kp_offsets[ims[row, 1]] + m[:, 1]].contiguous()
+        row_offsets = self.row_offsets
+        if self.is_undistorted:                                          # a keypoint that could not be undistorted is NaN: its matches are left out
+            keep = torch.isfinite(k0).all(1) & torch.isfinite(k1).all(1)
+            k0, k1, row = k0[keep].contiguous(), k1[keep].contiguous(), row[keep]
+            row_offsets = torch.zeros_like(self.row_offsets)
+            row_offsets[1:] = torch.cumsum(torch.bincount(row, minlength=n_rows), 0)
+        if dev.type == "cuda":
+            F, _, ninl = ops.estimate_geometry(k0.to(torch.float32), k1.to(torch.float32), row, n_rows, "fundamental", thresh_px, conf, seed)
+            return F, ninl
+        from .evaluation import estimate_fundamental_native
+        F, ninl = torch.zeros(n_rows, 3, 3), torch.full((n_rows,), -1, dtype=torch.int64)
+        off = row_offsets.tolist()
+        for r in range(n_rows):
+            sl = slice(off[r], off[r + 1])
+            est = estimate_fundamental_native(k0[sl].numpy(), k1[sl].numpy(), thresh_px, conf, seed)
+            if est is not None:
+                F[r], ninl[r] = torch.from_numpy(np.asarray(est[0])).float(), int(est[1].sum())
+        return F, ninl
+
+    def calibrate(self, f0=None, principal_point=None, camera_ids=None, thresh_px=1.0, seed=0, **params):
+        """A focal length for every image from the fundamental matrices of all rows at once (calibration.calibrate_view_graph; DESIGN
+        §28) -> ``ViewGraphCalibration`` on this result's device.  Edge ``e`` is row ``e`` with the F of ``pairwise_fundamentals`` at
+        ``thresh_px`` and its inlier count as the weight; a row without a model is invalid (state 0).  ``f0=None``: 1.2 max(H, W) for
+        every image, the usual guess without EXIF; ``principal_point=None``: (W / 2, H / 2), ASSUMED (both need the atlas's
+        ``image_hw``).  ``camera_ids [n_images]``: images with one id share one focal scale.  ``params``: calibrate_view_graph's; the
+        defaults are a prototype's, UNVALIDATED on real data."""
+        from .calibration import calibrate_view_graph, default_focal
+        if self.is_refined:
+            raise ValueError("SfmResult.calibrate: this is a refined view; calibrate the original result, then refine")
+        if (f0 is None or principal_point is None) and self.image_hw is None:
+            raise ValueError("SfmResult.calibrate: f0=None and principal_point=None need the atlas's image_hw; this result carries none")
+        dev = self.keypoints.device
+        n = self.kp_offsets.numel() - 1
+        if f0 is None:
+            f0 = default_focal(self.image_hw)
+        if principal_point is None:
+            principal_point = (float(self.image_hw[1]) / 2.0, float(self.image_hw[0]) / 2.0)
+        on = lambda x: x.to(dev) if isinstance(x, torch.Tensor) else (torch.as_tensor(np.asarray(x)).to(dev) if np.ndim(x) else x)
+        F, ninl = self.pairwise_fundamentals(thresh_px=thresh_px, seed=seed)
+        return calibrate_view_graph(self.row_images, F.to(torch.float64), ninl.clamp(min=0).to(torch.int32), n, on(principal_point), on(f0),
+                                    camera_ids=None if camera_ids is None else on(camera_ids), **params)
+
+    def reconstruct_uncalibrated(self, f0=None, camera_ids=None, global_=False, calibrate_kw=None, ba=None, **kw):
+        """Reconstruction without intrinsics -> Reconstruction on this result's device: ``calibrate`` gives every image a
+        focal length (the principal point is assumed), then ``reconstruct`` or, with ``global_=True``, ``reconstruct_global`` runs with
+        that ``K``.  ``ba`` defaults to ``{'refine_focal': True}`` (plus ``camera_ids`` when given), so the bundle adjustment refines what
+        the calibration left; ``calibrate_kw``: ``calibrate``'s other keywords; ``kw``: the reconstruction's.  The Reconstruction carries
+        the ``ViewGraphCalibration`` as ``.calibration`` and its counts as ``stats['calibration']``."""
+        cal = self.calibrate(f0=f0, camera_ids=camera_ids, **(calibrate_kw or {}))
+        if ba is None:
+            ba = {"refine_focal": True}
+            if camera_ids is not None:
+                ba["camera_ids"] = camera_ids
+        rec = (self.reconstruct_global if global_ else self.reconstruct)(cal.K, ba=ba, **kw)
+        rec.calibration = cal
+        rec.stats.update(calibration=cal.stats)
+        return rec
+
     def without_rows(self, rows_ok, min_track_len=2, max_rounds=32, timings=None):
         """This result without the matches of the rows where ``rows_ok [R]`` is false -> ``(sfm2, split)``.  Every track that holds a
         match of a rejected row loses its ``track_ok``; ``split_tracks`` then grows the keypoints of those tracks (and of the tracks

@@ -1,5 +1,5 @@
-"""Build libloftr_hip.so (the C-ABI of the HIP kernels) and libloftr_global.so (the global reconstruction stages,
-include/loftr_global.h) in-tree for gfx950.
+"""Build libloftr_hip.so (the C-ABI of the HIP kernels), libloftr_global.so (the global reconstruction stages,
+include/loftr_global.h) and libloftr_calib.so (view-graph calibration, include/loftr_calib.h) in-tree for gfx950.
 
     python -m loftr_amd.build [--force]
 
@@ -24,6 +24,11 @@ GLOBAL_SOURCES = ["position.hip", "position_gpu.hip"]
 # and its C ABI header.  The second: the headers its two units include, directly or through them, and both C ABI headers.
 GLOBAL_ONLY = GLOBAL_SOURCES + ["position_core.h"]
 GLOBAL_HEADERS = ["position_core.h", "bundle_core.h", "tracks_core.h", "stage_timer.h", "common.h"]
+# the third library (view-graph calibration): as the second, with its own units, core header and C ABI header
+CALIB_LIB_PATH = os.path.join(HERE, "libloftr_calib.so")
+CALIB_SOURCES = ["calib.hip", "calib_gpu.hip"]
+CALIB_ONLY = CALIB_SOURCES + ["calib_core.h"]
+CALIB_HEADERS = ["calib_core.h", "bundle_core.h", "tracks_core.h", "stage_timer.h", "common.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-parameter"]
 
 
@@ -39,14 +44,17 @@ def _deps_mtime(sources):
     include = os.path.join(os.path.dirname(HERE), "include")
     if sources is GLOBAL_SOURCES:
         paths = [os.path.join(CSRC, f) for f in GLOBAL_SOURCES + GLOBAL_HEADERS] + [os.path.join(include, "loftr_global.h")]
+    elif sources is CALIB_SOURCES:
+        paths = [os.path.join(CSRC, f) for f in CALIB_SOURCES + CALIB_HEADERS] + [os.path.join(include, "loftr_calib.h")]
     else:
-        paths = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip")) and f not in GLOBAL_ONLY]
+        paths = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip")) and f not in GLOBAL_ONLY + CALIB_ONLY]
     paths.append(os.path.join(include, "loftr_hip.h"))
     return max(os.path.getmtime(p) for p in paths)
 
 
 def build(force=False, verbose=True, extra_flags=(), lib_path=None, obj_dir=None):
-    """Compile every HIP source for gfx950 and link libloftr_hip.so and libloftr_global.so.  Returns the first one's path.
+    """Compile every HIP source for gfx950 and link libloftr_hip.so, libloftr_global.so and libloftr_calib.so.  Returns the first
+    one's path.
     extra_flags / lib_path / obj_dir build a variant of the first library next to the product (A/B experiments)."""
     global LIB_PATH, OBJ_DIR
     lib_default, obj_default = LIB_PATH, OBJ_DIR
@@ -56,6 +64,7 @@ def build(force=False, verbose=True, extra_flags=(), lib_path=None, obj_dir=None
         path = _build(force, verbose, tuple(extra_flags), LIB_PATH, SOURCES)
         if not lib_path:
             _build(force, verbose, tuple(extra_flags), GLOBAL_LIB_PATH, GLOBAL_SOURCES)
+            _build(force, verbose, tuple(extra_flags), CALIB_LIB_PATH, CALIB_SOURCES)
         return path
     finally:
         LIB_PATH, OBJ_DIR = lib_default, obj_default
@@ -79,7 +88,7 @@ def _build(force, verbose, extra_flags, lib, sources):
 
     with ThreadPoolExecutor(max_workers=min(8, len(sources))) as ex:
         objs = list(ex.map(compile_one, sources))
-    # export the C ABI only (include/loftr_hip.h, include/loftr_global.h: loftr_*); the C++ launch helpers shared between translation units stay internal
+    # export the C ABI only (include/loftr_hip.h, include/loftr_global.h, include/loftr_calib.h: loftr_*); the C++ launch helpers shared between translation units stay internal
     vs = os.path.join(OBJ_DIR, "exports.map")
     with open(vs, "w") as fh:
         fh.write("{ global: loftr_*; local: *; };\n")

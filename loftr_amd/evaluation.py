@@ -215,6 +215,18 @@ def verify_matches(data, model="fundamental", thresh_px=None, conf=0.999, seed=0
     return data
 
 
+def focal_errors(focal, K_gt):
+    """Relative focal error per image, |f / f_gt - 1| with f_gt the mean of the two diagonal entries of ``K_gt [n,3,3]``: ``focal [n]``
+    (e.g. ``ViewGraphCalibration.focal``), or ``[n,3,3]`` intrinsics, read the same way.  numpy in, numpy out (tensors are copied)."""
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    f, Kg = to_np(focal).astype(np.float64), to_np(K_gt).astype(np.float64)
+    if f.ndim == 3:
+        f = 0.5 * (f[:, 0, 0] + f[:, 1, 1])
+    if Kg.ndim != 3 or Kg.shape[1:] != (3, 3) or f.shape != (Kg.shape[0],):
+        raise ValueError(f"focal_errors: expected focal [n] (or [n,3,3]) and K_gt [n,3,3], got {f.shape}, {Kg.shape}")
+    return np.abs(f / (0.5 * (Kg[:, 0, 0] + Kg[:, 1, 1])) - 1.0)
+
+
 # ---- absolute pose from matches and depth (csrc/absolute_pose.hip, csrc/absolute_pose_gpu.hip) ---------------------------
 def estimate_absolute_pose_native(pts3d, kpts, K, thresh=3.0, conf=0.999, seed=0):
     """Camera pose x_cam = R X + t of one image from 2D-3D matches (numpy: pts3d [M,3], kpts [M,2] pixels, K [3,3]): P3P RANSAC + a

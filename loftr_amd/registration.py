@@ -67,6 +67,7 @@ class Reconstruction:
         self.sfm = None                                                 # the relabelled atlas of SfmResult.reconstruct(complete=True / merge=True)
         self.rotations = None                                           # the GlobalRotations of SfmResult.reconstruct(rotations=True)
         self.positions = None                                           # the GlobalPositions of SfmResult.reconstruct_global
+        self.calibration = None                                         # the ViewGraphCalibration of SfmResult.reconstruct_uncalibrated
 
     def transformed(self, s, R, t):
         """A copy moved by the similarity X' = s R X + t (``ops.transform_model``): new ``T_cam_from_world`` and
